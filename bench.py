@@ -14,17 +14,22 @@ Workload (BASELINE.json configs[2]/[3]): uw3-500 OCR shape -- BiLSTM(100) on 48-
 inputs (clip(N(0.2,0.3),0,1) smoothed along t), reference LCG init (seed 0.222, negbiased).
 A step = one pass of the hot path over one minibatch whose frames are already resident in HBM.
 
-Timing: W untimed warm-up steps (at least 0.3 s worth -- a 20-step command must not time clock ramp and first-touch
-effects), then the block of EXACTLY K steps, bracketed by barrier + synchronize on both sides and max-reduced over the
-ranks, is timed R times back to back (R such that the timed total is >= 0.5 s; `repeats` in the JSON) and the MEDIAN
-block is reported: `ms_per_step` = median block / K, `value` = lines of one block / median block.
+Timing: exactly W untimed warm-up steps, then ONE block of exactly K steps, bracketed by barrier + synchronize on both sides
+and max-reduced over the ranks: `ms_per_step` = block / K, `value` = lines of the block / block.  The number of steps is
+fixed by the arguments alone, so the state after the last timed step is too (--dump-outputs DIR writes it: parameters and
+momentum buffer as float32 .npy files, a fixed seeded sample of each above 4 Mi elements).
+
+A plain run measures the headline figure and nothing else.  --full adds, after the headline block and its dump, what the
+line carries beyond it: per-kernel device times and the roofline, the host enqueue cost, the isolated all-reduce, the CPU
+baseline and -- on the default single-GPU line -- the legs below.  The legs time their own workloads as before: warm-up of at
+least 0.3 s, then R blocks (R such that a leg's timed total reaches its bound) and the MEDIAN block.
 
 Test hooks (tests/test_bench_ranks.py runs this file's rank body at world size 2 on the CPU before the driver runs it on
 eight GPUs): CLSTM_BENCH_BACKEND=gloo (process-group backend), CLSTM_BENCH_DEVICE=cpu (tensors in host memory, no streams),
-CLSTM_BENCH_LIB=<path of a build of the library>, CLSTM_BENCH_MIN_TIMED_S / CLSTM_BENCH_MIN_WARMUP_S (bounds of the timing
-protocol).  None is set in a measurement.
+CLSTM_BENCH_LIB=<path of a build of the library>, CLSTM_BENCH_MIN_TIMED_S / CLSTM_BENCH_MIN_WARMUP_S (bounds of the legs'
+timing protocol).  None is set in a measurement.
 
-The default single-GPU line also carries `secondary`: BASELINE.json configs[4] (2 x BiLSTM(512), H = 64, T = 400,
+With --full the default single-GPU line also carries `secondary`: BASELINE.json configs[4] (2 x BiLSTM(512), H = 64, T = 400,
 bf16 MFMA) timed in the same process with the same protocol and its own `roofline` (MFMA, 2.5 PFLOP/s dense bf16).
 """
 import argparse
@@ -285,8 +290,27 @@ class Workload:
         return {"device_errors": "none", "params_finite": True, "max_param_change": moved}
 
 
-def timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s=None):
-    """warm-up (>= `warmup` steps and >= MIN_WARMUP_S), then R blocks of exactly `steps` steps; returns the block times"""
+MAX_DUMP_ELEMENTS = 1 << 22      # per array (16 MB of float32): configs[4]'s 8.7M parameters are sampled
+
+
+def dump_outputs(w, out_dir):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the updated parameters and the momentum
+    buffer (which folds in that step's gradient).  The step's per-line outputs are not addressable after
+    clstm_net_train_step_next (abi.inc).  An array longer than MAX_DUMP_ELEMENTS is written as the sample at fixed indices
+    (seed 0, ascending), the same for every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, a in (("params", w.net.get_params()), ("momentum", w.net.get_derivs())):
+        if a.size > MAX_DUMP_ELEMENTS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, MAX_DUMP_ELEMENTS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+        files[name] = int(a.size)
+    return files
+
+
+def timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s=None, exact=False):
+    """warm-up (>= `warmup` steps and >= MIN_WARMUP_S), then R blocks of exactly `steps` steps; returns the block times.
+    exact (the headline): exactly `warmup` steps, then one block -- a step count that depends on the arguments alone"""
     i = 0
     t0 = time.perf_counter()
     for _ in range(warmup):
@@ -294,7 +318,7 @@ def timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s=None):
         i += 1
     fence()
     # the time criterion looks at the max over ranks (a collective: every rank takes the same number of rounds)
-    while reduce_max(time.perf_counter() - t0) < MIN_WARMUP_S:
+    while not exact and reduce_max(time.perf_counter() - t0) < MIN_WARMUP_S:
         for _ in range(max(1, min(steps, 16))):
             w.step(i)
             i += 1
@@ -311,7 +335,7 @@ def timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s=None):
         dt = reduce_max(time.perf_counter() - t0)
         i += steps
         blocks.append(dt)
-        if k == 0:
+        if k == 0 and not exact:
             repeats = int(min(MAX_REPEATS, max(1, np.ceil((MIN_TIMED_S if min_timed_s is None else min_timed_s) / max(dt, 1e-9)))))   # identical on every rank: dt is max-reduced
         k += 1
     return blocks, i
@@ -548,15 +572,22 @@ def main():
     ap.add_argument("--weights", choices=["init", "trained"], default="init",
                     help="trained: the SURVEY 8(d) 'trained-like' regime -- weights after 500 online-SGD steps on the reference's fixture line, "
                          "inputs = jittered crops of that line (config b1 only); the default line carries it as the `trained_weights` leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline block, everything else the line reports: per-kernel timing and roofline, host enqueue "
+                         "cost, the isolated all-reduce, the CPU baseline and the legs of the default line (the options below "
+                         "marked [--full] select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (parameters and momentum buffer after the last timed step) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="[--full] no CPU baseline")
     ap.add_argument("--no-declare-next", action="store_true",
                     help="plain clstm_net_train_step calls: every step starts with an ingest launch of its own (default: the loop "
                          "declares its next minibatch, clstm_net_train_step_next, and the ingest rides the previous step's last launch)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="the headline workload only: skip the other legs of the default line (strict_f32, saturated, configs[4] in both precisions) -- "
+                    help="[--full] the headline workload only: skip the other legs of the default line (strict_f32, saturated, configs[4] in both precisions) -- "
                          "what the rocprofv3 passes use, so that their per-kernel averages are the headline workload's")
     ap.add_argument("--profile-steps", type=int, default=None,
-                    help="extra steps with per-kernel timing (events bound to each launch's dispatch packet); default 50 (b1) / 5 (b2)")
+                    help="[--full] extra steps with per-kernel timing (events bound to each launch's dispatch packet); default 50 (b1) / 5 (b2)")
     args = ap.parse_args()
     if args.no_declare_next:
         os.environ["CLSTM_BENCH_DECLARE_NEXT"] = "0"
@@ -665,17 +696,24 @@ def main():
 
     leg_validity = {}
 
-    def measure(w, steps, warmup, profile_steps, unfused_pass=False, min_timed_s=None, name="main"):
-        blocks, nxt = timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s)
+    def measure(w, steps, warmup, profile_steps, unfused_pass=False, min_timed_s=None, name="main", headline=False):
+        """headline: exactly `warmup` + `steps` steps, then the dump of their outputs (--dump-outputs), and only with --full
+        the diagnostics below, whose extra steps come after it"""
+        blocks, nxt = timed_blocks(w, steps, warmup, fence, reduce_max, min_timed_s, exact=headline)
         dt = float(np.median(blocks))
-        # host-side cost of issuing a step (diagnostic: is the loop host-bound?): a short burst on an idle stream, few
-        # enough steps that the library's pinned staging ring never makes the host wait for the GPU
-        t1 = time.perf_counter()
-        for i in range(4):
-            w.step(nxt + i)
-        t_enq = (time.perf_counter() - t1) / 4
-        fence()
+        dumped = dump_outputs(w, args.dump_outputs) if headline and args.dump_outputs and rank == 0 else None
+        t_enq = None
         kern, fps, kern_unfused = {}, 0, {}
+        if headline and not args.full:
+            profile_steps = 0
+        else:
+            # host-side cost of issuing a step (diagnostic: is the loop host-bound?): a short burst on an idle stream, few
+            # enough steps that the library's pinned staging ring never makes the host wait for the GPU
+            t1 = time.perf_counter()
+            for i in range(4):
+                w.step(nxt + i)
+            t_enq = (time.perf_counter() - t1) / 4
+            fence()
         if profile_steps > 0:
             # EVERY rank takes these steps (with a communicator a step is a collective: rank 0 stepping alone waited for its
             # peers forever -- found by tests/test_bench_ranks.py::test_bench_gpus2_on_the_real_library_sharing_one_gpu before
@@ -695,7 +733,8 @@ def main():
                 raise
             validity = {"error": str(e)[:400]}
         leg_validity[name] = validity
-        return {"dt": dt, "blocks": blocks, "enqueue": t_enq, "kern": kern, "kern_unfused": kern_unfused, "frames_per_step": fps, "validity": validity}
+        return {"dt": dt, "blocks": blocks, "enqueue": t_enq, "kern": kern, "kern_unfused": kern_unfused, "frames_per_step": fps, "validity": validity,
+                "dumped": dumped}
 
     precision = 2 if args.bf16 else 1 if args.bf16_gemm else 0
     w = Workload(lib, cfg, args.minibatch, args.T, args.ragged, precision, dev, rank, comm=comm, dist=dist, host_inputs=args.host_inputs,
@@ -716,7 +755,7 @@ def main():
         sys.stderr.write("bench.py: rank %d / %d on %s: clstm_comm_peer_active = %d (%s)\n" % (
             rank, world, dev, pa, "peer-read all-reduce over HIP IPC mappings, fused into the update kernel" if pa else
             "no peer mappings (ranks on different nodes, or hipIpcOpenMemHandle / the probe failed): RCCL ncclAllReduce"))
-    m = measure(w, args.steps, args.warmup, args.profile_steps, unfused_pass=max(cfg["nh"]) <= 128)
+    m = measure(w, args.steps, args.warmup, args.profile_steps, unfused_pass=max(cfg["nh"]) <= 128, headline=True)
     dt = m["dt"]
     ms_per_step = dt / args.steps * 1e3
     value = args.minibatch * world * args.steps / dt
@@ -731,7 +770,7 @@ def main():
     allreduce = None
     if allreduce_impl is not None:
         ar_ms = None
-        if comm is not None:
+        if comm is not None and args.full:
             n = int(w.grads.numel())
             for _ in range(5):
                 comm.allreduce(w.grads, n)
@@ -759,13 +798,13 @@ def main():
                              "to back on the library stream (max over ranks) -- inside a step the call sits between the last reduction and the update"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(w.params_h, cfg)
 
     # the same workload in the TRAINED regime: speed must not depend on the weights -- peaked posteriors and
     # saturated gates walk the same kernels (default single-GPU line only)
     trained = None
-    if rank == 0 and world == 1 and default_line and args.weights == "init" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and args.weights == "init" and not args.no_secondary:
         wt = Workload(lib, cfg, args.minibatch, args.T, args.ragged, 0, dev, rank, weights="trained")
         mt_ = measure(wt, args.steps, 5, 0, min_timed_s=0.5, name="trained_weights")
         trained = dict(wt.weights_info, value=round(args.minibatch * args.steps / mt_["dt"], 2), unit="lines/s",
@@ -778,7 +817,7 @@ def main():
     # 3d: NOT the default -- posteriors then agree with the reference's to 5.6e-5 absolute / 3.2e-4 relative at T = 200 instead of
     # 7.3e-6 / 1.1e-4; profiles/r06_ctc_float_logadd.txt); default single-GPU line only
     ctc_float = None
-    if rank == 0 and world == 1 and default_line and args.weights == "init" and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and args.weights == "init" and not args.no_secondary:
         lib.call("clstm_debug_set_option", b"ctc_float", 1)
         try:
             wc = Workload(lib, cfg, args.minibatch, args.T, args.ragged, 0, dev, rank)
@@ -797,7 +836,7 @@ def main():
     # weight-gradient / softmax-backward products on the bf16 MFMA from f32 operands split exactly into three bf16 terms);
     # default single-GPU line only
     strict = None
-    if rank == 0 and world == 1 and default_line and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and not args.no_secondary:
         ws = Workload(lib, cfg, args.minibatch, args.T, args.ragged, 0, dev, rank, strict_f32=True)
         ms_ = measure(ws, args.steps, 5, 20, min_timed_s=0.5, name="strict_f32")
         strict = {"value": round(args.minibatch * args.steps / ms_["dt"], 2), "unit": "lines/s", "ms_per_step": round(ms_["dt"] / args.steps * 1e3, 4),
@@ -812,7 +851,7 @@ def main():
     # recurrence sits from a bandwidth bound); here the fused gate kernel is VALU-throughput-bound, and its fraction of the
     # HBM roof and of the packed-FMA rate is the "how far from the machine" number for the kernel itself.
     saturated = None
-    if rank == 0 and world == 1 and default_line and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and not args.no_secondary:
         wsat = Workload(lib, cfg, 256, args.T, False, 0, dev, rank)
         ssat = max(5, min(args.steps, 20))
         msat = measure(wsat, ssat, 3, 20, unfused_pass=True, min_timed_s=0.5, name="saturated")
@@ -842,7 +881,7 @@ def main():
     # "GEMM fused in" figure; backward: activations, c, dH in, four deltas out = 40 B per cell-step -- dc and dh_rec never
     # leave the chip) against the HBM peak.
     large = None
-    if rank == 0 and world == 1 and default_line and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and not args.no_secondary:
         LB = 2048
         wl = Workload(lib, cfg, LB, args.T, False, 0, dev, rank)
         sl_ = max(5, min(args.steps, 10))
@@ -876,7 +915,7 @@ def main():
 
     # BASELINE.json configs[4] in the same process (default single-GPU line only): 2 x BiLSTM(512), bf16 MFMA
     secondary = None
-    if rank == 0 and world == 1 and default_line and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and not args.no_secondary:
         c2 = CONFIGS["b2"]
         if comm is not None:
             w.net.set_comm(None)
@@ -901,7 +940,7 @@ def main():
     # ... and its parity-grade form: every gate activation inside 1e-4 of the oracle at this size
     # (tests/test_gpu_e2e.py::test_configs4_full_shape_f32_vs_oracle); 10 steps x >= 3 repeats
     secondary_f32 = None
-    if rank == 0 and world == 1 and default_line and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and default_line and not args.no_secondary:
         c2 = CONFIGS["b2"]
         w3 = Workload(lib, c2, 64, c2["T"], False, 0, dev, rank)
         m3 = measure(w3, 10, 2, 0, min_timed_s=0.25, name="secondary_f32")        # 10 steps x >= 3 repeats
@@ -948,11 +987,12 @@ def main():
                                      "(one ingest per step, none in front of the forward launch)" if (w.one_call and w.declare_next and not w.host_inputs)
                                      else "clstm_net_train_step_h" if w.host_inputs else "clstm_net_train_step" if w.one_call else "separate calls + torch.distributed all-reduce"),
                        "parallelism": "dp%d" % world},
-            "timing": {"protocol": "median of `repeats` blocks of exactly `steps` steps, each bracketed by barrier + synchronize "
-                                   "and max-reduced over ranks; warm-up >= %.1f s" % MIN_WARMUP_S,
-                       "block_ms_min": round(min(m["blocks"]) * 1e3, 3), "block_ms_max": round(max(m["blocks"]) * 1e3, 3)},
+            "timing": {"protocol": "exactly `warmup` untimed steps, then one block of exactly `steps` steps bracketed by barrier + "
+                                   "synchronize and max-reduced over ranks",
+                       "block_ms": round(m["blocks"][0] * 1e3, 3), "full": bool(args.full)},
+            "outputs_dumped": m["dumped"],
             "roofline": roofline, "cpu_baseline": cpu, "kernels": m["kern"], "kernels_fusions_off": m["kern_unfused"],
-            "host_enqueue_ms_per_step": round(m["enqueue"] * 1e3, 4),   # host-side cost of issuing a step
+            "host_enqueue_ms_per_step": None if m["enqueue"] is None else round(m["enqueue"] * 1e3, 4),   # host-side cost of issuing a step
             # after the timed blocks of EVERY workload of this line (Workload.verify: it raises otherwise): no sticky device
             # error -- the library skips updates after one --, parameters finite and moved by the updates
             "validity": dict(m["validity"], learning_rate=w.lr,

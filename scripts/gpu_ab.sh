@@ -11,7 +11,7 @@ fi
 i=0
 for CFG in "" "$@"; do
   i=$((i+1))
-  env $CFG timeout 300 python bench.py --no-cpu-baseline $BENCH_ARGS > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"; tail -2 "$OUT/bench_$i.err" | grep -v amdgpu.ids
+  env $CFG timeout 300 python bench.py --full --no-cpu-baseline $BENCH_ARGS > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"; tail -2 "$OUT/bench_$i.err" | grep -v amdgpu.ids
   python - <<PY
 import json
 try:

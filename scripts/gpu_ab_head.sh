@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mk
 for r in $(seq 1 $ROUNDS); do
 for v in $VARS; do
 vv=$v; [ "$v" = "-" ] && vv=""
-CLSTM_HIP_VARIANT=$vv timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $ARGS > "$OUT/bench_${v}_$r.json" 2> "$OUT/bench.err"
+CLSTM_HIP_VARIANT=$vv timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $ARGS > "$OUT/bench_${v}_$r.json" 2> "$OUT/bench.err"
 python - "$OUT/bench_${v}_$r.json" "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -7,7 +7,7 @@ python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2
 timeout 300 python scripts/gpu_b1micro.py > "$OUT/xd.txt" 2>&1; cat "$OUT/xd.txt" | grep -v amdgpu.ids
 timeout 300 python scripts/gpu_ctcprof.py > "$OUT/ctc_phase_cycles.txt" 2>&1; head -3 "$OUT/ctc_phase_cycles.txt" | grep -v amdgpu.ids
 for opt in "" $EXTRA_OPTS; do
-CLSTM_DEBUG="$opt" timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > "$OUT/bench_$opt.json" 2> "$OUT/bench.err"
+CLSTM_DEBUG="$opt" timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > "$OUT/bench_$opt.json" 2> "$OUT/bench.err"
 python - "$OUT/bench_$opt.json" "$opt" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -11,7 +11,7 @@ fi
 for ENVS in "$@"; do
   [ "$ENVS" = "-" ] && ENVS=""
   NAME=$(echo "b2_${ENVS:-default}" | tr ' =' '__')
-  env $ENVS timeout 300 python bench.py --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/$NAME.json" 2> "$OUT/$NAME.err"
+  env $ENVS timeout 300 python bench.py --full --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/$NAME.json" 2> "$OUT/$NAME.err"
   python - "$OUT/$NAME.json" "$ENVS" <<'PY'
 import json, sys
 try:

@@ -6,7 +6,7 @@ TAG=${1:-c32}
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2>&1
 timeout 900 python -m pytest tests -m gpu -q -x -k "configs4 or bidi2 or wide or lockstep or 32_cells" > "$OUT/pytest.log" 2>&1; tail -3 "$OUT/pytest.log"; grep -E "^E  " "$OUT/pytest.log" | head -10
-B() { timeout 300 python bench.py --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 "$@"; }
+B() { timeout 300 python bench.py --full --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 "$@"; }
 show() { python - "$1" "$2" <<'PY'
 import json, sys
 try:

@@ -2,7 +2,7 @@
 # launch-internal timeline of the fused backward + weight-gradient launch (CLSTM_DW_TRACE): when does the recurrence end,
 # when do the items of each chunk become ready and finish
 TAG=${1:-dwtr}; ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
-CLSTM_DW_TRACE="$OUT/trace.txt" timeout 300 python bench.py --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
+CLSTM_DW_TRACE="$OUT/trace.txt" timeout 300 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - "$OUT/trace.txt" <<'PY' | tee "$OUT/summary.txt"
 import sys, collections
 rows = [tuple(int(x) for x in l.split()) for l in open(sys.argv[1]) if not l.startswith("#")]

@@ -6,7 +6,7 @@ python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2
 timeout 900 python -m pytest tests/test_mfma_recurrence.py -m gpu -q -x > "$OUT/pytest_mfma.log" 2>&1; tail -15 "$OUT/pytest_mfma.log"
 for mb in 256 1024; do
   for mode in 1 0; do
-    CLSTM_DEBUG="fwd_mfma=$mode,bwd_mfma=$mode" timeout 600 python bench.py --no-cpu-baseline --no-secondary --minibatch $mb --steps 20 --warmup 5 \
+    CLSTM_DEBUG="fwd_mfma=$mode,bwd_mfma=$mode" timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --minibatch $mb --steps 20 --warmup 5 \
         > "$OUT/bench_mb${mb}_mfma${mode}.json" 2> "$OUT/bench_mb${mb}_mfma${mode}.err"
     python - <<PY
 import json

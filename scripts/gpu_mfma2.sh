@@ -9,7 +9,7 @@ if [ -f clstm_amd/lib/libclstm_hip_prof.so ]; then
 fi
 for mb in ${MBS:-256 512 1024}; do
   for mode in 1; do
-    CLSTM_DEBUG="fwd_mfma=$mode,bwd_mfma=$mode" timeout 600 python bench.py --no-cpu-baseline --no-secondary --minibatch $mb --steps 20 --warmup 5 \
+    CLSTM_DEBUG="fwd_mfma=$mode,bwd_mfma=$mode" timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --minibatch $mb --steps 20 --warmup 5 \
         > "$OUT/bench_mb${mb}_mfma${mode}.json" 2> "$OUT/bench_mb${mb}_mfma${mode}.err"
     python - <<PY
 import json

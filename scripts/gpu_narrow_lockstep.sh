@@ -4,7 +4,7 @@
 # Usage: gpurun --timeout 900 -- 'bash scripts/gpu_narrow_lockstep.sh r04'
 TAG=${1:-r04}
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
-B() { timeout 300 python bench.py --no-cpu-baseline --no-secondary --steps 20 --warmup 5 --profile-steps 5 "$@"; }
+B() { timeout 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 20 --warmup 5 --profile-steps 5 "$@"; }
 show() { python - "$1" <<'PY'
 import json, sys
 try:

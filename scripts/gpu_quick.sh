@@ -4,7 +4,7 @@ TAG=${1:-q}; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2>&1
 timeout 900 python -m pytest tests -m gpu -q > "$OUT/pytest_gpu.log" 2>&1; tail -4 "$OUT/pytest_gpu.log"; grep -E "^E  .*mismatch|Error" "$OUT/pytest_gpu.log" | head -10
-timeout 600 python bench.py --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -2 "$OUT/bench.err"
+timeout 600 python bench.py --full --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -2 "$OUT/bench.err"
 python - <<PY
 import json
 d=json.load(open("$OUT/bench.json"))

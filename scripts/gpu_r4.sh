@@ -7,7 +7,7 @@ python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2
 if [ -n "$KEXPR" ]; then timeout 1500 python -m pytest tests -m gpu -q -x -s -k "$KEXPR" > "$OUT/pytest_gpu.log" 2>&1
 else timeout 1500 python -m pytest tests -m gpu -q -s > "$OUT/pytest_gpu.log" 2>&1; fi
 tail -4 "$OUT/pytest_gpu.log"; grep -E "^E  |FAILED|drop-in|ragged configs|configs\[4\]" "$OUT/pytest_gpu.log" | head -20
-timeout 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -2 "$OUT/bench_default.err" | grep -v amdgpu
+timeout 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -2 "$OUT/bench_default.err" | grep -v amdgpu
 python - "$OUT/bench_default.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -18,7 +18,7 @@ for k in ("secondary", "secondary_f32"):
     if s: print(k, s["value"], s["ms_per_step"], {a: b["ms_per_step"] for a, b in (s.get("kernels") or {}).items()})
 print("cpu_baseline", d["cpu_baseline"]["value"] if d.get("cpu_baseline") else None, "dtype:", d["dtype"][:60])
 PY
-timeout 300 python bench.py --config b2 --steps 5 --warmup 2 --profile-steps 2 > "$OUT/bench_b2_f32.json" 2>/dev/null
+timeout 300 python bench.py --full --config b2 --steps 5 --warmup 2 --profile-steps 2 > "$OUT/bench_b2_f32.json" 2>/dev/null
 python - "$OUT/bench_b2_f32.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

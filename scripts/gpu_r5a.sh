@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mk
 python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2>&1
 timeout 300 python scripts/gpu_gemm_r5.py 5 > "$OUT/gemm_r5.txt" 2>&1; cat "$OUT/gemm_r5.txt" | tail -12
 for st in 0 1; do
-  CLSTM_DEBUG=gemm_stag=$st timeout 200 python bench.py --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/bench_b2_bf16_stag$st.json" 2>/dev/null
+  CLSTM_DEBUG=gemm_stag=$st timeout 200 python bench.py --full --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/bench_b2_bf16_stag$st.json" 2>/dev/null
   python - "$OUT/bench_b2_bf16_stag$st.json" $st <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -16,7 +16,7 @@ PY
 done
 timeout 900 python -m pytest tests -m gpu -q -x -s -k "distributed or intrinsics or three_minibatch or 256_lines or two_minibatch or placement_fallback or test_states_and_step" > "$OUT/pytest_gpu_sel.log" 2>&1
 tail -4 "$OUT/pytest_gpu_sel.log"; grep -E "^E  |FAILED|Error" "$OUT/pytest_gpu_sel.log" | head -20
-timeout 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -2 "$OUT/bench_default.err" | grep -v amdgpu
+timeout 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -2 "$OUT/bench_default.err" | grep -v amdgpu
 python - "$OUT/bench_default.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/$TAG"; mk
 python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2>&1
 CLSTM_HIP_VARIANT=gprof timeout 300 python scripts/gpu_gemmprof_r5.py > "$OUT/gemmprof.txt" 2>&1; tail -32 "$OUT/gemmprof.txt"
 timeout 300 python scripts/gpu_gemm_r5.py 5 > "$OUT/gemm_r5.txt" 2>&1; tail -10 "$OUT/gemm_r5.txt"
-timeout 200 python bench.py --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/bench_b2_bf16.json" 2>/dev/null
+timeout 200 python bench.py --full --config b2 --bf16 --steps 10 --warmup 3 --profile-steps 3 > "$OUT/bench_b2_bf16.json" 2>/dev/null
 python - "$OUT/bench_b2_bf16.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

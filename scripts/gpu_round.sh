@@ -16,7 +16,7 @@ tail -3 "$OUT/pytest_gpu.log"
 echo "=== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log"
 
-B() { timeout 600 python bench.py "$@"; }
+B() { timeout 600 python bench.py --full "$@"; }
 echo "=== bench (default = minibatch 64, T=200)"
 B > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; cut -c1-400 "$OUT/bench_default.json"; tail -2 "$OUT/bench_default.err" | grep -v amdgpu
 B --weights trained --no-cpu-baseline --no-secondary > "$OUT/bench_trained.json" 2>/dev/null; cut -c1-220 "$OUT/bench_trained.json"

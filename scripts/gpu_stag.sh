@@ -6,7 +6,7 @@ python -c "from oracle.oracle import build; build()" > "$OUT/oracle_build.log" 2
 timeout 900 python -m pytest tests -m gpu -q -x -k "$SEL" > "$OUT/pytest.log" 2>&1; tail -3 "$OUT/pytest.log"; grep -E "^E  " "$OUT/pytest.log" | head -10
 CLSTM_OVERLAP=0 timeout 300 python scripts/gpu_width_sweep.py 2>&1 | grep -v amdgpu.ids | tee "$OUT/width_sweep.txt"
 for extra in "" "--ragged"; do
-timeout 600 python bench.py --no-cpu-baseline --no-secondary $extra > "$OUT/bench$extra.json" 2> "$OUT/bench$extra.err"; tail -2 "$OUT/bench$extra.err" | grep -v amdgpu
+timeout 600 python bench.py --full --no-cpu-baseline --no-secondary $extra > "$OUT/bench$extra.json" 2> "$OUT/bench$extra.err"; tail -2 "$OUT/bench$extra.err" | grep -v amdgpu
 python - <<PY
 import json
 d = json.load(open("$OUT/bench$extra.json"))

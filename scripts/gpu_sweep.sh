@@ -1,7 +1,7 @@
 #!/bin/bash
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd "$ROOT"; OUT="$ROOT/gpurun_out/sweep"; mkdir -p "$OUT"
 for V in "$@"; do
-  env $SWEEP_VAR=$V timeout 300 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > "$OUT/b_$V.json" 2>/dev/null
+  env $SWEEP_VAR=$V timeout 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > "$OUT/b_$V.json" 2>/dev/null
   python - <<PY
 import json
 d=json.load(open("$OUT/b_$V.json"))

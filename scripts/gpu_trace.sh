@@ -3,7 +3,7 @@
 TAG=${1:-tr}; ROOT=${GRAFT_REPO_ROOT:-/root/repo}; OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
 for OV in 0 1; do
-  CLSTM_OVERLAP=$OV timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace_ov$OV" -o t -- python "$ROOT/bench.py" --steps 6 --warmup 3 --no-cpu-baseline --profile-steps 0 > "$OUT/trace_ov$OV.log" 2>&1
+  CLSTM_OVERLAP=$OV timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace_ov$OV" -o t -- python "$ROOT/bench.py" --full --steps 6 --warmup 3 --no-cpu-baseline --profile-steps 0 > "$OUT/trace_ov$OV.log" 2>&1
   tail -1 "$OUT/trace_ov$OV.log" | cut -c1-200
   F=$(find "$OUT/trace_ov$OV" -name "*kernel_trace.csv" | head -1)
   python - "$F" "$OUT/timeline_ov$OV.txt" <<'PY'

@@ -10,7 +10,7 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout 900 python -m pytest tests -m gpu -q -x > "$OUT/pytest_gpu.log" 2>&1; grep -E "passed|failed" "$OUT/pytest_gpu.log" | tail -2; grep -E "^E  .*mismatch|Error|FAILED" "$OUT/pytest_gpu.log" | head -10
 fi
 for V in "" "$@"; do
-  CLSTM_HIP_VARIANT=$V timeout 300 python bench.py --no-cpu-baseline $BENCH_ARGS > "$OUT/bench_${V:-base}.json" 2> "$OUT/bench_${V:-base}.err"; tail -2 "$OUT/bench_${V:-base}.err" | grep -v amdgpu.ids
+  CLSTM_HIP_VARIANT=$V timeout 300 python bench.py --full --no-cpu-baseline $BENCH_ARGS > "$OUT/bench_${V:-base}.json" 2> "$OUT/bench_${V:-base}.err"; tail -2 "$OUT/bench_${V:-base}.err" | grep -v amdgpu.ids
   python - <<PY
 import json
 try:

@@ -23,7 +23,7 @@ def test_bench_rank_body_world2_on_the_emulator(how):
                OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--minibatch", "2", "--T", "6", "--profile-steps", "2", "--no-cpu-baseline"]
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--minibatch", "2", "--T", "6", "--profile-steps", "2", "--no-cpu-baseline", "--full"]
     if how == "self_relaunch":      # the plain command: the script becomes the launcher
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
     else:                           # the driver's command line
@@ -80,6 +80,96 @@ def test_bench_refuses_steps_whose_updates_were_skipped():
         w.verify()
 
 
+def _bench_line(args, env, timeout):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True,
+                       timeout=timeout, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+FULL_ONLY = ("roofline", "cpu_baseline", "host_enqueue_ms_per_step", "trained_weights", "ctc_float_logadd", "strict_f32", "saturated",
+             "large_minibatch", "secondary", "secondary_f32")
+
+
+def test_bench_plain_line_steps_and_dump_on_the_emulator(tmp_path):
+    """The plain command measures the headline only, and its step count is the arguments' alone: warm-up W + timed K steps
+    leave the same parameters and momentum buffer (--dump-outputs) as any other split of W + K, bit for bit on the
+    emulator, and one step more does not."""
+    import numpy as np
+    from common import EMU_DIR, emu_lib
+    emu_lib()
+    env = dict(os.environ, CLSTM_BENCH_DEVICE="cpu", CLSTM_BENCH_LIB=os.path.join(EMU_DIR, "build", "libclstm_emu.so"), OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = {}
+    for steps, warmup in ((2, 1), (1, 2), (2, 2)):
+        d = tmp_path / ("s%d_w%d" % (steps, warmup))
+        out = _bench_line(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--minibatch", "2", "--T", "6",
+                           "--dump-outputs", str(d)], env, 900)
+        assert out["steps"] == steps and out["warmup"] == warmup and out["repeats"] == 1 and out["unit"] == "lines/s"
+        assert abs(out["value"] - 2 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-2
+        assert abs(out["timing"]["block_ms"] - steps * out["ms_per_step"]) < 1e-2 * out["timing"]["block_ms"]
+        assert all(out[k] is None for k in FULL_ONLY) and out["kernels"] == {} and out["timing"]["full"] is False
+        assert out["validity"]["max_param_change"] > 0
+        assert out["outputs_dumped"] == {"params": 135883, "momentum": 135883}
+        dumps[(steps, warmup)] = [np.load(str(d / (n + ".npy"))) for n in ("params", "momentum")]
+        assert all(a.dtype == np.float32 and a.shape == (135883,) and np.isfinite(a).all() for a in dumps[(steps, warmup)])
+    for a, b, c in zip(dumps[(2, 1)], dumps[(1, 2)], dumps[(2, 2)]):
+        assert np.array_equal(a, b) and not np.array_equal(a, c)
+
+
+def test_bench_dump_samples_large_arrays_at_fixed_indices(tmp_path):
+    """configs[4] has 8.7M parameters: each dumped array above bench.MAX_DUMP_ELEMENTS is the sample at the same seeded,
+    ascending indices in every run, so two builds' dumps stay comparable element for element (and under 64 MB in all)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Net:
+        def __init__(self, n):
+            self.p = np.arange(n, dtype=np.float32)
+
+        def get_params(self):
+            return self.p
+
+        def get_derivs(self):
+            return -self.p
+
+    w = bench.Workload.__new__(bench.Workload)
+    n = bench.MAX_DUMP_ELEMENTS + 12345
+    w.net = Net(n)
+    assert bench.dump_outputs(w, str(tmp_path / "a")) == {"params": bench.MAX_DUMP_ELEMENTS, "momentum": bench.MAX_DUMP_ELEMENTS}
+    bench.dump_outputs(w, str(tmp_path / "b"))
+    a, m = np.load(str(tmp_path / "a" / "params.npy")), np.load(str(tmp_path / "a" / "momentum.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, np.load(str(tmp_path / "b" / "params.npy")))
+    assert np.array_equal(m, -a) and (np.diff(a) > 0).all() and a[-1] < n     # the same indices for both arrays, ascending
+    assert 2 * 4 * bench.MAX_DUMP_ELEMENTS <= 64 << 20
+    w.net = Net(10)                                            # small arrays: whole
+    bench.dump_outputs(w, str(tmp_path / "c"))
+    assert np.array_equal(np.load(str(tmp_path / "c" / "params.npy")), np.arange(10, dtype=np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump_on_one_gpu(tmp_path):
+    """The plain command on one GPU: the headline fields, nothing of --full, and the dump of the last timed step."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = _bench_line(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)], env, 300)
+    assert out["metric"].startswith("text-line images/sec") and out["unit"] == "lines/s" and out["higher_is_better"] is True
+    assert out["steps"] == 20 and out["warmup"] == 5 and out["repeats"] == 1 and out["dtype"].startswith("f32")
+    assert abs(out["value"] - 64 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-2
+    assert all(out[k] is None for k in FULL_ONLY) and out["kernels"] == {}
+    v = out["validity"]
+    assert v["device_errors"] == "none" and v["params_finite"] is True and v["max_param_change"] > 0
+    for n in ("params", "momentum"):
+        a = np.load(str(tmp_path / (n + ".npy")))
+        assert a.dtype == np.float32 and a.shape == (135883,) and np.isfinite(a).all() and np.abs(a).max() > 0
+
+
 @pytest.mark.gpu
 def test_bench_gpus2_on_the_real_library_sharing_one_gpu():
     """the `--gpus 2` bench body on the REAL library before the driver's first multi-GPU run.  Two rank processes
@@ -95,7 +185,7 @@ def test_bench_gpus2_on_the_real_library_sharing_one_gpu():
                CLSTM_BENCH_MIN_TIMED_S="0.2", CLSTM_BENCH_MIN_WARMUP_S="0.1", CLSTM_REPLICA_CHECK_EVERY="2")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CLSTM_BENCH_DEVICE", "CLSTM_BENCH_LIB"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -120,7 +210,8 @@ def test_bench_line_contract_on_one_gpu():
     env = dict(os.environ, CLSTM_BENCH_MIN_TIMED_S="0.2", CLSTM_BENCH_MIN_WARMUP_S="0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-secondary",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

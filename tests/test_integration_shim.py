@@ -70,19 +70,17 @@ def test_literal_per_operator_drop_in_rate_on_the_gpu():
 
 
 # ---- the reference's OWN drivers over the fused-level INetwork adapter (integration/inetwork/) ------------------------------
-REF = "/root/reference"
-REFBIN = os.path.join(INTEG, "_ref")
+REFBIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _build_drop_in():
-    """integration/Makefile ref_drop_in: clstmocrtrain.cc, clstmocr.cc, clstmhl.h, extras.h, utils.h, pstring.h compiled
-    UNMODIFIED from /root/reference (a directory of symbolic links shadows only clstm.h and tensor.h).  The reference tree
-    exists in the build container only: on the GPU box the prebuilt binaries under integration/_ref/ are used as shipped."""
-    if os.path.isdir(REF):
-        subprocess.check_call(["make", "-C", INTEG, "-s", "ref_drop_in"])
+    """`make -C oracle ref` (integration/Makefile ref_drop_in): clstmocrtrain.cc, clstmocr.cc, clstmhl.h, extras.h, utils.h,
+    pstring.h compiled UNMODIFIED from the reference tree (a directory of symbolic links shadows only clstm.h and tensor.h).
+    Where that tree is absent the binaries that __graft_entry__.build() left under oracle/_ref/ are used as they are."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
     for name in ("clstmocrtrain_emu", "clstmocr_emu", "clstmocrtrain_hip", "clstmocr_hip"):
         if not os.path.exists(os.path.join(REFBIN, name)):
-            pytest.skip("integration/_ref/%s not built (needs /root/reference at build time: __graft_entry__.build())" % name)
+            pytest.skip("oracle/_ref/%s not built (needs the reference tree at build time: __graft_entry__.build())" % name)
 
 
 def test_reference_drivers_unmodified_over_the_inetwork_adapter_on_the_emulator(tmp_path):
