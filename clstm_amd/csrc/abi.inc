@@ -395,7 +395,6 @@ int clstm_net_train_step_next(clstm_net* h, const int* T_h, int bs, const float*
         IngestTail t{};
         t.x = xn_d; t.X = n.X.p; t.S = y.S.p; t.N = (unsigned long long)n.N; t.ni = y.ni; t.lds = y.lds; t.ndir = n.ndir; t.sdir = (long long)n.N * y.lds;
         t.nbi = nblocks(vec16 ? (size_t)n.N * (y.ni / 4 + 1) : (size_t)n.N * (1 + y.ni));
-        if (const int cap = dbg_opt("tail_nbi", 0)) t.nbi = std::min(t.nbi, std::max(1, cap));   // (experiment: fewer, longer ingest workgroups behind the reduction's)
         t.lo_src = n.lo_pending ? n.lo_stage : nullptr; t.lo_dst = n.line_off.p; t.lo_n = 2 * n.bs + 1;
         t.aux_src = meta.nwords > 0 ? meta.src : nullptr; t.aux_dst = meta.dst; t.aux_n = meta.nwords;
         n.launch_deferred_reduce(&t);
@@ -723,11 +722,11 @@ int clstm_net_set_overlap(clstm_net* h, int mode) {
 int clstm_net_set_strict_f32(clstm_net* h, int on) {
   ABI_BEGIN
   Net& n = h->net;
-  if (on) { n.dw_x3 = 0; n.gemm_x3_on = false; }
+  if (on) { n.dw_x3 = false; n.gemm_x3_on = false; }
   else {
-    n.dw_x3 = dbg_opt("dw_x3", 1);
-    n.gemm_x3_on = dbg_opt("gemm_x3", 1) != 0;
-    n.split_terms = dbg_opt("split_terms", 3);
+    n.dw_x3 = dbg_opt("dw_x3") != 0;
+    n.gemm_x3_on = dbg_opt("gemm_x3") != 0;
+    n.split_terms = dbg_opt("split_terms");
   }
   n.packed_dirty = true;   // (the hi | lo weights of the f32-grade backward recurrence are only packed while that mode is on)
   ABI_END
@@ -792,7 +791,12 @@ int clstm_debug_set_device_error(int which, int value) {   // tests: what a fail
 int clstm_debug_set_option(const char* name, int value) {   // experiment switches (dbgopt.h); name NULL: forget every option set so far
   ABI_BEGIN
   HIPCHECK(hipStreamSynchronize(g_stream));
-  if (!name) dbg_opts().clear(); else dbg_opts()[name] = value;
+  if (!name) {
+    dbg_opts().clear();
+  } else {
+    REQUIRE(dbg_opt_def(name), std::string("unknown option '") + name + "' (clstm_amd/csrc/dbgopt.h lists them)");
+    dbg_opts()[name] = value;
+  }
   ABI_END
 }
 int clstm_debug_path_count(int which, long long* out_h) {
@@ -801,14 +805,6 @@ int clstm_debug_path_count(int which, long long* out_h) {
   *out_h = g_path_count[which];
   ABI_END
 }
-#ifdef CLSTM_GEMM_PROF
-int clstm_debug_gemm_prof(long long* out_h) {   // diagnostics build only (not in the product ABI)
-  ABI_BEGIN
-  HIPCHECK(hipStreamSynchronize(g_stream));
-  HIPCHECK(hipMemcpyFromSymbol(out_h, HIP_SYMBOL(clstm_gemm_prof), 16 * sizeof(long long)));
-  ABI_END
-}
-#endif
 int clstm_debug_lane_ops(float* out) {
   ABI_BEGIN
   CLSTM_LAUNCH(k_debug_lane_ops, dim3(1), dim3(64), 0, g_stream, out);
@@ -842,7 +838,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* Cm, int R,
                StorePlain{Cm, Cn}, R, Cn, K, 2);
   } else if (mode == 30 || mode == 31) {   // A: [R][K] bf16, B: [Cn][K] bf16 (the caller passes halfs in float-typed pointers); 31: the one-barrier loop
     gemm_b16kk(g_stream, GemmOperand16{(const unsigned short*)A, K, (long long)R * K}, GemmOperand16{(const unsigned short*)B, K, (long long)Cn * K},
-               StorePlain{Cm, Cn}, R, Cn, K, mode == 31 ? 0 : 1 | (nsplit > 1 ? nsplit << 4 : 0));   // (diagnostics build: nsplit = leave-out bits)
+               StorePlain{Cm, Cn}, R, Cn, K, mode == 31 ? 0 : 1);
   } else if (mode == 32 || mode == 33 || mode == 35) {   // A: [K][R] bf16, B: [K][Cn] bf16 (R, Cn multiples of 8), split-K slabs reduced afterwards; 33: the one-barrier loop
     if (!part) part = new DevBuf<float>();
     if (nsplit < 1) nsplit = 1;

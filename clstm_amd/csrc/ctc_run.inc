@@ -58,7 +58,7 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   a.states = (const int*)(w.meta.p + nln);
   a.lat = w.lat.p; a.nc = nc;
   w.prof.reserve(16); a.prof = w.prof.p; g_last_ctc_prof = w.prof.p;
-  a.float_logadd = dbg_opt("ctc_float", 0) != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
+  a.float_logadd = dbg_opt("ctc_float") != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
   if (!w.tables.p) {
     w.tables.reserve(CTC_TABLE_DOUBLES);
     std::vector<double> tb(CTC_TABLE_DOUBLES);

@@ -190,7 +190,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128_kernel(GemmOperand A, Ge
                                                                int K, int ksplit, int nsplit) {
   __shared__ __attribute__((aligned(16))) unsigned short As[2 * GB2_TILE];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[2 * GB2_TILE];
-  constexpr bool COAL = false;   // (the row-per-load mapping of gemm_x3_128_kernel is not built for this kernel)
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -211,17 +210,17 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128_kernel(GemmOperand A, Ge
   const int kbeg = (z - batch * nsplit) * ksplit;
   const int kend = (kbeg + ksplit < K) ? kbeg + ksplit : K;
 
-  const int a_mn = AMODE == GEMM_KC ? (COAL ? (tid >> 3) : (tid >> 1)) : wave * 32 + (lane & 7) * 4;
-  const int a_k = AMODE == GEMM_KC ? (COAL ? (tid & 7) * 4 : (tid & 1) * 16) : (lane >> 3) * 4;
-  const int b_mn = BMODE == GEMM_KC ? (COAL ? (tid >> 3) : (tid >> 1)) : wave * 32 + (lane & 7) * 4;
-  const int b_k = BMODE == GEMM_KC ? (COAL ? (tid & 7) * 4 : (tid & 1) * 16) : (lane >> 3) * 4;
+  const int a_mn = AMODE == GEMM_KC ? (tid >> 1) : wave * 32 + (lane & 7) * 4;
+  const int a_k = AMODE == GEMM_KC ? (tid & 1) * 16 : (lane >> 3) * 4;
+  const int b_mn = BMODE == GEMM_KC ? (tid >> 1) : wave * 32 + (lane & 7) * 4;
+  const int b_k = BMODE == GEMM_KC ? (tid & 1) * 16 : (lane >> 3) * 4;
   const BufF32 abuf = make_buf(A.p + batch * A.bstride, (size_t)(A.elems - batch * A.bstride) * 4);
   const BufF32 bbuf = make_buf(B.p + batch * B.bstride, (size_t)(B.elems - batch * B.bstride) * 4);
   const unsigned a_base = AMODE == GEMM_KC ? (unsigned)(r0 + a_mn) * A.ld + a_k : (unsigned)a_k * A.ld + r0 + a_mn;
   const unsigned b_base = BMODE == GEMM_KC ? (unsigned)(c0 + b_mn) * B.ld + b_k : (unsigned)b_k * B.ld + c0 + b_mn;
   const unsigned a_kstep = AMODE == GEMM_KC ? 1u : (unsigned)A.ld, b_kstep = BMODE == GEMM_KC ? 1u : (unsigned)B.ld;
-  const unsigned a_next = AMODE == GEMM_KC ? (COAL ? 32u * (unsigned)A.ld : 4u) : (unsigned)A.ld;   // load j: 32 rows on / 4 k on / 1 k row on
-  const unsigned b_next = BMODE == GEMM_KC ? (COAL ? 32u * (unsigned)B.ld : 4u) : (unsigned)B.ld;
+  const unsigned a_next = AMODE == GEMM_KC ? 4u : (unsigned)A.ld;   // load j: 4 k on / 1 k row on
+  const unsigned b_next = BMODE == GEMM_KC ? 4u : (unsigned)B.ld;
 
   // Block addresses: per-lane byte offsets of the four float4 (fixed) + the block's offset (one add per load, the sum
   // stays inside the descriptor's bounds check).  Blocks past the slab re-read its last block (their products are
@@ -337,10 +336,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128_kernel(GemmOperand A, Ge
 // Their f32-MFMA form runs near its own roof (96-114 TFLOP/s of 157) and was 6.5 of the 15.2 ms of a configs[4] step; three
 // bf16 MFMAs of 16 cycles replace eight f32 MFMAs of 32.)  Each operand block lives in LDS as a hi and a lo image
 // (4 x 8 KB per buffer, two buffers = 64 KB: one workgroup per CU by LDS... two by registers).
-// COAL (k-contiguous operands): a thread's four 16-byte loads of a block are four ROWS, eight neighbouring lanes covering 128
-// contiguous bytes of one row -- the address pipeline takes a 16-byte access of a lane that has no neighbour as a request of its
-// own, and the older form (a thread = 64 contiguous bytes of one row, neighbouring lanes 64 bytes apart) issued 64 per instruction.
-// ILV: the conversion of block t + 1 (VALU + LDS writes into the other buffer) and the loads of block t + 4 are issued BETWEEN the 48
+// k-contiguous operands: a thread's four 16-byte loads of a block are four ROWS, eight neighbouring lanes covering 128 contiguous
+// bytes of one row -- the address pipeline takes a 16-byte access of a lane that has no neighbour as a request of its own, and the
+// older form (a thread = 64 contiguous bytes of one row, neighbouring lanes 64 bytes apart) issued 64 per instruction.
+// The conversion of block t + 1 (VALU + LDS writes into the other buffer) and the loads of block t + 4 are issued BETWEEN the 48
 // MFMAs of block t (sched_group_barrier pattern) instead of in front of them: a workgroup is four waves, one per SIMD, and a wave
 // issues in order -- staged first, its ~130 conversion instructions (4 cycles each) and its MFMAs (16 cycles each) ran one after
 // the other.
@@ -349,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128_kernel(GemmOperand A, Ge
 #else
 #define GX3_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 #endif
-template <int AMODE, int BMODE, class FE, bool COAL = true, bool ILV = true>
+template <int AMODE, int BMODE, class FE>
 __global__ __launch_bounds__(256, 2) void gemm_x3_128_kernel(GemmOperand A, GemmOperand B, FE fe, int R, int Cn,
                                                              int K, int ksplit, int nsplit) {
   unsigned short* const x3_smem = dyn_smem<unsigned short>();   // [A hi | A lo | B hi | B lo] x 2 buffers
@@ -375,17 +374,17 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_128_kernel(GemmOperand A, Gemm
   const int kbeg = (z - batch * nsplit) * ksplit;
   const int kend = (kbeg + ksplit < K) ? kbeg + ksplit : K;
 
-  const int a_mn = AMODE == GEMM_KC ? (COAL ? (tid >> 3) : (tid >> 1)) : wave * 32 + (lane & 7) * 4;
-  const int a_k = AMODE == GEMM_KC ? (COAL ? (tid & 7) * 4 : (tid & 1) * 16) : (lane >> 3) * 4;
-  const int b_mn = BMODE == GEMM_KC ? (COAL ? (tid >> 3) : (tid >> 1)) : wave * 32 + (lane & 7) * 4;
-  const int b_k = BMODE == GEMM_KC ? (COAL ? (tid & 7) * 4 : (tid & 1) * 16) : (lane >> 3) * 4;
+  const int a_mn = AMODE == GEMM_KC ? (tid >> 3) : wave * 32 + (lane & 7) * 4;
+  const int a_k = AMODE == GEMM_KC ? (tid & 7) * 4 : (lane >> 3) * 4;
+  const int b_mn = BMODE == GEMM_KC ? (tid >> 3) : wave * 32 + (lane & 7) * 4;
+  const int b_k = BMODE == GEMM_KC ? (tid & 7) * 4 : (lane >> 3) * 4;
   const BufF32 abuf = make_buf(A.p + batch * A.bstride, (size_t)(A.elems - batch * A.bstride) * 4);
   const BufF32 bbuf = make_buf(B.p + batch * B.bstride, (size_t)(B.elems - batch * B.bstride) * 4);
   const unsigned a_base = AMODE == GEMM_KC ? (unsigned)(r0 + a_mn) * A.ld + a_k : (unsigned)a_k * A.ld + r0 + a_mn;
   const unsigned b_base = BMODE == GEMM_KC ? (unsigned)(c0 + b_mn) * B.ld + b_k : (unsigned)b_k * B.ld + c0 + b_mn;
   const unsigned a_kstep = AMODE == GEMM_KC ? 1u : (unsigned)A.ld, b_kstep = BMODE == GEMM_KC ? 1u : (unsigned)B.ld;
-  const unsigned a_next = AMODE == GEMM_KC ? (COAL ? 32u * (unsigned)A.ld : 4u) : (unsigned)A.ld;   // load j: 32 rows on / 4 k on / 1 k row on
-  const unsigned b_next = BMODE == GEMM_KC ? (COAL ? 32u * (unsigned)B.ld : 4u) : (unsigned)B.ld;
+  const unsigned a_next = AMODE == GEMM_KC ? 32u * (unsigned)A.ld : (unsigned)A.ld;   // load j: 32 rows on / 1 k row on
+  const unsigned b_next = BMODE == GEMM_KC ? 32u * (unsigned)B.ld : (unsigned)B.ld;
 
   // Block addresses: per-lane byte offsets of the four float4 (fixed) + the block's offset (one add per load, the sum
   // stays inside the descriptor's bounds check).  Blocks past the slab re-read its last block (their products are
@@ -410,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_128_kernel(GemmOperand A, Gemm
   // zero blocks behind it) mask contraction indices >= kend per element (one wave-uniform branch per block).
   auto stage = [&](const int MODE, unsigned short* S, const int mn, const int kk, const int k0, const f32x4 (&r)[4]) {
     const bool whole = wave_uniform(k0 + GB_BK <= kend ? 1 : 0) != 0;
-    if (MODE == GEMM_KC && COAL) {
+    if (MODE == GEMM_KC) {
 #pragma unroll
       for (int j = 0; j < 4; j++) {   // row mn + 32 j, contraction indices kk .. kk + 3
         f32x4 v = r[j];
@@ -427,25 +426,6 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_128_kernel(GemmOperand A, Gemm
         const int at = row * GB2_LDH + (((kk >> 3) ^ gb2_sw(row)) << 3) + (kk & 4);
         *reinterpret_cast<u32x2*>(&S[at]) = w2;
         *reinterpret_cast<u32x2*>(&S[at + 2 * GB2_TILE]) = l2;
-      }
-    } else if (MODE == GEMM_KC) {
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        float x[8];
-        if (whole) {
-#pragma unroll
-          for (int i = 0; i < 8; i++) x[i] = r[2 * h + (i >> 2)][i & 3];
-        } else {
-#pragma unroll
-          for (int i = 0; i < 8; i++) x[i] = (k0 + kk + 8 * h + i < kend) ? r[2 * h + (i >> 2)][i & 3] : 0.0f;
-        }
-        const u16x8 hi = bf16_pack8(x);
-        float y[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) y[i] = x[i] - __builtin_bit_cast(float, (unsigned)hi[i] << 16);   // exact
-        const int at = mn * GB2_LDH + ((((kk >> 3) + h) ^ gb2_sw(mn)) << 3);
-        *reinterpret_cast<u16x8*>(&S[at]) = hi;
-        *reinterpret_cast<u16x8*>(&S[at + 2 * GB2_TILE]) = bf16_pack8(y);
       }
     } else {
       f32x4 v[4];
@@ -498,70 +478,45 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_128_kernel(GemmOperand A, Gemm
     for (int p = 0; p < GB2_PF; p++) {
       const int k0 = kb + p * GB_BK;   // block in LDS buffer `cur` (phases past the slab multiply zeros)
       constexpr int pn_of[3] = {1, 2, 0};
-      const int pn = pn_of[p];         // register set of block k0 + 32: convert it into the other buffer ...
-      if (!ILV) {
-      stage(AMODE, As + (cur ^ GB2_TILE), a_mn, a_k, k0 + GB_BK, ra[pn]);
-      stage(BMODE, Bs + (cur ^ GB2_TILE), b_mn, b_k, k0 + GB_BK, rb[pn]);
-      load_tile(k0 + GB_BK + GB2_PF * GB_BK, ra[pn], rb[pn]);   // ... and re-use the set for the block three ahead
-      SCHED_FENCE();
+      const int pn = pn_of[p];         // register set of block k0 + 32: converted into the other buffer between the MFMAs
+      // two halves of 24 MFMAs (A row tiles 0-1, then 2-3: 48 instead of 64 fragment registers live), the A conversion between the
+      // MFMAs of the first, the B conversion and the loads between those of the second
+      u16x8 bf[4], bl[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        bf[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
+        bl[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + 2 * GB2_TILE + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
       }
-      if (!ILV) {
-        u16x8 af[4], bf[4], al[4], bl[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          af[i] = *reinterpret_cast<const u16x8*>(&As[cur + (wm * 64 + i * 16 + fi) * GB2_LDH + fsw]);
-          bf[i] = *reinterpret_cast<const u16x8*>(&Bs[cur + (wn * 64 + i * 16 + fi) * GB2_LDH + fsw]);
-          al[i] = *reinterpret_cast<const u16x8*>(&As[cur + 2 * GB2_TILE + (wm * 64 + i * 16 + fi) * GB2_LDH + fsw]);
-          bl[i] = *reinterpret_cast<const u16x8*>(&Bs[cur + 2 * GB2_TILE + (wn * 64 + i * 16 + fi) * GB2_LDH + fsw]);
+      for (int hf = 0; hf < 2; hf++) {
+        u16x8 af[2], al[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          af[i] = *reinterpret_cast<const u16x8*>(&As[cur + (wm * 64 + (2 * hf + i) * 16 + fi) * GB2_LDH + fsw]);
+          al[i] = *reinterpret_cast<const u16x8*>(&As[cur + 2 * GB2_TILE + (wm * 64 + (2 * hf + i) * 16 + fi) * GB2_LDH + fsw]);
+        }
+        SCHED_FENCE();
+        if (hf == 0) stage(AMODE, As + (cur ^ GB2_TILE), a_mn, a_k, k0 + GB_BK, ra[pn]);
+        else {
+          stage(BMODE, Bs + (cur ^ GB2_TILE), b_mn, b_k, k0 + GB_BK, rb[pn]);
+          load_tile(k0 + GB_BK + GB2_PF * GB_BK, ra[pn], rb[pn]);
         }
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 2; i++)
 #pragma unroll
-          for (int j = 0; j < 4; j++) {   // small terms first (transposed: see gb2_store)
-            acc[i][j] = mfma16x16x32_bf16(bl[j], af[i], acc[i][j]);
-            acc[i][j] = mfma16x16x32_bf16(bf[j], al[i], acc[i][j]);
-            acc[i][j] = mfma16x16x32_bf16(bf[j], af[i], acc[i][j]);
+          for (int j = 0; j < 4; j++) {
+            acc[2 * hf + i][j] = mfma16x16x32_bf16(bl[j], af[i], acc[2 * hf + i][j]);
+            acc[2 * hf + i][j] = mfma16x16x32_bf16(bf[j], al[i], acc[2 * hf + i][j]);
+            acc[2 * hf + i][j] = mfma16x16x32_bf16(bf[j], af[i], acc[2 * hf + i][j]);
           }
-      } else {
-        // two halves of 24 MFMAs (A row tiles 0-1, then 2-3: 48 instead of 64 fragment registers live), the A conversion between the
-        // MFMAs of the first, the B conversion and the loads between those of the second
-        u16x8 bf[4], bl[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-          bf[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
-          bl[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + 2 * GB2_TILE + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
+        for (int q = 0; q < 24; q++) {   // one MFMA, three conversion instructions; an LDS write every third, a load every third of the second half
+          GX3_SGB(0x008, 1);
+          GX3_SGB(0x002, 3);
+          if (q % 3 == 0) GX3_SGB(0x200, 1);
+          if (hf == 1 && q % 3 == 1) GX3_SGB(0x020, 1);
         }
-#pragma unroll
-        for (int hf = 0; hf < 2; hf++) {
-          u16x8 af[2], al[2];
-#pragma unroll
-          for (int i = 0; i < 2; i++) {
-            af[i] = *reinterpret_cast<const u16x8*>(&As[cur + (wm * 64 + (2 * hf + i) * 16 + fi) * GB2_LDH + fsw]);
-            al[i] = *reinterpret_cast<const u16x8*>(&As[cur + 2 * GB2_TILE + (wm * 64 + (2 * hf + i) * 16 + fi) * GB2_LDH + fsw]);
-          }
-          SCHED_FENCE();
-          if (hf == 0) stage(AMODE, As + (cur ^ GB2_TILE), a_mn, a_k, k0 + GB_BK, ra[pn]);
-          else {
-            stage(BMODE, Bs + (cur ^ GB2_TILE), b_mn, b_k, k0 + GB_BK, rb[pn]);
-            load_tile(k0 + GB_BK + GB2_PF * GB_BK, ra[pn], rb[pn]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              acc[2 * hf + i][j] = mfma16x16x32_bf16(bl[j], af[i], acc[2 * hf + i][j]);
-              acc[2 * hf + i][j] = mfma16x16x32_bf16(bf[j], al[i], acc[2 * hf + i][j]);
-              acc[2 * hf + i][j] = mfma16x16x32_bf16(bf[j], af[i], acc[2 * hf + i][j]);
-            }
-#pragma unroll
-          for (int q = 0; q < 24; q++) {   // one MFMA, three conversion instructions; an LDS write every third, a load every third of the second half
-            GX3_SGB(0x008, 1);
-            GX3_SGB(0x002, 3);
-            if (q % 3 == 0) GX3_SGB(0x200, 1);
-            if (hf == 1 && q % 3 == 1) GX3_SGB(0x020, 1);
-          }
-          SCHED_FENCE();
-        }
+        SCHED_FENCE();
       }
       __syncthreads();
       cur ^= GB2_TILE;
@@ -590,20 +545,7 @@ struct GemmOperand16 { const unsigned short* p; int ld; long long elems; };   //
 //   B:                       B [stage t+1 | frags t] B [MFMA t]             B ...
 // Block t+1's buffer is the one block t-1 lived in: its last reader was group B between the two barriers before group A's
 // stage of t+1 (reads are complete at a barrier: __syncthreads waits for lgkmcnt).
-#ifdef CLSTM_GEMM_PROF   // diagnostics build (make variant VARIANT=gprof EXTRA=-DCLSTM_GEMM_PROF; scripts/gpu_gemmprof_r5.py)
-// per-segment shader-clock sums of waves 0 and 4 of workgroup 0: [wave group][segment]; LO: parts of the loop left out
-__device__ long long clstm_gemm_prof[2 * 8];
-#define GPROF_DECL long long gp_t = 0, gp_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const bool gp_on = blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x & 255) == 0
-#define GPROF_TOP() do { if (gp_on) gp_t = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#define GPROF(i) do { if (gp_on) { const long long t_ = (long long)__builtin_amdgcn_s_memtime(); gp_s[i] += t_ - gp_t; gp_t = t_; } } while (0)
-#define GPROF_WRITE() do { if (gp_on) for (int i_ = 0; i_ < 8; i_++) clstm_gemm_prof[(threadIdx.x >> 8) * 8 + i_] = gp_s[i_]; } while (0)
-#else
-#define GPROF_DECL
-#define GPROF_TOP()
-#define GPROF(i)
-#define GPROF_WRITE()
-#endif
-template <class FE, int WI, bool STAG = false, int LO = 0>
+template <class FE, int WI, bool STAG = false>
 __global__ __launch_bounds__(64 * WI, 2) void gemm_b16kk_kernel(GemmOperand16 A, GemmOperand16 B, FE fe, int R, int Cn, int K) {
   static_assert(!STAG || WI == 8, "the staggered loop pairs the two waves of each SIMD of an eight-wave workgroup");
   constexpr int NWN = WI / 2, BT = 32 * WI, TILE = BT * GB2_LDH;
@@ -670,35 +612,21 @@ __global__ __launch_bounds__(64 * WI, 2) void gemm_b16kk_kernel(GemmOperand16 A,
   const int fk = lane >> 4, fi = lane & 15;
   const int fsw = (fk ^ gb2_sw(fi)) << 3;
   int cur = 0;
-  GPROF_DECL;
   u16x8 af[WI], bf[4];
-  if (LO & 8) {   // (diagnostics: fragments read once)
-#pragma unroll
-    for (int i = 0; i < WI; i++) af[i] = *reinterpret_cast<const u16x8*>(&As[(wm * (16 * WI) + i * 16 + fi) * GB2_LDH + fsw]);
-#pragma unroll
-    for (int j = 0; j < 4; j++) bf[j] = *reinterpret_cast<const u16x8*>(&Bs[(wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
-  }
   if (STAG && wm == 1) __syncthreads();   // group B runs one barrier behind group A (wave-uniform)
   for (int kb = 0; kb < K; kb += GB2_PF * GB_BK) {
 #pragma unroll
     for (int p = 0; p < GB2_PF; p++) {
       const int k0 = kb + p * GB_BK;
       const int pn = p == GB2_PF - 1 ? 0 : p + 1;
-      GPROF_TOP();
-      if (!(LO & 4)) {
-        stage(As + (cur ^ TILE), k0 + GB_BK, ra[pn]);
-        stage(Bs + (cur ^ TILE), k0 + GB_BK, rb[pn]);
-      }
-      GPROF(0);   // staged (incl. the wait for the block's loads)
-      if (!(LO & 2)) load_tile(k0 + GB_BK + GB2_PF * GB_BK, ra[pn], rb[pn]);
+      stage(As + (cur ^ TILE), k0 + GB_BK, ra[pn]);
+      stage(Bs + (cur ^ TILE), k0 + GB_BK, rb[pn]);
+      load_tile(k0 + GB_BK + GB2_PF * GB_BK, ra[pn], rb[pn]);
       SCHED_FENCE();
-      if (!(LO & 8)) {
 #pragma unroll
-        for (int i = 0; i < WI; i++) af[i] = *reinterpret_cast<const u16x8*>(&As[cur + (wm * (16 * WI) + i * 16 + fi) * GB2_LDH + fsw]);
+      for (int i = 0; i < WI; i++) af[i] = *reinterpret_cast<const u16x8*>(&As[cur + (wm * (16 * WI) + i * 16 + fi) * GB2_LDH + fsw]);
 #pragma unroll
-        for (int j = 0; j < 4; j++) bf[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
-      }
-      GPROF(1);   // loads + fragment reads issued
+      for (int j = 0; j < 4; j++) bf[j] = *reinterpret_cast<const u16x8*>(&Bs[cur + (wn * 64 + j * 16 + fi) * GB2_LDH + fsw]);
       if (STAG) {                          // ... the other group's MFMAs ran beside the staging and the reads above
         // (the fences pin the MFMAs BETWEEN the two barriers: they touch no memory, so nothing else keeps hipcc from issuing
         //  them in front of the first one as the fragments arrive -- which is the one-barrier loop again)
@@ -706,32 +634,21 @@ __global__ __launch_bounds__(64 * WI, 2) void gemm_b16kk_kernel(GemmOperand16 A,
         __syncthreads();
         SCHED_FENCE();
       }
-      GPROF(2);   // fragments arrived + barrier
-      if (LO & 1) {
-#pragma unroll
-        for (int i = 0; i < WI; i++) asm volatile("" ::"v"(af[i]));
-#pragma unroll
-        for (int j = 0; j < 4; j++) asm volatile("" ::"v"(bf[j]));
-      } else {
 #pragma unroll
       for (int i = 0; i < WI; i++)
 #pragma unroll
         for (int j = 0; j < 4; j++) acc[i][j] = mfma16x16x32_bf16(bf[j], af[i], acc[i][j]);   // transposed: see gb2_store
-      }
       if (STAG) SCHED_FENCE();
-      GPROF(3);   // MFMAs issued
       __syncthreads();
       if (STAG) SCHED_FENCE();
-      GPROF(4);   // barrier
       cur ^= TILE;
     }
   }
-  GPROF_WRITE();
   if (STAG && wm == 0) __syncthreads();   // (group A's epilogue stores run beside group B's last MFMAs)
   gb2_store<FE, WI>(fe, acc, r0 + wm * (16 * WI), c0 + wn * 64, lane, R, Cn, 0);
 }
 // ---- the same product with the operand tiles brought in by LDS-DMA (round 5) ----------------------------------------------
-// Phase stamps and leave-out builds of the staggered loop above (scripts/gpu_gemmprof_r5.py, profiles/r05_gemm_phases.txt): of the
+// Phase stamps and leave-out builds of the staggered loop above (profiles/r05_gemm_phases.txt; EXPERIMENTS.md): of the
 // ~1,950 cycles a 32-k block takes, ~500 are the four ds_write_b128 per thread that stage the next block (the VGPR -> LDS
 // transfer path: ~125 cycles per wave instruction beside the other group's MFMAs) and with them gone the kernel ran 37 % faster
 // (4096^3: 163 -> 103 us) -- more than without global loads (-13 %) or fragment reads (-18 %).  Here nothing is staged through
@@ -876,7 +793,7 @@ __global__ __launch_bounds__(512, 2) void gemm_b16kk_dma_kernel(GemmOperand16 A,
 }
 inline bool gemm_tile256(int R, int Cn);
 inline int gemm_stag_default() {   // experiment switch (dbgopt.h): 2 LDS-DMA tiles + staggered wave groups, 1 register-staged + staggered, 0 the one-barrier loop
-  return dbg_opt("gemm_stag", 2);
+  return dbg_opt("gemm_stag");
 }
 template <class FE>
 inline void gemm_b16kk(hipStream_t stream, GemmOperand16 A, GemmOperand16 B, FE fe, int R, int Cn, int K, int stag = -1) {
@@ -888,18 +805,6 @@ inline void gemm_b16kk(hipStream_t stream, GemmOperand16 A, GemmOperand16 B, FE 
       CLSTM_LAUNCH((gemm_b16kk_dma_kernel<FE>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K);
       return;
     }
-#ifdef CLSTM_GEMM_PROF
-    switch (stag >> 4) {   // (diagnostics: stag = 1 | leave-out bits << 4)
-      case 1: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 1>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      case 2: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 2>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      case 4: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 4>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      case 8: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 8>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      case 12: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 12>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      case 14: CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true, 14>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K); return;
-      default: break;
-    }
-    stag &= 1;
-#endif
     if (stag) CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, true>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K);
     else CLSTM_LAUNCH((gemm_b16kk_kernel<FE, 8, false>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K);
     return;
@@ -1556,30 +1461,6 @@ inline void gemm_x3_big(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe,
   }
 #endif
   dim3 grid((Cn + GB2_BT - 1) / GB2_BT, (R + GB2_BT - 1) / GB2_BT, nsplit * nbatch);
-  static const bool coal = dbg_opt("x3_coal", 1) != 0;   // (the older k-contiguous load mapping: 0)
-  if ((AMODE == GEMM_KC || BMODE == GEMM_KC) && !coal) {
-#ifndef CLSTM_HIP_EMU
-    static bool attr_set0 = false;
-    if (!attr_set0) {
-      (void)hipFuncSetAttribute((const void*)gemm_x3_128_kernel<AMODE, BMODE, FE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      attr_set0 = true;
-    }
-#endif
-    CLSTM_LAUNCH((gemm_x3_128_kernel<AMODE, BMODE, FE, false>), grid, dim3(256), smem, stream, A, B, fe, R, Cn, K, ksplit, nsplit);
-    return;
-  }
-  static const bool ilv = dbg_opt("x3_ilv", 1) != 0;     // (conversion in front of the MFMAs instead of between them: 0)
-  if (!ilv) {
-#ifndef CLSTM_HIP_EMU
-    static bool attr_set1 = false;
-    if (!attr_set1) {
-      (void)hipFuncSetAttribute((const void*)gemm_x3_128_kernel<AMODE, BMODE, FE, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      attr_set1 = true;
-    }
-#endif
-    CLSTM_LAUNCH((gemm_x3_128_kernel<AMODE, BMODE, FE, true, false>), grid, dim3(256), smem, stream, A, B, fe, R, Cn, K, ksplit, nsplit);
-    return;
-  }
   CLSTM_LAUNCH((gemm_x3_128_kernel<AMODE, BMODE, FE>), grid, dim3(256), smem, stream, A, B, fe, R, Cn, K, ksplit, nsplit);
 }
 

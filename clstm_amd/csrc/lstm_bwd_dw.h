@@ -14,12 +14,16 @@
 
 namespace clstm {
 
+// The item role's k-tile table area: 1024 entries although the items use DW_STAB_MAX = 256 -- 8 KB more than they need, on
+// purpose: with 50 KB a third item workgroup fits a CU beside the recurrence's, and the 64-line step measured 0.3 us slower for
+// it (three interleaved runs, 0.2866 vs 0.2861 ms)
+constexpr int DW_FUSED_STAB_ENTRIES = 1024;
+static_assert(DW_FUSED_STAB_ENTRIES >= DW_STAB_MAX, "the items' k-tile table fits");
+
 // NT: the weight-gradient items' arithmetic (gemm_dw_body): 0 f32 MFMA, 2 / 3 bf16 terms per operand
 template <int NK4, int KU, int NT>
 __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_bwd_dw_kernel(LstmSeqArgs a, GemmDwArgs g, int nrec) {
-  // (8 KB more than the items need since their k-tile table shrank to DW_STAB_MAX = 256 entries: with 50 KB a third item workgroup
-  //  fits a CU beside the recurrence's, and the 64-line step measured 0.3 us slower for it -- three interleaved runs, 0.2866 vs 0.2861 ms)
-  __shared__ __attribute__((aligned(16))) float gsm[dw_img_floats(NT) + 2 * 1024];
+  __shared__ __attribute__((aligned(16))) float gsm[dw_img_floats(NT) + 2 * DW_FUSED_STAB_ENTRIES];
   if ((int)blockIdx.x < nrec) {
 #ifndef CLSTM_HIP_EMU
     __builtin_amdgcn_s_setprio(3);

@@ -56,7 +56,6 @@ struct LstmMfmaArgs {
   const int* line_off;
   const int* order;          // [bs] lines, longest first (a group of 16 consecutive entries shares a workgroup), or null
   int bs, ndir, ldh, hofs, lds, sofs;
-  int dbg;                   // experiments (mfma_dbg): 1 no activation-row stores, 2 no c / h / source stores, 4 no input loads
   int store_s;               // 1: deposit h_t in the next frame's source row (else k_source_h rebuilds those columns from H)
   long long sdir;
   long long N;               // frames in the batch
@@ -217,7 +216,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const BufF32 hbuf = make_buf(a.H, (size_t)a.N * hstr);
   const BufF32 sbuf = make_buf(a.S + (size_t)dir * a.sdir, (size_t)a.N * sstr);
   const BufF32 xbuf = make_buf(a.X, (size_t)a.N * xstr);
-  const unsigned dbg_g = (a.dbg & 1) ? 0x80000000u : 0u, dbg_ch = (a.dbg & 2) ? 0x80000000u : 0u, dbg_x = (a.dbg & 4) ? 0x80000000u : 0u;
   unsigned gvo[RH];   // gate rows: lane = cell (16 bytes) within the half row
 #pragma unroll
   for (int hh = 0; hh < RH; hh++) gvo[hh] = 64 * hh + lane < NO ? (unsigned)(64 * hh + lane) * 16u : BUF_OOB_BASE;
@@ -241,7 +239,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const unsigned xvl = xon ? (unsigned)xq * 16u : BUF_OOB_BASE;
   auto load_x = [&](int t) -> f32x4 {
     const unsigned tok = (unsigned)(offx + (dir == 0 ? t : Tx - 1 - t));
-    return buf_load4(xbuf, (tok * xstr + xvl) | oob_lane(t, Tx) | dbg_x);
+    return buf_load4(xbuf, (tok * xstr + xvl) | oob_lane(t, Tx));
   };
   // k = NO + 4 xq .. + 3 of line xrow (lanes without an input: the dump slot)
   const unsigned xwo_h = (unsigned)((((NO + 4 * xq) >> 3) * 16 + xrow) * 16 + ((NO + 4 * xq) & 7) * 2);
@@ -284,18 +282,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bool ok = row_valid(j, tp);
     const unsigned so = (unsigned)row_tok(j, tp) * gstr + (unsigned)dir * NO * 16u;   // (an invalid row: every lane out of range)
 #pragma unroll
-    for (int hh = 0; hh < RH; hh++) buf_store4(gbuf, (gvo[hh] | oob_if(ok) | dbg_g) + so, av[hh]);
+    for (int hh = 0; hh < RH; hh++) buf_store4(gbuf, (gvo[hh] | oob_if(ok)) + so, av[hh]);
   };
   auto store_ch = [&](const char* out, const int tp) {  // c, h of lines 2w, 2w + 1
     const int lo = l5 < NO / 4 ? l5 : 0;
     const f32x4 cv = *reinterpret_cast<const f32x4*>(out + Gm::CS_REL + rrow * NO * 4 + lo * 16);
     const f32x4 hv = *reinterpret_cast<const f32x4*>(out + Gm::HS_REL + rrow * NO * 4 + lo * 16);
-    const unsigned bad = oob_lane(tp, Tr) | (unsigned)(tp >> 31 & 0x80000000) | dbg_ch;
+    const unsigned bad = oob_lane(tp, Tr) | (unsigned)(tp >> 31 & 0x80000000);
     const unsigned tok = (unsigned)(offr + (dir == 0 ? tp : Tr - 1 - tp));
     buf_store4(cbuf, (tok * cstr + (unsigned)dir * NO * 4u + chl) | bad, cv);
     buf_store4(hbuf, (tok * hstr + (unsigned)(a.hofs + dir * NO) * 4u + chl) | bad, hv);
     // h_t is the recurrent part of the NEXT step's source row (forward_stack_delay, clstm_compute.cc:377-397)
-    const unsigned bads = oob_lane(tp + 1, Tr) | (unsigned)(tp >> 31 & 0x80000000) | s_off_mask | dbg_ch;
+    const unsigned bads = oob_lane(tp + 1, Tr) | (unsigned)(tp >> 31 & 0x80000000) | s_off_mask;
     const unsigned toks = (unsigned)(offr + (dir == 0 ? tp + 1 : Tr - 2 - tp));
     buf_store4(sbuf, (toks * sstr + (unsigned)a.sofs * 4u + chl) | bads, hv);
   };

@@ -288,7 +288,7 @@ struct Net {
       const int M = ndir * 4 * y.no, KQP = 4 * y.nk4;
       const size_t nr = y.wide ? 0 : (size_t)ndir * 4 * KQP * y.nthreads;
       if (y.wide && bf16_rec && y.no % 128 == 0 && y.ni % 32 == 0 && wide_kp16_fwd(y.no) == y.no && wide_kp16_bwd(y.no) == 4 * y.no &&
-          dbg_opt("pack_tiles", 1) != 0) {
+          dbg_opt("pack_tiles") != 0) {
         // every bf16-mode copy of the layer in one tiled pass (ops.h:k_pack_wide_tiles)
         const int rf = (y.no + 3) / 4 * 16, kf = wide_kp16_fwd(y.no), rb = (y.no + 15) / 16 * 16, kb = wide_kp16_bwd(y.no);
         y.Wtb.reserve((size_t)y.ni * M + 64);
@@ -411,7 +411,7 @@ struct Net {
         w.skip_d = bf16_gemm;
         y.dbias.reserve((size_t)bs * ndir * 4 * y.no + 64); w.dbias = y.dbias.p;   // per-line bias-gradient sums (lstm_wide.h: LstmWideArgs::dbias)
       }
-      const bool b16mc_on = dbg_opt("gemm_b16mc", 1) != 0;
+      const bool b16mc_on = dbg_opt("gemm_b16mc") != 0;
       if (fwd && b16mc_on && bf16_gemm && (y.ni & 7) == 0 && (y.no & 7) == 0 && wide_kp16_bwd(y.no) == 4 * y.no) {
         const int ldsb = y.ni + y.no + 8;
         { const size_t cap0 = y.Sbf.cap; y.Sbf.reserve((size_t)N * ndir * ldsb + 64); if (y.Sbf.cap != cap0) y.sbf_one_key = -1; }
@@ -477,7 +477,7 @@ struct Net {
 #ifdef CLSTM_HIP_EMU
     return false;
 #else
-    const int mode = dbg_opt("fwd_mfma", 1);
+    const int mode = dbg_opt("fwd_mfma");
     if (!mode || y.wide || bf16_gemm) return false;
     if (!((y.no == 64 || y.no == 100 || y.no == 128) && y.ni == 48)) return false;   // the instantiated (cells, inputs) geometries
     const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
@@ -504,7 +504,7 @@ struct Net {
     a.W = y.Wmf.p; a.inv_scale = y.mf_scale.p; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.S = y.S.p; a.dH = y.dH.p; a.D = y.D.p;
     a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.bs = bs; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
     a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds; a.N = N;
-    a.X = layer_input(l); a.ldx = layer_input_ld(l); a.store_s = 1; a.dbg = dbg_opt("mfma_dbg", 0);
+    a.X = layer_input(l); a.ldx = layer_input_ld(l); a.store_s = 1;
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); a.prof = lstm_prof.p;
 #endif
@@ -522,7 +522,7 @@ struct Net {
 #ifdef CLSTM_HIP_EMU
     return false;
 #else
-    const int mode = dbg_opt("bwd_mfma", 1);
+    const int mode = dbg_opt("bwd_mfma");
     if (!mode || y.wide || bf16_gemm) return false;
     if (!(y.no == 64 || y.no == 100)) return false;   // (128 cells: image + operand staging would need 176 KB of LDS)
     const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
@@ -545,16 +545,11 @@ struct Net {
     }
     LstmMfmaBwdArgs a{};
     a.W = y.Wmfb.p; a.G = sa.G; a.C = sa.C; a.dH = sa.dH; a.D = sa.D; a.line_off = sa.line_off; a.order = sa.order;
-    a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base; a.dbg = dbg_opt("mfma_bwd_dbg", 0);
-    static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_kernel<NO, NT>, (size_t)Gm::SMEM), true);
+    a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base;
+    using Gr = MfmaBwdRowsGeom<NO, NT>;
+    static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
     (void)smem_set;
-    if (dbg_opt("bwd_mfma_rows", 1)) {   // every global access a whole row (lstm_bwd_mfma_rows_kernel; 0: the 64-byte-piece form)
-      using Gr = MfmaBwdRowsGeom<NO, NT>;
-      static const bool smem_set_r = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
-      (void)smem_set_r;
-      CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
-    } else
-    CLSTM_LAUNCH((lstm_bwd_mfma_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
+    CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
     g_path_count[17]++;
   }
 #endif
@@ -575,7 +570,7 @@ struct Net {
     }
     LstmMfmaBwdArgs a{};
     a.W = y.Wmfb.p; a.G = sa.G; a.C = sa.C; a.dH = sa.dH; a.D = sa.D; a.line_off = sa.line_off; a.order = sa.order;
-    a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base; a.dbg = 0;
+    a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base;
     const int ngroups = (bs + 15) / 16, nrec = ngroups * ndir;
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM), true);
     (void)smem_set;
@@ -587,8 +582,8 @@ struct Net {
   //  vs 374.8k, 896: 398.0k vs 395.1k, 960: 406.6k vs 407.9k, 1024: 414.6k vs 419.0k, 1536: 430.2k vs 471.2k; option bwd_mfma_fused:
   //  0 never, 1 that rule, 2 always (tests))
   bool mfma_bwd_fused_ok(const Layer& y, const GemmDwArgs& g) const {
-    const int mode = dbg_opt("bwd_mfma_fused", 1);
-    return mfma_bwd_eligible(y) && mode && dbg_opt("bwd_mfma_rows", 1) && g.x3 == 1 && g.terms >= 3 && (mode >= 2 || bs < 900);
+    const int mode = dbg_opt("bwd_mfma_fused");
+    return mfma_bwd_eligible(y) && mode && g.x3 && g.terms >= 3 && (mode >= 2 || bs < 900);
   }
 #endif
   // the narrow layer's backward recurrence: batched over lines on the MFMA where that pays, else one workgroup per line
@@ -670,7 +665,7 @@ struct Net {
       // one L2 round trip of the poll, not waiting for late tiles -- so the fused work lands on the chain: +400 cycles per step
       // for 64 inputs (67 us per pass against the 121 us of product + bf16 copy it replaces: kept), +2,950 for 1024 inputs
       // (490 us against 321: not kept).  (read per pass: tests switch it inside one process)
-      const int fx_mode = dbg_opt("fuse_wx", 1);
+      const int fx_mode = dbg_opt("fuse_wx");
       if (fx_mode > 0 && (fx_mode > 1 || y.ni <= 128) && y.wide && bf16_gemm && bf16_rec && y.WtbT.p && (y.ni & 31) == 0 && (l == 0 || x_from_hbf)) {
         const int ngx = y.ni <= 128 ? 1 : y.ni <= 512 ? 4 : y.ni <= 1024 ? 8 : 0;
         if (ngx) {
@@ -858,23 +853,23 @@ struct Net {
     }
   }
 
-  // overlapped weight-gradient GEMM: 1 = bf16 MFMA on f32 operands split into bf16 terms (gemm_dw.h), 0 = f32 MFMA
+  // overlapped weight-gradient GEMM: true = bf16 MFMA on f32 operands split into bf16 terms (gemm_dw.h), false = f32 MFMA
   // (experiment option dw_x3=0)
-  int dw_x3 = dbg_opt("dw_x3", 1);
+  bool dw_x3 = dbg_opt("dw_x3") != 0;
   // terms per operand of those split products and of the softmax layer's (gemm_x3): 3 = operand-exact (x1 + x2 + x3 is the f32
   // itself, six products), 2 = hi + lo, three products (< 2^-16 per product; rounds 3-5)
-  int split_terms = dbg_opt("split_terms", 3);
+  int split_terms = dbg_opt("split_terms");
   // the softmax layer's backward products W.d / x.d the same way (gemm_x3, gemm_bf16.h); experiment option gemm_x3=0 (CLSTM_DEBUG): f32 MFMA.
   // NOT the forward product W_x.x: its ~2^-17 relative error per product shows up in gate pre-activations that cancel to
   // ~0 (a tanh gate at -0.0021 came out 5.6e-6 off where the parity bar allows 2.2e-6), and with K = 49 the split costs
   // more staging than it saves MFMA time (28.5 vs 20.9 us).
-  bool gemm_x3_on = dbg_opt("gemm_x3", 1) != 0;
+  bool gemm_x3_on = dbg_opt("gemm_x3") != 0;
   // exact-f32 mode, wide layers: the persistent BACKWARD recurrence as an f32-grade x3 product on the bf16 MFMA (lstm_wide.h:
   // lstm_xcd_bwd_x3) like the backward GEMMs of this mode; off with them (gemm_x3=0 / strict f32) or alone (rec_x3=0, CLSTM_DEBUG options;
   // read per pass: tests compare both kernels in one process)
   bool rec_x3() const {
     if (bf16_gemm || bf16_rec || !gemm_x3_on) return false;
-    return dbg_opt("rec_x3", 1) != 0;
+    return dbg_opt("rec_x3") != 0;
   }
   // split-K slabs for the weight-gradient GEMMs: enough workgroups to cover the 256 CUs
   // big tiles of the contraction-major bf16 product (gemm_b16mc: 256 or 192 rows x 256 columns): one workgroup per CU, never a second round
@@ -908,19 +903,23 @@ struct Net {
     if ((double)y.D.cap * 4.0 >= 2147483000.0) return false;         // 32-bit byte offsets inside one descriptor
     return overlap == 2 || y.nthreads >= 256;                        // one launch, two workgroup roles (lstm_bwd_dw.h)
   }
+  // Slab geometry of the chunked weight-gradient GEMM (measured at the bench shape unless said otherwise):
+  // - chunks of DW_CHUNK iterations (8: 0.407 ms per step, 16: 0.356, 32: 0.359, 48: 0.360, a decreasing plan 64..16: 0.3615);
+  // - ~16 slabs per direction, at most DW_STAB_MAX k-tiles (of 16 frames) each: a slab's table must fit the items' LDS copy.  At
+  //   1024 / 2048 lines 256 instead of 800 / 1024 tiles: 1,092 long items on 512 workgroup slots became 3,000+ shorter ones --
+  //   weight-gradient launch 0.613 -> 0.559 / 1.259 -> 1.119 ms;
+  // - the last DW_TAIL_CHUNKS chunks (those whose items still run when the recurrence ends) in at least DW_TAIL_PARTS slabs: parts
+  //   1: 118 us, 4: 112, 8: 115 -- more items than free CUs at the end; with the six-product items 2 chunks instead of 3: -1 us.
+  static constexpr int DW_CHUNK = 16, DW_TAIL_PARTS = 4, DW_TAIL_CHUNKS = 2;
   // k-tile tables and slabs of the chunked weight-gradient GEMM for the current batch geometry (rebuilt only when the
   // line lengths change).  Chunks are ranges of recurrence iterations, longest first: the work left when the
   // recurrence ends is what the last (short) chunk holds.
   void build_dw_tables() {
     if (dw_key == line_off_h && dw_nslabs > 0) return;
-    std::vector<int> cb;   // chunk ends (iterations), multiples of 8 except the last
-    // equal chunks of 16 iterations measured best at the bench shape (8: 0.407 ms per step, 16: 0.356, 32: 0.359,
-    // 48: 0.360, a decreasing plan 64..16: 0.3615)
-    const int chunk = std::max(8, dbg_opt("dw_chunk", 16) & ~7);   // (experiment option; multiples of 8)
-    for (int done = chunk; done < tmax; done += chunk) cb.push_back(done);
+    std::vector<int> cb;   // chunk ends (iterations), multiples of DW_CHUNK except the last
+    for (int done = DW_CHUNK; done < tmax; done += DW_CHUNK) cb.push_back(done);
     cb.push_back(tmax);
-    const int tps_opt = dbg_opt("dw_slab_tiles", 0);   // experiment option: k-tiles (of 16 frames) per slab
-    const int tiles_per_slab = tps_opt > 0 ? std::min(DW_STAB_MAX, std::max(8, tps_opt)) : std::min(256, std::max(8, (int)((N / 16 + 15) / 16)));   // ~16 slabs per direction, at most 256 k-tiles = 4096 frames each (a slab's table must fit the items' LDS copy: DW_STAB_MAX; at 1024 / 2048 lines 256 instead of 800 / 1024 tiles: 1,092 long items on 512 workgroup slots became 3,000+ shorter ones -- weight-gradient launch 0.613 -> 0.559 / 1.259 -> 1.119 ms)
+    const int tiles_per_slab = std::min(DW_STAB_MAX, std::max(8, (int)((N / 16 + 15) / 16)));
     std::vector<std::vector<int>> tab(ndir);                            // (first frame, count) pairs
     struct Sl { int tb, nt, need, dir, chunk, part; };
     std::vector<std::vector<Sl>> sl(ndir);
@@ -942,10 +941,10 @@ struct Net {
         // The items of the LAST chunks cannot start before the recurrence ends, so their latency -- a serial walk over a
         // slab's frames, ~1 us per 32 -- is the launch's tail (profiles/r02_dw_timeline.txt): cut those chunks into
         // more, shorter slabs (>= 2 table entries each).
-        const int tail_parts = dbg_opt("dw_tail_parts", 4), tail_chunks = dbg_opt("dw_tail_chunks", 2);   // (parts 1: 118 us, 4: 112, 8: 115 -- more items than free CUs at the end; round 6, six-product items: chunks 2 instead of 3: -1 us, scripts/dbg/sweep_tail.sh)
-        if (c + tail_chunks >= cb.size()) parts = std::max(parts, std::min(tail_parts, std::max(1, nt / 2)));   // (those whose items still run when the recurrence ends)
+        if (c + DW_TAIL_CHUNKS >= cb.size()) parts = std::max(parts, std::min(DW_TAIL_PARTS, std::max(1, nt / 2)));
         for (int p = 0; p < parts; p++) {
           const int a0 = t0 + (int)((long long)nt * p / parts), a1 = t0 + (int)((long long)nt * (p + 1) / parts);
+          REQUIRE(a1 - a0 <= DW_STAB_MAX, "internal: weight-gradient slab longer than its LDS table");
           sl[dir].push_back(Sl{a0, a1 - a0, ce, dir, (int)c, p});
         }
         cs = ce;
@@ -1057,9 +1056,7 @@ struct Net {
     launch_bwd_narrow(y, a, s);
     timing.end(s);
     timing.begin("gemm_gates_dw", s);
-    static const bool dw_ilv = dbg_opt("dw_ilv", 0) != 0;   // (experiment, measured slower: the conversion between the MFMAs -- two workgroups per CU overlap by themselves)
-    if (g.x3 && g.terms >= 3 && dw_ilv) CLSTM_LAUNCH((gemm_dw_kernel<3, true>), dim3(nblk), dim3(256), 0, s, g);
-    else if (g.x3 && g.terms >= 3) CLSTM_LAUNCH(gemm_dw_kernel<3>, dim3(nblk), dim3(256), 0, s, g);
+    if (g.x3 && g.terms >= 3) CLSTM_LAUNCH(gemm_dw_kernel<3>, dim3(nblk), dim3(256), 0, s, g);
     else if (g.x3) CLSTM_LAUNCH(gemm_dw_kernel<2>, dim3(nblk), dim3(256), 0, s, g);
     else CLSTM_LAUNCH(gemm_dw_kernel<0>, dim3(nblk), dim3(256), 0, s, g);
     timing.end(s);
@@ -1097,7 +1094,7 @@ struct Net {
       // (lstm_bwd_dw.h) its slabs are items of THAT launch -- they execute on the idle half of the chip during the ~14 us
       // before the recurrence's first chunk is released -- and only x.d stays in front of the recurrence.
       // (only while the recurrence leaves CUs idle: with 256 lines the same items cost the fused launch +42 us for 19 saved)
-      dwx_active = !bf16_gemm && (dw_x3 & 1) && overlap_eligible(top) &&
+      dwx_active = !bf16_gemm && dw_x3 && overlap_eligible(top) &&
                    (long long)bs * ndir * 4 <= 3LL * device_cu_count();
       if (dwx_active) {
         if (dwx_N != N) {   // contiguous frames: entries of 16, slabs of 32 entries (512 frames: one short item each)
@@ -1110,6 +1107,7 @@ struct Net {
           for (int e = 0; e < dwx_entries; e++) { stage[2 * e] = 16 * e; stage[2 * e + 1] = (int)std::min<long long>(16, N - 16LL * e); }
           DwSlab* sl = (DwSlab*)(stage + 2 * dwx_entries);
           for (int i = 0; i < dwx_nslabs; i++) sl[i] = DwSlab{eps * i, std::min(eps, dwx_entries - eps * i), 0, 0, i, {0, 0, 0}};
+          for (int i = 0; i < dwx_nslabs; i++) REQUIRE(sl[i].ntiles <= DW_STAB_MAX, "internal: weight-gradient slab longer than its LDS table");
           HIPCHECK(hipMemcpyAsync(dwx_tab.p, stage, ((size_t)2 * dwx_entries + nsw) * sizeof(int), hipMemcpyHostToDevice, s));
           ring.commit(s);
           dwx_N = N;
@@ -1342,7 +1340,7 @@ struct Net {
       // a single narrow layer whose packed copies are current: the update keeps them current (ops.h: PackDst) and the next
       // step's ingest launch has nothing to repack
       packs_follow_update = false;
-      if (L.size() == 1 && !L[0].wide && !packed_dirty && dbg_opt("update_repack", 1) && pack_inverse(L[0])) {
+      if (L.size() == 1 && !L[0].wide && !packed_dirty && pack_inverse(L[0])) {
         Layer& y = L[0];
         const size_t nr = (size_t)ndir * 4 * 4 * y.nk4 * y.nthreads;
         uf.pk = PackDst{y.pack_inv.p, PACK_KD, y.Wt, y.bias, y.Rf, y.Rb, y.pd, pack_fused_desc(y), (unsigned)((size_t)(1 + y.ni) * ndir * 4 * y.no), (unsigned)nr};

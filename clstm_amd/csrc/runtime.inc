@@ -263,8 +263,7 @@ static std::vector<char> graph_key(A a) {
 template <class A, class F>
 static void launch_steps(StepGraphCache& cache, int kind, const A& a, int tmax, hipStream_t s, F&& body) {
 #ifndef CLSTM_HIP_EMU
-  const bool use_graph = dbg_opt("wide_graph", 1) != 0;
-  if (use_graph && tmax >= 8) {
+  if (tmax >= 8) {
     const std::vector<char> key = graph_key(a);
     hipGraphExec_t exec = cache.find(kind, key, tmax);
     if (!exec && !cache.unsupported) {
@@ -503,7 +502,7 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
     if (fits && !bf16 && (size_t)xcd_bwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_bwd_f32, (size_t)xcd_bwd_f32_lds_bytes(a.kp))) return true;
     // 32 cells per workgroup, two groups per XCD, groups of 8 / 16 / 32 lines (lstm_wide.h:lstm_xcd_bwd_bf16_c32): half the
     // delta block per step and CU of the 16-cell kernel below, which stays for hidden sizes that are not multiples of 32
-    const bool c32_on = dbg_opt("bwd_c32", 1) != 0;   // (read per pass: tests compare both kernels in one process)
+    const bool c32_on = dbg_opt("bwd_c32") != 0;   // (read per pass: tests compare both kernels in one process)
     if (fits && bf16 && a.kp16 <= 2048 && c32_on && no % 32 == 0 && a.ndir <= 2) {
       const int per = 16 / a.ndir;   // line groups per launch
       const int ept = a.bs <= 8 * per ? 1 : a.bs <= 16 * per ? 2 : 4;

@@ -30,6 +30,37 @@ def _forget_debug_options(request):
             pass
 
 
+def test_debug_options_unknown_name_is_an_error():
+    """dbgopt.h holds the one table of experiment switches: clstm_debug_set_option refuses a name it does not hold, and so does
+    CLSTM_DEBUG -- the first library call that reads an option (here: creating a net) fails and names it.  A retired or
+    misspelt option must not do nothing silently.  (Emulator build: the same dbgopt.h and abi.inc as the GPU library.)"""
+    import subprocess
+    import sys
+    from clstm_amd.abi import ClstmError
+    from common import emu_lib
+    lib = emu_lib()
+    with pytest.raises(ClstmError, match="unknown option 'no_such_option'"):
+        lib.call("clstm_debug_set_option", b"no_such_option", 0)
+    lib.call("clstm_debug_set_option", b"gemm_stag", 1)
+    lib.call("clstm_debug_set_option", None, 0)
+    code = """import sys
+sys.path[:0] = [%r, %r]
+from clstm_amd.abi import ClstmError
+from clstm_amd.net import Network
+from common import emu_lib
+try:
+    Network(4, 8, 3, lib=emu_lib())
+except ClstmError as e:
+    print(e)
+else:
+    print("created")
+""" % (ROOT, os.path.join(ROOT, "tests"))
+    env = dict(os.environ, CLSTM_DEBUG="gemm_stag=1,no_such_option=0")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-800:]
+    assert "unknown option 'no_such_option'" in r.stdout, r.stdout
+
+
 def run_case(backend, ora32, ni, nh, nc, T, uni=False, scale=30.0, seed=1, lr=1e-2, check_dx=False,
              ctc_rtol=1e-4, grad_tol=1e-4, overlap=None, params=None, lines=None, trs=None, strict_f32=False, act_atol=None, delta_tol=None):
     """`params` / `lines` / `trs` given: that weight set, those input lines and transcripts instead of init x scale on noise"""
