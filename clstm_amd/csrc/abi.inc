@@ -722,6 +722,7 @@ int clstm_net_set_overlap(clstm_net* h, int mode) {
 int clstm_net_set_strict_f32(clstm_net* h, int on) {
   ABI_BEGIN
   Net& n = h->net;
+  n.strict_f32 = on != 0;
   if (on) { n.dw_x3 = false; n.gemm_x3_on = false; }
   else {
     n.dw_x3 = dbg_opt("dw_x3") != 0;
@@ -802,6 +803,13 @@ int clstm_debug_set_option(const char* name, int value) {   // experiment switch
 int clstm_debug_path_count(int which, long long* out_h) {
   ABI_BEGIN
   REQUIRE(which >= 0 && which < 24 && out_h, "bad path index");
+  if (which == 21) {   // counted on the device: minibatches whose forward pass the batched recurrence handed to its routed per-line twins (lstm_mfma.h)
+    int n = 0;
+    HIPCHECK(hipStreamSynchronize(g_stream));
+    HIPCHECK(hipMemcpy(&n, dev_err_words() + 8, sizeof(int), hipMemcpyDeviceToHost));
+    *out_h = n;
+    return 0;
+  }
   *out_h = g_path_count[which];
   ABI_END
 }

@@ -12,12 +12,24 @@
 //
 // Arithmetic.  Both operands are f32 values split into TWO f16 terms, x = hi + lo with hi = f16(x), lo = f16(x - hi) (the
 // difference is exact), after a power-of-two scaling that keeps lo out of the f16 subnormal range ([R | W_x | b] by 2^e with
-// max |.| 2^e in [2^13, 2^14); h in [-1, 1], x and the constant 1 by 2^8: inputs must stay below 255 in magnitude, normalised
-// text lines are in [0, 1]; the inverse scale rides the multiply in front of the gate nonlinearity).  f16 carries 11 significant
+// max |.| 2^e in [2^13, 2^14); h in [-1, 1], x and the constant 1 by 2^8: 255 x 2^8 = 65280 is the last input below f16's 65504
+// -- see "Input range" --, normalised text lines are in [0, 1]; the inverse scale rides the multiply in front of the gate nonlinearity).  f16 carries 11 significant
 // bits, so hi + lo represents x to 2^-22 |x| or better (f32 itself: 2^-24), each f16 x f16 product is exact in the f32
 // accumulator, and a product is hi.hi + hi.lo + lo.hi: what is dropped (lo.lo) is < 2^-22 |x y|.  That is the f32 MFMA's
 // accuracy class at 5x its rate, NOT the 2^-16 of a bf16 hi + lo split.  Parity: every saved activation within 1e-4 of the
-// oracle (tests/test_mfma_recurrence.py).
+// oracle (tests/test_mfma_recurrence.py, tests/test_mfma_bench_shapes.py).
+//
+// Input range.  The caller's frames may hold any float (include/clstm_abi.h), this kernel's operand scale does not, and a split
+// product's error grows with |W x| where an f32 product's is 4..12 times smaller: a minibatch whose first-layer inputs leave
+// [-255, 255] is NOT computed here.  The decision is the device's -- the host never waits for it: k_mfma_xmax (one small launch in
+// front of the recurrence) leaves the partial maxima of |x| over the input block; every workgroup of this kernel reduces them
+// and returns at once, having written nothing, if the maximum is above 255 or not finite; behind it the per-line forward pass of
+// smaller minibatches (the hoisted f32 W_x.x product, lstm_seq.h) is launched as ROUTED twins (gemm_f32_routed_kernel,
+// lstm_fwd_routed_kernel) whose workgroups return at once in the opposite case.  Either family leaves the same arrays (activations,
+// c, h, source rows), so nothing behind the forward recurrence knows which one ran.  In range, the twins cost two launches of
+// workgroups that end at their first branch; out of range, the minibatch has the arithmetic -- and the speed -- of the per-line
+// kernels, NaN and infinity included (a non-finite pixel stays what it is).  Upper layers (inputs = h of the layer below,
+// in [-1, 1]) have nothing to decide.
 //
 // Geometry (NO cells, NO % 4 == 0, NO <= 128; NI inputs, NI % 4 == 0, NI <= 64).  M = gate rows in tiles of 16 = 4 cells x 4
 // gates (row m = 4 cs + q, q = 0 gi, 1 gf, 2 go, 3 ci), N = 16 lines, K = [cells | inputs | 1] in blocks of 32.  In the MFMA's
@@ -46,10 +58,13 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MF_HS = 8;   // h, x and the constant 1 are scaled by 2^MF_HS before the f16 split
+constexpr int MF_XMAX_SLOTS = 256;            // k_mfma_xmax: one partial maximum per block
+constexpr unsigned MF_XMAX_BITS = 0x437f0000u;   // 255.0f: the largest |x| the 2^MF_HS operand scale carries
 
 struct LstmMfmaArgs {
   const unsigned short* W;   // A fragments [dir][tile][k-block][hi | lo][lane][8 halfs]   (k_pack_mfma)
   const float* inv_scale;    // [dir] 2^-(e + MF_HS)
+  const unsigned* xmax;      // [MF_XMAX_SLOTS] partial maxima of |x| as bit patterns (k_mfma_xmax), or null: inputs known to be in range
   const float* X; int ldx;   // the layer's input frames [N][ldx]
   float *G, *C, *H, *S;      // as LstmSeqArgs (G: activations out only)
   const float* dH; float* D;
@@ -138,6 +153,62 @@ __global__ __launch_bounds__(1024) void k_pack_mfma(MfmaPackArgs p) {
   }
 }
 
+// max |x| of the input block, as the bit pattern of |x| (unsigned order = float order for non-negative values, and any NaN
+// sorts above infinity: a non-finite pixel makes the maximum non-finite).  Block b leaves its partial maximum in slot b; the
+// kernels that ask finish the reduction themselves (no atomics, nothing to zero between minibatches).
+__global__ __launch_bounds__(256) void k_mfma_xmax(const float* x, size_t n, unsigned* slots) {
+  __shared__ unsigned red[4];
+  unsigned mx = 0u;
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x, str = (size_t)gridDim.x * 256;
+  if ((n & 3) == 0 && ((size_t)x & 15) == 0) {
+    for (size_t i = i0; i < n / 4; i += str) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(x + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; e++) { const unsigned u = v[e] & 0x7fffffffu; mx = u > mx ? u : mx; }
+    }
+  } else {
+    for (size_t i = i0; i < n; i += str) { const unsigned u = __builtin_bit_cast(unsigned, x[i]) & 0x7fffffffu; mx = u > mx ? u : mx; }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)mx, m, 64); mx = o > mx ? o : mx; }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; i++) mx = red[i] > mx ? red[i] : mx;
+    slots[blockIdx.x] = mx;
+  }
+}
+// true (wave-uniform, every wave by itself: 16 bytes per lane): the minibatch's inputs leave [-255, 255] or are not finite
+DEVFN bool mfma_x_routed(const unsigned* slots, const int lane) {
+  static_assert(MF_XMAX_SLOTS == 256, "one u32x4 per lane");
+  const u32x4 v = *reinterpret_cast<const u32x4*>(slots + 4 * lane);
+  unsigned um = v[0] > v[1] ? v[0] : v[1];
+  um = v[2] > um ? v[2] : um;
+  um = v[3] > um ? v[3] : um;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)um, m, 64); um = o > um ? o : um; }
+  return (unsigned)wave_uniform((int)um) > MF_XMAX_BITS;
+}
+// the per-line forward pass of such a minibatch: the kernels of smaller minibatches behind a first branch (see "Input range");
+// `routed` counts the minibatches that took them (clstm_debug_path_count 21)
+template <int AMODE, int BMODE, class FE>
+__global__ __launch_bounds__(256) void gemm_f32_routed_kernel(GemmOperand A, GemmOperand B, FE fe, int R, int Cn, int K, int ksplit,
+                                                              unsigned gx, unsigned gy, const unsigned* xmax) {
+  __shared__ __attribute__((aligned(16))) float smem[gemm_smem_floats(GEMM_BK)];
+  if (!mfma_x_routed(xmax, threadIdx.x & 63)) return;
+  // (a capped grid walks the tiles: in range, the launch is a few thousand workgroups that end here, not one per tile)
+  for (unsigned lin = blockIdx.x; lin < gx * gy; lin += gridDim.x) {
+    gemm_f32_body<AMODE, BMODE, FE, GEMM_BK, GEMM_PF>(smem, A, B, fe, R, Cn, K, ksplit, 1, lin, gx, gy, 1);
+    __syncthreads();
+  }
+}
+template <int NK4, int KU>
+__global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_routed_kernel(LstmSeqArgs a, const unsigned* xmax, int* routed) {
+  if (!mfma_x_routed(xmax, threadIdx.x & 63)) return;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomic_add_i32(routed, 1);
+  lstm_fwd_body<NK4, KU, false>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
+}
+
 DEVFN f32x4 mfma16x16x32_f16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 // LDS rendezvous that leaves global loads / stores in flight (__syncthreads() would wait vmcnt(0)); one asm statement with a
 // memory clobber, so that neither LDS stores sink below it nor LDS loads rise above it
@@ -161,6 +232,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int n = lane & 15, cl = lane >> 4;
   const int dir = blockIdx.y, grp = blockIdx.x;
   const int nd = a.ndir;
+  if (a.xmax && mfma_x_routed(a.xmax, lane)) return;   // inputs out of range: the routed per-line twins compute this minibatch
 
   // this lane's line (column n of the product) and, as scalars, the two lines whose rows this wave moves
   const int gl = grp * 16 + n;

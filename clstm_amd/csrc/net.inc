@@ -16,6 +16,7 @@ struct Layer {
   // the parameters have moved (Net::params_epoch)
   DevBuf<unsigned short> Wmf;
   DevBuf<float> mf_scale;
+  DevBuf<unsigned> mf_xmax;   // partial maxima of |x| of the current minibatch (k_mfma_xmax): batched recurrence or its routed per-line twins
   long long mf_epoch = -1;
   DevBuf<unsigned short> Wmfb;   // R^T fragments of the batched backward recurrence (lstm_mfma_bwd.h)
   long long mfb_epoch = -1;
@@ -266,7 +267,7 @@ struct Net {
     for (auto& y : L) {
       (void)hipFree(y.Wt); (void)hipFree(y.bias); (void)hipFree(y.Rf); (void)hipFree(y.Rb); (void)hipFree(y.moff); (void)hipFree(y.Wk);
       (void)hipFree(y.Rwf); (void)hipFree(y.Rwb); (void)hipFree(y.Rbf); (void)hipFree(y.Rbb); y.dCc.release(); y.Hb.release(); y.Db.release(); y.Rf32.release(); y.R2b.release(); y.D2.release();
-      y.G.release(); y.C.release(); y.H.release(); y.D.release(); y.dH.release(); y.S.release(); y.Sbf.release(); y.sbf_ready = false; y.pack_tab.release(); y.pack_inv.release(); y.Wmf.release(); y.mf_scale.release(); y.Wmfb.release(); y.pack_inv_state = 0; y.partial.release(); y.dbias.release();
+      y.G.release(); y.C.release(); y.H.release(); y.D.release(); y.dH.release(); y.S.release(); y.Sbf.release(); y.sbf_ready = false; y.pack_tab.release(); y.pack_inv.release(); y.Wmf.release(); y.mf_scale.release(); y.mf_xmax.release(); y.Wmfb.release(); y.pack_inv_state = 0; y.partial.release(); y.dbias.release();
     }
     (void)hipFree(W1k); fw_items.release(); fw_flags.release();
     for (int i = 0; i < 2; i++) { hf.xin[i].release(); if (hf.pin[i]) (void)hipHostFree(hf.pin[i]); if (hf.copied[i]) (void)hipEventDestroy(hf.copied[i]); }
@@ -472,13 +473,15 @@ struct Net {
 
   // ---- narrow layers, chip-filling minibatches: the recurrence batched over 16 lines per workgroup on the MFMA (lstm_mfma.h) ----
   // fwd_mfma: 0 never, 1 (default) from 640 lines per GPU on (measured crossover, profiles/r06_mfma_v3_vs_perline.txt: below
-  // that the launch has fewer 16-line workgroups than the chip has CUs and the per-line kernel wins), 2 always (tests)
+  // that the launch has fewer 16-line workgroups than the chip has CUs and the per-line kernel wins), 2 always (tests).
+  // clstm_net_set_strict_f32: never by the rule (its products are f16 split products, not the f32 MFMA's); the forced option wins.
   bool mfma_eligible(const Layer& y) const {
 #ifdef CLSTM_HIP_EMU
     return false;
 #else
     const int mode = dbg_opt("fwd_mfma");
     if (!mode || y.wide || bf16_gemm) return false;
+    if (strict_f32 && mode < 2) return false;
     if (!((y.no == 64 || y.no == 100 || y.no == 128) && y.ni == 48)) return false;   // the instantiated (cells, inputs) geometries
     const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
     if ((double)N * ndir * 4 * y.no * 4 >= lim || (double)N * y.ldh * 4 >= lim || (double)N * y.lds * 4 >= lim) return false;
@@ -505,6 +508,11 @@ struct Net {
     a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.bs = bs; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
     a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds; a.N = N;
     a.X = layer_input(l); a.ldx = layer_input_ld(l); a.store_s = 1;
+    if (l == 0) {   // the caller's frames, any magnitude: the device decides between this kernel and its routed twins (lstm_mfma.h: Input range)
+      y.mf_xmax.reserve(MF_XMAX_SLOTS);
+      CLSTM_LAUNCH(k_mfma_xmax, dim3(MF_XMAX_SLOTS), dim3(256), 0, s, (const float*)X.p, (size_t)N * desc.ninput, y.mf_xmax.p);
+      a.xmax = y.mf_xmax.p;
+    }
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); a.prof = lstm_prof.p;
 #endif
@@ -512,6 +520,30 @@ struct Net {
     (void)smem_set; (void)fwd;
     CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
     g_path_count[16]++;
+    if (l == 0) launch_routed_per_line(y, s);
+  }
+  // the per-line forward pass of layer 0 (hoisted f32 W_x.x product + lstm_seq.h recurrence, as forward() launches them for
+  // smaller minibatches) behind the branch that lets it run only when the batched kernel has declined the minibatch
+  template <int NK4, int KU>
+  void launch_routed_lstm(Layer& y, const LstmSeqArgs& a, hipStream_t s) {
+    REQUIRE(y.nk4 == NK4 && y.pd.ku == KU, "internal: per-line geometry of a batched layer");
+    const size_t smem = (2 * 4 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
+    CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
+  }
+  void launch_routed_per_line(Layer& y, hipStream_t s) {
+    const int M = ndir * 4 * y.no;
+    const int ksplit = (y.ni + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
+    const unsigned gx = (unsigned)((M + GEMM_BT - 1) / GEMM_BT), gy = (unsigned)((N + GEMM_BT - 1) / GEMM_BT);
+    CLSTM_LAUNCH((gemm_f32_routed_kernel<GEMM_KC, GEMM_MC, StoreBias>), dim3(std::min(gx * gy, 2048u)), dim3(256), 0, s,
+                 gemm_kc(layer_input(0), layer_input_ld(0), N), gemm_mc(y.Wt, M, y.ni, 0), StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni, ksplit,
+                 gx, gy, (const unsigned*)y.mf_xmax.p);
+    LstmSeqArgs a{};
+    a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
+    a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
+    a.S = y.S.p; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
+    if (y.no == 64) launch_routed_lstm<4, 16>(y, a, s);
+    else if (y.no == 100) launch_routed_lstm<7, 25>(y, a, s);
+    else launch_routed_lstm<8, 32>(y, a, s);
   }
 #endif
   // bwd_mfma: the backward twin (lstm_mfma_bwd.h): 0 never, 1 (default) from 640 lines per GPU on, 2 always (tests).  It gives up
@@ -524,6 +556,7 @@ struct Net {
 #else
     const int mode = dbg_opt("bwd_mfma");
     if (!mode || y.wide || bf16_gemm) return false;
+    if (strict_f32 && mode < 2) return false;   // (R^T.delta from two bf16 terms: not what strict promises; forced: the option wins)
     if (!(y.no == 64 || y.no == 100)) return false;   // (128 cells: image + operand staging would need 176 KB of LDS)
     const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
     if ((double)N * ndir * 4 * y.no * 4 >= lim) return false;
@@ -864,6 +897,7 @@ struct Net {
   // ~0 (a tanh gate at -0.0021 came out 5.6e-6 off where the parity bar allows 2.2e-6), and with K = 49 the split costs
   // more staging than it saves MFMA time (28.5 vs 20.9 us).
   bool gemm_x3_on = dbg_opt("gemm_x3") != 0;
+  bool strict_f32 = false;   // clstm_net_set_strict_f32: no split-product recurrences by the library's own rule either (mfma_eligible)
   // exact-f32 mode, wide layers: the persistent BACKWARD recurrence as an f32-grade x3 product on the bf16 MFMA (lstm_wide.h:
   // lstm_xcd_bwd_x3) like the backward GEMMs of this mode; off with them (gemm_x3=0 / strict f32) or alone (rec_x3=0, CLSTM_DEBUG options;
   // read per pass: tests compare both kernels in one process)

@@ -162,7 +162,13 @@ int clstm_net_set_gradient_clip(clstm_net* net, float clip);
 
 /* Declare the next minibatch: bs lines of T_h[b] frames each (HOST).  N = sum T. */
 int clstm_net_set_batch(clstm_net* net, const int* T_h, int bs);
-/* set_inputs (clstm.cc:684-690): x [N][ninput], frame-major, feature contiguous. */
+/* set_inputs (clstm.cc:684-690): x [N][ninput], frame-major, feature contiguous.
+ * Input range: any float32.  The result class does not depend on the minibatch size: the batched recurrence that single-layer
+ * narrow nets take from 640 lines per GPU on (csrc/lstm_mfma.h) scales its operands for |x| <= 255 -- normalised text lines are
+ * in [0, 1] -- and a minibatch that holds a larger or a non-finite input is computed by the per-line f32 kernels of smaller
+ * minibatches instead, at their speed.  The device decides (no host synchronisation; csrc/lstm_mfma.h "Input range");
+ * clstm_debug_path_count(21) counts the minibatches that went that way.  A non-finite pixel stays what it is on every path:
+ * non-finite outputs, the update skipped and reported (clstm_last_error). */
 int clstm_net_set_inputs_h(clstm_net* net, const float* x_h);
 int clstm_net_set_inputs_d(clstm_net* net, const float* x_d);
 /* net->forward() */
@@ -208,8 +214,11 @@ int clstm_net_get_state_h(clstm_net* net, int layer, int dir, int which, float* 
  * (must stay 0). */
 int clstm_net_set_overlap(clstm_net* net, int mode);
 /* on != 0: every product of the training step on the f32 MFMA -- the backward products that default to operand-exact split
- * products on the bf16 MFMA (weight gradients, the softmax layer's W.d / x.d) included.  Same as
- * CLSTM_DEBUG="dw_x3=0,gemm_x3=0", per net (bench.py's `strict_f32` leg and --strict-f32). */
+ * products on the bf16 MFMA (weight gradients, the softmax layer's W.d / x.d) included, and no batched split-product recurrence
+ * (csrc/lstm_mfma.h f16 x 2, csrc/lstm_mfma_bwd.h bf16 x 2) by the library's own rule at any minibatch size: a strict net of 640
+ * lines and more keeps the per-line f32 kernels.  Same as CLSTM_DEBUG="dw_x3=0,gemm_x3=0,fwd_mfma=0,bwd_mfma=0", per net
+ * (bench.py's `strict_f32` leg and --strict-f32).  An experiment option that FORCES a kernel family (CLSTM_DEBUG /
+ * clstm_debug_set_option "fwd_mfma=2", "bwd_mfma=2": tests) wins over this flag. */
 int clstm_net_set_strict_f32(clstm_net* net, int on);
 int clstm_net_overlap_stats(clstm_net* net, long long* launches, int* timeouts);
 int clstm_net_enable_timing(clstm_net* net, int on);
@@ -315,7 +324,9 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
 /* how often this process has taken an optional fast path (HOST out): which = 0 persistent per-XCD forward recurrence,
  * 1 persistent backward recurrence, 2 W_x.x from the lower layer's bf16 outputs, 3 x.d from the bf16 delta array,
  * 4 weight-gradient product from contraction-major bf16 operands (LDS transpose reads), 5 the forward half as one
- * launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h).  Tests use it to make sure the
+ * launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h), 16 / 17 / 18 the recurrences batched over 16 lines on the
+ * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 21 minibatches whose forward pass the
+ * batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255]; blocking).  Tests use it to make sure the
  * path they mean to cover is the one that ran. */
 int clstm_debug_path_count(int which, long long* out_h);
 /* Experiment switches of the library (clstm_amd/csrc/dbgopt.h: the table of names and defaults, e.g. "gemm_stag", "bwd_c32",

@@ -6,7 +6,9 @@ uw3 architecture on it exactly as a user would (`clstmocrtrain batch=64`, 1,000 
 device), saves the model through the clstm.proto writer, and then EVERY line of the corpus is decoded three ways on that saved
 model:
   * `clstmocr` (the drop-in CLI, clstmocr.cc:56-111) -- text files next to the images,
-  * the C ABI's network (default arithmetic and clstm_net_set_strict_f32) on the normalised frames,
+  * the C ABI's network (default arithmetic, clstm_net_set_strict_f32, and the recurrence batched over 16 lines on the f16 MFMA
+    -- csrc/lstm_mfma.h, forced with fwd_mfma = 2: in launches of 64 lines and as ONE launch of all 512 ragged lines) on the
+    normalised frames,
   * the oracle (oracle/clstm_oracle.c: forward of clstm.cc:600-621 + trivial_decode of ctc.cc:159-190) on the same frames
     and the same parameters.
 Required: 0 mismatching decodes (class sequences bit-identical, BASELINE.json north_star), and a model that is really in the
@@ -108,6 +110,29 @@ def test_corpus_decodes_identical_to_oracle(trained_corpus, ora32, tmp_path):
             net.forward()
             out += [c.tolist() for c in net.decode()]
         got[mode] = out
+    # ... and the batched forward kernel (the default from 640 lines per launch on), forced: the path counter proves it ran
+    import ctypes
+    lib = net.lib
+
+    def count(which):
+        c = ctypes.c_longlong(0)
+        lib.call("clstm_debug_path_count", which, ctypes.byref(c))
+        return c.value
+    try:
+        lib.call("clstm_debug_set_option", b"fwd_mfma", 2)
+        net = Network(ni, nh, nc)
+        net.set_params(params)
+        for mode, step in (("mfma_64", 64), ("mfma_one_launch", len(frames))):
+            before, routed, out = count(16), count(21), []
+            for i in range(0, len(frames), step):
+                net.set_inputs(frames[i:i + step])
+                net.forward()
+                out += [c.tolist() for c in net.decode()]
+            assert count(16) == before + (len(frames) + step - 1) // step, "the batched forward kernel did not run (%s)" % mode
+            assert count(21) == routed, "the batched forward kernel handed a launch to the per-line kernels (%s)" % mode
+            got[mode] = out
+    finally:
+        lib.call("clstm_debug_set_option", None, 0)
 
     mism = {m: [i for i in range(len(names)) if got[m][i] != want[i]] for m in got}
     cli_mism = [i for i in range(len(names)) if cli_text[i] != "".join(chr(codec[c]) for c in want[i])]
@@ -119,6 +144,31 @@ def test_corpus_decodes_identical_to_oracle(trained_corpus, ora32, tmp_path):
                      % (len(names), sum(len(x) for x in frames), min(len(x) for x in frames), max(len(x) for x in frames), UPDATES,
                         len(mism["default"]), len(mism["strict_f32"]), len(cli_mism), nonempty, cer))
     assert mism["default"] == [] and mism["strict_f32"] == [], mism
+    # the batched kernel: 0 mismatches required.  A mismatching line is reported with its smallest top-2 posterior gap under the
+    # float64 oracle and excused only if it is near a tie -- gap < 16 x max |outputs32 - outputs64| over the corpus (the rule of
+    # tests/test_mfma_bench_shapes.py::run_sampled) -- and such lines are at most 1 % of the corpus
+    bad = sorted(set(mism["mfma_64"]) | set(mism["mfma_one_launch"]))
+    sys.stderr.write("corpus: mismatching decodes vs oracle through the batched f16 MFMA forward kernel: launches of 64 lines %d, one launch "
+                     "of %d lines %d\n" % (len(mism["mfma_64"]), len(frames), len(mism["mfma_one_launch"])))
+    if bad:
+        from oracle.oracle import Oracle
+        r64 = OracleNet(Oracle("f64"), ni, nh, nc, init=False)
+        r64.set_params(params.astype(np.float64))
+        e_out, gaps = 0.0, {}
+        for i, x in enumerate(frames):
+            ref.set_inputs(x)
+            o32 = ref.forward()[:, 0, :]
+            r64.set_inputs(x)
+            o64 = r64.forward()[:, 0, :]
+            e_out = max(e_out, float(np.abs(o32 - o64).max()))
+            if i in bad:
+                top = np.sort(o64, axis=1)
+                gaps[i] = float((top[:, -1] - top[:, -2]).min())
+        for i in bad:
+            sys.stderr.write("corpus: line %d differs through the batched kernel: smallest top-2 gap under the float64 oracle %.3g "
+                             "(near a tie below %.3g)\n" % (i, gaps[i], 16.0 * e_out))
+        assert all(gaps[i] < 16.0 * e_out for i in bad), {i: gaps[i] for i in bad}
+        assert len(bad) <= 0.01 * len(names), bad
     assert got["default"] == got["strict_f32"]
     assert cli_mism == [], [(cli_text[i], want[i]) for i in cli_mism[:3]]
     assert nonempty >= 0.9 * len(names) and cer < 0.1, (nonempty, cer)     # trained regime, not the near-uniform start

@@ -163,6 +163,23 @@ def test_full_bench_shape_trained_weights_real_line_crops(ora32, shape, strict):
     No float32 implementation (Eigen's included) can be held closer to another than both are to exact arithmetic, so the
     floor is 3 x max |oracle32 - oracle64| of that array (never below 1e-5), and the referee check is explicit: the HIP
     activations must be as close to the float64 oracle as the float32 oracle's are (within 3x + 1e-6; both printed)."""
+    _trained_crops_case(ora32, shape, strict, forced_mfma=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["fixed", "ragged"])
+@pytest.mark.parametrize("strict", [False, True])
+def test_full_bench_shape_trained_weights_forced_batched_kernels(ora32, shape, strict):
+    """The SAME 64 crops, weights, bars and referee check as the test above through the other kernel family: the recurrences
+    batched over 16 lines on the MFMA (lstm_mfma.h f16 x 2, lstm_mfma_bwd.h bf16 x 2; the default from 640 lines per GPU on),
+    forced with fwd_mfma = 2 / bwd_mfma = 2 -- path counters 16 / 17 must move.  strict: the forced option wins over
+    clstm_net_set_strict_f32 (include/clstm_abi.h), which then still selects the f32 MFMA for the weight-gradient products.
+    The 640-line minibatches by the library's own rule: tests/test_mfma_bench_shapes.py."""
+    _trained_crops_case(ora32, shape, strict, forced_mfma=True)
+
+
+def _trained_crops_case(ora32, shape, strict, forced_mfma):
+    import ctypes
     from common import Backend, oracle_minibatch
     from oracle.oracle import Oracle, OracleNet
     from test_net_parity import run_case
@@ -188,17 +205,36 @@ def test_full_bench_shape_trained_weights_real_line_crops(ora32, shape, strict):
     g_tol = max(1e-3, 3.0 * rel(o32["derivs"], ex["derivs"]))
     print("trained %s: float32 oracle vs float64 oracle: gradient %.3g of max, gate deltas up to %.3g of a line's max"
           % (shape, rel(o32["derivs"], ex["derivs"]), max(d_tol.values()) / 3.0))
-    net, _ = run_case(Backend("hip"), ora32, NI, NH, NC, T, lr=1e-4, ctc_rtol=1e-3, grad_tol=g_tol, params=params, lines=lines,
-                      trs=trs, strict_f32=strict, act_atol={k: max(1e-5, 3.0 * e_ora[k]) for k in keys}, delta_tol=d_tol)
-    net2 = net.__class__(NI, NH, NC, lib=net.lib)        # (run_case's net has been updated: a fresh forward pass)
-    net2.set_params(params)
-    net2.set_inputs(lines)
-    net2.forward()
-    for k in keys:
-        got = net2.split(net2.state(*k))
-        e_hip = max(float(np.abs(got[b] - exact[k][b]).max()) for b in range(len(T)))
-        print("trained %s %s: max |hip - f64| %.3g, max |oracle32 - f64| %.3g" % (shape, k, e_hip, e_ora[k]))
-        assert e_hip <= 3.0 * e_ora[k] + 1e-6, (k, e_hip, e_ora[k])
+    be = Backend("hip")
+
+    def count(which):
+        out = ctypes.c_longlong(0)
+        be.lib.call("clstm_debug_path_count", which, ctypes.byref(out))
+        return out.value
+    try:
+        if forced_mfma:
+            be.lib.call("clstm_debug_set_option", b"fwd_mfma", 2)
+            be.lib.call("clstm_debug_set_option", b"bwd_mfma", 2)
+        before, routed = (count(16), count(17)), count(21)
+        net, _ = run_case(be, ora32, NI, NH, NC, T, lr=1e-4, ctc_rtol=1e-3, grad_tol=g_tol, params=params, lines=lines,
+                          trs=trs, strict_f32=strict, act_atol={k: max(1e-5, 3.0 * e_ora[k]) for k in keys}, delta_tol=d_tol)
+        net2 = net.__class__(NI, NH, NC, lib=net.lib)        # (run_case's net has been updated: a fresh forward pass)
+        net2.set_params(params)
+        net2.set_inputs(lines)
+        net2.forward()
+        after = count(16), count(17)
+        assert count(21) == routed, "the batched forward kernel handed the minibatch to the per-line kernels"
+        if forced_mfma:
+            assert after == (before[0] + 2, before[1] + 1), "the batched kernels did not run: %s -> %s" % (before, after)
+        else:
+            assert after == before, "64 lines took the batched kernels: %s -> %s" % (before, after)
+        for k in keys:
+            got = net2.split(net2.state(*k))
+            e_hip = max(float(np.abs(got[b] - exact[k][b]).max()) for b in range(len(T)))
+            print("trained %s%s %s: max |hip - f64| %.3g, max |oracle32 - f64| %.3g" % (shape, " (batched kernels)" if forced_mfma else "", k, e_hip, e_ora[k]))
+            assert e_hip <= 3.0 * e_ora[k] + 1e-6, (k, e_hip, e_ora[k])
+    finally:
+        be.lib.call("clstm_debug_set_option", None, 0)
 
 
 @pytest.mark.gpu
@@ -647,14 +683,16 @@ def test_fused_launches_randomised_stress(seed):
 
 
 # ---- trajectories at the bench shapes, the chip-filling minibatch, the one-call step ------------------
-def _trajectory(ora, ni, nh, nc, Ts, L, scale, nsteps, lr, mom, one_call, precision=0, seed=70, grad_tol=1e-3):
+def _trajectory(ora, ni, nh, nc, Ts, L, scale, nsteps, lr, mom, one_call, precision=0, seed=70, grad_tol=1e-3, nthreads=None, on_step=None):
     """`nsteps` consecutive minibatch updates (a fresh synthetic minibatch every step, momentum carried) on the GPU and in the
     oracle (reference semantics: every line an independent fwd/CTC/bwd accumulating into Params.d on top of the carried
     mom * d, then ONE sgd_update -- clstmhl.h:201-223, clstm.cc:201-217, clstm_compute.cc:553-563; OpenMP over lines).
     Every step: the CTC argmax decodes of all lines IDENTICAL; afterwards the parameters within the tolerance the accepted
     gradient tolerance implies -- a gradient accepted within grad_tol of its largest entry moves d by that, and v by lr x the
     accumulated d error: after step k (1-based) sum_{j<=k} sum_{i<=j} mom^(j-i) of them -- and the momentum buffer within
-    grad_tol of ITS largest entry times the same geometric factor."""
+    grad_tol of ITS largest entry times the same geometric factor.
+    `nthreads`: host threads of the oracle (default: one per CPU of the machine); `on_step(step, net)`: called behind every
+    step's checks.  Returns the GPU net."""
     import torch
     from common import Backend, synth_lines
     from clstm_amd.init import init_params
@@ -673,7 +711,7 @@ def _trajectory(ora, ni, nh, nc, Ts, L, scale, nsteps, lr, mom, one_call, precis
     for step in range(1, nsteps + 1):
         lines = synth_lines(rng, Ts, ni)
         trs = [rng.integers(1, nc, L).astype(np.int32) for _ in Ts]
-        want = ref.minibatch(lines, trs)
+        want = ref.minibatch(lines, trs, nthreads=nthreads)
         gmax = float(np.abs(want["derivs"]).max())          # (Params.d right before the update: carried momentum + this minibatch)
         ref.update()
         if one_call:                                         # what the bench times: clstm_net_train_step, inputs resident in HBM
@@ -690,7 +728,10 @@ def _trajectory(ora, ni, nh, nc, Ts, L, scale, nsteps, lr, mom, one_call, precis
                      what="parameters after step %d" % step)
         assert_close(net.get_derivs(), ref.get_derivs(), rtol=grad_tol, atol=1e-9, scale_atol=d_fac * grad_tol,
                      what="momentum buffer after step %d" % step)
+        if on_step is not None:
+            on_step(step, net)
     lib.call("clstm_synchronize")
+    return net
 
 
 @pytest.mark.gpu

@@ -3,7 +3,13 @@
 -m gpu only: the kernels exist for gfx950 alone (the host emulator keeps the per-line kernels).  The path is forced onto small
 minibatches (experiment switch fwd_mfma=2; the default takes it from 640 lines per GPU on); `run_case` then checks EVERY saved
 activation (gi, gf, go, ci, c, h of both directions, 1e-4 relative: BASELINE.json north_star), the softmax outputs, bit-exact
-decodes, CTC, every gate delta, the minibatch gradient and the update -- and the path counter proves the MFMA kernel really ran.
+decodes, CTC, every gate delta, the minibatch gradient and the update -- and the path counters prove the MFMA kernel really ran
+(16 / 17 / 18 launched; 21, counted on the device, stays: no minibatch here is handed to the per-line kernels for its inputs).
+What lives elsewhere: the sizes the batched kernels are the default for (640 / 2048 lines x 200 frames, the trained regime, the
+one-call step, trajectories across the 640-line rule), the variants (unidirectional, input deltas, stacked, 64 / 128 cells at 200
+frames), inputs outside [0, 1] and clstm_net_set_strict_f32 at 640 lines: tests/test_mfma_bench_shapes.py; the trained weight set
+on 64 crops through both kernel families: tests/test_gpu_e2e.py; corpus decodes through the batched forward kernel:
+tests/test_corpus_decode.py.
 Reference semantics: /root/reference/clstm.cc:600-653, clstm_compute.cc:275-320,504-547."""
 import ctypes
 
@@ -25,6 +31,13 @@ def _count(backend, which):
     out = ctypes.c_longlong(0)
     backend.lib.call("clstm_debug_path_count", which, ctypes.byref(out))
     return out.value
+
+
+@pytest.fixture(autouse=True)
+def _computed_by_the_batched_kernel(backend):
+    before = _count(backend, 21)
+    yield
+    assert _count(backend, 21) == before, "the batched forward kernel handed a minibatch to the per-line kernels"
 
 
 @pytest.mark.parametrize("nh,T", [
