@@ -91,6 +91,9 @@ _SIGS = {
     "clstm_net_update": [_P],
     "clstm_net_decode": [_P, _P, _P, _P],
     "clstm_net_get_state_h": [_P, _I, _I, _I, _P],
+    "clstm_net_predict": [_P, _P, _I, _P, _P, _P, _P, _P],
+    "clstm_net_predict_h": [_P, _P, _I, _P, _P, _P, _P, _P],
+    "clstm_net_device_bytes": [_P, _P],
     "clstm_net_enable_timing": [_P, _I],
     "clstm_net_kernel_time_ms": [_P, C.c_char_p, _P, _P],
     "clstm_net_reset_timing": [_P],
@@ -113,6 +116,7 @@ _SIGS = {
     "clstm_net_replica_check": [_P],
     "clstm_net_set_training": [_P, _I],
     "clstm_net_set_overlap": [_P, _I],
+    "clstm_net_get_overlap": [_P, _P],
     "clstm_net_set_strict_f32": [_P, _I],
     "clstm_net_overlap_stats": [_P, _P, _P],
     "clstm_debug_lane_ops": [_P],

@@ -2,6 +2,9 @@
 // training step, communicator, debug hooks).  Included once by clstm_hip.hip behind the namespace.
 using namespace clstm;
 struct clstm_net {
+  // bytes held by the grow-only buffers of the members below (runtime.inc: AcctScope).  Declared first = destroyed last: the buffers
+  // report their release to it
+  std::unique_ptr<size_t> dev_bytes;
   Net net;
   CtcWorkspace ctc;
   DecodeWorkspace dec;
@@ -10,6 +13,7 @@ struct clstm_net {
 #define EW(kernel, len, ...) \
   CLSTM_LAUNCH(kernel, dim3(nblocks(len)), dim3(256), 0, g_stream, __VA_ARGS__); check_launch();
 
+#define REFUSE_NOSAVE(h, what) REQUIRE(!(h)->net.nosave, what ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)")
 extern "C" {
 
 const char* clstm_last_error(void) { return g_err.c_str(); }
@@ -154,7 +158,11 @@ int clstm_net_nparams_for(const clstm_net_desc* ds) {
 int clstm_net_create(clstm_net** out, const clstm_net_desc* ds, float* pv, float* pd, float* pg) {
   ABI_BEGIN
   REQUIRE(out && ds, "null argument");
-  clstm_net* h = new clstm_net();
+  size_t* bytes = new size_t(0);
+  AcctScope acct_(bytes);   // every DevBuf constructed from here to the end of build() reports to this net's counter
+  clstm_net* h = nullptr;
+  try { h = new clstm_net(); } catch (...) { delete bytes; throw; }
+  h->dev_bytes.reset(bytes);
   try { h->net.build(*ds, pv, pd, pg); } catch (...) { delete h; throw; }
   *out = h;
   ABI_END
@@ -191,6 +199,7 @@ int clstm_net_set_inputs_h(clstm_net* h, const float* x) {
   ABI_BEGIN
   REQUIRE(h->net.N > 0, "set_batch first");
   h->net.next.valid = false;   // (a declared next minibatch whose frames the caller replaces is not that minibatch any more)
+  h->net.ensure_training_buffers();
   copy_h2d(h->net.X.p, x, (size_t)h->net.N * h->net.desc.ninput);
   h->net.src0_ready = false;
   ABI_END
@@ -198,6 +207,7 @@ int clstm_net_set_inputs_h(clstm_net* h, const float* x) {
 static void net_set_inputs_d(clstm_net* h, const float* x, const CtcMetaCopy* aux = nullptr) {
   Net& n = h->net;
   REQUIRE(n.N > 0, "set_batch first");
+  n.ensure_training_buffers();   // (the ingest writes layer 0's source rows)
   RoctxRange range_("clstm:ingest");
   Layer& y = n.L[0];
   bool aux_done = false;
@@ -247,7 +257,7 @@ int clstm_net_outputs(clstm_net* h, float** p, float** d) {
   return 0;
 }
 int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)"); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
-int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
+int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN REFUSE_NOSAVE(h, "clstm_net_set_output_deltas_h"); copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
 static void net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h, CtcMetaCopy* defer = nullptr,
                     bool launch = true) {
   Net& n = h->net;
@@ -284,13 +294,15 @@ static void net_ctc_launch(clstm_net* h) {
 int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h) {
   ABI_BEGIN
   REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
+  REFUSE_NOSAVE(h, "clstm_net_ctc");
   net_ctc(h, labels_h, L_h, aligned_h);
   ABI_END
 }
-int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }
+int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)"); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }
 int clstm_net_enable_input_deltas(clstm_net* h, int on) { h->net.want_dx0 = on != 0; return 0; }
 int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
   ABI_BEGIN
+  REFUSE_NOSAVE(h, "clstm_net_get_input_deltas_h");
   REQUIRE(h->net.want_dx0 && h->net.dX0.p, "input deltas not enabled / no backward yet");
   copy_d2h(dx, h->net.dX0.p, (size_t)h->net.N * h->net.desc.ninput);
   ABI_END
@@ -304,11 +316,43 @@ int clstm_net_decode(clstm_net* h, int* cls, int* locs, int* cnt) {
   run_decode(h->dec, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, cls, locs, cnt, g_stream);
   ABI_END
 }
+// ---- recognition: CLSTMOCR::predict for a whole minibatch in one call (include/clstm_abi.h) ------------------------
+static void net_predict(clstm_net* h, const int* T_h, int bs, const float* x, bool x_host, int* cls, int* locs, float* conf, int* cnt) {
+  REQUIRE(h && T_h && x && cnt && bs > 0, "null argument (counts_h is required)");
+  Net& n = h->net;
+  n.set_batch_predict(T_h, bs);   // (validates T_h / bs before it touches the net; drops a minibatch declared by clstm_net_train_step_next)
+  // the frames into the net's input block: no ingest launch -- that one writes layer 0's source rows, which predict does not have
+  const size_t nx = (size_t)n.N * n.desc.ninput;
+  if (x_host) HIPCHECK(hipMemcpyAsync(n.X.p, x, nx * sizeof(float), hipMemcpyHostToDevice, g_stream));
+  else {   // device frames: one launch, the line offsets riding it (ops.h: k_ingest_predict)
+    const int nbx = nblocks(nx);
+    CLSTM_LAUNCH(k_ingest_predict, dim3(nbx + (n.lo_pending ? 1 : 0)), dim3(256), 0, g_stream, x, n.X.p, nx, nbx,
+                 n.lo_pending ? n.lo_stage : (const int*)nullptr, n.line_off.p, 2 * n.bs + 1);
+    check_launch();
+    if (n.lo_pending) { n.ring.commit(g_stream); n.lo_pending = false; }
+  }
+  n.predict();
+  run_decode(h->dec, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, cls, locs, cnt, g_stream, conf);
+  // (as clstm_net_decode: the device error words are left to the next synchronisation point of the training loop)
+}
+int clstm_net_predict(clstm_net* h, const int* T_h, int bs, const float* x_d, int* cls, int* locs, float* conf, int* cnt) {
+  ABI_BEGIN net_predict(h, T_h, bs, x_d, false, cls, locs, conf, cnt); ABI_END
+}
+int clstm_net_predict_h(clstm_net* h, const int* T_h, int bs, const float* x_h, int* cls, int* locs, float* conf, int* cnt) {
+  ABI_BEGIN net_predict(h, T_h, bs, x_h, true, cls, locs, conf, cnt); ABI_END
+}
+int clstm_net_device_bytes(clstm_net* h, long long* bytes) {
+  ABI_BEGIN
+  REQUIRE(h && bytes, "null argument");
+  *bytes = (long long)(h->net.fixed_bytes + *h->dev_bytes);
+  ABI_END
+}
 int clstm_net_get_state_h(clstm_net* h, int layer, int dir, int which, float* out) {
   ABI_BEGIN
   REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
   Net& n = h->net;
   REQUIRE(layer >= 0 && layer < (int)n.L.size() && dir >= 0 && dir < n.ndir && which >= 0 && which <= 9, "bad state selector");
+  if (which != 5) REFUSE_NOSAVE(h, "clstm_net_get_state_h (which != 5)");
   Layer& y = n.L[layer];
   n.tmp.reserve((size_t)n.N * y.no);
   if (which >= 6) n.ensure_delta_f32(layer);   // (a persistent bf16 backward pass leaves the deltas as bf16 only)
@@ -580,6 +624,7 @@ static long long states_total(const Net& n, int T) {
 int clstm_net_n_states(clstm_net* h, long long* out) {
   ABI_BEGIN
   REQUIRE(out, "null argument");
+  REFUSE_NOSAVE(h, "clstm_net_n_states");
   *out = states_total(h->net, states_T(h->net));
   ABI_END
 }
@@ -641,6 +686,7 @@ static void states_transfer(clstm_net* h, float* data, long long total, bool get
 int clstm_net_get_states_h(clstm_net* h, float* data, long long total) {
   ABI_BEGIN
   REQUIRE(data, "null argument");
+  REFUSE_NOSAVE(h, "clstm_net_get_states_h");
   states_transfer(h, data, total, true);
   ABI_END
 }
@@ -730,6 +776,12 @@ int clstm_net_set_strict_f32(clstm_net* h, int on) {
     n.split_terms = dbg_opt("split_terms");
   }
   n.packed_dirty = true;   // (the hi | lo weights of the f32-grade backward recurrence are only packed while that mode is on)
+  ABI_END
+}
+int clstm_net_get_overlap(clstm_net* h, int* mode) {
+  ABI_BEGIN
+  REQUIRE(h && mode, "null argument");
+  *mode = h->net.overlap;
   ABI_END
 }
 int clstm_net_overlap_stats(clstm_net* h, long long* launches, int* timeouts) {

@@ -34,6 +34,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>

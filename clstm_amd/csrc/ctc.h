@@ -1298,9 +1298,10 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* P, int* idx, f
 }
 
 // trivial_decode (ctc.cc:159-190): one wave per line; 64 frames are loaded at once and replayed
-// through the run-length state machine with wave-uniform lane reads.
+// through the run-length state machine with wave-uniform lane reads.  out_val (may be null): the peak value of every emitted
+// class = the softmax output at (out_loc, out_cls), what CLSTMOCR::predict reports as CharPrediction::p (clstmhl.h:259-281).
 __global__ __launch_bounds__(64) void decode_kernel(const int* idx, const float* val, const int* line_off,
-                                                     int* out_cls, int* out_loc, int* out_cnt) {
+                                                     int* out_cls, int* out_loc, int* out_cnt, float* out_val = nullptr) {
   const int b = blockIdx.x, lane = threadIdx.x & 63;
   const int off = line_off[b], T = line_off[b + 1] - off;
   int n = 0;
@@ -1317,7 +1318,7 @@ __global__ __launch_bounds__(64) void decode_kernel(const int* idx, const float*
       if (k < cnt) {
         if (index == 0) {
           if (mc != -1 && mc != 0) {
-            if (lane == 0) { out_cls[off + n] = mc; out_loc[off + n] = mt; }
+            if (lane == 0) { out_cls[off + n] = mc; out_loc[off + n] = mt; if (out_val) out_val[off + n] = mv; }
             n++;
           }
           mv = 0.0f; mc = -1; mt = -1;

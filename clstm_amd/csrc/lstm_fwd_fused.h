@@ -261,7 +261,8 @@ DEVFN void fwd_fused_helper(const LstmSeqArgs& a, const FwdFusedArgs& h, const i
   }
 }
 
-template <int NK4, int KU>
+// SAVE = false: the recurrence role in its no-save form (lstm_seq.h); producers and consumers are the same code
+template <int NK4, int KU, bool SAVE = true>
 __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_fused_kernel(FwdFusedKernelArgs k) {
   if ((int)blockIdx.x < k.h.nrec) {
 #ifndef CLSTM_HIP_EMU
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_fu
 #endif
     const int bl = (int)blockIdx.x % k.a.bs;
     const long long t0 = k.h.trace ? wall_clock() : 0;
-    lstm_fwd_body<NK4, KU, true>(k.a, k.a.order ? k.a.order[bl] : bl, (int)blockIdx.x / k.a.bs, &k.h);
+    lstm_fwd_body<NK4, KU, true, SAVE>(k.a, k.a.order ? k.a.order[bl] : bl, (int)blockIdx.x / k.a.bs, &k.h);
     if (k.h.trace && threadIdx.x == 0) { k.h.trace[blockIdx.x * 4] = t0; k.h.trace[blockIdx.x * 4 + 2] = wall_clock(); }
   } else {
     fwd_fused_helper(k.a, k.h, (int)blockIdx.x - k.h.nrec);

@@ -47,6 +47,17 @@
 // conflict-free for the epilogue's per-tile writes and for the row reads going out) that is double-buffered, and leave -- spread
 // over the NEXT step's MFMA stream, so that the memory pipeline drains beside the matrix pipe instead of in front of it.  One
 // barrier per step.
+//
+// No-save form (SAVE = false; recognition, Net::predict).  The same arithmetic, expression for expression; of the 28 B per
+// cell-step above (16 B activations, 4 B c, 4 B h, 4 B source row) only the 4 B of h leave.  No store_g, no c store, no S store,
+// no h_{-1} = 0 row; the epilogue writes h alone into a row image that holds h alone: [line][cell] f32, 16 NO 4 bytes per buffer
+// instead of 16 (RS + 8 NO).  Dynamic LDS, training -> no-save: 64 cells 65,600 -> 24,640 B, 100 cells 113,728 -> 43,584 B.
+// a.G / a.C / a.S / a.dH / a.D are not addressed (Net::predict does not even reserve C and S).  The input-range decision and the
+// routed twins are the same; the twins run the per-line kernels' own no-save form.  Outputs (H) are bit-identical to the training
+// form's.  Instantiated for 64 and 100 cells.  NOT for 128 cells: its 192 fragment registers do not fit the 128 AGPRs the pins
+// ask for, the training form already spills (840 bytes of scratch per lane) and the no-save form still does (576; 41,024 B of
+// LDS) -- a kernel with scratch on its step chain is not shipped as new code; predict runs the training form for that geometry
+// (EXPERIMENTS.md).
 #pragma once
 #include "devintrin.h"
 #ifndef CLSTM_HIP_EMU
@@ -77,7 +88,7 @@ struct LstmMfmaArgs {
   long long* prof;           // diagnostics build (-DCLSTM_LSTM_PROF): [4 waves][8] summed phase cycles of workgroup (0, 0)
 };
 
-template <int NO, int NI>
+template <int NO, int NI, bool SAVE = true>
 struct MfmaGeom {
   static_assert(NO % 4 == 0 && NO >= 32 && NO <= 128 && NI % 4 == 0 && NI >= 4 && NI <= 64, "cells / inputs");
   static constexpr int NW = 8;                               // waves: two per SIMD -- one wave's epilogue beside the other's MFMAs
@@ -89,7 +100,7 @@ struct MfmaGeom {
   static constexpr int SLOTS = (NO + 15) / 16 * 16;   // 16-byte slots (one per cell) in a staged row of gate values
   static constexpr int RS = SLOTS * 16, RH = (SLOTS + 63) / 64;
   static constexpr int PART = NCH * 256, HBUF = 2 * PART;   // B image: [buffer][hi | lo][chunk of 8 k][16 lines][8 halfs]
-  static constexpr int OUT_OFF = 2 * HBUF, CS_REL = 16 * RS, HS_REL = CS_REL + 16 * NO * 4, OUTSZ = HS_REL + 16 * NO * 4;
+  static constexpr int OUT_OFF = 2 * HBUF, CS_REL = 16 * RS, HS_REL = SAVE ? CS_REL + 16 * NO * 4 : 0, OUTSZ = HS_REL + 16 * NO * 4;   // (no-save: h rows only)
   static constexpr int WS_OFF = OUT_OFF + 2 * OUTSZ;        // the extra tile's A fragments [k-block][hi | lo][lane][16 bytes]
   static constexpr int DUMP_OFF = WS_OFF + EXTRA * KB * 2048;   // where lanes without a datum write
   static constexpr int SMEM = DUMP_OFF + 64;
@@ -202,11 +213,11 @@ __global__ __launch_bounds__(256) void gemm_f32_routed_kernel(GemmOperand A, Gem
     __syncthreads();
   }
 }
-template <int NK4, int KU>
+template <int NK4, int KU, bool SAVE = true>
 __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_routed_kernel(LstmSeqArgs a, const unsigned* xmax, int* routed) {
   if (!mfma_x_routed(xmax, threadIdx.x & 63)) return;
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomic_add_i32(routed, 1);
-  lstm_fwd_body<NK4, KU, false>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
+  lstm_fwd_body<NK4, KU, false, SAVE>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
 }
 
 DEVFN f32x4 mfma16x16x32_f16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
@@ -223,9 +234,9 @@ DEVFN f32x4 buf_load4_s(BufF32 b, unsigned lane_off, unsigned uniform_off) {
 #define MF_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 constexpr int SG_VALU = 0x2, SG_MFMA = 0x8, SG_VMEM_W = 0x40, SG_DS_R = 0x100, SG_DS_W = 0x200;
 
-template <int NO, int NI>
+template <int NO, int NI, bool SAVE = true>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void lstm_fwd_mfma_kernel(LstmMfmaArgs a) {
-  using Gm = MfmaGeom<NO, NI>;
+  using Gm = MfmaGeom<NO, NI, SAVE>;
   constexpr int TW = Gm::TW, NPW = Gm::NPW, LONE = Gm::LONE, EXTRA = Gm::EXTRA, KB = Gm::KB, RH = Gm::RH, RS = Gm::RS, NW = Gm::NW;
   char* const smem = dyn_smem<char>();
   const int tid = threadIdx.x, lane = tid & 63, w = wave_uniform(tid >> 6);
@@ -283,10 +294,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // ---- global side: whole rows, wave w owns lines 2w, 2w + 1 ----
   const unsigned gstr = (unsigned)nd * 4 * NO * 4, cstr = (unsigned)nd * NO * 4, hstr = (unsigned)a.ldh * 4, sstr = (unsigned)a.lds * 4;
   const unsigned xstr = (unsigned)a.ldx * 4;
-  const BufF32 gbuf = make_buf(a.G, (size_t)a.N * gstr);
-  const BufF32 cbuf = make_buf(a.C, (size_t)a.N * cstr);
   const BufF32 hbuf = make_buf(a.H, (size_t)a.N * hstr);
-  const BufF32 sbuf = make_buf(a.S + (size_t)dir * a.sdir, (size_t)a.N * sstr);
+  // (no-save: the three descriptors below cover nothing and are never addressed)
+  const BufF32 gbuf = SAVE ? make_buf(a.G, (size_t)a.N * gstr) : make_buf(a.H, 0);
+  const BufF32 cbuf = SAVE ? make_buf(a.C, (size_t)a.N * cstr) : make_buf(a.H, 0);
+  const BufF32 sbuf = SAVE ? make_buf(a.S + (size_t)dir * a.sdir, (size_t)a.N * sstr) : make_buf(a.H, 0);
   const BufF32 xbuf = make_buf(a.X, (size_t)a.N * xstr);
   unsigned gvo[RH];   // gate rows: lane = cell (16 bytes) within the half row
 #pragma unroll
@@ -346,6 +358,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // outputs of a step leave as rows during the next one: activations (G), c, h (H and, shifted by one frame, the source rows S);
   // each portion reads its rows from the LDS image right in front of its stores
   auto store_g = [&](const char* out, const int tp, const int j) {   // the activation row of line 2w + j
+    if constexpr (!SAVE) { (void)out; (void)tp; (void)j; return; }
     const int row = 2 * w + j;
     f32x4 av[RH];
 #pragma unroll
@@ -358,19 +371,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   auto store_ch = [&](const char* out, const int tp) {  // c, h of lines 2w, 2w + 1
     const int lo = l5 < NO / 4 ? l5 : 0;
-    const f32x4 cv = *reinterpret_cast<const f32x4*>(out + Gm::CS_REL + rrow * NO * 4 + lo * 16);
+    f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SAVE) cv = *reinterpret_cast<const f32x4*>(out + Gm::CS_REL + rrow * NO * 4 + lo * 16);
     const f32x4 hv = *reinterpret_cast<const f32x4*>(out + Gm::HS_REL + rrow * NO * 4 + lo * 16);
     const unsigned bad = oob_lane(tp, Tr) | (unsigned)(tp >> 31 & 0x80000000);
     const unsigned tok = (unsigned)(offr + (dir == 0 ? tp : Tr - 1 - tp));
-    buf_store4(cbuf, (tok * cstr + (unsigned)dir * NO * 4u + chl) | bad, cv);
+    if constexpr (SAVE) buf_store4(cbuf, (tok * cstr + (unsigned)dir * NO * 4u + chl) | bad, cv);
     buf_store4(hbuf, (tok * hstr + (unsigned)(a.hofs + dir * NO) * 4u + chl) | bad, hv);
     // h_t is the recurrent part of the NEXT step's source row (forward_stack_delay, clstm_compute.cc:377-397)
-    const unsigned bads = oob_lane(tp + 1, Tr) | (unsigned)(tp >> 31 & 0x80000000) | s_off_mask;
-    const unsigned toks = (unsigned)(offr + (dir == 0 ? tp + 1 : Tr - 2 - tp));
-    buf_store4(sbuf, (toks * sstr + (unsigned)a.sofs * 4u + chl) | bads, hv);
+    if constexpr (SAVE) {
+      const unsigned bads = oob_lane(tp + 1, Tr) | (unsigned)(tp >> 31 & 0x80000000) | s_off_mask;
+      const unsigned toks = (unsigned)(offr + (dir == 0 ? tp + 1 : Tr - 2 - tp));
+      buf_store4(sbuf, (toks * sstr + (unsigned)a.sofs * 4u + chl) | bads, hv);
+    }
   };
   // h_{-1} = 0 in the first source row of every line (forward_stack_delay with last < 0)
-  {
+  if constexpr (SAVE) {
     const unsigned tok = (unsigned)(offr + (dir == 0 ? 0 : Tr - 1));
     buf_store4(sbuf, a.store_s && Tr > 0 ? tok * sstr + (unsigned)a.sofs * 4u + chl : BUF_OOB, (f32x4){0.f, 0.f, 0.f, 0.f});
   }
@@ -445,8 +461,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const float c = fmaf(gf, cprev[i], ci * gi);
       const float h = go * tanh_fast(c);
       cprev[i] = c;
-      *reinterpret_cast<f32x4*>(outw + gxo[i]) = (f32x4){gi, gf, go, ci};
-      *reinterpret_cast<float*>(outw + Gm::CS_REL + cho + 4 * cellv[i]) = c;
+      if constexpr (SAVE) {
+        *reinterpret_cast<f32x4*>(outw + gxo[i]) = (f32x4){gi, gf, go, ci};
+        *reinterpret_cast<float*>(outw + Gm::CS_REL + cho + 4 * cellv[i]) = c;
+      }
       *reinterpret_cast<float*>(outw + Gm::HS_REL + cho + 4 * cellv[i]) = h;
       return h * (float)(1 << MF_HS);   // the next step's B operand: two f16 terms of 2^8 h
     };
@@ -484,7 +502,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       A0 = N0; A1 = N1;
       MF_STAMP(2 + (u < 2 ? u : 2));
     }
-    if (LONE) {
+    if constexpr (LONE && EXTRA && !SAVE) {
+      // (no-save: the lone tile's epilogue is common code and the extra tile's state is touched in one place only.  In the form below
+      //  hipcc merges the two branches' last epilogues, selects between cprev[TW - 1] and cprev[TW] by POINTER and keeps those
+      //  arrays in scratch: 40 bytes per lane in the training form, which stays as it was measured.)
+      if (NPW == 1) store_ch(outr, t - 1);
+      const bool xt = w == NW - 1;   // the last wave: the extra tile, fragments from LDS
+      f32x4 X0 = {0.f, 0.f, 0.f, 0.f}, X1 = X0;
+      if (xt) {
+#pragma unroll
+        for (int kb = 0; kb < KB; kb++) {
+          const f16x8 sh = *reinterpret_cast<const f16x8*>(smem + Gm::WS_OFF + kb * 2048 + lane * 16);
+          const f16x8 sl = *reinterpret_cast<const f16x8*>(smem + Gm::WS_OFF + kb * 2048 + 1024 + lane * 16);
+          f32x4& ax = (kb & 1) ? X1 : X0;   // (mm1's two chains, summed behind the lone tile's epilogue)
+          ax = mfma16x16x32_f16(sl, Bh[kb], ax);
+          ax = mfma16x16x32_f16(sh, Bl[kb], ax);
+          ax = mfma16x16x32_f16(sh, Bh[kb], ax);
+        }
+      }
+      put_h1(TW - 1, epi(TW - 1, A0));
+      if (xt) put_h1(TW, epi(TW, X0 + X1));
+    } else if (LONE) {
       if (NPW == 1) store_ch(outr, t - 1);
       store_g(outr, t - 1, 1);
       if (EXTRA && w == NW - 1) {   // the last wave: the extra tile, fragments from LDS

@@ -76,6 +76,9 @@ struct LstmSeqArgs {
 #else
 #define CLSTM_TWO_WAVES_PER_SIMD __attribute__((amdgpu_waves_per_eu(1, 2)))
 #endif
+#ifndef CLSTM_NOSAVE_EARLY_WAVES
+#define CLSTM_NOSAVE_EARLY_WAVES 4
+#endif
 constexpr int lstm_qstride(int nk4) { return 4 * nk4 + ((nk4 & 1) ? 0 : 4); }
 
 // NK4: float4 groups of k per lane (register / LDS capacity 4*NK4); KU <= 4*NK4: k values a lane really
@@ -92,10 +95,16 @@ constexpr int lstm_qstride(int nk4) { return 4 * nk4 + ((nk4 & 1) ? 0 : 4); }
 //    store with its own address and data: at the flush of step tp it writes that iterations < tp - 2 are complete
 //    (every wave has passed the barrier of step tp, i.e. has waited for a load it issued behind its stores of step
 //    tp - 3; VMEM operations of a wave complete in order), exactly as the backward kernel reports its deltas.
+//
+// SAVE = false (recognition, Net::predict): the same recurrence, expression for expression, that leaves only what a forward
+// pass without a backward pass behind it reads -- h.  Gone are the activation store over the pre-activations in G (which stay
+// what the hoisted product / the producers wrote), the c store and the h_{t-1} deposit in the source rows S (the h_{-1} = 0 row
+// included), and with them two of the three store-data pins.  The pre-activation loads, the fused launch's chunk polling and
+// its progress word on the H store are unchanged; outputs are bit-identical to SAVE = true.  a.C and a.S may be null.
 struct FwdFusedArgs;
 // (lstm_fwd_fused.h) the workgroup computes the gate pre-activations of its own first 16 iterations
 DEVFN void fwd_self_produce(const LstmSeqArgs& a, const FwdFusedArgs& h, int b, int dir, int off, int T);
-template <int NK4, int KU, bool FUSED>
+template <int NK4, int KU, bool FUSED, bool SAVE = true>
 DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const FwdFusedArgs* fh = nullptr) {
   constexpr int KQP = 4 * NK4;
   constexpr int QS = KQP + ((NK4 & 1) ? 0 : 4);
@@ -127,7 +136,7 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
   // lane part + wave-uniform frame part, masked lanes sit at BUF_OOB_BASE
   const unsigned gstride4 = (unsigned)nd * 4 * no * 4, cstride4 = (unsigned)nd * no * 4;
   const BufF32 gbuf = make_buf(a.G + (size_t)off * (gstride4 / 4), (size_t)T * gstride4);
-  const BufF32 cbuf = make_buf(a.C + (size_t)off * (cstride4 / 4), (size_t)T * cstride4);
+  const BufF32 cbuf = SAVE ? make_buf(a.C + (size_t)off * (cstride4 / 4), (size_t)T * cstride4) : make_buf(a.H, 0);   // (no-save: never addressed)
   const unsigned hstride4 = (unsigned)a.ldh * 4;
   // (fused: the descriptor reaches this line's progress word behind the array)
   const long long prog_rel = FUSED ? a.prog_off + ((long long)dir * a.bs + b) * PROG_STRIDE - (long long)off * a.ldh : 0;
@@ -135,7 +144,7 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
   const bool tagl = FUSED && tid == nthreads - 1;          // requires cell(tid) >= no (checked by the host)
   const unsigned ptag = (unsigned)prog_rel * 4u;
   const unsigned sstride4 = (unsigned)a.lds * 4;
-  const BufF32 sbuf = make_buf(a.S + (size_t)dir * a.sdir + (size_t)off * a.lds, (size_t)T * sstride4);
+  const BufF32 sbuf = SAVE ? make_buf(a.S + (size_t)dir * a.sdir + (size_t)off * a.lds, (size_t)T * sstride4) : make_buf(a.H, 0);
   const unsigned gl = valid ? ((unsigned)dir * 4 * no + cell * 4 + q) * 4u : BUF_OOB_BASE;
   const unsigned cl = lead ? ((unsigned)dir * no + cell) * 4u : BUF_OOB_BASE;
   const unsigned sl = lead ? ((unsigned)a.sofs + cell) * 4u : BUF_OOB_BASE;
@@ -193,7 +202,7 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
   float gxA = gload(gl + fr(0) * gstride4);
   float gxB = gload(gl + fr(1) * gstride4);
   float kaA0 = 0.f, kaA1 = 0.f, kaA2 = 0.f, kaB0 = 0.f, kaB1 = 0.f, kaB2 = 0.f;  // store-data pins
-  buf_store(sbuf, sl + fr(0) * sstride4, 0.0f);  // h_{-1} = 0 (forward_stack_delay, last < 0)
+  if constexpr (SAVE) buf_store(sbuf, sl + fr(0) * sstride4, 0.0f);  // h_{-1} = 0 (forward_stack_delay, last < 0)
   // Touch every value loaded so far HERE.  hipcc otherwise places the wait for the weight loads at their
   // first use inside the time loop -- a static s_waitcnt vmcnt(3) at the top of every step, sized for the
   // first iteration, which in steady state also waits for the previous step's stores (measured: ~80
@@ -224,15 +233,17 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
     constexpr bool REPORT = decltype(report_tag)::value;
     const bool any = tp >= 0;
     const unsigned f = fr(tp < 0 ? 0 : tp);
-    buf_store(gbuf, any ? gl + f * gstride4 : BUF_OOB, pa0);
-    buf_store(cbuf, any ? cl + f * cstride4 : BUF_OOB, pa1);
+    if constexpr (SAVE) {
+      buf_store(gbuf, any ? gl + f * gstride4 : BUF_OOB, pa0);
+      buf_store(cbuf, any ? cl + f * cstride4 : BUF_OOB, pa1);
+    }
     if constexpr (REPORT) {   // (the wave with the reporting lane: address and data by select)
       const float sdat = tagl ? __builtin_bit_cast(float, a.prog_base + (tp - 2 > 0 ? tp - 2 : 0)) : pa2;
       buf_store_wt(hbuf, tagl ? (any ? ptag : BUF_OOB) : (any ? hl + f * hstride4 : BUF_OOB), sdat);
     } else if constexpr (FUSED) buf_store_wt(hbuf, any ? hl + f * hstride4 : BUF_OOB, pa2);
     else buf_store(hbuf, any ? hl + f * hstride4 : BUF_OOB, pa2);
     // h_t is the recurrent part of the NEXT step's source row (dropped after the last step)
-    buf_store(sbuf, any && tp + 1 < T ? sl + fr(tp + 1) * sstride4 : BUF_OOB, pa2);
+    if constexpr (SAVE) buf_store(sbuf, any && tp + 1 < T ? sl + fr(tp + 1) * sstride4 : BUF_OOB, pa2);
   };
   // WHICH side of the barrier a wave stores on depends on its role (measured: the four stores of all seven waves
   // issued together right behind the barrier queue at the texture addresser -- 28 wave-instructions at ~10-16
@@ -240,7 +251,14 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
   // stores at all the kernel runs 91.6 us instead of 115.4).  The first-dispatched waves (one per SIMD, they win the
   // VALU arbitration and then sit ~400 cycles at the barrier) store at the END of their step; the later waves, whose
   // FMAs wait for the older wave of their SIMD anyway, store right behind the barrier.
-  constexpr int EARLY_WAVES = 4;
+  // (Staggered kernels: the split IS the group structure -- waves 0..3 are group A -- and both groups store under their first LDS
+  //  reads.  Kernels of up to four waves: every wave is an early one.  No-save, one store per step instead of four: measured for the
+  //  up-to-four-wave kernels with the build-time knob CLSTM_NOSAVE_EARLY_WAVES -- 64 cells, predict of 256 x 200, two alternations
+  //  of the two builds: every wave storing at the top of its next step (0) 67.33 / 67.31 us per launch, at the end of its step (4,
+  //  kept) 66.42 / 66.43 -- profiles/predict_rate.txt, EXPERIMENTS 13.3.)
+  constexpr int EARLY_WAVES = (SAVE || STAG) ? 4 : CLSTM_NOSAVE_EARLY_WAVES;
+// the store-data pins of a step: the no-save form has one datum (h) to pin
+#define LSTM_PIN3(PIN, x0, x1, x2) do { if constexpr (SAVE) { PIN(x0); PIN(x1); } PIN(x2); } while (0)
   // The two roles are two copies of the whole time loop (one wave-uniform branch in front): inside a copy the
   // stores sit at a fixed place in straight-line code, so hipcc still counts the VMEM queue exactly (a branch
   // inside the step made it wait with vmcnt(1), i.e. for the previous step's stores).
@@ -253,10 +271,10 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
   auto step = [&](const int t, float& gxr, int& rdy, const float* hq, float* hw, float& ka0, float& ka1, float& ka2,
                   float pa0, float pa1, float pa2) {
     if constexpr (!EARLY && !STAG) {
-      KEEP_ALIVE(ka0); KEEP_ALIVE(ka1); KEEP_ALIVE(ka2);  // stores of step t-2 have long completed
+      LSTM_PIN3(KEEP_ALIVE, ka0, ka1, ka2);  // stores of step t-2 have long completed
       flush(t - 1, pa0, pa1, pa2, report_tag);
     }
-    if constexpr (STAG) { KEEP_ALIVE(ka0); KEEP_ALIVE(ka1); KEEP_ALIVE(ka2); }
+    if constexpr (STAG) { LSTM_PIN3(KEEP_ALIVE, ka0, ka1, ka2); }
     f32x2 a01 = splat2(0.0f), a23 = splat2(0.0f);
     LSTM_STAMP(0);   // loop overhead since the barrier
     // (hipcc copies element w of every ds_read_b128 into a fresh pair -- 6 v_mov_b32 per step; spelling the
@@ -305,7 +323,7 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
     // (early role: the pins end only here, so that the LDS reads above cannot land in the store-data registers --
     //  hipcc guards an LDS return into such a register with s_waitcnt vmcnt(0), i.e. it would wait for the stores
     //  just issued)
-    if constexpr (EARLY && !STAG) { KEEP_ALIVE(ka0); KEEP_ALIVE(ka1); KEEP_ALIVE(ka2); }
+    if constexpr (EARLY && !STAG) { LSTM_PIN3(KEEP_ALIVE, ka0, ka1, ka2); }
     LSTM_STAMP(1);   // LDS reads + FMAs
     if constexpr (STAG && !EARLY) {
       __syncthreads();   // X_{t+1}: group A has written its half of h_t
@@ -338,7 +356,7 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
     if constexpr (EARLY && !STAG) {
       // store FROM the pinned registers: a VMEM store reads its data late, and a copy of the value in a register
       // that the next step's LDS reads overwrite would put s_waitcnt vmcnt(0) at the top of every step
-      OPAQUE(ka0); OPAQUE(ka1); OPAQUE(ka2);
+      LSTM_PIN3(OPAQUE, ka0, ka1, ka2);
       flush(t, ka0, ka1, ka2, report_tag);
     }
     LSTM_STAMP(5);   // LDS write issued
@@ -389,9 +407,10 @@ DEVFN void lstm_fwd_body(const LstmSeqArgs& a, const int b, const int dir, const
     for (int k = 0; k < 12; k++) a.prof[wave * 12 + k] = pacc[k];
 #endif
 }
-template <int NK4, int KU>
+#undef LSTM_PIN3
+template <int NK4, int KU, bool SAVE = true>
 __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_kernel(LstmSeqArgs a) {
-  lstm_fwd_body<NK4, KU, false>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
+  lstm_fwd_body<NK4, KU, false, SAVE>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
 }
 
 template <int NK4, int KU>

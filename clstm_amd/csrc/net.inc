@@ -141,6 +141,11 @@ struct Net {
   long long fw_launches = 0;
 
   hipStream_t stream() const { return g_stream; }
+  // recognition (predict): the current minibatch was declared with the buffers of a forward-only pass (geom_predict) and
+  // computed by kernels that saved nothing for a backward pass (nosave); in_predict: no training NaN flag (fwd_nanflag)
+  bool geom_predict = false, nosave = false, in_predict = false;
+  size_t fixed_bytes = 0;       // device allocations of build() (clstm_net_device_bytes; the grow-only buffers count themselves: DevBuf)
+  void dev_malloc(void** q, size_t bytes) { HIPCHECK(hipMalloc(q, bytes)); fixed_bytes += bytes; }
 
   static bool l_is_only_layer(const clstm_net_desc& ds) { return ds.nlayers == 1; }
   // source-index table of a narrow layer's per-step repack (ops.h:k_pack_index), built at first use
@@ -224,7 +229,7 @@ struct Net {
     auto own = [&](float*& dst, float* given, bool& flag) {
       if (given) { dst = given; flag = false; }
       else {
-        HIPCHECK(hipMalloc((void**)&dst, (size_t)nparams * sizeof(float)));
+        dev_malloc((void**)&dst, (size_t)nparams * sizeof(float));
         zero_fill(dst, (size_t)nparams * sizeof(float));
         flag = true;
       }
@@ -232,28 +237,28 @@ struct Net {
     own(v, pv, own_v); own(d, pd, own_d); own(g, pg, own_g);
     for (auto& y : L) {
       const int M = ndir * 4 * y.no, KQP = 4 * y.nk4;
-      HIPCHECK(hipMalloc((void**)&y.Wt, ((size_t)y.ni * M + y.wt_slack) * sizeof(float)));
+      dev_malloc((void**)&y.Wt, ((size_t)y.ni * M + y.wt_slack) * sizeof(float));
       zero_fill(y.Wt, ((size_t)y.ni * M + y.wt_slack) * sizeof(float));
-      HIPCHECK(hipMalloc((void**)&y.bias, (size_t)M * sizeof(float)));
+      dev_malloc((void**)&y.bias, (size_t)M * sizeof(float));
       if (y.wide) {
         y.kpf = wide_kp_fwd(y.no); y.kpb = wide_kp_bwd(y.no);
         y.nwf = (long long)ndir * ((y.no + 3) / 4) * 16 * y.kpf;
         y.nwb = (long long)ndir * ((y.no + 15) / 16) * 16 * y.kpb;
-        HIPCHECK(hipMalloc((void**)&y.Rwf, (size_t)(y.nwf + 4) * sizeof(float)));
-        HIPCHECK(hipMalloc((void**)&y.Rwb, (size_t)(y.nwb + 4) * sizeof(float)));
-        HIPCHECK(hipMalloc((void**)&y.Rbf, ((size_t)ndir * ((y.no + 3) / 4) * 16 * wide_kp16_fwd(y.no) + 8) * sizeof(unsigned short)));
-        HIPCHECK(hipMalloc((void**)&y.Rbb, ((size_t)ndir * ((y.no + 15) / 16) * 16 * wide_kp16_bwd(y.no) + 8) * sizeof(unsigned short)));
+        dev_malloc((void**)&y.Rwf, (size_t)(y.nwf + 4) * sizeof(float));
+        dev_malloc((void**)&y.Rwb, (size_t)(y.nwb + 4) * sizeof(float));
+        dev_malloc((void**)&y.Rbf, ((size_t)ndir * ((y.no + 3) / 4) * 16 * wide_kp16_fwd(y.no) + 8) * sizeof(unsigned short));
+        dev_malloc((void**)&y.Rbb, ((size_t)ndir * ((y.no + 15) / 16) * 16 * wide_kp16_bwd(y.no) + 8) * sizeof(unsigned short));
       } else {
-        HIPCHECK(hipMalloc((void**)&y.Rf, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float)));
-        HIPCHECK(hipMalloc((void**)&y.Rb, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float)));
+        dev_malloc((void**)&y.Rf, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float));
+        dev_malloc((void**)&y.Rb, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float));
       }
       if (!y.wide && l_is_only_layer(ds) && ds.nclasses <= SMX_COLS) {
         y.wk_kp = (y.ni + 15) / 16 * 16; y.wk_njp = (4 * y.no + 15) / 16;
-        HIPCHECK(hipMalloc((void**)&y.Wk, ((size_t)ndir * y.wk_njp * 16 * y.wk_kp + 64) * sizeof(float)));
+        dev_malloc((void**)&y.Wk, ((size_t)ndir * y.wk_njp * 16 * y.wk_kp + 64) * sizeof(float));
         w1k_kps = (ndir * y.no + 15) / 16 * 16;
-        HIPCHECK(hipMalloc((void**)&W1k, ((size_t)96 * w1k_kps + 64) * sizeof(float)));
+        dev_malloc((void**)&W1k, ((size_t)96 * w1k_kps + 64) * sizeof(float));
       }
-      HIPCHECK(hipMalloc((void**)&y.moff, (size_t)M * sizeof(long long)));
+      dev_malloc((void**)&y.moff, (size_t)M * sizeof(long long));
       std::vector<long long> mo(M);
       for (int m = 0; m < M; m++) {
         const int dir = m / (4 * y.no), c = (m % (4 * y.no)) >> 2, s = m & 3;
@@ -328,9 +333,30 @@ struct Net {
     packed_dirty = false;
   }
 
-  void set_batch(const int* T_h, int nb) {
+  void set_batch(const int* T_h, int nb) { declare_batch(T_h, nb); reserve_batch(false); }
+  // forward-only geometry (clstm_net_predict): T_h / nb are validated BEFORE the net is touched
+  void set_batch_predict(const int* T_h, int nb) {
+    REQUIRE(T_h && nb > 0, "empty batch");
+    long long n = 0;
+    for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
+    REQUIRE(n > 0, "batch has no frames");
+    REQUIRE(n < 2147483000LL, "batch has too many frames");
+    declare_batch(T_h, nb);
+    reserve_batch(true);
+  }
+  // a minibatch declared by predict that something else now wants to train on / write into: the buffers of a training pass
+  void ensure_training_buffers() { if (geom_predict) reserve_batch(false); }
+  // no-save kernels exist for narrow layers in f32 mode (lstm_seq.h, lstm_fwd_fused.h, lstm_mfma.h); a net with a wide layer
+  // (lstm_wide.h) or in a bf16 mode runs the unchanged forward pass under predict
+  bool predict_nosave_ok() const {
+    if (bf16_gemm || bf16_rec) return false;
+    for (auto& y : L) if (y.wide) return false;
+    return true;
+  }
+  void declare_batch(const int* T_h, int nb) {
     REQUIRE(nb > 0, "empty batch");
     next.valid = false;   // (whatever a step's tail had prepared is replaced by this declaration)
+    nosave = false;
     bs = nb;
     line_off_h.assign(nb + 1, 0);
     for (int b = 0; b < nb; b++) {
@@ -348,17 +374,26 @@ struct Net {
     for (int b = 0; b < nb; b++) order_h[b] = b;
     std::stable_sort(order_h.begin(), order_h.end(), [&](int x, int y) { return T_h[x] > T_h[y]; });
     line_off.reserve(2 * nb + 1);
-    hipStream_t s = stream();
     int* stage = (int*)ring.acquire((2 * nb + 1) * sizeof(int));
     memcpy(stage, line_off_h.data(), (nb + 1) * sizeof(int));
     memcpy(stage + nb + 1, order_h.data(), nb * sizeof(int));
     // The device copy is made by the next input-ingest launch (which reads the pinned slot directly: one DMA
     // launch of ~4 us less per step) or, if something else needs it first, by flush_line_off().
     lo_stage = stage; lo_pending = true;
+  }
+  // predict: only what a forward-only pass writes -- the input block, H, Z and, for the families that stage pre-activations in
+  // it (every one but the batched-MFMA recurrence of an upper layer; layer 0's routed twins stage theirs there when the device
+  // finds |x| > 255), G.  No C, S, D, dH, Dz.  A net that has no no-save kernels (predict_nosave_ok) reserves everything.
+  void reserve_batch(bool predict) {
+    if (predict && !predict_nosave_ok()) predict = false;
+    geom_predict = predict;
+    hipStream_t s = stream();
     X.reserve((size_t)N * desc.ninput);
     for (auto& y : L) {
-      y.G.reserve((size_t)N * ndir * 4 * y.no);
-      y.C.reserve((size_t)N * ndir * y.no);
+      const bool mf_full = predict && mfma_eligible(y) && !mfma_nosave_ok(y);   // (the training-form kernel under predict: it writes G, C, S)
+      const bool mf_upper = predict && &y != &L[0] && mfma_eligible(y) && !mf_full;
+      if (!mf_upper) y.G.reserve((size_t)N * ndir * 4 * y.no);
+      if (!predict || mf_full) y.C.reserve((size_t)N * ndir * y.no);
       {
         const size_t cap0 = y.H.cap;
         y.H.reserve((size_t)N * y.ldh + 64 + (y.Wk ? PROG_WORDS : 0));   // (fused forward: progress words behind the rows)
@@ -367,6 +402,8 @@ struct Net {
           CLSTM_LAUNCH(k_fill_col0, dim3(nblocks(rows)), dim3(256), 0, s, y.H.p, rows, y.ldh, y.hofs - 1);
         }
       }
+      if (mf_full) y.S.reserve((size_t)N * ndir * y.lds + 64);
+      if (predict) continue;
       y.D.reserve((size_t)N * ndir * 4 * y.no + (y.wide ? 0 : PROG_WORDS + 64));
       y.dH.reserve((size_t)N * ndir * y.no);
       if (y.wide && bf16_rec) {
@@ -377,7 +414,7 @@ struct Net {
       y.S.reserve((size_t)N * ndir * y.lds + 64);
     }
     Z.reserve((size_t)N * desc.nclasses);
-    Dz.reserve((size_t)N * desc.nclasses);
+    if (!predict) Dz.reserve((size_t)N * desc.nclasses);
   }
 
   const float* layer_input(int l) const { return l == 0 ? X.p : L[l - 1].hrow(); }
@@ -489,10 +526,12 @@ struct Net {
     return mode >= 2 || bs >= 640;
 #endif
   }
+  // geometries whose batched forward recurrence has a no-save instantiation (lstm_mfma.h: not the 128-cell one, which spills)
+  static bool mfma_nosave_ok(const Layer& y) { return y.no == 64 || y.no == 100; }
 #ifndef CLSTM_HIP_EMU
-  template <int NO, int NI>
+  template <int NO, int NI, bool SAVE = true>
   void launch_mfma_no(Layer& y, bool fwd, hipStream_t s) {
-    using Gm = MfmaGeom<NO, NI>;
+    using Gm = MfmaGeom<NO, NI, SAVE>;
     const int l = (int)(&y - L.data());
     if (y.mf_epoch != params_epoch) {
       y.Wmf.reserve((size_t)ndir * Gm::W_HALFS_PER_DIR + 64);
@@ -508,6 +547,7 @@ struct Net {
     a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.bs = bs; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
     a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds; a.N = N;
     a.X = layer_input(l); a.ldx = layer_input_ld(l); a.store_s = 1;
+    if (!SAVE) { a.G = a.C = a.S = nullptr; a.dH = nullptr; a.D = nullptr; a.store_s = 0; }   // (not addressed by the no-save form)
     if (l == 0) {   // the caller's frames, any magnitude: the device decides between this kernel and its routed twins (lstm_mfma.h: Input range)
       y.mf_xmax.reserve(MF_XMAX_SLOTS);
       CLSTM_LAUNCH(k_mfma_xmax, dim3(MF_XMAX_SLOTS), dim3(256), 0, s, (const float*)X.p, (size_t)N * desc.ninput, y.mf_xmax.p);
@@ -516,21 +556,22 @@ struct Net {
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); a.prof = lstm_prof.p;
 #endif
-    static const bool smem_set = (coop_set_smem(lstm_fwd_mfma_kernel<NO, NI>, (size_t)Gm::SMEM), true);
+    static const bool smem_set = (coop_set_smem(lstm_fwd_mfma_kernel<NO, NI, SAVE>, (size_t)Gm::SMEM), true);
     (void)smem_set; (void)fwd;
-    CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
-    g_path_count[16]++;
-    if (l == 0) launch_routed_per_line(y, s);
+    CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI, SAVE>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
+    g_path_count[SAVE ? 16 : 15]++;
+    if (l == 0) launch_routed_per_line(y, s, SAVE);
   }
   // the per-line forward pass of layer 0 (hoisted f32 W_x.x product + lstm_seq.h recurrence, as forward() launches them for
   // smaller minibatches) behind the branch that lets it run only when the batched kernel has declined the minibatch
   template <int NK4, int KU>
-  void launch_routed_lstm(Layer& y, const LstmSeqArgs& a, hipStream_t s) {
+  void launch_routed_lstm(Layer& y, const LstmSeqArgs& a, hipStream_t s, bool save) {
     REQUIRE(y.nk4 == NK4 && y.pd.ku == KU, "internal: per-line geometry of a batched layer");
     const size_t smem = (2 * 4 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
-    CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
+    if (save) CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
+    else CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU, false>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
   }
-  void launch_routed_per_line(Layer& y, hipStream_t s) {
+  void launch_routed_per_line(Layer& y, hipStream_t s, bool save = true) {
     const int M = ndir * 4 * y.no;
     const int ksplit = (y.ni + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
     const unsigned gx = (unsigned)((M + GEMM_BT - 1) / GEMM_BT), gy = (unsigned)((N + GEMM_BT - 1) / GEMM_BT);
@@ -541,9 +582,10 @@ struct Net {
     a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
     a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
     a.S = y.S.p; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
-    if (y.no == 64) launch_routed_lstm<4, 16>(y, a, s);
-    else if (y.no == 100) launch_routed_lstm<7, 25>(y, a, s);
-    else launch_routed_lstm<8, 32>(y, a, s);
+    if (!save) { a.C = nullptr; a.S = nullptr; }
+    if (y.no == 64) launch_routed_lstm<4, 16>(y, a, s, save);
+    else if (y.no == 100) launch_routed_lstm<7, 25>(y, a, s, save);
+    else launch_routed_lstm<8, 32>(y, a, s, save);
   }
 #endif
   // bwd_mfma: the backward twin (lstm_mfma_bwd.h): 0 never, 1 (default) from 640 lines per GPU on, 2 always (tests).  It gives up
@@ -631,20 +673,28 @@ struct Net {
 #endif
     launch_lstm(false, y.nk4, y.pd.ku, a, bs, y.nthreads, s);
   }
-  void launch_mfma(Layer& y, bool fwd, hipStream_t s) {
+  void launch_mfma(Layer& y, bool fwd, hipStream_t s, bool save = true) {
 #ifndef CLSTM_HIP_EMU
-    if (y.no == 64) launch_mfma_no<64, 48>(y, fwd, s);
-    else if (y.no == 100) launch_mfma_no<100, 48>(y, fwd, s);
-    else launch_mfma_no<128, 48>(y, fwd, s);
+    if (save) {
+      if (y.no == 64) launch_mfma_no<64, 48>(y, fwd, s);
+      else if (y.no == 100) launch_mfma_no<100, 48>(y, fwd, s);
+      else launch_mfma_no<128, 48>(y, fwd, s);
+    } else {
+      REQUIRE(mfma_nosave_ok(y), "internal: no no-save instantiation of the batched recurrence for this layer");
+      if (y.no == 64) launch_mfma_no<64, 48, false>(y, fwd, s);
+      else launch_mfma_no<100, 48, false>(y, fwd, s);
+    }
     check_launch();
 #else
-    (void)y; (void)fwd; (void)s;
+    (void)y; (void)fwd; (void)s; (void)save;
 #endif
   }
 
   void forward() {
     REQUIRE(N > 0, "set_batch first");
     RoctxRange range_("clstm:forward");
+    ensure_training_buffers();   // (a minibatch that clstm_net_predict declared)
+    nosave = false;
     flush_line_off();
     repack();
     hipStream_t s = stream();
@@ -770,6 +820,11 @@ struct Net {
       }
       if (!y.sbf_ready) ensure_source_x(l);
     }
+    forward_softmax();
+  }
+  // the softmax layer behind the top recurrence (every family but the fused launch, whose consumer items are that layer)
+  void forward_softmax() {
+    hipStream_t s = stream();
     const int nc = desc.nclasses;
     const float* W1 = v + sm_off;
     // the top layer's output rows are [1 | h]: they ARE the softmax layer's source rows
@@ -793,6 +848,55 @@ struct Net {
       timing.end(s);
       check_launch();
     }
+  }
+
+  // ---- recognition: the forward pass of a minibatch nobody will run backward on (clstm_net_predict) ----
+  // The SAME family as forward() would pick for this minibatch (fused launch / batched MFMA / per line, strict and forced options
+  // included) in its no-save form: identical arithmetic, so identical outputs.  Nothing is saved for a backward pass (no
+  // activations over G, no C, no source rows S -- ensure_source_x is never called), the training NaN flag is not passed
+  // (what clstm_net_set_training(net, 0) does, without changing that setting), nbackward and the training state are untouched.
+  // Wide layers and the bf16 modes have no no-save kernels: today's forward pass, without the NaN flag.
+  // clstm_debug_path_count: 22 per-line no-save recurrences, 23 fused no-save launches, 15 batched-MFMA no-save launches.
+  // The batched recurrence of a 128-cell layer has no no-save instantiation (lstm_mfma.h): its training form runs (counter 16).
+  void predict() {
+    REQUIRE(N > 0, "set_batch first");
+    RoctxRange range_("clstm:predict");
+    struct Guard { bool& f; Guard(bool& x) : f(x) { f = true; } ~Guard() { f = false; } } guard_(in_predict);
+    if (!geom_predict) { forward(); return; }   // (no no-save kernels for this net: see reserve_batch)
+    flush_line_off();
+    repack();
+    hipStream_t s = stream();
+    nosave = true;
+    src0_ready = false;
+    for (auto& y : L) { y.sx_valid = y.sh_valid = false; y.h_f32_valid = true; y.sbf_ready = false; y.fwd_persistent = false; }
+    if (forward_fused_eligible() && !(L.size() == 1 && mfma_eligible(L[0]))) { forward_fused(false); return; }
+    for (int l = 0; l < (int)L.size(); l++) {
+      Layer& y = L[l];
+      const int M = ndir * 4 * y.no;
+      if (mfma_eligible(y)) {
+        // (128 cells: no no-save instantiation -- the training form, whose arrays reserve_batch kept for this layer; still no
+        //  ensure_source_x: the kernel reads the frames themselves, the [1 | x] columns are the weight gradient's)
+        timing.begin("lstm_fwd", s);
+        launch_mfma(y, true, s, !mfma_nosave_ok(y));
+        timing.end(s);
+        continue;
+      }
+      REQUIRE(y.G.p && y.G.cap >= (size_t)N * M, "internal: predict geometry without a pre-activation array");
+      timing.begin("gemm_gates_x", s);
+      gemm_f32<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), layer_input_ld(l), N), gemm_mc(y.Wt, M, y.ni, 0),
+                                 StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
+      timing.end(s);
+      check_launch();
+      LstmSeqArgs a{};
+      a.Rpk = y.Rf; a.G = y.G.p; a.C = nullptr; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
+      a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
+      a.S = nullptr; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
+      timing.begin("lstm_fwd", s);
+      launch_lstm_fwd_nosave(y.nk4, y.pd.ku, a, bs, y.nthreads, s);
+      timing.end(s);
+      g_path_count[22]++;
+    }
+    forward_softmax();
   }
 
   // ---- the forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h) ----
@@ -837,7 +941,7 @@ struct Net {
     ring.commit(s);
     fw_key = line_off_h;
   }
-  void forward_fused() {
+  void forward_fused(bool save = true) {   // save = false: the recurrence role in its no-save form (predict)
     hipStream_t s = stream();
     Layer& y = L[0];
     build_fwd_items();
@@ -845,7 +949,7 @@ struct Net {
     fw_prog_base += tmax + 64;
     if (fw_prog_base > (1 << 30)) fw_prog_base = 1024;
     fw_launches++;
-    g_path_count[5]++;
+    g_path_count[save ? 5 : 23]++;
     FwdFusedKernelArgs k{};
     LstmSeqArgs& a = k.a;
     a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
@@ -865,13 +969,15 @@ struct Net {
     h.prog = (const int*)(y.H.p + a.prog_off);
     h.nrec = bs * ndir; h.npb = fw_npitems;
     const unsigned nblk = (unsigned)(h.nrec + h.npb + fw_ncitems);   // one item per helper workgroup
-    y.sx_valid = src0_ready;
-    ensure_source_x(0);
+    if (save) {
+      y.sx_valid = src0_ready;
+      ensure_source_x(0);
+    } else { a.C = nullptr; a.S = nullptr; }
     static const char* trace_path = getenv("CLSTM_FW_TRACE");   // diagnostics: wall-clock stamps of every workgroup / item of the launch
     const size_t trace_rows = (size_t)h.nrec + fw_npitems + fw_ncitems;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); HIPCHECK(hipMemsetAsync(dw_trace.p, 0, trace_rows * 4 * sizeof(long long), s)); h.trace = dw_trace.p; }
     timing.begin("lstm_fwd", s);
-    REQUIRE(launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s), "internal: no fused forward instantiation");
+    REQUIRE(launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s, save), "internal: no fused forward instantiation");
     timing.end(s);
     if (trace_path) {
       HIPCHECK(hipStreamSynchronize(s));
@@ -1397,7 +1503,7 @@ struct Net {
   // training step (predict, the test-set pass of clstmocrtrain: clstm_net_set_training(net, 0)) must not arm the process-wide
   // word -- one NaN logit in an inference pass would block the updates of every net of the process.
   bool training = true;
-  int* fwd_nanflag() const { return training ? nanflag() : nullptr; }
+  int* fwd_nanflag() const { return training && !in_predict ? nanflag() : nullptr; }
   static int* nanflag() {            // device error word [3], or null when CLSTM_NANCHECK=0
     static const bool on = !(getenv("CLSTM_NANCHECK") && atoi(getenv("CLSTM_NANCHECK")) == 0);
     return on ? dev_err_words() + 3 : nullptr;

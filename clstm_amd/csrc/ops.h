@@ -923,6 +923,16 @@ __global__ void k_reduce_scatter_ingest(ReduceDesc d0, ReduceDesc d1, float* g, 
   if (blk < t.nbi) { ingest_rows(t.x, t.X, t.S, (size_t)t.N, t.ni, t.lds, t.ndir, t.sdir, (unsigned)blk, (unsigned)t.nbi); return; }
   ingest_small(blk - t.nbi, t.lo_src, t.lo_dst, t.lo_n, t.aux_src, t.aux_dst, t.aux_n);
 }
+// predict's ingest: the frames into the input block (no source rows: nobody will run backward) and, by the last block, the line
+// offsets from their pinned slot -- one launch instead of two DMA copies (with those and one result copy per array, predict of
+// 1 x 200 took 210-224 us per call against 199-205 of forward + decode; EXPERIMENTS 13.4)
+__global__ void k_ingest_predict(const float* x, float* X, size_t n, int nbx, const int* lo_src, int* lo_dst, int lo_n) {
+  if ((int)blockIdx.x >= nbx) {
+    for (int i = threadIdx.x; i < lo_n; i += blockDim.x) lo_dst[i] = lo_src[i];
+    return;
+  }
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)nbx * blockDim.x) X[e] = x[e];
+}
 __global__ void k_fill_col0(float* H, size_t rows, int ld, int col) {
   CLSTM_GRID_STRIDE(e, rows) H[e * ld + col] = 1.0f;
 }

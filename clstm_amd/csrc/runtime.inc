@@ -45,14 +45,26 @@ static void zero_fill(void* p, size_t bytes) {
   HIPCHECK(hipMemsetAsync(p, 0, bytes, g_stream));
   HIPCHECK(hipStreamSynchronize(g_stream));
 }
+// Byte accounting (clstm_net_device_bytes): a DevBuf constructed inside an AcctScope -- every buffer of a net and of its CTC / decode
+// workspaces: clstm_net_create -- keeps the address of that net's counter and moves it whenever it grows or is released, so a buffer
+// added to any of those structs later is counted without anyone listing it.  Buffers constructed outside a scope are not counted.
+static thread_local size_t* g_acct = nullptr;
+struct AcctScope {
+  size_t* prev;
+  explicit AcctScope(size_t* c) : prev(g_acct) { g_acct = c; }
+  ~AcctScope() { g_acct = prev; }
+};
 template <class T>
 struct DevBuf {  // grow-only device buffer
   T* p = nullptr;
   size_t cap = 0;
+  size_t* acct = g_acct;
   void reserve(size_t n) {
     if (n <= cap) return;
     if (p) HIPCHECK(hipFree(p));
     p = nullptr;
+    if (acct) *acct -= cap * sizeof(T);
+    cap = 0;
     size_t want = n + n / 4 + 64;
     HIPCHECK(hipMalloc((void**)&p, want * sizeof(T)));
     // zero-fill on the library stream and wait for it: whatever initialises parts of the fresh buffer next --
@@ -61,10 +73,12 @@ struct DevBuf {  // grow-only device buffer
     // Buffers only grow, so this drain happens a handful of times per process (hipFree drains the device anyway).
     zero_fill(p, want * sizeof(T));
     cap = want;
+    if (acct) *acct += cap * sizeof(T);
   }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
+    if (acct) *acct -= cap * sizeof(T);
     cap = 0;
   }
 };
@@ -162,27 +176,28 @@ static int pick_nk4(int no) {
     if (v >= need) return v;
   return -1;
 }
-template <int NK4, int KU>
+template <int NK4, int KU, bool SAVE = true>
 static void launch_fwd(const LstmSeqArgs& a, int bs, int nthreads, hipStream_t s) {
   const size_t smem = (2 * 4 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
-  CLSTM_LAUNCH((lstm_fwd_kernel<NK4, KU>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a);
+  CLSTM_LAUNCH((lstm_fwd_kernel<NK4, KU, SAVE>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a);
 }
 template <int NK4, int KU>
 static void launch_bwd(const LstmSeqArgs& a, int bs, int nthreads, hipStream_t s) {
   const size_t smem = (2 * 16 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
   CLSTM_LAUNCH((lstm_bwd_kernel<NK4, KU>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a);
 }
-template <int NK4, int KU>
+template <int NK4, int KU, bool SAVE = true>
 static void launch_fwd_fused(const FwdFusedKernelArgs& k, unsigned nblk, int nthreads, hipStream_t s) {
   const size_t smem = (2 * 4 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
 #ifdef CLSTM_HIP_EMU
-  CLSTM_LAUNCH_COOP((lstm_fwd_fused_kernel<NK4, KU>), dim3(nblk), dim3(nthreads), smem, s, k);   // emulator: every workgroup live at once
+  CLSTM_LAUNCH_COOP((lstm_fwd_fused_kernel<NK4, KU, SAVE>), dim3(nblk), dim3(nthreads), smem, s, k);   // emulator: every workgroup live at once
 #else
-  CLSTM_LAUNCH((lstm_fwd_fused_kernel<NK4, KU>), dim3(nblk), dim3(nthreads), smem, s, k);
+  CLSTM_LAUNCH((lstm_fwd_fused_kernel<NK4, KU, SAVE>), dim3(nblk), dim3(nthreads), smem, s, k);
 #endif
 }
-static bool launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, unsigned nblk, int nthreads, hipStream_t s) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { launch_fwd_fused<N, K>(k, nblk, nthreads, s); check_launch(); return true; }
+// save = false: the recurrence role in its no-save form (recognition; lstm_seq.h)
+static bool launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, unsigned nblk, int nthreads, hipStream_t s, bool save = true) {
+#define CASE_(N, K) if (nk4 == N && ku == K) { if (save) launch_fwd_fused<N, K>(k, nblk, nthreads, s); else launch_fwd_fused<N, K, false>(k, nblk, nthreads, s); check_launch(); return true; }
   CASE_(7, 25) CASE_(7, 28) CASE_(8, 32)    // (the fused form needs >= 5 waves: a polling wave among the first four, a reporting wave behind them)
 #undef CASE_
   return false;
@@ -191,6 +206,13 @@ static bool launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, 
 static int pick_ku(int no, int nk4) { return (nk4 == 7 && (no + 3) / 4 == 25) ? 25 : 4 * nk4; }
 static void launch_lstm(bool fwd, int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s) {
 #define CASE_(N, K) if (nk4 == N && ku == K) { if (fwd) launch_fwd<N, K>(a, bs, nthreads, s); else launch_bwd<N, K>(a, bs, nthreads, s); check_launch(); return; }
+  CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
+#undef CASE_
+  throw Error("unsupported nhidden for the register-resident recurrence");
+}
+// the forward recurrence in its no-save form (recognition: only h leaves; lstm_seq.h)
+static void launch_lstm_fwd_nosave(int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s) {
+#define CASE_(N, K) if (nk4 == N && ku == K) { launch_fwd<N, K, false>(a, bs, nthreads, s); check_launch(); return; }
   CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
 #undef CASE_
   throw Error("unsupported nhidden for the register-resident recurrence");

@@ -279,6 +279,75 @@ struct CLSTMOCR {
     for (int i = 0; i < (int)cs.size(); i++)
       preds.push_back(CharPrediction{i, where[i], (char32_t)codec.codec[cs[i]], out(where[i], cs[i])});
   }
+  // ---- batched recognition: predict() for many lines through ONE clstm_net_predict_h call (the no-save forward kernels; the
+  // same outputs as the per-line loop above, which runs the same kernel families through clstm_net_forward) -------------------
+  // GPU-free and thread-safe (own normaliser, as prepare_line): a driver normalises lines ahead on helper threads
+  void normalize_line(Image& frames, const Image& raw) const {
+    CenterNormalizer nz;
+    nz.target_height = target_height;
+    nz.measure(raw);
+    nz.normalize(frames, raw);
+  }
+  // Recognition results should not depend on how many lines share a call.  A line alone (predict above) is computed by the per-line
+  // kernels -- unless it has 2048 frames or more, see below --, and those give a line the same bits in any minibatch; but from 2048
+  // frames per call on (64 lines of 32) the library would pick its fused forward launch, whose producer / consumer items sum in
+  // another order (outputs differ in the last bit, ~4e-7).  So the batched calls keep the per-line family (overlap mode 0 for the
+  // call; the mode the net had is read and put back): clstmocr batch=N prints what batch=1 prints, byte for byte.
+  // Two limits.  (1) A single line of >= 2048 frames takes the fused launch in predict() (the library's rule admits one line) and
+  // the per-line kernels here: for such a line batch=1 and batch=N agree to the last bit but one, not byte for byte.  (2) From 640
+  // lines per call on the library's batched MFMA recurrence takes over (f16 split products, 1e-4 class: same text on trained
+  // models, not the same bits); CLSTM_DEBUG="fwd_mfma=0" keeps the per-line kernels there too.
+  vector<int> batch_T;   // line lengths of the last predict_frames() minibatch (get_outputs_batch)
+  void predict_frames(const vector<const Image*>& lines, vector<ustring>& out, vector<vector<CharPrediction>>* preds = nullptr) {
+    const int bs = (int)lines.size();
+    out.clear();
+    if (preds) preds->clear();
+    if (bs == 0) return;
+    batch_T.clear();
+    vector<float> frames;
+    for (const Image* l : lines) { batch_T.push_back(l->w); frames.insert(frames.end(), l->d.begin(), l->d.end()); }
+    int N = 0;
+    for (int t : batch_T) N += t;
+    vector<int> cls(N), loc(N), cnt(bs);
+    vector<float> conf(preds ? N : 0);
+    int train_overlap = 1;
+    chk(clstm_net_get_overlap(net, &train_overlap), "clstm_net_get_overlap");
+    chk(clstm_net_set_overlap(net, 0), "clstm_net_set_overlap");
+    const int rc = clstm_net_predict_h(net, batch_T.data(), bs, frames.data(), cls.data(), loc.data(), preds ? conf.data() : nullptr, cnt.data());
+    const string err = rc ? clstm_last_error() : "";
+    chk(clstm_net_set_overlap(net, train_overlap), "clstm_net_set_overlap");
+    if (rc) fail("clstm_net_predict_h: " + err);
+    int o = 0;
+    for (int b = 0; b < bs; b++) {
+      out.push_back(codec.decode(Classes(cls.begin() + o, cls.begin() + o + cnt[b])));
+      if (preds) {
+        preds->emplace_back();
+        for (int i = 0; i < cnt[b]; i++)
+          preds->back().push_back(CharPrediction{i, loc[o + i], (char32_t)codec.codec[cls[o + i]], conf[o + i]});
+      }
+      o += batch_T[b];
+    }
+    T = batch_T.back();
+  }
+  void predict_batch(const vector<Image>& raws, vector<ustring>& out, vector<vector<CharPrediction>>* preds = nullptr) {
+    vector<Image> frames(raws.size());
+    vector<const Image*> ptrs;
+    for (size_t b = 0; b < raws.size(); b++) { normalize_line(frames[b], raws[b]); ptrs.push_back(&frames[b]); }
+    predict_frames(ptrs, out, preds);
+  }
+  void get_outputs_batch(vector<Image>& outs) {   // [T_b][nclasses] of every line of the last predict_frames() minibatch
+    int N = 0;
+    for (int t : batch_T) N += t;
+    vector<float> z((size_t)N * nclasses);
+    chk(clstm_net_get_outputs_h(net, z.data()), "clstm_net_get_outputs_h");
+    outs.resize(batch_T.size());
+    size_t o = 0;
+    for (size_t b = 0; b < batch_T.size(); b++) {
+      outs[b].resize(batch_T[b], nclasses);
+      std::copy(z.begin() + o, z.begin() + o + (size_t)batch_T[b] * nclasses, outs[b].d.begin());
+      o += (size_t)batch_T[b] * nclasses;
+    }
+  }
 };
 
 // CLSTMText (clstmhl.h:24-144): text in, text out through the same BiLSTM + CTC path; characters are

@@ -13,7 +13,8 @@ static float scaled_log(float x) {  // clstmocr.cc:33-40 (float arithmetic, clam
 
 static int main1(int argc, char** argv) {
   if (argc != 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
-    std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " IMAGEFILE-LIST\n  Variables: load (required) conf output save_text\n";
+    std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " IMAGEFILE-LIST\n  Variables: load (required) conf output save_text\n"
+              << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)   (not in the reference)\n";
     return EXIT_FAILURE;
   }
   string load_name = getsenv("load", "");
@@ -23,6 +24,69 @@ static int main1(int argc, char** argv) {
   bool conf = getienv("conf", 0);
   string output = getsenv("output", "text");
   bool save_text = getienv("save_text", 1);
+  // batch=N (not in the reference; default 1 = the loop below, line by line): N lines per clstm_net_predict_h call.  Lines are read
+  // and normalised ahead on up to prep_threads (<= 16) helper threads -- a chunk is prepared while the device recognises the one
+  // before it -- and results are printed and written in input order, in the formats of the per-line loop.
+  const int batch = std::max(1, getienv("batch", 1));
+  const int prep_threads = std::max(1, std::min(std::min(getienv("prep_threads", 16), 16), std::max(1, (int)std::thread::hardware_concurrency())));
+  if (batch > 1) {
+    if (output != "text" && output != "logs" && output != "posteriors") fail("unknown output format");
+    vector<string> names;
+    read_lines(names, argv[1]);
+    struct Chunk { vector<string> names; vector<Image> frames; };
+    auto prepare = [&](Chunk& c, size_t first) {
+      c.names.assign(names.begin() + first, names.begin() + std::min(names.size(), first + (size_t)batch));
+      c.frames.assign(c.names.size(), Image());
+      auto work = [&](int k0) {
+        for (size_t k = k0; k < c.names.size(); k += prep_threads) {
+          Image raw;
+          read_png(raw, c.names[k]);
+          for (float& v : raw.d) v = -v + 1.0f;
+          clstm.normalize_line(c.frames[k], raw);
+        }
+      };
+      vector<std::future<void>> pool;
+      for (int t = 1; t < prep_threads && t < (int)c.names.size(); t++) pool.push_back(std::async(std::launch::async, work, t));
+      work(0);
+      for (auto& f : pool) f.get();   // (rethrows a worker's exception)
+    };
+    Chunk cur, next;
+    std::future<void> helper;
+    if (!names.empty()) prepare(next, 0);
+    for (size_t first = 0; first < names.size(); first += batch) {
+      std::swap(cur, next);
+      if (first + batch < names.size()) helper = std::async(std::launch::async, [&, first] { prepare(next, first + batch); });
+      vector<const Image*> ptrs;
+      for (auto& f : cur.frames) ptrs.push_back(&f);
+      vector<ustring> outs;
+      vector<vector<CharPrediction>> preds;
+      clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
+      vector<Image> posteriors;
+      if (output != "text") clstm.get_outputs_batch(posteriors);
+      for (size_t k = 0; k < cur.names.size(); k++) {
+        const string& name = cur.names[k];
+        string basename = name.substr(0, name.find_last_of("."));
+        if (!conf) {
+          string out = utf32_to_utf8(outs[k]);
+          std::cout << name << "\t" << out << std::endl;
+          if (save_text) write_text(basename + ".txt", out);
+        } else {
+          std::cout << "file " << name << std::endl;
+          for (auto& p : preds[k]) {
+            ustring c(1, p.c);
+            std::cout << p.i << "\t" << p.x << "\t" << utf32_to_utf8(c) << "\t" << p.p << std::endl;
+          }
+        }
+        if (output != "text") {
+          if (output == "logs")
+            for (float& v : posteriors[k].d) v = scaled_log(v);
+          write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), posteriors[k]);
+        }
+      }
+      if (helper.valid()) helper.get();
+    }
+    return 0;
+  }
   std::ifstream stream(argv[1]);
   string line;
   while (getline(stream, line)) {

@@ -148,7 +148,7 @@ static int print_usage(char** argv) {
   std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " TRAININGLIST [TESTLIST]\n"
             << "  Variables: load save_name nhidden lrate momentum target_height ntrain start charsep\n"
             << "             report_time test_every report_every save_every params   (clstmocrtrain.cc:99-115)\n"
-            << "             batch (lines per update, default 1)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
+            << "             batch (lines per update, default 1)  test_batch (lines per recognition call of the test-set pass, default batch)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
   return EXIT_FAILURE;
 }
 
@@ -238,6 +238,7 @@ static int main1(int argc, char** argv) {
   // from the second visit of a file on, a line costs one memcpy.  Preparation is deterministic, so neither changes what
   // is trained on.
   const bool use_cache = getienv("cache", 1) != 0;
+  const int test_batch = std::max(1, getienv("test_batch", batch));
   const int prep_threads = std::max(1, std::min(getienv("prep_threads", 16), (int)std::thread::hardware_concurrency()));
   vector<std::shared_ptr<CLSTMOCR::Line>> cache(use_cache ? trainingset.size() : 0);
   auto draw = [&](CLSTMOCR::Prepared& p) {
@@ -311,13 +312,35 @@ static int main1(int argc, char** argv) {
     }
     if (test_trigger(tend) && testset.size() > 0 && lead) {
       double count = 0.0, errors = 0.0;
-      for (int test = 0; test < testset.size(); test++) {
+      // test_batch=N (default: batch): the test set through clstm_net_predict_h in chunks of N lines (CLSTMOCR::predict_frames;
+      // read + normalised on the preparation threads) instead of testset.size() single-line launches; 1: the reference's loop
+      for (int test = 0; test_batch <= 1 && test < testset.size(); test++) {
         Image traw;
         ustring tgt;
         testset.readSample(traw, tgt, test);
         ustring tpred = clstm.predict(traw);
         count += tgt.size();
         errors += levenshtein(tpred, tgt);
+      }
+      for (int first = 0; test_batch > 1 && first < testset.size(); first += test_batch) {
+        const int n = std::min(test_batch, testset.size() - first);
+        vector<Image> frames(n);
+        vector<ustring> tgts(n), tpreds;
+        auto work = [&](int k0) {
+          for (int k = k0; k < n; k += prep_threads) {
+            Image traw;
+            testset.readSample(traw, tgts[k], first + k);
+            clstm.normalize_line(frames[k], traw);
+          }
+        };
+        vector<std::future<void>> pool;
+        for (int t = 1; t < prep_threads && t < n; t++) pool.push_back(std::async(std::launch::async, work, t));
+        work(0);
+        for (auto& f : pool) f.get();
+        vector<const Image*> ptrs;
+        for (auto& f : frames) ptrs.push_back(&f);
+        clstm.predict_frames(ptrs, tpreds);
+        for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += levenshtein(tpreds[k], tgts[k]); }
       }
       test_error = errors / count;
       std::cout << "ERROR " << trial << " " << test_error << "     " << errors << " " << count << std::endl;

@@ -247,6 +247,33 @@ class Network:
             o += t
         return out
 
+    def predict(self, lines):
+        """CLSTMOCR::predict (clstmhl.h:225-262) for a whole minibatch in one call (clstm_net_predict_h): the forward pass in
+        its no-save form + trivial_decode.  lines: list of [T_b, ninput] arrays.  Returns (decodes, locs, confs), one array per
+        line each: the classes, their frames, and the softmax output at (frame, class).  The minibatch is the current one
+        afterwards (outputs(), decode(), state(.., 'outputs')); nothing was saved for a backward pass."""
+        self._declared = None
+        self.T = [len(x) for x in lines]
+        self.N = int(sum(self.T))
+        x = f32(np.concatenate([f32(x).reshape(-1, self.ninput) for x in lines], 0))
+        t = i32(self.T)
+        cls, loc = np.zeros(self.N, np.int32), np.zeros(self.N, np.int32)
+        conf, cnt = np.zeros(self.N, np.float32), np.zeros(len(self.T), np.int32)
+        self.lib.call("clstm_net_predict_h", self.h, ptr(t), len(self.T), ptr(x), ptr(cls), ptr(loc), ptr(conf), ptr(cnt))
+        dec, locs, confs, o = [], [], [], 0
+        for b, tb in enumerate(self.T):
+            dec.append(cls[o:o + cnt[b]].copy())
+            locs.append(loc[o:o + cnt[b]].copy())
+            confs.append(conf[o:o + cnt[b]].copy())
+            o += tb
+        return dec, locs, confs
+
+    def device_bytes(self):
+        """sum of this net's device allocations in bytes (clstm_net_device_bytes)"""
+        n = C.c_longlong()
+        self.lib.call("clstm_net_device_bytes", self.h, C.byref(n))
+        return n.value
+
     def state(self, layer, direction, which):
         a = np.empty((self.N, self.nhidden[layer]), np.float32)
         self.lib.call("clstm_net_get_state_h", self.h, layer, direction, STATE_CODES[which], ptr(a))

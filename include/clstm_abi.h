@@ -193,6 +193,31 @@ int clstm_net_get_input_deltas_h(clstm_net* net, float* dx_h);
 int clstm_net_update(clstm_net* net);
 /* trivial_decode of every line; HOST outputs as clstm_trivial_decode_batch.  Blocking. */
 int clstm_net_decode(clstm_net* net, int* classes_h, int* locs_h, int* counts_h);
+/* CLSTMOCR::predict (clstmhl.h:225-262) for a whole minibatch in ONE call: declare the minibatch (T_h[bs] line lengths, HOST), take
+ * its frames (x_d DEVICE / x_h HOST, [sum T][ninput]), run the forward pass and trivial_decode.  Blocking: it returns results.
+ *   Outputs (HOST) are laid out as clstm_net_decode's: line b's entries start at its first frame's index, counts_h[b] of them;
+ * conf_h[i] is the softmax output at (locs_h[i], classes_h[i]) -- CharPrediction::p.  classes_h / locs_h / conf_h may be NULL,
+ * counts_h is required.
+ *   The forward pass is the one clstm_net_forward would run for this minibatch -- same kernel family by the same rule (fused
+ * launch, batched MFMA recurrence from 640 lines on with its input-range routing, per-line kernels; clstm_net_set_strict_f32 and
+ * the forced experiment options apply) -- in its NO-SAVE form: identical arithmetic, bit-identical outputs, but nothing is kept for
+ * a backward pass (no gate activations, no cell states, no source rows) and the buffers only a training step needs are not even
+ * reserved (clstm_net_device_bytes).  Nets with a wide layer (> 128 cells) or in a bf16 mode (clstm_net_set_gemm_precision) have
+ * no no-save kernels: predict runs their ordinary forward pass.  T_h / bs are validated before the net is touched.
+ *   Afterwards the minibatch is the net's current one: clstm_net_outputs, clstm_net_get_outputs_h, clstm_net_decode and
+ * clstm_net_get_state_h(which = 5) work; clstm_net_ctc, clstm_net_backward, clstm_net_set_output_deltas_h, clstm_net_get_state_h
+ * (other `which`), clstm_net_n_states / clstm_net_get_states_h and clstm_net_get_input_deltas_h refuse and name clstm_net_predict;
+ * clstm_net_forward (and clstm_net_set_inputs_*) reserve what a training pass needs and go on as usual.
+ *   Training state is untouched: parameters, derivs, grads, the step count, the device error words (a non-finite pixel gives
+ * non-finite outputs and arms nothing, whatever clstm_net_set_training says).  A minibatch declared by clstm_net_train_step_next is
+ * dropped exactly as by clstm_net_set_batch: the next step takes the ordinary path with identical results.  With a communicator
+ * attached predict is rank-local (no collective). */
+int clstm_net_predict(clstm_net* net, const int* T_h, int bs, const float* x_d, int* classes_h, int* locs_h, float* conf_h,
+                      int* counts_h);
+int clstm_net_predict_h(clstm_net* net, const int* T_h, int bs, const float* x_h, int* classes_h, int* locs_h, float* conf_h,
+                        int* counts_h);
+/* sum of the net's device allocations in bytes (parameters, packed weights, every per-minibatch buffer, CTC / decode scratch) */
+int clstm_net_device_bytes(clstm_net* net, long long* bytes);
 /* internal NPLSTM state for parity tests: which = 0 gi,1 gf,2 go,3 ci,4 state,5 output h,
  * 6 gate delta gi,7 gf,8 go,9 ci (pre-activation deltas after backward_nonlin0).
  * dir 0 = forward NPLSTM, 1 = the NPLSTM inside Reversed.  out_h: HOST [N][nhidden] in FRAME
@@ -213,6 +238,7 @@ int clstm_net_get_state_h(clstm_net* net, int layer, int dir, int which, float* 
  * products, < 2^-16 -- and "dw_x3=0" -- the f32 MFMA), and the top layer's launch also computes the softmax layer's W.d.  stats: overlapped backward passes so far; slabs that gave up waiting for the recurrence
  * (must stay 0). */
 int clstm_net_set_overlap(clstm_net* net, int mode);
+int clstm_net_get_overlap(clstm_net* net, int* mode);   /* the current mode (default: environment CLSTM_OVERLAP, else 1) */
 /* on != 0: every product of the training step on the f32 MFMA -- the backward products that default to operand-exact split
  * products on the bf16 MFMA (weight gradients, the softmax layer's W.d / x.d) included, and no batched split-product recurrence
  * (csrc/lstm_mfma.h f16 x 2, csrc/lstm_mfma_bwd.h bf16 x 2) by the library's own rule at any minibatch size: a strict net of 640
@@ -325,7 +351,9 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  * 1 persistent backward recurrence, 2 W_x.x from the lower layer's bf16 outputs, 3 x.d from the bf16 delta array,
  * 4 weight-gradient product from contraction-major bf16 operands (LDS transpose reads), 5 the forward half as one
  * launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h), 16 / 17 / 18 the recurrences batched over 16 lines on the
- * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 21 minibatches whose forward pass the
+ * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 22 / 23 / 15 the no-save forward
+ * passes of clstm_net_predict (per-line recurrence launches, fused forward launches, batched MFMA launches; the training counters 5 /
+ * 16 do not move for them), 21 minibatches whose forward pass the
  * batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255]; blocking).  Tests use it to make sure the
  * path they mean to cover is the one that ran. */
 int clstm_debug_path_count(int which, long long* out_h);
