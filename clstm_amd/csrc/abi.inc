@@ -13,6 +13,7 @@ struct clstm_net {
 #define EW(kernel, len, ...) \
   CLSTM_LAUNCH(kernel, dim3(nblocks(len)), dim3(256), 0, g_stream, __VA_ARGS__); check_launch();
 
+#define REQUIRE_CURRENT(h) REQUIRE(!(h)->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)")
 #define REFUSE_NOSAVE(h, what) REQUIRE(!(h)->net.nosave, what ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)")
 extern "C" {
 
@@ -256,7 +257,7 @@ int clstm_net_outputs(clstm_net* h, float** p, float** d) {
   if (d) *d = h->net.Dz.p;
   return 0;
 }
-int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)"); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
+int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN REQUIRE_CURRENT(h); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
 int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN REFUSE_NOSAVE(h, "clstm_net_set_output_deltas_h"); copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
 static void net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h, CtcMetaCopy* defer = nullptr,
                     bool launch = true) {
@@ -293,12 +294,12 @@ static void net_ctc_launch(clstm_net* h) {
 }
 int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h) {
   ABI_BEGIN
-  REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
+  REQUIRE_CURRENT(h);
   REFUSE_NOSAVE(h, "clstm_net_ctc");
   net_ctc(h, labels_h, L_h, aligned_h);
   ABI_END
 }
-int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)"); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }
+int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }
 int clstm_net_enable_input_deltas(clstm_net* h, int on) { h->net.want_dx0 = on != 0; return 0; }
 int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
   ABI_BEGIN
@@ -310,7 +311,7 @@ int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
 int clstm_net_update(clstm_net* h) { ABI_BEGIN h->net.update(); ABI_END }
 int clstm_net_decode(clstm_net* h, int* cls, int* locs, int* cnt) {
   ABI_BEGIN
-  REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
+  REQUIRE_CURRENT(h);
   Net& n = h->net;
   REQUIRE(n.N > 0, "set_batch first");
   run_decode(h->dec, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, cls, locs, cnt, g_stream);
@@ -320,7 +321,7 @@ int clstm_net_decode(clstm_net* h, int* cls, int* locs, int* cnt) {
 static void net_predict(clstm_net* h, const int* T_h, int bs, const float* x, bool x_host, int* cls, int* locs, float* conf, int* cnt) {
   REQUIRE(h && T_h && x && cnt && bs > 0, "null argument (counts_h is required)");
   Net& n = h->net;
-  n.set_batch_predict(T_h, bs);   // (validates T_h / bs before it touches the net; drops a minibatch declared by clstm_net_train_step_next)
+  n.set_batch_predict(T_h, bs);   // (T_h / bs are validated before the net is touched; drops a minibatch declared by clstm_net_train_step_next)
   // the frames into the net's input block: no ingest launch -- that one writes layer 0's source rows, which predict does not have
   const size_t nx = (size_t)n.N * n.desc.ninput;
   if (x_host) HIPCHECK(hipMemcpyAsync(n.X.p, x, nx * sizeof(float), hipMemcpyHostToDevice, g_stream));
@@ -349,7 +350,7 @@ int clstm_net_device_bytes(clstm_net* h, long long* bytes) {
 }
 int clstm_net_get_state_h(clstm_net* h, int layer, int dir, int which, float* out) {
   ABI_BEGIN
-  REQUIRE(!h->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
+  REQUIRE_CURRENT(h);
   Net& n = h->net;
   REQUIRE(layer >= 0 && layer < (int)n.L.size() && dir >= 0 && dir < n.ndir && which >= 0 && which <= 9, "bad state selector");
   if (which != 5) REFUSE_NOSAVE(h, "clstm_net_get_state_h (which != 5)");

@@ -1,6 +1,8 @@
 // net.inc -- part of clstm_hip.hip (namespace clstm): Layer and Net = the step scheduler of the fused path -- arenas per layer,
 // batch geometry, forward / CTC hand-off / backward / update with every launch decision (which recurrence kernel, fused or separate
 // launches, which GEMM form), the chunk tables of the in-launch weight-gradient items, reductions, the gradient exchange.
+// The forward recurrence family of a layer is chosen in ONE place, Net::forward_family: forward() and predict() are the same
+// layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by the same answer.
 // Not a stand-alone header: included once by clstm_hip.hip behind runtime.inc.
 struct Layer {
   int ni, no, nk4, nthreads;
@@ -52,6 +54,10 @@ struct Layer {
   float* hrow() const { return H.p + hofs; }            // h block of frame 0
   float* srow() const { return H.p + hofs - 1; }        // [1 | h] = the next layer's / softmax's source row
 };
+
+// the forward recurrence of one layer of the current minibatch (Net::forward_family): the whole forward half as one launch
+// (lstm_fwd_fused.h), batched over 16 lines on the MFMA (lstm_mfma.h), one workgroup per line (lstm_seq.h), lock-step (lstm_wide.h)
+enum class FwdFamily { Fused, Mfma, PerLine, Wide };
 
 struct Net {
   clstm_net_desc desc;
@@ -334,16 +340,7 @@ struct Net {
   }
 
   void set_batch(const int* T_h, int nb) { declare_batch(T_h, nb); reserve_batch(false); }
-  // forward-only geometry (clstm_net_predict): T_h / nb are validated BEFORE the net is touched
-  void set_batch_predict(const int* T_h, int nb) {
-    REQUIRE(T_h && nb > 0, "empty batch");
-    long long n = 0;
-    for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
-    REQUIRE(n > 0, "batch has no frames");
-    REQUIRE(n < 2147483000LL, "batch has too many frames");
-    declare_batch(T_h, nb);
-    reserve_batch(true);
-  }
+  void set_batch_predict(const int* T_h, int nb) { declare_batch(T_h, nb); reserve_batch(true); }   // forward-only geometry (clstm_net_predict)
   // a minibatch declared by predict that something else now wants to train on / write into: the buffers of a training pass
   void ensure_training_buffers() { if (geom_predict) reserve_batch(false); }
   // no-save kernels exist for narrow layers in f32 mode (lstm_seq.h, lstm_fwd_fused.h, lstm_mfma.h); a net with a wide layer
@@ -353,18 +350,19 @@ struct Net {
     for (auto& y : L) if (y.wide) return false;
     return true;
   }
+  // T_h / nb are validated BEFORE the net is touched: a refused declaration leaves the previous minibatch the current one
   void declare_batch(const int* T_h, int nb) {
-    REQUIRE(nb > 0, "empty batch");
+    REQUIRE(T_h && nb > 0, "empty batch");
+    long long n = 0;
+    for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
+    REQUIRE(n > 0, "batch has no frames");
+    REQUIRE(n < 2147483000LL, "batch has too many frames");   // (the line offsets are ints)
     next.valid = false;   // (whatever a step's tail had prepared is replaced by this declaration)
     nosave = false;
     bs = nb;
     line_off_h.assign(nb + 1, 0);
-    for (int b = 0; b < nb; b++) {
-      REQUIRE(T_h[b] >= 0, "negative line length");
-      line_off_h[b + 1] = line_off_h[b] + T_h[b];
-    }
-    N = line_off_h[nb];
-    REQUIRE(N > 0, "batch has no frames");
+    for (int b = 0; b < nb; b++) line_off_h[b + 1] = line_off_h[b] + T_h[b];
+    N = n;
     tmax = 0;
     for (int b = 0; b < nb; b++) tmax = std::max(tmax, T_h[b]);
     src0_ready = false;
@@ -384,14 +382,16 @@ struct Net {
   // predict: only what a forward-only pass writes -- the input block, H, Z and, for the families that stage pre-activations in
   // it (every one but the batched-MFMA recurrence of an upper layer; layer 0's routed twins stage theirs there when the device
   // finds |x| > 255), G.  No C, S, D, dH, Dz.  A net that has no no-save kernels (predict_nosave_ok) reserves everything.
+  // (By forward_family, as forward_pass launches: the fused launch's rule looks at H, which grows here, but it stages like the per-line kernels.)
   void reserve_batch(bool predict) {
     if (predict && !predict_nosave_ok()) predict = false;
     geom_predict = predict;
     hipStream_t s = stream();
     X.reserve((size_t)N * desc.ninput);
     for (auto& y : L) {
-      const bool mf_full = predict && mfma_eligible(y) && !mfma_nosave_ok(y);   // (the training-form kernel under predict: it writes G, C, S)
-      const bool mf_upper = predict && &y != &L[0] && mfma_eligible(y) && !mf_full;
+      const FwdFamily fam = forward_family(y);
+      const bool mf_full = predict && forward_saves(y, fam, false);   // (the training-form kernel under predict: it writes G, C, S)
+      const bool mf_upper = predict && &y != &L[0] && fam == FwdFamily::Mfma && !mf_full;
       if (!mf_upper) y.G.reserve((size_t)N * ndir * 4 * y.no);
       if (!predict || mf_full) y.C.reserve((size_t)N * ndir * y.no);
       {
@@ -528,6 +528,17 @@ struct Net {
   }
   // geometries whose batched forward recurrence has a no-save instantiation (lstm_mfma.h: not the 128-cell one, which spills)
   static bool mfma_nosave_ok(const Layer& y) { return y.no == 64 || y.no == 100; }
+  // THE launch rule of the forward pass: forward_pass (training and recognition) launches by it and reserve_batch sizes the
+  // predict geometry by it -- nothing else decides.  The batched recurrence goes before the fused launch (which only a net of
+  // one narrow layer can take); the strict and forced options act through the two predicates.
+  FwdFamily forward_family(const Layer& y) {
+    if (y.wide) return FwdFamily::Wide;
+    if (mfma_eligible(y)) return FwdFamily::Mfma;
+    return forward_fused_eligible() ? FwdFamily::Fused : FwdFamily::PerLine;
+  }
+  // ... and whether that family runs its training form -- G, C and S written -- in a pass that asked for save or not: always when
+  // asked to, and where the family has no no-save instantiation for the layer
+  static bool forward_saves(const Layer& y, FwdFamily fam, bool save) { return save || (fam == FwdFamily::Mfma && !mfma_nosave_ok(y)); }
 #ifndef CLSTM_HIP_EMU
   template <int NO, int NI, bool SAVE = true>
   void launch_mfma_no(Layer& y, bool fwd, hipStream_t s) {
@@ -566,7 +577,6 @@ struct Net {
   // smaller minibatches) behind the branch that lets it run only when the batched kernel has declined the minibatch
   template <int NK4, int KU>
   void launch_routed_lstm(Layer& y, const LstmSeqArgs& a, hipStream_t s, bool save) {
-    REQUIRE(y.nk4 == NK4 && y.pd.ku == KU, "internal: per-line geometry of a batched layer");
     const size_t smem = (2 * 4 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
     if (save) CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
     else CLSTM_LAUNCH((lstm_fwd_routed_kernel<NK4, KU, false>), dim3(bs, ndir), dim3(y.nthreads), smem, s, a, (const unsigned*)y.mf_xmax.p, dev_err_words() + 8);
@@ -578,16 +588,24 @@ struct Net {
     CLSTM_LAUNCH((gemm_f32_routed_kernel<GEMM_KC, GEMM_MC, StoreBias>), dim3(std::min(gx * gy, 2048u)), dim3(256), 0, s,
                  gemm_kc(layer_input(0), layer_input_ld(0), N), gemm_mc(y.Wt, M, y.ni, 0), StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni, ksplit,
                  gx, gy, (const unsigned*)y.mf_xmax.p);
-    LstmSeqArgs a{};
-    a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
-    a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
-    a.S = y.S.p; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
-    if (!save) { a.C = nullptr; a.S = nullptr; }
-    if (y.no == 64) launch_routed_lstm<4, 16>(y, a, s, save);
-    else if (y.no == 100) launch_routed_lstm<7, 25>(y, a, s, save);
-    else launch_routed_lstm<8, 32>(y, a, s, save);
+    const LstmSeqArgs a = seq_args(y, true, save);
+#define CASE_(N, K) if (y.nk4 == N && y.pd.ku == K) { launch_routed_lstm<N, K>(y, a, s, save); return; }
+    CASE_(4, 16) CASE_(7, 25) CASE_(8, 32)    // (the cell counts mfma_eligible admits: 64, 100, 128)
+#undef CASE_
+    REQUIRE(false, "internal: per-line geometry of a batched layer");
   }
 #endif
+  // the argument block of the per-line recurrence kernels (lstm_seq.h) for one layer and pass; save = false: C and S stay null
+  // -- the no-save kernels do not address them and the predict geometry does not have them.  No progress words (prog_off = -1);
+  // the launches that overlap consumers with the recurrence set theirs.
+  LstmSeqArgs seq_args(const Layer& y, bool fwd, bool save = true) const {
+    LstmSeqArgs a{};
+    a.Rpk = fwd ? y.Rf : y.Rb; a.G = y.G.p; a.C = save ? y.C.p : nullptr; a.H = y.H.p; a.dH = fwd ? nullptr : y.dH.p; a.D = fwd ? nullptr : y.D.p;
+    a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.bs = bs; a.ldh = y.ldh; a.hofs = y.hofs;
+    a.S = save ? y.S.p : nullptr; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
+    a.prog_off = -1; a.prog_base = 0;
+    return a;
+  }
   // bwd_mfma: the backward twin (lstm_mfma_bwd.h): 0 never, 1 (default) from 640 lines per GPU on, 2 always (tests).  It gives up
   // the fused launch (the weight-gradient items then run behind it as a launch of their own).  Crossover with the per-line fused
   // launch, whole step (profiles/r06_mfma_bwd_leaveout.txt): 512 lines 311.9k vs 327.3k lines/s, 640: 343.6k vs 330.4k,
@@ -606,9 +624,9 @@ struct Net {
 #endif
   }
 #ifndef CLSTM_HIP_EMU
-  template <int NO>
-  void launch_mfma_bwd_no(Layer& y, const LstmSeqArgs& sa, hipStream_t s) {
-    constexpr int NT = 2;
+  // argument block of the batched backward kernels from the per-line one; the R^T fragments repacked when the parameters have moved
+  template <int NO, int NT>
+  LstmMfmaBwdArgs mfma_bwd_args(Layer& y, const LstmSeqArgs& sa, hipStream_t s) {
     using Gm = MfmaBwdGeom<NO, NT>;
     if (y.mfb_epoch != params_epoch) {
       y.Wmfb.reserve((size_t)ndir * Gm::W_HALFS_PER_DIR + 64);
@@ -621,31 +639,24 @@ struct Net {
     LstmMfmaBwdArgs a{};
     a.W = y.Wmfb.p; a.G = sa.G; a.C = sa.C; a.dH = sa.dH; a.D = sa.D; a.line_off = sa.line_off; a.order = sa.order;
     a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base;
+    return a;
+  }
+  template <int NO>
+  void launch_mfma_bwd_no(Layer& y, const LstmSeqArgs& sa, hipStream_t s) {
+    constexpr int NT = 2;
     using Gr = MfmaBwdRowsGeom<NO, NT>;
+    const LstmMfmaBwdArgs a = mfma_bwd_args<NO, NT>(y, sa, s);
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
     (void)smem_set;
     CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
     g_path_count[17]++;
   }
-#endif
-#ifndef CLSTM_HIP_EMU
   // ... and as ONE launch with the weight-gradient items (lstm_mfma_bwd_dw.h); false: not instantiated for this layer / arithmetic
   template <int NO>
   bool launch_mfma_bwd_dw_no(Layer& y, const LstmSeqArgs& sa, const GemmDwArgs& g, unsigned ngemm, hipStream_t s) {
     constexpr int NT = 2;
-    using Gm = MfmaBwdGeom<NO, NT>;
     using Gr = MfmaBwdRowsGeom<NO, NT>;
-    if (y.mfb_epoch != params_epoch) {
-      y.Wmfb.reserve((size_t)ndir * Gm::W_HALFS_PER_DIR + 64);
-      MfmaBwdPackArgs p{};
-      p.v = v; p.ni = y.ni; p.no = y.no; p.ntl = Gm::NTL; p.kb = Gm::KB; p.nt = NT; p.W = y.Wmfb.p;
-      for (int d = 0; d < 2; d++) for (int q = 0; q < 4; q++) p.p_off[d][q] = y.pd.p_off[d][q];
-      CLSTM_LAUNCH(k_pack_mfma_bwd, dim3(64, (unsigned)ndir), dim3(256), 0, s, p);
-      y.mfb_epoch = params_epoch;
-    }
-    LstmMfmaBwdArgs a{};
-    a.W = y.Wmfb.p; a.G = sa.G; a.C = sa.C; a.dH = sa.dH; a.D = sa.D; a.line_off = sa.line_off; a.order = sa.order;
-    a.bs = bs; a.ndir = ndir; a.N = N; a.prog_off = sa.prog_off; a.prog_base = sa.prog_base;
+    const LstmMfmaBwdArgs a = mfma_bwd_args<NO, NT>(y, sa, s);
     const int ngroups = (bs + 15) / 16, nrec = ngroups * ndir;
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM), true);
     (void)smem_set;
@@ -695,13 +706,21 @@ struct Net {
     RoctxRange range_("clstm:forward");
     ensure_training_buffers();   // (a minibatch that clstm_net_predict declared)
     nosave = false;
+    forward_pass(true);
+  }
+  // The forward pass of training (save) and of recognition (!save: predict, on its own geometry).  Every layer runs the family
+  // forward_family names, in the form forward_saves names; without save nothing is kept for a backward pass -- no C, no source
+  // rows S (ensure_source_x is never called), G only as staging -- and the per-layer validity flags are left as predict set them.
+  // Wide layers and the bf16 modes exist with save only (predict_nosave_ok).
+  void forward_pass(bool save) {
     flush_line_off();
     repack();
     hipStream_t s = stream();
-    if (forward_fused_eligible() && !(L.size() == 1 && mfma_eligible(L[0]))) { forward_fused(); return; }
+    if (forward_family(L[0]) == FwdFamily::Fused) { forward_fused(save); return; }
     for (int l = 0; l < (int)L.size(); l++) {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
+      const FwdFamily fam = forward_family(y);
       const bool x_from_hbf = bf16_gemm && bf16_rec && l > 0 && L[l - 1].fwd_persistent && L[l - 1].Hbf.p && y.WtbT.p && y.ni == ndir * L[l - 1].no && (y.ni & 1) == 0;
       // the lock-step recurrence of a wide layer + what follows it (bf16 source rows for the weight gradient); fx_ngx > 0: the
       // persistent kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) -- false if it did not run
@@ -766,17 +785,19 @@ struct Net {
       }
       if (fx_done) { if (!y.sbf_ready) ensure_source_x(l); continue; }
       if (l > 0 && !x_from_hbf) ensure_h_f32(l - 1);   // the products below read the f32 outputs of the layer underneath
-      if (mfma_eligible(y)) {
+      if (fam == FwdFamily::Mfma) {
         // chip-filling minibatch of a narrow layer: the input product is part of the batched recurrence (lstm_mfma.h) -- no
         // hoisted W_x GEMM, no pre-activation array; the [1 | x] columns of the source rows are still the weight gradient's
-        y.sx_valid = l == 0 && src0_ready;
-        ensure_source_x(l);
+        // (so not built without save, not even for the 128-cell layer whose training form runs then -- it has no no-save
+        //  instantiation, reserve_batch kept its arrays: the kernel reads the frames themselves)
+        if (save) { y.sx_valid = l == 0 && src0_ready; ensure_source_x(l); }
         timing.begin("lstm_fwd", s);
-        launch_mfma(y, true, s);
-        y.h_f32_valid = y.sh_valid = true;
+        launch_mfma(y, true, s, forward_saves(y, fam, save));
+        if (save) y.h_f32_valid = y.sh_valid = true;
         timing.end(s);
         continue;
       }
+      if (!save) REQUIRE(y.G.p && y.G.cap >= (size_t)N * M, "internal: predict geometry without a pre-activation array");
       timing.begin("gemm_gates_x", s);
       if (x_from_hbf)
       {
@@ -803,22 +824,21 @@ struct Net {
       // the [1 | x] columns of the f32 source rows: written now -- unless this is an upper layer whose weight-gradient
       // product will read the bf16 rows instead (decided after the recurrence below; ensure_source_x() then builds them
       // only if something still asks for them: a fallback path or the state API)
-      y.sx_valid = l == 0 && src0_ready;
-      if (l == 0 || !y.wide) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
-      LstmSeqArgs a{};
-      a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
-      a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
-      a.S = y.S.p; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
-#ifdef CLSTM_LSTM_PROF
-      lstm_prof.reserve(128); a.prof = lstm_prof.p;
-#endif
-      if (y.wide) run_wide(wide_args(y, true), 0);
+      if (save) y.sx_valid = l == 0 && src0_ready;
+      if (save && (l == 0 || !y.wide)) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
+      if (fam == FwdFamily::Wide) run_wide(wide_args(y, true), 0);
       else {
+        LstmSeqArgs a = seq_args(y, true, save);
+#ifdef CLSTM_LSTM_PROF
+        if (save) { lstm_prof.reserve(128); a.prof = lstm_prof.p; }
+#endif
         timing.begin("lstm_fwd", s);
-        launch_lstm(true, y.nk4, y.pd.ku, a, bs, y.nthreads, s); y.h_f32_valid = y.sh_valid = true;
+        launch_lstm(true, y.nk4, y.pd.ku, a, bs, y.nthreads, s, save);
+        if (save) y.h_f32_valid = y.sh_valid = true;
+        else g_path_count[22]++;
         timing.end(s);
       }
-      if (!y.sbf_ready) ensure_source_x(l);
+      if (save && !y.sbf_ready) ensure_source_x(l);
     }
     forward_softmax();
   }
@@ -851,10 +871,10 @@ struct Net {
   }
 
   // ---- recognition: the forward pass of a minibatch nobody will run backward on (clstm_net_predict) ----
-  // The SAME family as forward() would pick for this minibatch (fused launch / batched MFMA / per line, strict and forced options
-  // included) in its no-save form: identical arithmetic, so identical outputs.  Nothing is saved for a backward pass (no
-  // activations over G, no C, no source rows S -- ensure_source_x is never called), the training NaN flag is not passed
-  // (what clstm_net_set_training(net, 0) does, without changing that setting), nbackward and the training state are untouched.
+  // forward_pass without save: the family of every layer is chosen by forward_family, the one function forward() and
+  // reserve_batch ask too (fused launch / batched MFMA / per line, strict and forced options included), and runs in its no-save
+  // form: identical arithmetic, so identical outputs.  The training NaN flag is not passed (what clstm_net_set_training(net, 0)
+  // does, without changing that setting), nbackward and the training state are untouched.
   // Wide layers and the bf16 modes have no no-save kernels: today's forward pass, without the NaN flag.
   // clstm_debug_path_count: 22 per-line no-save recurrences, 23 fused no-save launches, 15 batched-MFMA no-save launches.
   // The batched recurrence of a 128-cell layer has no no-save instantiation (lstm_mfma.h): its training form runs (counter 16).
@@ -863,40 +883,10 @@ struct Net {
     RoctxRange range_("clstm:predict");
     struct Guard { bool& f; Guard(bool& x) : f(x) { f = true; } ~Guard() { f = false; } } guard_(in_predict);
     if (!geom_predict) { forward(); return; }   // (no no-save kernels for this net: see reserve_batch)
-    flush_line_off();
-    repack();
-    hipStream_t s = stream();
     nosave = true;
     src0_ready = false;
     for (auto& y : L) { y.sx_valid = y.sh_valid = false; y.h_f32_valid = true; y.sbf_ready = false; y.fwd_persistent = false; }
-    if (forward_fused_eligible() && !(L.size() == 1 && mfma_eligible(L[0]))) { forward_fused(false); return; }
-    for (int l = 0; l < (int)L.size(); l++) {
-      Layer& y = L[l];
-      const int M = ndir * 4 * y.no;
-      if (mfma_eligible(y)) {
-        // (128 cells: no no-save instantiation -- the training form, whose arrays reserve_batch kept for this layer; still no
-        //  ensure_source_x: the kernel reads the frames themselves, the [1 | x] columns are the weight gradient's)
-        timing.begin("lstm_fwd", s);
-        launch_mfma(y, true, s, !mfma_nosave_ok(y));
-        timing.end(s);
-        continue;
-      }
-      REQUIRE(y.G.p && y.G.cap >= (size_t)N * M, "internal: predict geometry without a pre-activation array");
-      timing.begin("gemm_gates_x", s);
-      gemm_f32<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), layer_input_ld(l), N), gemm_mc(y.Wt, M, y.ni, 0),
-                                 StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
-      timing.end(s);
-      check_launch();
-      LstmSeqArgs a{};
-      a.Rpk = y.Rf; a.G = y.G.p; a.C = nullptr; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
-      a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
-      a.S = nullptr; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
-      timing.begin("lstm_fwd", s);
-      launch_lstm_fwd_nosave(y.nk4, y.pd.ku, a, bs, y.nthreads, s);
-      timing.end(s);
-      g_path_count[22]++;
-    }
-    forward_softmax();
+    forward_pass(false);
   }
 
   // ---- the forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h) ----
@@ -952,9 +942,7 @@ struct Net {
     g_path_count[save ? 5 : 23]++;
     FwdFusedKernelArgs k{};
     LstmSeqArgs& a = k.a;
-    a.Rpk = y.Rf; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = nullptr; a.D = nullptr;
-    a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.ldh = y.ldh; a.hofs = y.hofs;
-    a.S = y.S.p; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds; a.bs = bs;
+    a = seq_args(y, true, save);
     a.prog_off = (long long)y.H.cap - 64 - PROG_WORDS;
     REQUIRE(a.prog_off >= (long long)N * y.ldh + 16, "internal: progress words overlap the output rows");
     a.prog_base = fw_prog_base;
@@ -969,10 +957,7 @@ struct Net {
     h.prog = (const int*)(y.H.p + a.prog_off);
     h.nrec = bs * ndir; h.npb = fw_npitems;
     const unsigned nblk = (unsigned)(h.nrec + h.npb + fw_ncitems);   // one item per helper workgroup
-    if (save) {
-      y.sx_valid = src0_ready;
-      ensure_source_x(0);
-    } else { a.C = nullptr; a.S = nullptr; }
+    if (save) { y.sx_valid = src0_ready; ensure_source_x(0); }
     static const char* trace_path = getenv("CLSTM_FW_TRACE");   // diagnostics: wall-clock stamps of every workgroup / item of the launch
     const size_t trace_rows = (size_t)h.nrec + fw_npitems + fw_ncitems;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); HIPCHECK(hipMemsetAsync(dw_trace.p, 0, trace_rows * 4 * sizeof(long long), s)); h.trace = dw_trace.p; }
@@ -1283,15 +1268,12 @@ struct Net {
     for (int l = (int)L.size() - 1; l >= 0; l--) {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
-      LstmSeqArgs a{};
-      a.Rpk = y.Rb; a.G = y.G.p; a.C = y.C.p; a.H = y.H.p; a.dH = y.dH.p; a.D = y.D.p;
-      a.line_off = line_off.p; a.order = line_off.p + bs + 1; a.no = y.no; a.ndir = ndir; a.bs = bs;
+      const LstmSeqArgs a = seq_args(y, false);   // (no progress words: backward_layer_overlapped sets them in its copy)
       // W.d += delta [1; x_t; h_{t-1}]^T for the four gates of each direction
       // (both directions in one batched launch: half the slabs per direction fill the chip)
       const int R = 1 + y.ni + y.no, Cn = 4 * y.no;
       int ns;
       bool bwd_persistent = false;
-      a.prog_off = -1; a.prog_base = 0;
       if (!bf16_gemm && overlap_eligible(y)) {
         // the recurrence and the weight-gradient GEMM run side by side (gemm_dw.h)
         backward_layer_overlapped(y, a, R, Cn);

@@ -204,15 +204,11 @@ static bool launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, 
 }
 // k values per lane actually used: the padded 4*nk4 in general, exact for the 97..100-cell case (uw3 BiLSTM(100))
 static int pick_ku(int no, int nk4) { return (nk4 == 7 && (no + 3) / 4 == 25) ? 25 : 4 * nk4; }
-static void launch_lstm(bool fwd, int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { if (fwd) launch_fwd<N, K>(a, bs, nthreads, s); else launch_bwd<N, K>(a, bs, nthreads, s); check_launch(); return; }
-  CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
-#undef CASE_
-  throw Error("unsupported nhidden for the register-resident recurrence");
-}
-// the forward recurrence in its no-save form (recognition: only h leaves; lstm_seq.h)
-static void launch_lstm_fwd_nosave(int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { launch_fwd<N, K, false>(a, bs, nthreads, s); check_launch(); return; }
+// save = false (forward only): the recurrence in its no-save form (recognition: only h leaves; lstm_seq.h)
+static void launch_lstm(bool fwd, int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s, bool save = true) {
+#define CASE_(N, K) if (nk4 == N && ku == K) { \
+    if (!fwd) launch_bwd<N, K>(a, bs, nthreads, s); else if (save) launch_fwd<N, K>(a, bs, nthreads, s); else launch_fwd<N, K, false>(a, bs, nthreads, s); \
+    check_launch(); return; }
   CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
 #undef CASE_
   throw Error("unsupported nhidden for the register-resident recurrence");

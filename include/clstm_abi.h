@@ -160,7 +160,8 @@ int clstm_net_params_changed(clstm_net* net);
 int clstm_net_set_learning_rate(clstm_net* net, float lr, float momentum);
 int clstm_net_set_gradient_clip(clstm_net* net, float clip);
 
-/* Declare the next minibatch: bs lines of T_h[b] frames each (HOST).  N = sum T. */
+/* Declare the next minibatch: bs lines of T_h[b] frames each (HOST).  N = sum T.  T_h / bs are validated before the net is touched
+ * (no negative length, at least one frame, fewer than 2147483000): a refused call leaves the previous minibatch the current one. */
 int clstm_net_set_batch(clstm_net* net, const int* T_h, int bs);
 /* set_inputs (clstm.cc:684-690): x [N][ninput], frame-major, feature contiguous.
  * Input range: any float32.  The result class does not depend on the minibatch size: the batched recurrence that single-layer
@@ -198,7 +199,7 @@ int clstm_net_decode(clstm_net* net, int* classes_h, int* locs_h, int* counts_h)
  *   Outputs (HOST) are laid out as clstm_net_decode's: line b's entries start at its first frame's index, counts_h[b] of them;
  * conf_h[i] is the softmax output at (locs_h[i], classes_h[i]) -- CharPrediction::p.  classes_h / locs_h / conf_h may be NULL,
  * counts_h is required.
- *   The forward pass is the one clstm_net_forward would run for this minibatch -- same kernel family by the same rule (fused
+ *   The forward pass is the one clstm_net_forward runs for this minibatch -- one scheduler, one rule for the kernel family (fused
  * launch, batched MFMA recurrence from 640 lines on with its input-range routing, per-line kernels; clstm_net_set_strict_f32 and
  * the forced experiment options apply) -- in its NO-SAVE form: identical arithmetic, bit-identical outputs, but nothing is kept for
  * a backward pass (no gate activations, no cell states, no source rows) and the buffers only a training step needs are not even

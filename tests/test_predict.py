@@ -321,6 +321,26 @@ def test_accessors_refuse_after_predict_and_training_recovers(backend):
     backend.lib.call("clstm_net_predict_h", net.h, ptr(i32([2, 2])), 2, ptr(xx), None, None, None, ptr(cnt))
 
 
+def test_refused_set_batch_leaves_the_minibatch_intact(backend):
+    """clstm_net_set_batch validates the line lengths before it changes the net: after a declaration with a negative length is
+    refused, forward + decode of the minibatch declared before give the bytes they gave before"""
+    from clstm_amd.abi import ClstmError, i32, ptr
+    ni, nh, nc = 12, [30], 20
+    rng = np.random.default_rng(19)
+    lines = synth_lines(rng, [9, 1, 14, 30], ni)
+    net = make_net(backend, ni, nh, nc, varied_params(backend, ni, nh, nc, lines))
+    net.set_inputs(lines)
+    net.forward()
+    z, (cls, loc, cnt) = net.outputs(), raw_decode(net)
+    assert cnt.sum() > 0
+    with pytest.raises(ClstmError, match="negative line length"):
+        backend.lib.call("clstm_net_set_batch", net.h, ptr(i32([7, -1])), 2)
+    net.forward()
+    fcls, floc, fcnt = raw_decode(net)
+    assert same_bytes(net.outputs(), z)
+    assert same_bytes(fcnt, cnt) and same_bytes(fcls, cls) and same_bytes(floc, loc)
+
+
 # ---- 5. training is undisturbed -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nh", [[10], [7, 5]])
 def test_training_trajectory_undisturbed_by_predict(backend, nh):
