@@ -158,6 +158,9 @@ int clstm_net_get_grads_h(clstm_net* net, float* grads_h);
 int clstm_net_params_changed(clstm_net* net);
 /* INetwork::setLearningRate (clstm.cc:158-161) + gradient_clip attr (clstm.cc:204) */
 int clstm_net_set_learning_rate(clstm_net* net, float lr, float momentum);
+/* What every update clamps to +-clip is derivs + grads (the carried momentum plus the fresh minibatch gradient), before the momentum
+ * multiply, as the reference does (clstm.cc:201-217); a clip >= 1e6 switches the clamp off.  clip must be > 0 (0, a negative value
+ * and NaN are refused and the previous clip stays in force). */
 int clstm_net_set_gradient_clip(clstm_net* net, float clip);
 
 /* Declare the next minibatch: bs lines of T_h[b] frames each (HOST).  N = sum T.  T_h / bs are validated before the net is touched

@@ -911,6 +911,8 @@ void ora_net_set_params(OraNet *net, const Float *in) { memcpy(net->params, in, 
 void ora_net_get_derivs(OraNet *net, Float *out) { memcpy(out, net->derivs, net->nparams * sizeof(Float)); }
 void ora_net_set_derivs(OraNet *net, const Float *in) { memcpy(net->derivs, in, net->nparams * sizeof(Float)); }
 void ora_net_set_lr(OraNet *net, Float lr, Float mom) { net->lr = lr; net->momentum = mom; }
+/* the "gradient_clip" attribute sgd_update reads (clstm.cc:204): test-only setter, the default stays 100 */
+void ora_net_set_gclip(OraNet *net, Float clip) { net->gclip = clip; }
 
 /* set_inputs(Network, TensorMap2): clstm.cc:684-690 generalised to a batch:
  * x is [T][bs][ni] (feature contiguous) -> inputs[t].v(i,b); resize memsets v and d. */

@@ -99,6 +99,7 @@ class Oracle:
             "ora_net_get_derivs": (None, [P, P]),
             "ora_net_set_derivs": (None, [P, P]),
             "ora_net_set_lr": (None, [P, F, F]),
+            "ora_net_set_gclip": (None, [P, F]),
             "ora_net_set_inputs": (None, [P, P, I, I]),
             "ora_net_forward": (None, [P]),
             "ora_net_backward": (None, [P]),
@@ -215,6 +216,10 @@ class OracleNet:
 
     def set_lr(self, lr, mom):
         self.o.lib.ora_net_set_lr(self.h, lr, mom)
+
+    def set_gradient_clip(self, clip):
+        """+-clip on derivs (gradient + carried momentum) in update(); >= 1e6 switches it off (clstm_compute.cc:553-558)"""
+        self.o.lib.ora_net_set_gclip(self.h, clip)
 
     def set_inputs(self, x):
         """x: [T][bs][ni] or [T][ni]"""

@@ -82,6 +82,70 @@ def oracle_minibatch(ora, OracleNet, params, ninput, nhidden, nclasses, lines, t
     return res
 
 
+# ---- the SGD update, stated exactly (tests/test_update_rule.py, tests/test_distributed.py) ---------------------------------------
+F32 = np.float32
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+def fma_f32(a, b, c):
+    """round_to_float32(a * b + c) with ONE rounding, elementwise, for float32 inputs.
+    The product of two float32 is exact in float64 (48 significant bits).  s = p + c is rounded once to float64 and the TwoSum
+    error term e (s + e == p + c exactly) is exact.  Rounding s to float32 is then wrong only when s lies exactly half way between
+    two neighbouring float32 values while e != 0: the true sum lies on e's side of the tie."""
+    a, b, c = (np.asarray(x, np.float64) for x in (a, b, c))
+    with np.errstate(all="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+        r = s.astype(F32)
+        r64 = r.astype(np.float64)
+        diff = s - r64                                    # exact: r is within half a float32 ulp of s
+        nb = np.nextafter(r, np.where(diff > 0, F32(np.inf), F32(-np.inf)).astype(F32))
+        tie = np.isfinite(s) & np.isfinite(nb) & (diff != 0) & (diff == (nb.astype(np.float64) - r64) / 2)
+        beyond = tie & (e != 0) & ((e > 0) == (diff > 0))
+    return np.where(beyond, nb, r).astype(F32)
+
+
+def update_of_clamped(v0, di, lr, mom):
+    """what `v += lr * di ; d = di * mom` leaves, for the already clamped di = clip(d0 + g), in numpy float32 with one operation per
+    rounding: (d', v' unfused, v' as the single-rounding fused multiply-add -- the compilers may contract `v += di * lr`)"""
+    v0, di, lr, mom = np.asarray(v0, F32), np.asarray(di, F32), F32(lr), F32(mom)
+    with np.errstate(invalid="ignore"):                    # (inf * 0: test_update_rule.py feeds +-inf to the per-operator entry points)
+        return (di * mom).astype(F32), (v0 + (di * lr).astype(F32)).astype(F32), fma_f32(di, lr, v0)
+
+
+def assert_update_bits(v1, d1, want, what, **inputs):
+    """the acceptance rule of the update tests: d' bit for bit, v' bit for bit the unfused or the fused value.  want: what
+    update_of_clamped returned; inputs: arrays quoted at the first differing entry"""
+    ed, ev, evf = want
+    at = lambda i: " ".join("%s %r" % (k, np.asarray(a).ravel()[i]) for k, a in inputs.items())
+    bad = np.flatnonzero(bits(d1) != bits(ed))
+    assert bad.size == 0, "%s: d' differs at %d of %d entries, first %d: got %r want %r (%s)" % (
+        what, bad.size, d1.size, bad[0], d1[bad[0]], ed[bad[0]], at(bad[0]))
+    bad = np.flatnonzero((bits(v1) != bits(ev)) & (bits(v1) != bits(evf)))
+    assert bad.size == 0, "%s: v' differs at %d of %d entries, first %d: got %r want %r or %r (%s)" % (
+        what, bad.size, v1.size, bad[0], v1[bad[0]], ev[bad[0]], evf[bad[0]], at(bad[0]))
+
+
+def pm200(n):
+    """derivs of +-200, the sign by index parity"""
+    return np.where(np.arange(n) % 2 == 0, 200.0, -200.0).astype(F32)
+
+
+def assert_every_entry_once(v0, d0, g, v1, d1, lr, mom, what):
+    """d0 = pm200, |g| < 100, clip 100: d0 + g lies beyond the clip whatever the gradient arithmetic did, so the clamped sum is
+    +-100, d' = +-f32(100 mom) and v' = v0 +- 100 lr exactly -- an entry the update missed, or visited twice, stands out.
+    Returns max |g|."""
+    assert np.isfinite(g).all() and np.abs(g).max() < 100.0, "inconclusive: max |g| = %g (%s)" % (np.abs(g).max(), what)
+    assert np.array_equal(d0, pm200(d0.size))
+    assert_update_bits(v1, d1, update_of_clamped(v0, d0 / F32(2.0), lr, mom), what, v0=v0, d0=d0, g=g)
+    return float(np.abs(g).max())
+
+
 class Backend:
     """Where the C ABI runs: 'emu' = host-thread emulator build of the kernel sources (CPU
     tests), 'hip' = the real libclstm_hip.so on an MI355X (-m gpu tests)."""

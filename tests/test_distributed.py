@@ -15,33 +15,45 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NI, NH, NC = 4, 5, 4
+SAT_SHAPE = (4, 5, 5)     # 455 parameters, 455 % 4 == 3: the four-wide loop of k_peer_allreduce_update ends in a partial group
 
 
-def make_data(step, world=2):
+def make_data(step, world=2, shape=None):
     """four lines for two ranks (the original case); world lines + 3 beyond that: uneven shards, every rank owns a line"""
     from common import synth_lines
+    ni, _, nc = shape or (NI, NH, NC)
     rng = np.random.default_rng(100 + step)
     T = [5, 3, 4, 6] if world <= 2 else [3 + (7 * i + step) % 4 for i in range(world + 3)]
-    lines = synth_lines(rng, T, NI)
-    trs = [rng.integers(1, NC, 2).astype(np.int32) for _ in T]
+    lines = synth_lines(rng, T, ni)
+    trs = [rng.integers(1, nc, 2).astype(np.int32) for _ in T]
     return lines, trs
 
 
-def oracle_after(ora32, nsteps, world):
+def oracle_after(ora32, nsteps, world, shape=None, clip=None, shares=None):
+    """clip: the oracle's gradient clip (None: its default of 100); shares (a list): takes, per step, the share of the entries of
+    derivs (carried momentum + minibatch gradient) that lie beyond the clip before update() clamps them"""
     from clstm_amd.init import init_params
     from oracle.oracle import OracleNet
-    ref = OracleNet(ora32, NI, NH, NC, init=False)
-    ref.set_params(init_params(NI, NH, NC, seed=0.222) * 30)
+    ni, nh, nc = shape or (NI, NH, NC)
+    ref = OracleNet(ora32, ni, nh, nc, init=False)
+    ref.set_params(init_params(ni, nh, nc, seed=0.222) * 30)
     ref.set_lr(5e-2, 0.9)
+    if clip is not None:
+        ref.set_gradient_clip(clip)
     for step in range(nsteps):
-        lines, trs = make_data(step, world)
+        lines, trs = make_data(step, world, shape)
         for x, t in zip(lines, trs):
             ref.set_inputs(x); ref.forward(); ref.ctc_deltas(t); ref.backward()
+        if shares is not None:
+            shares.append(float((np.abs(ref.get_derivs()) > (100.0 if clip is None else clip)).mean()))
         ref.update()
     return ref
 
 
-def worker(rank, world, port, outdir, use_lib_comm, slow_rank0_s=0.0, sabotage=False):
+def worker(rank, world, port, outdir, use_lib_comm, slow_rank0_s=0.0, sabotage=False, clip=None, derivs0=None, shape=None):
+    """clip: clstm_net_set_gradient_clip (None: the library's default); derivs0 "pm200": the derivs are preloaded with +-200 before
+    EVERY step and parameters / derivs / gradient around every step are saved for the exact check; shape: (ni, nh, nc)"""
+    ni, nh, nc = shape or (NI, NH, NC)
     if slow_rank0_s:
         os.environ["CLSTM_PEER_TIMEOUT_S"] = "1"      # far below the time rank 0 stays away: the HOST wait must cover it
     os.environ["CLSTM_REPLICA_CHECK_EVERY"] = "1" if use_lib_comm else "0"
@@ -57,13 +69,15 @@ def worker(rank, world, port, outdir, use_lib_comm, slow_rank0_s=0.0, sabotage=F
     from clstm_amd.parallel import Trainer, shard
     from common import emu_lib
     lib = emu_lib()
-    p0 = init_params(NI, NH, NC, seed=0.222) * 30
+    p0 = init_params(ni, nh, nc, seed=0.222) * 30
     params = torch.from_numpy(p0.copy())
     derivs = torch.zeros_like(params)
     grads = torch.zeros_like(params)
-    net = Network(NI, NH, NC, lib=lib, params=params, derivs=derivs, grads=grads)
+    net = Network(ni, nh, nc, lib=lib, params=params, derivs=derivs, grads=grads)
     net.params_changed()
     net.setLearningRate(5e-2, 0.9)
+    if clip is not None:
+        net.set_gradient_clip(clip)
     if use_lib_comm:
         from clstm_amd.net import Comm
 
@@ -81,7 +95,11 @@ def worker(rank, world, port, outdir, use_lib_comm, slow_rank0_s=0.0, sabotage=F
     import ctypes
     import time
     for step in range(2):
-        lines, trs = make_data(step, world)
+        lines, trs = make_data(step, world, shape)
+        if derivs0 == "pm200":
+            from common import pm200
+            derivs.copy_(torch.from_numpy(pm200(derivs.numel())))
+            np.save(os.path.join(outdir, "v0_%d_%d.npy" % (step, rank)), params.numpy())
         if slow_rank0_s and rank == 0 and step == 1:
             time.sleep(slow_rank0_s)       # clstmocrtrain's rank 0 in its test / save phase: the others are already at the next exchange
         if sabotage and rank == world - 1 and step == 1:
@@ -92,6 +110,10 @@ def worker(rank, world, port, outdir, use_lib_comm, slow_rank0_s=0.0, sabotage=F
             net.train_step([len(l) for l in mine_l], np.ascontiguousarray(np.concatenate(mine_l, 0), np.float32), mine_t)
         else:
             tr.train(shard(lines, rank, world), shard(trs, rank, world))
+        if derivs0 == "pm200":
+            lib.call("clstm_synchronize")
+            for name, t in (("v1", params), ("d1", derivs), ("g", grads)):
+                np.save(os.path.join(outdir, "%s_%d_%d.npy" % (name, step, rank)), t.numpy())
     if sabotage:                          # every rank must be told, with the step number
         try:
             lib.call("clstm_synchronize")
@@ -121,13 +143,15 @@ def _port(base):
     return base + (os.getpid() % 1500) + 13 * _port.n
 
 
-def _check_replicas_and_oracle(tmp_path, ora32, world, what):
+def _check_replicas_and_oracle(tmp_path, ora32, world, what, ref=None):
+    """ref: the oracle net to compare with (default: oracle_after two steps at the module's shape and the default clip)"""
     from common import assert_close
     p = [np.load(tmp_path / ("params_%d.npy" % r)) for r in range(world)]
     d = [np.load(tmp_path / ("derivs_%d.npy" % r)) for r in range(world)]
     for r in range(1, world):
         assert np.array_equal(p[0], p[r]) and np.array_equal(d[0], d[r]), "rank %d differs from rank 0" % r    # replicas stay identical
-    ref = oracle_after(ora32, 2, world)
+    if ref is None:
+        ref = oracle_after(ora32, 2, world)
     # (the minibatch gradient is summed shard by shard, then over ranks in rank order: with more shards the float32 sum is
     #  grouped differently from the oracle's line-by-line accumulation -- lr x 1e-5 of a gradient entry of order 1)
     assert_close(p[0], ref.get_params(), rtol=2e-5, atol=2e-7 if world <= 2 else 1e-6, what="params after 2 DP steps, " + what)
@@ -177,6 +201,61 @@ def test_replica_check_reports_a_diverged_rank(tmp_path, use_lib_comm):
     assert all(told), verdicts
 
 
+def _check_pm200(outdir, world, what, lr=5e-2, mom=0.9):
+    """common.assert_every_entry_once (the exact check of tests/test_update_rule.py (b)) on what worker(derivs0="pm200") saved:
+    with derivs of +-200, a summed gradient below 100 and the default clip of 100, every entry of derivs ends at +-f32(100 mom)
+    and every parameter moves by +-100 lr -- whatever the number of ranks, because the gradient drops out.  Both steps, every rank."""
+    from common import assert_every_entry_once, pm200
+    for step in range(2):
+        for r in range(world):
+            v0, v1, d1, g = (np.load(os.path.join(outdir, "%s_%d_%d.npy" % (n, step, r))) for n in ("v0", "v1", "d1", "g"))
+            assert_every_entry_once(v0, pm200(v0.size), g, v1, d1, lr, mom, "%s, step %d rank %d" % (what, step, r))
+            if r:
+                assert np.array_equal(g, g0) and np.array_equal(v1, v10), "rank %d differs from rank 0" % r
+            else:
+                g0, v10 = g, v1
+
+
+def _saturating_clip(ora32, world, shape):
+    """a clip that bites in a two-step run from zero derivs: the median of |derivs| the oracle holds before its first update.
+    Returns it with the oracle after two steps under it; the share of entries beyond it is asserted for both steps."""
+    from oracle.oracle import OracleNet
+    from clstm_amd.init import init_params
+    ni, nh, nc = shape
+    first = OracleNet(ora32, ni, nh, nc, init=False)
+    first.set_params(init_params(ni, nh, nc, seed=0.222) * 30)
+    lines, trs = make_data(0, world, shape)
+    for x, t in zip(lines, trs):
+        first.set_inputs(x); first.forward(); first.ctc_deltas(t); first.backward()
+    clip = float(np.median(np.abs(first.get_derivs())))
+    shares = []
+    ref = oracle_after(ora32, 2, world, shape, clip, shares)
+    assert clip > 0 and all(0.1 <= s <= 0.9 for s in shares), "inconclusive: clip %g, shares beyond it %r" % (clip, shares)
+    return clip, ref
+
+
+@pytest.mark.parametrize("use_lib_comm,world", [(True, 2), (True, 4), ("one_call", 2), ("one_call", 4), (False, 2)],
+                         ids=["library_communicator-2", "library_communicator-4", "one_call_peer_allreduce-2", "one_call_peer_allreduce-4",
+                              "torch_distributed_fallback-2"])
+def test_data_parallel_update_where_the_clip_saturates(tmp_path, ora32, use_lib_comm, world):
+    """The update behind an exchange -- all-reduce then k_update (library communicator, torch fallback), or k_peer_allreduce_update
+    (one call; the worker holds path count 7 to the number of steps) -- where the clamp is not the identity, on a net of 455
+    parameters (455 % 4 == 3: the four-wide loop ends in a partial group and its last load reaches past the end of the buffer).
+    (1) derivs of +-200: exact, see _check_pm200.  (2) two steps from zero derivs under a clip at the median of the first step's
+    gradient, against the oracle with the same clip: tolerances of _check_replicas_and_oracle, replicas bit-identical."""
+    import torch.multiprocessing as mp
+    from common import emu_lib
+    emu_lib()
+    what = "%d ranks, %s" % (world, use_lib_comm)
+    (tmp_path / "pm200").mkdir()
+    mp.spawn(worker, args=(world, _port(24000), str(tmp_path / "pm200"), use_lib_comm, 0.0, False, None, "pm200", SAT_SHAPE), nprocs=world, join=True)
+    _check_pm200(str(tmp_path / "pm200"), world, what)
+    clip, ref = _saturating_clip(ora32, world, SAT_SHAPE)
+    (tmp_path / "sat").mkdir()
+    mp.spawn(worker, args=(world, _port(24000), str(tmp_path / "sat"), use_lib_comm, 0.0, False, clip, None, SAT_SHAPE), nprocs=world, join=True)
+    _check_replicas_and_oracle(tmp_path / "sat", ora32, world, "clip %g, %s" % (clip, what), ref=ref)
+
+
 def test_shard_covers_everything():
     from clstm_amd.parallel import shard
     items = list(range(11))
@@ -191,10 +270,12 @@ def test_shard_covers_everything():
         shard([1, 2], 0, 4)
 
 
-def gpu_worker(rank, world, port, outdir, share_device=False, one_call=False, slow_rank0_s=0.0):
+def gpu_worker(rank, world, port, outdir, share_device=False, one_call=False, slow_rank0_s=0.0, clip=None, derivs0=None, shape=None):
     """one rank per GPU: the library's RCCL communicator (clstm_comm_create + clstm_net_set_comm), gloo for the id.
     share_device: every rank on GPU 0 with a communicator WITHOUT RCCL (CLSTM_COMM_NO_RCCL=1: RCCL refuses duplicate GPUs) --
-    the exchange is the peer-read path over HIP IPC mappings alone.  one_call: clstm_net_train_step (the fused path)."""
+    the exchange is the peer-read path over HIP IPC mappings alone.  one_call: clstm_net_train_step (the fused path).
+    clip / derivs0 / shape: as in worker()."""
+    ni, nh, nc = shape or (NI, NH, NC)
     if share_device:
         os.environ["CLSTM_COMM_NO_RCCL"] = "1"
     if slow_rank0_s:
@@ -218,13 +299,15 @@ def gpu_worker(rank, world, port, outdir, share_device=False, one_call=False, sl
     torch.cuda.set_stream(stream)
     lib.call("clstm_set_stream", stream.cuda_stream)
     dev = torch.device("cuda", 0 if share_device else rank)
-    p0 = init_params(NI, NH, NC, seed=0.222) * 30
+    p0 = init_params(ni, nh, nc, seed=0.222) * 30
     params = torch.from_numpy(p0.copy()).to(dev)
     derivs = torch.zeros_like(params)
     grads = torch.zeros_like(params)
-    net = Network(NI, NH, NC, lib=lib, params=params, derivs=derivs, grads=grads)
+    net = Network(ni, nh, nc, lib=lib, params=params, derivs=derivs, grads=grads)
     net.params_changed()
     net.setLearningRate(5e-2, 0.9)
+    if clip is not None:
+        net.set_gradient_clip(clip)
 
     def exchange(ident):
         box = [ident]
@@ -235,8 +318,14 @@ def gpu_worker(rank, world, port, outdir, share_device=False, one_call=False, sl
     import ctypes
     import time
     for step in range(2):
-        lines, trs = make_data(step, world)
+        lines, trs = make_data(step, world, shape)
         mine_l, mine_t = shard(lines, rank, world), shard(trs, rank, world)
+        if derivs0 == "pm200":
+            from common import pm200
+            lib.call("clstm_synchronize")
+            derivs.copy_(torch.from_numpy(pm200(derivs.numel())).to(dev))
+            torch.cuda.current_stream().synchronize()
+            np.save(os.path.join(outdir, "v0_%d_%d.npy" % (step, rank)), params.cpu().numpy())
         if slow_rank0_s and rank == 0 and step == 1:
             time.sleep(slow_rank0_s)
         if one_call:
@@ -244,6 +333,10 @@ def gpu_worker(rank, world, port, outdir, share_device=False, one_call=False, sl
             net.train_step([len(l) for l in mine_l], x, mine_t)
         else:
             tr.train(mine_l, mine_t)
+        if derivs0 == "pm200":
+            lib.call("clstm_synchronize")
+            for name, t in (("v1", params), ("d1", derivs), ("g", grads)):
+                np.save(os.path.join(outdir, "%s_%d_%d.npy" % (name, step, rank)), t.cpu().numpy())
     lib.call("clstm_synchronize")         # (also the verdict of the replica checks that followed both updates)
     if one_call:
         cnt = ctypes.c_longlong(0)
@@ -300,6 +393,29 @@ def test_two_processes_on_one_gpu_peer_read_allreduce(tmp_path, ora32, world, on
     if one_call:
         assert [open(tmp_path / ("peer_%d.txt" % r)).read() for r in range(world)] == ["2"] * world
     _check_replicas_and_oracle(tmp_path, ora32, world, "%d processes on one GPU" % world)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("one_call", [True, False], ids=["train_step_fused_update", "separate_calls_plain_allreduce"])
+def test_two_processes_on_one_gpu_update_where_the_clip_saturates(tmp_path, ora32, one_call):
+    """test_data_parallel_update_where_the_clip_saturates on the MI355X: two rank processes on device 0, the peer-read exchange
+    over HIP IPC, 455 parameters.  Which clamp each mode covers: in the one-call form (clstm_net_train_step) k_peer_allreduce_update
+    sums the ranks' gradients AND applies the update, so the clamp under test is its own, partial last group included (path count 7
+    is held to the number of steps).  With separate calls the same kernel runs only as the plain all-reduce (no parameters handed
+    to it, nothing clamped there), and the clamp under test is k_update's, on the sum that all-reduce left."""
+    import torch.multiprocessing as mp
+    what = "2 processes on one GPU, one_call=%s" % one_call
+    (tmp_path / "pm200").mkdir()
+    mp.spawn(gpu_worker, args=(2, _port(35500), str(tmp_path / "pm200"), True, one_call, 0.0, None, "pm200", SAT_SHAPE), nprocs=2, join=True)
+    if one_call:
+        assert [open(tmp_path / "pm200" / ("peer_%d.txt" % r)).read() for r in range(2)] == ["2"] * 2
+    _check_pm200(str(tmp_path / "pm200"), 2, what)
+    clip, ref = _saturating_clip(ora32, 2, SAT_SHAPE)
+    (tmp_path / "sat").mkdir()
+    mp.spawn(gpu_worker, args=(2, _port(35500), str(tmp_path / "sat"), True, one_call, 0.0, clip, None, SAT_SHAPE), nprocs=2, join=True)
+    if one_call:
+        assert [open(tmp_path / "sat" / ("peer_%d.txt" % r)).read() for r in range(2)] == ["2"] * 2
+    _check_replicas_and_oracle(tmp_path / "sat", ora32, 2, "clip %g, %s" % (clip, what), ref=ref)
 
 
 @pytest.mark.gpu
