@@ -111,6 +111,7 @@ _SIGS = {
     "clstm_comm_rank": [_P],
     "clstm_comm_size": [_P],
     "clstm_comm_peer_active": [_P],
+    "clstm_comm_peer_capacity": [_P, _P],
     "clstm_allreduce_flat": [_P, _P, C.c_longlong],
     "clstm_net_set_comm": [_P, _P],
     "clstm_net_replica_check": [_P],

@@ -754,6 +754,12 @@ int clstm_comm_destroy(clstm_comm* c) { ABI_BEGIN delete c; ABI_END }
 int clstm_comm_rank(clstm_comm* c) { return c ? c->c.rank : 0; }
 int clstm_comm_size(clstm_comm* c) { return c ? c->c.nranks : 1; }
 int clstm_comm_peer_active(clstm_comm* c) { return c && c->c.peer.ok ? 1 : 0; }
+int clstm_comm_peer_capacity(clstm_comm* c, long long* floats) {
+  ABI_BEGIN
+  REQUIRE(c && floats, "null argument");
+  *floats = c->c.peer.ok ? (long long)c->c.peer.cap : 0;
+  ABI_END
+}
 int clstm_allreduce_flat(clstm_comm* c, float* buf_d, long long n) {
   ABI_BEGIN
   REQUIRE(c && buf_d && n >= 0, "bad all-reduce arguments");
@@ -855,7 +861,7 @@ int clstm_debug_set_option(const char* name, int value) {   // experiment switch
 }
 int clstm_debug_path_count(int which, long long* out_h) {
   ABI_BEGIN
-  REQUIRE(which >= 0 && which < 24 && out_h, "bad path index");
+  REQUIRE(which >= 0 && which < 25 && out_h, "bad path index");
   if (which == 21) {   // counted on the device: minibatches whose forward pass the batched recurrence handed to its routed per-line twins (lstm_mfma.h)
     int n = 0;
     HIPCHECK(hipStreamSynchronize(g_stream));

@@ -1,8 +1,30 @@
 // comm.h -- the gradient exchange of the data-parallel ranks: the library's communicator (RCCL, bound at first use;
 // the host emulator: a shared-memory all-reduce between rank processes), the one-shot peer-read all-reduce over HIP IPC mappings
-// (exchange slots, flag handshake, set-up probe, the hosts' announce words) and the replica check's buffers.  Included by
-// clstm_hip.hip inside namespace clstm, behind Error / REQUIRE / HIPCHECK / DevBuf / dev_err_words / check_launch and ops.h (the
-// device side: k_peer_barrier, k_peer_fill, k_peer_probe, k_peer_allreduce_update).  Split out of clstm_hip.hip in round 5.
+// (exchange slots that grow with the gradient, flag handshake, set-up probe, the hosts' announce words), the choice between its
+// one-shot and its two-phase form, and the replica check's buffers.  Included by clstm_hip.hip inside namespace clstm, behind
+// Error / REQUIRE / HIPCHECK / DevBuf / dev_err_words / check_launch and ops.h (the device side: k_peer_barrier, k_peer_fill,
+// k_peer_probe, k_peer_allreduce_update, k_peer_reduce_scatter, k_peer_gather_update).  Split out of clstm_hip.hip in round 5.
+// ---- which form an exchange of n floats takes (both builds) ------------------------------------------
+// One-shot (every rank reads every rank's whole slot, (R-1).n floats, one barrier) up to PEER_ONE_SHOT_FLOATS and, above that, at
+// two ranks, where both forms move the same bytes and the one-shot form has a barrier and a launch fewer; two-phase (reduce-scatter
+// + all-gather, 2.(R-1).n/R floats, two barriers) above it at three or more ranks.  The 4 MB boundary is the former size limit of
+// the peer path, inherited and NOT measured over xGMI.  Experiment option peer_two_phase (dbgopt.h): 0 one-shot at
+// every size, 2 two-phase at every size and rank count.  Both forms add in rank order: their results are bit-identical.
+constexpr size_t PEER_ONE_SHOT_FLOATS = 1u << 20;
+constexpr int PEER_FLAG_ROWS = 4;   // a rank's flag array: barrier A in rows 0 / 1 (step parity), the two-phase form's barrier B in rows 2 / 3
+static bool peer_use_two_phase(size_t n, int nranks) {
+  const int o = dbg_opt("peer_two_phase");
+  if (o == 0) return false;
+  if (o >= 2) return true;
+  return n > PEER_ONE_SHOT_FLOATS && nranks >= 3;
+}
+struct Comm;
+// barrier A (the hosts announce the exchange first) and, in the two-phase form, the reduce-scatter and barrier B: after this the
+// reduced values lie where peer_exchange_finish reads them.  No host-side wait behind the announce of barrier A.
+static void peer_exchange_begin(Comm& c, int sq, bool two_phase, size_t n, hipStream_t s);
+// the sum into g and, with v, k_update's arithmetic (v null: a plain in-place all-reduce into g)
+static void peer_exchange_finish(Comm& c, int sq, bool two_phase, float* v, float* d, float* g, size_t n, float lr, float mom, float clip, const int* err,
+                                 int* step_word, int step_id, int* nanflag, int step_no, hipStream_t s);
 // ---- RCCL communicator (data-parallel gradient exchange) ----------------------------------------------
 // librccl.so.1 is bound at first use (dlopen): the library loads and runs single-GPU on a box without RCCL,
 // and inside a PyTorch process the already-loaded RCCL/HIP runtime pair is reused (same SONAMEs).
@@ -47,22 +69,26 @@ struct RcclApi {
 // tests the protocol).  IPC mappings exist between processes of one host only, so the handles travel through a POSIX
 // shared-memory rendezvous named after the communicator's id (no RCCL involved: RCCL refuses two ranks on one device, and
 // the test needs exactly that); every rank publishes whether it could export and map, and the peer path is used only if ALL
-// ranks could -- otherwise all stay on ncclAllReduce.  Buffers up to PEER_MAX_FLOATS (4 MB): the 35 MB gradient of configs[4]
-// is bandwidth-bound and stays with RCCL.
-constexpr size_t PEER_MAX_FLOATS = 1u << 20;
+// ranks could -- otherwise all stay on ncclAllReduce.  The slots hold PEER_ONE_SHOT_FLOATS (4 MB) to begin with; a gradient
+// larger than the slots in use (the 35 MB of configs[4]) makes the ranks set the exchange up again, collectively, at a capacity
+// that holds it (Comm::peer_ready), and above 4 MB at three or more ranks the exchange takes its two-phase form (ops.h:
+// k_peer_reduce_scatter / k_peer_gather_update), which moves 2/R of the one-shot form's bytes.
+constexpr size_t PEER_CAP_STEP = 1u << 18;                 // capacities above PEER_ONE_SHOT_FLOATS are multiples of 1 MB
+constexpr size_t PEER_SLOT_LIMIT = 0x7FFFFFF0u / 4;        // a slot is read through ONE buffer descriptor (devintrin.h:make_buf)
 struct PeerExchange {
   bool tried = false, ok = false;
   size_t cap = 0;                       // floats per slot
+  int gen = 0;                          // set-ups so far (the rendezvous segment's name carries it)
   float* xbuf = nullptr;                // own exchange buffer [2][cap]
-  int* flags = nullptr;                 // own flag array [2][PEER_MAX_RANKS]
+  int* flags = nullptr;                 // own flag array [PEER_FLAG_ROWS][PEER_MAX_RANKS]
   float* px[PEER_MAX_RANKS] = {};       // every rank's buffer / flags as mapped here (own rank: the own pointers)
   int* pf[PEER_MAX_RANKS] = {};
   int seq = 0;                          // all-reduces so far (identical on every rank)
   float* slot_ptr(int sq) const { return xbuf + (size_t)(sq & 1) * cap; }
-  PeerArgs args(int sq, int rank, int nranks) const {
+  PeerArgs args(int sq, int rank, int nranks, int barrier_b = 0) const {   // barrier_b: the flag rows of the two-phase form's second barrier
     PeerArgs a{};
     a.nranks = nranks; a.rank = rank;
-    for (int r = 0; r < nranks; r++) { a.x[r] = px[r] + (size_t)(sq & 1) * cap; a.f[r] = pf[r] + (sq & 1) * PEER_MAX_RANKS; }
+    for (int r = 0; r < nranks; r++) { a.x[r] = px[r] + (size_t)(sq & 1) * cap; a.f[r] = pf[r] + ((sq & 1) + 2 * barrier_b) * PEER_MAX_RANKS; }
     return a;
   }
 };
@@ -126,22 +152,22 @@ struct Comm {
     const PeerArgs pa = peer.args(sq, rank, nranks);
     CLSTM_LAUNCH(k_peer_barrier, dim3(1), dim3(64), 0, s, pa, sq, dev_err_words() + 6, peer_device_timeout_ticks());
   }
-  void allreduce(float* buf, long long n, hipStream_t s) {
+  // one_shot: the caller's few floats (the replica check's four) never take the two-phase form
+  void allreduce(float* buf, long long n, hipStream_t s, bool one_shot = false) {
     if (comm) { RCCLCHECK(RcclApi::get().AllReduce(buf, buf, (size_t)n, ncclFloat32, ncclSum, comm, s)); return; }
     if (nranks == 1) return;
-    // no RCCL: the peer path as a plain in-place all-reduce (copy into the exchange slot, barrier, rank-ordered sum)
+    // no RCCL: the peer path as a plain in-place all-reduce (copy into the exchange slot, barrier(s), rank-ordered sum), at any n
     REQUIRE(peer_ready((size_t)n, s), "communicator without RCCL: the ranks could not map each other's exchange buffers (HIP IPC)");
     const int sq = ++peer.seq;
+    const bool two = !one_shot && peer_use_two_phase((size_t)n, nranks);
     HIPCHECK(hipMemcpyAsync(peer.slot_ptr(sq), buf, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    peer_barrier(sq, s);
-    const PeerArgs pa = peer.args(sq, rank, nranks);
-    CLSTM_LAUNCH(k_peer_allreduce_update, dim3(nblocks((size_t)(n + 3) / 4)), dim3(256), 0, s, pa, (float*)nullptr, (float*)nullptr, buf, (size_t)n, 0.0f, 0.0f, 0.0f,
-                 (const int*)nullptr, (int*)nullptr, 0, (int*)nullptr, 0);
+    peer_exchange_begin(*this, sq, two, (size_t)n, s);
+    peer_exchange_finish(*this, sq, two, nullptr, nullptr, buf, (size_t)n, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 0, nullptr, 0, s);
     check_launch();
   }
   // rendezvous of the ranks of this host: a shared segment named after the communicator id.  It stays mapped for the life of
   // the communicator (the hosts' announce words live in it); its NAME goes as soon as every rank has it open.
-  struct Handles { hipIpcMemHandle_t x, f; int ok; int pad[3]; };
+  struct Handles { hipIpcMemHandle_t x, f; int ok; int pad; unsigned long long cap; };
   struct Rendezvous { std::atomic<int> magic, arrived, mapped, good, probed, probe_good; PeerHostWords hw; Handles h[PEER_MAX_RANKS]; };
   Rendezvous* rv = nullptr;
   static bool wait_for(std::atomic<int>& w, int target, double seconds) {
@@ -176,33 +202,67 @@ struct Comm {
     (void)hipFree(perr);
     return ran;
   }
-  // collective (every rank calls it at the same point of its first one-call training step): true if the peer path is up
+  // collective (every rank calls it at the same point with the same n: its one-call training steps, Comm::allreduce): true if the
+  // peer path is up AND its slots hold n floats.  The first call sets the exchange up; a later call with an n beyond the capacity in
+  // use sets it up AGAIN at a larger one (a 4-float replica check or a small net may well come before a large one) -- new slots, new
+  // IPC handles, a new rendezvous segment, the probe over the new slots.  The capacity is a function of n alone, so the ranks agree
+  // on it without a message; the rendezvous still compares.  A set-up that fails, the first or a later one, leaves the communicator
+  // without the peer path for good: ncclAllReduce for every rank, or Comm::allreduce's error where there is no RCCL.
   bool peer_ready(size_t n, hipStream_t s) {
     PeerExchange& p = peer;
-    if (p.tried) return p.ok && n <= p.cap;
-    p.tried = true;
-    static const bool on = !(getenv("CLSTM_PEER_ALLREDUCE") && atoi(getenv("CLSTM_PEER_ALLREDUCE")) == 0);
-    if (!on || nranks < 2 || nranks > PEER_MAX_RANKS || n > PEER_MAX_FLOATS) return false;
-    HIPCHECK(hipStreamSynchronize(s));
+    if (p.tried && (!p.ok || n <= p.cap)) return p.ok;
+    if (!p.tried) {
+      p.tried = true;
+      static const bool on = !(getenv("CLSTM_PEER_ALLREDUCE") && atoi(getenv("CLSTM_PEER_ALLREDUCE")) == 0);
+      if (!on || nranks < 2 || nranks > PEER_MAX_RANKS) return false;
+    }
+    // (never the first caller's n below 4 MB: a 4-float replica check may come before the first gradient exchange)
+    const size_t cap = n <= PEER_ONE_SHOT_FLOATS ? PEER_ONE_SHOT_FLOATS : (n + PEER_CAP_STEP - 1) / PEER_CAP_STEP * PEER_CAP_STEP;
+    p.ok = peer_setup(cap, s);
+    if (!p.ok) peer_release();
+    return p.ok;
+  }
+  bool peer_setup(size_t cap, hipStream_t s) {
+    PeerExchange& p = peer;
+    HIPCHECK(hipStreamSynchronize(s));   // (a later set-up: this rank has left every exchange it enqueued on the slots in use)
+    // the slots in use so far stay mapped until EVERY rank has arrived at the new rendezvous, i.e. has left the exchanges on them
+    const PeerExchange old = p;
+    Rendezvous* const old_rv = rv;
+    rv = nullptr; p.xbuf = nullptr; p.flags = nullptr;
+    for (int r = 0; r < PEER_MAX_RANKS; r++) { p.px[r] = nullptr; p.pf[r] = nullptr; }
+    bool old_held = old.xbuf != nullptr || old_rv != nullptr;
+    auto release_old = [&](bool own_buffers) {
+      for (int r = 0; r < PEER_MAX_RANKS && !own_buffers; r++) {
+        if (r != rank && old.px[r]) (void)hipIpcCloseMemHandle(old.px[r]);
+        if (r != rank && old.pf[r]) (void)hipIpcCloseMemHandle(old.pf[r]);
+      }
+      if (!own_buffers && old_rv) munmap(old_rv, sizeof(Rendezvous));
+      if (own_buffers && old.xbuf) (void)hipFree(old.xbuf);
+      if (own_buffers && old.flags) (void)hipFree(old.flags);
+    };
+    const int gen = p.gen++;
     Handles mine{};
-    mine.ok = 1;
-    p.cap = PEER_MAX_FLOATS;   // (not the first caller's n: a 4-float replica check may come before the first gradient exchange)
+    mine.ok = cap <= PEER_SLOT_LIMIT ? 1 : 0;
+    mine.cap = cap;
+    p.cap = cap;
+    const size_t flag_bytes = (size_t)PEER_FLAG_ROWS * PEER_MAX_RANKS * sizeof(int);
     // Exchange slots AND flags are fine-grained device memory: what a peer reads through its mapping while kernels of the owner
     // are still running must not depend on when the owner's L2 writes a line back, nor on a cache of the reader's side holding
     // the slot's lines of two steps ago -- fine-grained allocations are coherent at system scope by construction (the readers
-    // also use system-scope loads, ops.h).  0.5 MB written once per step by the gradient reductions: the uncached stores cost
-    // nothing measurable.  Coarse-grained memory only if the fine-grained allocation fails; the probe below judges either.
-    if (hipExtMallocWithFlags((void**)&p.xbuf, 2 * p.cap * sizeof(float), hipDeviceMallocFinegrained) != hipSuccess) {
+    // also use system-scope loads, ops.h).  The gradient reductions write the slot once per step with uncached stores: nothing
+    // measurable at 0.5 MB; what it costs at 35 MB is in DESIGN.md 6.  Coarse-grained memory only if the fine-grained allocation
+    // fails; the probe below judges either.
+    if (mine.ok && hipExtMallocWithFlags((void**)&p.xbuf, 2 * p.cap * sizeof(float), hipDeviceMallocFinegrained) != hipSuccess) {
       (void)hipGetLastError();
       if (hipMalloc((void**)&p.xbuf, 2 * p.cap * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); mine.ok = 0; p.xbuf = nullptr; }
     }
-    if (hipExtMallocWithFlags((void**)&p.flags, 2 * PEER_MAX_RANKS * sizeof(int), hipDeviceMallocFinegrained) != hipSuccess) {
+    if (mine.ok && hipExtMallocWithFlags((void**)&p.flags, flag_bytes, hipDeviceMallocFinegrained) != hipSuccess) {
       (void)hipGetLastError();
-      if (hipMalloc((void**)&p.flags, 2 * PEER_MAX_RANKS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); mine.ok = 0; p.flags = nullptr; }
+      if (hipMalloc((void**)&p.flags, flag_bytes) != hipSuccess) { (void)hipGetLastError(); mine.ok = 0; p.flags = nullptr; }
     }
     if (mine.ok) {
       HIPCHECK(hipMemset(p.xbuf, 0, 2 * p.cap * sizeof(float)));
-      HIPCHECK(hipMemset(p.flags, 0, 2 * PEER_MAX_RANKS * sizeof(int)));
+      HIPCHECK(hipMemset(p.flags, 0, flag_bytes));
       HIPCHECK(hipDeviceSynchronize());
       if (hipIpcGetMemHandle(&mine.x, p.xbuf) != hipSuccess || hipIpcGetMemHandle(&mine.f, p.flags) != hipSuccess) { (void)hipGetLastError(); mine.ok = 0; }
     }
@@ -210,7 +270,7 @@ struct Comm {
     unsigned long long hsh = 1469598103934665603ull;
     for (int i = 0; i < CLSTM_COMM_ID_BYTES; i++) hsh = (hsh ^ (unsigned char)id[i]) * 1099511628211ull;
     char name[64];
-    snprintf(name, sizeof name, "/clstm_px_%016llx", hsh);
+    snprintf(name, sizeof name, "/clstm_px_%016llx_%d", hsh, gen);
     const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);
     if (fd >= 0 && ftruncate(fd, sizeof(Rendezvous)) == 0) {
       void* m = mmap(nullptr, sizeof(Rendezvous), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
@@ -223,7 +283,8 @@ struct Comm {
       rv->h[rank] = mine;
       rv->arrived.fetch_add(1);
       good = wait_for(rv->arrived, nranks, setup_s);
-      for (int r = 0; good && r < nranks; r++) good = rv->h[r].ok != 0;
+      if (old_held) release_old(false);          // every rank is here (or the set-up has failed): nobody reads the former slots any more
+      for (int r = 0; good && r < nranks; r++) good = rv->h[r].ok != 0 && rv->h[r].cap == cap;
       for (int r = 0; good && r < nranks; r++) {
         if (r == rank) { p.px[r] = p.xbuf; p.pf[r] = p.flags; continue; }
         void *x = nullptr, *f = nullptr;
@@ -235,6 +296,7 @@ struct Comm {
       if (good) rv->good.fetch_add(1);
       rv->mapped.fetch_add(1);
       const bool all_here = wait_for(rv->mapped, nranks, setup_s);
+      if (old_held) { release_old(true); old_held = false; }   // ... and every rank has closed its mappings of them
       good = all_here && rv->good.load() == nranks;
       // ... and the mappings DELIVER: four handshakes through the mapped flag arrays, each followed by a look at EVERY element of
       // every rank's slot through this rank's mapping of it (probe_rounds) -- a path that maps but does not deliver (flags that
@@ -246,9 +308,8 @@ struct Comm {
       }
       if (rank == 0) shm_unlink(name);          // (every rank that will ever come has it open or has given up)
     }
-    p.ok = good;
-    if (!p.ok) peer_release();
-    return p.ok && n <= p.cap;
+    if (old_held) { release_old(false); release_old(true); }
+    return good;
   }
   void peer_release() {
     PeerExchange& p = peer;
@@ -260,7 +321,7 @@ struct Comm {
     }
     if (p.xbuf) (void)hipFree(p.xbuf);
     if (p.flags) (void)hipFree(p.flags);
-    p.xbuf = nullptr; p.flags = nullptr; p.ok = false;
+    p.xbuf = nullptr; p.flags = nullptr; p.ok = false; p.cap = 0;
   }
   ~Comm() {
     peer_release();
@@ -293,10 +354,10 @@ struct PeerExchange {   // (host emulator: the "mapped" buffers and flags of the
   int* pf[PEER_MAX_RANKS] = {};
   int seq = 0;
   float* slot_ptr(int sq) const { return xbuf + (size_t)(sq & 1) * PEER_MAX_FLOATS; }
-  PeerArgs args(int sq, int rank, int nranks) const {
+  PeerArgs args(int sq, int rank, int nranks, int barrier_b = 0) const {
     PeerArgs a{};
     a.nranks = nranks; a.rank = rank;
-    for (int r = 0; r < nranks; r++) { a.x[r] = px[r] + (size_t)(sq & 1) * PEER_MAX_FLOATS; a.f[r] = pf[r] + (sq & 1) * PEER_MAX_RANKS; }
+    for (int r = 0; r < nranks; r++) { a.x[r] = px[r] + (size_t)(sq & 1) * PEER_MAX_FLOATS; a.f[r] = pf[r] + ((sq & 1) + 2 * barrier_b) * PEER_MAX_RANKS; }
     return a;
   }
 };
@@ -343,8 +404,8 @@ struct Comm {
     const PeerArgs pa = peer.args(sq, rank, nranks);
     CLSTM_LAUNCH(k_peer_barrier, dim3(1), dim3(64), 0, s, pa, sq, dev_err_words() + 6, peer_device_timeout_ticks());
   }
-  // per rank behind the all-reduce slots: exchange buffer [2][SLOT] floats, then flags [2][PEER_MAX_RANKS] ints (zero pages)
-  static size_t peer_region_bytes() { return (size_t)2 * SLOT * sizeof(float) + 2 * PEER_MAX_RANKS * sizeof(int) + 64; }
+  // per rank behind the all-reduce slots: exchange buffer [2][SLOT] floats, then flags [PEER_FLAG_ROWS][PEER_MAX_RANKS] ints (zero pages)
+  static size_t peer_region_bytes() { return (size_t)2 * SLOT * sizeof(float) + (size_t)PEER_FLAG_ROWS * PEER_MAX_RANKS * sizeof(int) + 64; }
   bool peer_ready(size_t n, hipStream_t s) {
     PeerExchange& p = peer;
     if (p.tried) return p.ok && n <= p.cap;
@@ -404,8 +465,17 @@ struct Comm {
     if (shm->arrived.fetch_add(1) + 1 == nranks) { shm->arrived.store(0); shm->gen.store(g + 1); }
     else while (shm->gen.load() == g) sched_yield();
   }
-  void allreduce(float* buf, long long n, hipStream_t) {
+  // The plain chunked all-reduce over the shared slots -- except under peer_two_phase=2, where a buffer that fits an exchange slot
+  // goes through the peer path's two-phase kernels like the GPU build's communicator without RCCL (one_shot: never, the replica check)
+  void allreduce(float* buf, long long n, hipStream_t s, bool one_shot = false) {
     if (nranks == 1) return;
+    if (!one_shot && dbg_opt("peer_two_phase") == 2 && n <= SLOT && peer_ready((size_t)n, s)) {
+      const int sq = ++peer.seq;
+      memcpy(peer.slot_ptr(sq), buf, (size_t)n * sizeof(float));
+      peer_exchange_begin(*this, sq, true, (size_t)n, s);
+      peer_exchange_finish(*this, sq, true, nullptr, nullptr, buf, (size_t)n, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 0, nullptr, 0, s);
+      return;
+    }
     for (long long o = 0; o < n; o += SLOT) {
       const long long m = std::min(SLOT, n - o);
       memcpy(shm->slots + (size_t)rank * SLOT, buf + o, (size_t)m * sizeof(float));
@@ -421,4 +491,17 @@ struct Comm {
   ~Comm() { if (shm) { shm->hw.left[rank].store(1); munmap(shm, bytes); } chk.release(); chk_acc.release(); }
 };
 #endif
+static void peer_exchange_begin(Comm& c, int sq, bool two_phase, size_t n, hipStream_t s) {
+  c.peer_barrier(sq, s);
+  if (!two_phase) return;
+  CLSTM_LAUNCH(k_peer_reduce_scatter, dim3(nblocks(peer_seg_floats(n, c.nranks) / 4)), dim3(256), 0, s, c.peer.args(sq, c.rank, c.nranks), c.peer.slot_ptr(sq), n);
+  // barrier B, on flag rows of its own: waits only for the peers' reduce-scatter, which their hosts have queued behind barrier A
+  CLSTM_LAUNCH(k_peer_barrier, dim3(1), dim3(64), 0, s, c.peer.args(sq, c.rank, c.nranks, 1), sq, dev_err_words() + 6, peer_device_timeout_ticks());
+}
+static void peer_exchange_finish(Comm& c, int sq, bool two_phase, float* v, float* d, float* g, size_t n, float lr, float mom, float clip, const int* err,
+                                 int* step_word, int step_id, int* nanflag, int step_no, hipStream_t s) {
+  const PeerArgs pa = c.peer.args(sq, c.rank, c.nranks);
+  if (two_phase) CLSTM_LAUNCH(k_peer_gather_update, dim3(nblocks((n + 3) / 4)), dim3(256), 0, s, pa, v, d, g, n, lr, mom, clip, err, step_word, step_id, nanflag, step_no);
+  else CLSTM_LAUNCH(k_peer_allreduce_update, dim3(nblocks((n + 3) / 4)), dim3(256), 0, s, pa, v, d, g, n, lr, mom, clip, err, step_word, step_id, nanflag, step_no);
+}
 

@@ -1512,21 +1512,22 @@ struct Net {
       packs_follow_update = false;
       return;
     }
-    if (peer_pending && comm) {   // one-shot peer-read all-reduce fused into the update (ops.h: k_peer_barrier / k_peer_allreduce_update)
+    if (peer_pending && comm) {   // peer all-reduce fused into the update, one-shot or two-phase (comm.h: peer_use_two_phase; ops.h)
       peer_pending = false;
       RoctxRange range2_("clstm:allreduce+update");
       const int sq = ++comm->peer.seq;
-      const PeerArgs pa = comm->peer.args(sq, comm->rank, comm->nranks);
+      const bool two = peer_use_two_phase((size_t)nparams, comm->nranks);
       timing.begin("allreduce_grads", s);
-      comm->peer_barrier(sq, s);   // (the hosts announce the exchange to each other first: Comm::peer_barrier)
+      peer_exchange_begin(*comm, sq, two, (size_t)nparams, s);   // (the hosts announce the exchange to each other first: Comm::peer_barrier)
       timing.end(s);
       timing.begin("sgd_update", s);
-      CLSTM_LAUNCH(k_peer_allreduce_update, dim3(nblocks((size_t)(nparams + 3) / 4)), dim3(256), 0, s, pa, v, d, g, (size_t)nparams, lr, mom, gclip,
-                   (const int*)dev_err_words(), update_step_word, update_step_id, nanflag(), step_no());
+      peer_exchange_finish(*comm, sq, two, v, d, g, (size_t)nparams, lr, mom, gclip, (const int*)dev_err_words(), update_step_word, update_step_id, nanflag(),
+                           step_no(), s);
       update_step_word = nullptr;
       timing.end(s);
       check_launch();
       g_path_count[7]++;
+      if (two) g_path_count[24]++;
       packed_dirty = true;
       maybe_replica_check(s);
       return;
@@ -1565,7 +1566,7 @@ struct Net {
     comm->chk_acc.reserve(2);
     CLSTM_LAUNCH(k_param_checksum, dim3(std::min<unsigned>(nblocks(nparams), 1024u)), dim3(256), 0, s, (const float*)v, (size_t)nparams, comm->chk_acc.p);
     CLSTM_LAUNCH(k_checksum_pieces, dim3(1), dim3(64), 0, s, comm->chk_acc.p, comm->chk.p);
-    comm->allreduce(comm->chk.p + 4, 4, s);
+    comm->allreduce(comm->chk.p + 4, 4, s, true);   // (four floats: one-shot whatever the rule says)
     CLSTM_LAUNCH(k_replica_verify, dim3(1), dim3(64), 0, s, (const float*)comm->chk.p, comm->nranks, dev_err_words() + 7, step_no());
     check_launch();
     g_path_count[12]++;

@@ -312,6 +312,60 @@ __global__ void k_peer_allreduce_update(PeerArgs p, float* v, float* d, float* g
   }
 }
 
+// ---- two-phase peer all-reduce fused into the update (reduce-scatter + all-gather) ----------------------
+// The one-shot form above reads (R-1).len floats of peer memory per rank: right while latency dominates, wrong once bytes do.
+// Here rank r owns segment r of the buffer -- seg = 4.ceil(ceil(len/4)/R) floats, so every bound is a multiple of 16 bytes; the last
+// non-empty segment may be partial, trailing ones empty.  Behind barrier A (every rank's slot is complete) k_peer_reduce_scatter
+// sums the rank's OWN segment over all ranks' slots, in rank order starting from rank 0's value like k_peer_allreduce_update, and
+// writes the sum in place into its own slot: in this phase nobody else reads segment r of any slot.  Behind barrier B (a second
+// k_peer_barrier on flag rows of its own: every segment is reduced) k_peer_gather_update reads every element from its owner's
+// slot, leaves it in g and applies k_update's arithmetic.  2.(R-1).len/R floats of peer memory per rank instead of (R-1).len, and
+// the same additions in the same order: the result is bit-identical to the one-shot form's, on every rank.  Neither kernel waits
+// for anything -- only k_peer_barrier does -- so neither needs to be co-resident with another process's work.
+inline __host__ __device__ size_t peer_seg_floats(size_t len, int nranks) { return 4 * (((len + 3) / 4 + (size_t)nranks - 1) / (size_t)nranks); }
+__global__ void k_peer_reduce_scatter(PeerArgs p, float* own, size_t len) {   // own: this rank's slot of the step, writable
+  const size_t seg = peer_seg_floats(len, p.nranks);
+  const size_t lo = seg * (size_t)p.rank < len ? seg * (size_t)p.rank : len, hi = lo + seg < len ? lo + seg : len;
+  CLSTM_GRID_STRIDE(q, (hi - lo + 3) / 4) {
+    const size_t i0 = lo + q * 4;
+    f32x4 acc = buf_load4_wt(make_buf(p.x[0], len * 4), (unsigned)(i0 * 4));   // (past the end: zeros, the descriptor ends at len)
+    for (int r = 1; r < p.nranks; r++) {
+      const f32x4 t = buf_load4_wt(make_buf(p.x[r], len * 4), (unsigned)(i0 * 4));
+      acc[0] += t[0]; acc[1] += t[1]; acc[2] += t[2]; acc[3] += t[3];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+      if (i0 + e < hi) own[i0 + e] = acc[e];
+  }
+}
+__global__ void k_peer_gather_update(PeerArgs p, float* v, float* d, float* g, size_t len, float lr, float mom, float clip, const int* err,
+                                     int* step_word, int step_id, int* nanflag, int step_no) {
+  if (step_word && blockIdx.x == 0 && threadIdx.x == 0) store_i32_wt(step_word, step_id);
+  const bool apply = v != nullptr && !dev_err_set(err);   // (v null: a plain in-place all-reduce into g)
+  const size_t seg4 = peer_seg_floats(len, p.nranks) / 4, n4 = (len + 3) / 4;
+  for (int o = 0; o < p.nranks; o++) {                     // owner by owner: the descriptor stays wave-uniform
+    const size_t lo4 = seg4 * (size_t)o < n4 ? seg4 * (size_t)o : n4, hi4 = lo4 + seg4 < n4 ? lo4 + seg4 : n4;
+    const BufF32 xb = make_buf(p.x[o], len * 4);
+    CLSTM_GRID_STRIDE(qq, hi4 - lo4) {
+      const size_t q = lo4 + qq;
+      const f32x4 acc = buf_load4_wt(xb, (unsigned)(q * 16));
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const size_t i = q * 4 + e;
+        if (i >= len) break;
+        const float gi = acc[e];
+        g[i] = gi;
+        if (!apply) continue;
+        if (nanflag && !f32_finite(gi)) { raise_nonfinite(nanflag, step_no); continue; }
+        float di = d[i] + gi;
+        if (clip < 1e6f) di = fmaxf(-clip, fminf(clip, di));
+        v[i] += di * lr;
+        d[i] = di * mom;
+      }
+    }
+  }
+}
+
 // ---- replica consistency check (every rank applies the identical update, so the replicas must stay bit-identical; the
 // reference re-synchronises instead, distribute_weights / average_weights, clstm.cc:718-729, 746-760) -------------------------
 // Every `check_every` training steps each rank folds its parameter buffer into two 32-bit integer sums (the bit patterns, and

@@ -337,6 +337,12 @@ class Comm:
     def allreduce(self, buf, n):
         self.lib.call("clstm_allreduce_flat", self.h, ptr(buf), int(n))
 
+    def peer_capacity(self):
+        """floats one exchange buffer of the peer path holds at present; 0 before its set-up or after a fallback"""
+        n = C.c_longlong(0)
+        self.lib.call("clstm_comm_peer_capacity", self.h, C.byref(n))
+        return int(n.value)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.call("clstm_comm_destroy", self.h)

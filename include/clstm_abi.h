@@ -314,9 +314,15 @@ int clstm_comm_destroy(clstm_comm* comm);
 int clstm_comm_rank(clstm_comm* comm);
 int clstm_comm_size(clstm_comm* comm);
 /* 1 once the ranks have mapped each other's exchange buffers (HIP IPC; decided collectively at the first clstm_net_train_step with
- * the communicator attached): clstm_net_train_step then runs the one-shot peer-read all-reduce fused into the update kernel
- * (gradient buffers up to 4 MB; environment CLSTM_PEER_ALLREDUCE=0: always ncclAllReduce + update).  0: ncclAllReduce. */
+ * the communicator attached): clstm_net_train_step then runs the peer-read all-reduce fused into the update -- one-shot (every
+ * rank sums every rank's whole buffer) for gradients up to 4 MB and at two ranks, two-phase (reduce-scatter, then all-gather
+ * inside the update kernel) above 4 MB at three or more ranks; the exchange buffers grow, collectively, to the largest gradient
+ * seen.  Environment CLSTM_PEER_ALLREDUCE=0: always ncclAllReduce + update.  0: ncclAllReduce (also after a set-up, the first or a
+ * later, larger one, that did not succeed on every rank). */
 int clstm_comm_peer_active(clstm_comm* comm);
+/* floats: what one exchange buffer of the peer path holds at present (at least 1 << 20 once it is up; it grows when a larger
+ * gradient arrives and never shrinks); 0 before the set-up and while clstm_comm_peer_active is 0. */
+int clstm_comm_peer_capacity(clstm_comm* comm, long long* floats);
 /* in-place sum over ranks of buf_d[0..n) (DEVICE, f32), enqueued on the library stream: no cross-stream
  * event, no host synchronisation. */
 int clstm_allreduce_flat(clstm_comm* comm, float* buf_d, long long n);
@@ -357,7 +363,8 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  * launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h), 16 / 17 / 18 the recurrences batched over 16 lines on the
  * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 22 / 23 / 15 the no-save forward
  * passes of clstm_net_predict (per-line recurrence launches, fused forward launches, batched MFMA launches; the training counters 5 /
- * 16 do not move for them), 21 minibatches whose forward pass the
+ * 16 do not move for them), 7 training steps whose gradient exchange was the peer-read all-reduce fused with the update (either
+ * form), 24 those of them that took the two-phase form, 21 minibatches whose forward pass the
  * batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255]; blocking).  Tests use it to make sure the
  * path they mean to cover is the one that ran. */
 int clstm_debug_path_count(int which, long long* out_h);
