@@ -5,4 +5,4 @@ include/clstm_abi.h), abi.py (ctypes plumbing) and net.py (host mirror of the re
 INetwork / make_net / sgd_update surface).  See DESIGN.md and INTEGRATION.md.
 """
 from .abi import ClstmError, load  # noqa: F401
-from .net import Network, make_net, sgd_update, mktargets  # noqa: F401
+from .net import Network, Normalizer, make_net, sgd_update, mktargets  # noqa: F401

@@ -94,6 +94,12 @@ _SIGS = {
     "clstm_net_predict": [_P, _P, _I, _P, _P, _P, _P, _P],
     "clstm_net_predict_h": [_P, _P, _I, _P, _P, _P, _P, _P],
     "clstm_net_device_bytes": [_P, _P],
+    "clstm_normalizer_create": [_P, _I, _F, _F, _F],
+    "clstm_normalizer_destroy": [_P],
+    "clstm_normalizer_run_h": [_P, _P, _P, _P, _I, _P, _P, _P],
+    "clstm_normalizer_run_d": [_P, _P, _P, _P, _I, _P, _P, _P],
+    "clstm_normalizer_get_frames_h": [_P, _P],
+    "clstm_normalizer_device_bytes": [_P, _P],
     "clstm_net_enable_timing": [_P, _I],
     "clstm_net_kernel_time_ms": [_P, C.c_char_p, _P, _P],
     "clstm_net_reset_timing": [_P],

@@ -15,6 +15,10 @@ struct clstm_net {
 
 #define REQUIRE_CURRENT(h) REQUIRE(!(h)->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)")
 #define REFUSE_NOSAVE(h, what) REQUIRE(!(h)->net.nosave, what ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)")
+struct clstm_normalizer {
+  std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
+  Normalizer nz;
+};
 extern "C" {
 
 const char* clstm_last_error(void) { return g_err.c_str(); }
@@ -341,6 +345,43 @@ int clstm_net_predict(clstm_net* h, const int* T_h, int bs, const float* x_d, in
 }
 int clstm_net_predict_h(clstm_net* h, const int* T_h, int bs, const float* x_h, int* cls, int* locs, float* conf, int* cnt) {
   ABI_BEGIN net_predict(h, T_h, bs, x_h, true, cls, locs, conf, cnt); ABI_END
+}
+// ---- line normalisation on the device (normalize.h, normalize_run.inc) ---------------------------------------------
+int clstm_normalizer_create(clstm_normalizer** out, int target_height, float smooth2d, float smooth1d, float range) {
+  ABI_BEGIN
+  REQUIRE(out, "null argument");
+  REQUIRE(target_height >= 1, "clstm_normalizer_create: target_height must be at least 1");
+  REQUIRE(smooth2d > 0.0f && smooth1d > 0.0f && range > 0.0f && std::isfinite(smooth2d) && std::isfinite(smooth1d) && std::isfinite(range),
+          "clstm_normalizer_create: smooth2d, smooth1d and range must be positive and finite");
+  size_t* bytes = new size_t(0);
+  AcctScope acct_(bytes);
+  clstm_normalizer* h = nullptr;
+  try { h = new clstm_normalizer(); } catch (...) { delete bytes; throw; }
+  h->dev_bytes.reset(bytes);
+  h->nz.target_height = target_height; h->nz.smooth2d = smooth2d; h->nz.smooth1d = smooth1d; h->nz.range = range;
+  *out = h;
+  ABI_END
+}
+int clstm_normalizer_destroy(clstm_normalizer* h) { ABI_BEGIN delete h; ABI_END }
+int clstm_normalizer_run_h(clstm_normalizer* h, const float* pix_h, const int* w_h, const int* h_h, int bs, int* T_h, float* r_h, float** frames_d) {
+  ABI_BEGIN REQUIRE(h, "null argument"); h->nz.run(pix_h, true, w_h, h_h, bs, T_h, r_h, frames_d); ABI_END
+}
+int clstm_normalizer_run_d(clstm_normalizer* h, const float* pix_d, const int* w_h, const int* h_h, int bs, int* T_h, float* r_h, float** frames_d) {
+  ABI_BEGIN REQUIRE(h, "null argument"); h->nz.run(pix_d, false, w_h, h_h, bs, T_h, r_h, frames_d); ABI_END
+}
+int clstm_normalizer_get_frames_h(clstm_normalizer* h, float* frames_h) {
+  ABI_BEGIN
+  REQUIRE(h && frames_h, "null argument");
+  REQUIRE(h->nz.last_frames > 0, "clstm_normalizer_get_frames_h: the last clstm_normalizer_run_* call on this normalizer produced no frames");
+  HIPCHECK(hipMemcpyAsync(frames_h, h->nz.frames.p, h->nz.last_frames * sizeof(float), hipMemcpyDeviceToHost, g_stream));
+  HIPCHECK(hipStreamSynchronize(g_stream));
+  ABI_END
+}
+int clstm_normalizer_device_bytes(clstm_normalizer* h, long long* bytes) {
+  ABI_BEGIN
+  REQUIRE(h && bytes, "null argument");
+  *bytes = (long long)*h->dev_bytes;
+  ABI_END
 }
 int clstm_net_device_bytes(clstm_net* h, long long* bytes) {
   ABI_BEGIN
@@ -861,7 +902,7 @@ int clstm_debug_set_option(const char* name, int value) {   // experiment switch
 }
 int clstm_debug_path_count(int which, long long* out_h) {
   ABI_BEGIN
-  REQUIRE(which >= 0 && which < 25 && out_h, "bad path index");
+  REQUIRE(which >= 0 && which < 26 && out_h, "bad path index");
   if (which == 21) {   // counted on the device: minibatches whose forward pass the batched recurrence handed to its routed per-line twins (lstm_mfma.h)
     int n = 0;
     HIPCHECK(hipStreamSynchronize(g_stream));

@@ -27,9 +27,11 @@
 #include "lstm_mfma_bwd.h"
 #include "lstm_mfma_bwd_dw.h"
 #include "ops.h"
+#include "normalize.h"
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <sched.h>
 #include <cstring>
 #include <cstdlib>
@@ -43,6 +45,7 @@ namespace clstm {
 #include "runtime.inc"   // errors, buffers, launch helpers, timing
 #include "net.inc"       // Layer / Net: the step scheduler
 #include "ctc_run.inc"   // CTC / decode launches, host side
+#include "normalize_run.inc"   // the line normaliser (normalize.h), host side
 }  // namespace clstm
 
 #include "abi.inc"       // extern "C": include/clstm_abi.h

@@ -137,7 +137,7 @@ struct StoreBias {  // out[r*ld + c] = val + bias[c]
     *reinterpret_cast<f32x4*>(out + (long long)r * ld + c) = o;
   }
 };
-static long long g_path_count[25];   // clstm_debug_path_count (diagnostics)
+static long long g_path_count[26];   // clstm_debug_path_count (diagnostics)
 struct StorePlain {
   float* out; long long ld;
   DEVMFN void operator()(int r, int c, float v, int) const { out[(long long)r * ld + c] = v; }

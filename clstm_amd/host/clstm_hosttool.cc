@@ -3,6 +3,7 @@
 #include "model.h"
 #include "normalizer.h"
 #include "png_io.h"
+#include <thread>
 using namespace clstmhost;
 
 static void dump(const string& fname, const Image& im) {
@@ -29,6 +30,52 @@ int main(int argc, char** argv) {
       nz.normalize(out, im);
       dump(argv[3], out);
       std::cout << "r " << nz.r << " width " << out.w << std::endl;
+    } else if (cmd == "normalize-raw" && (argc == 5 || argc == 8)) {  // IN.raw OUT.raw HEIGHT [SMOOTH2D SMOOTH1D RANGE]
+      // CenterNormalizer on a raw dump with ink = 1: the bit-level referee of the device normaliser for arbitrary images
+      std::ifstream f(argv[2], std::ios::binary);
+      int hdr[2] = {0, 0};
+      f.read((char*)hdr, 8);
+      if (!f || hdr[0] < 1 || hdr[1] < 1) fail(string("bad raw image: ") + argv[2]);
+      Image im, out;
+      im.resize(hdr[0], hdr[1]);
+      f.read((char*)im.d.data(), im.d.size() * 4);
+      if ((size_t)f.gcount() != im.d.size() * 4) fail(string("short raw image: ") + argv[2]);
+      CenterNormalizer nz;
+      nz.target_height = atoi(argv[4]);
+      if (argc == 8) { nz.smooth2d = (float)atof(argv[5]); nz.smooth1d = (float)atof(argv[6]); nz.range = (float)atof(argv[7]); }
+      nz.measure(im);
+      nz.normalize(out, im);
+      dump(argv[3], out);
+      std::cout << "r " << nz.r << " width " << out.w << std::endl;
+    } else if (cmd == "normalize-bench" && argc == 5) {  // IN.raws HEIGHT THREADS: the host CenterNormalizer's rate on a file of raw dumps
+      std::ifstream f(argv[2], std::ios::binary);
+      vector<Image> ims;
+      int hdr[2];
+      while (f.read((char*)hdr, 8)) {
+        ims.emplace_back();
+        ims.back().resize(hdr[0], hdr[1]);
+        f.read((char*)ims.back().d.data(), ims.back().d.size() * 4);
+      }
+      const int height = atoi(argv[3]), nthreads = std::max(1, atoi(argv[4]));
+      vector<int> widths(ims.size());
+      const double t0 = now();
+      vector<std::thread> pool;
+      for (int t = 0; t < nthreads; t++)
+        pool.emplace_back([&, t] {
+          for (size_t k = t; k < ims.size(); k += nthreads) {
+            CenterNormalizer nz;
+            Image out;
+            nz.target_height = height;
+            nz.measure(ims[k]);
+            nz.normalize(out, ims[k]);
+            widths[k] = out.w;
+          }
+        });
+      for (auto& th : pool) th.join();
+      const double dt = now() - t0;
+      long long frames = 0;
+      for (int w : widths) frames += w;
+      std::cout << ims.size() << " lines " << frames << " frames in " << dt << " s = " << ims.size() / dt << " lines/s" << std::endl;
     } else if (cmd == "writepng" && argc == 4) {  // raw -> png (write_png)
       std::ifstream f(argv[2], std::ios::binary);
       int hdr[2];
@@ -57,7 +104,7 @@ int main(int argc, char** argv) {
       std::ofstream f(argv[3], std::ios::binary);
       f.write((const char*)m.params.data(), m.params.size() * 4);
     } else {
-      std::cerr << "usage: clstm_hosttool png2raw|normalize|writepng|init-model|roundtrip|params ...\n";
+      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params ...\n";
       return 2;
     }
     return 0;

@@ -103,7 +103,11 @@ struct CLSTMOCR {
   vector<float> aligned;  // [T][nclasses] of the last fwdbwd
   int T = 0;
 
-  ~CLSTMOCR() { if (net) clstm_net_destroy(net); }
+  clstm_normalizer* gpu_normalizer = nullptr;   // the device twin of `normalizer` (created at first use: predict_batch_gpu, normalize_batch_gpu)
+  ~CLSTMOCR() {
+    if (gpu_normalizer) clstm_normalizer_destroy(gpu_normalizer);
+    if (net) clstm_net_destroy(net);
+  }
   void attach() {  // device network from the host model
     if (net) { clstm_net_destroy(net); net = nullptr; }
     chk(clstm_net_create(&net, &model.desc, nullptr, nullptr, nullptr), "clstm_net_create");
@@ -111,6 +115,7 @@ struct CLSTMOCR {
     nclasses = model.desc.nclasses;
     target_height = model.desc.ninput;
     normalizer.target_height = target_height;
+    if (gpu_normalizer) { clstm_normalizer_destroy(gpu_normalizer); gpu_normalizer = nullptr; }
     codec.set(model.codec);
     const float lr = atof(attr_get("learning_rate", "1e-4").c_str());
     const float mom = atof(attr_get("momentum", "0.9").c_str());
@@ -297,15 +302,19 @@ struct CLSTMOCR {
   // the per-line kernels here: for such a line batch=1 and batch=N agree to the last bit but one, not byte for byte.  (2) From 640
   // lines per call on the library's batched MFMA recurrence takes over (f16 split products, 1e-4 class: same text on trained
   // models, not the same bits); CLSTM_DEBUG="fwd_mfma=0" keeps the per-line kernels there too.
-  vector<int> batch_T;   // line lengths of the last predict_frames() minibatch (get_outputs_batch)
+  vector<int> batch_T;   // line lengths of the last predict_frames() / predict_batch_gpu() minibatch (get_outputs_batch)
   void predict_frames(const vector<const Image*>& lines, vector<ustring>& out, vector<vector<CharPrediction>>* preds = nullptr) {
-    const int bs = (int)lines.size();
     out.clear();
     if (preds) preds->clear();
-    if (bs == 0) return;
+    if (lines.empty()) return;
     batch_T.clear();
     vector<float> frames;
     for (const Image* l : lines) { batch_T.push_back(l->w); frames.insert(frames.end(), l->d.begin(), l->d.end()); }
+    predict_packed(frames.data(), true, out, preds);
+  }
+  // one clstm_net_predict_h (frames on the host) / clstm_net_predict (frames on the device) call on the lines of batch_T
+  void predict_packed(const float* frames, bool on_host, vector<ustring>& out, vector<vector<CharPrediction>>* preds) {
+    const int bs = (int)batch_T.size();
     int N = 0;
     for (int t : batch_T) N += t;
     vector<int> cls(N), loc(N), cnt(bs);
@@ -313,10 +322,11 @@ struct CLSTMOCR {
     int train_overlap = 1;
     chk(clstm_net_get_overlap(net, &train_overlap), "clstm_net_get_overlap");
     chk(clstm_net_set_overlap(net, 0), "clstm_net_set_overlap");
-    const int rc = clstm_net_predict_h(net, batch_T.data(), bs, frames.data(), cls.data(), loc.data(), preds ? conf.data() : nullptr, cnt.data());
+    const int rc = on_host ? clstm_net_predict_h(net, batch_T.data(), bs, frames, cls.data(), loc.data(), preds ? conf.data() : nullptr, cnt.data())
+                           : clstm_net_predict(net, batch_T.data(), bs, frames, cls.data(), loc.data(), preds ? conf.data() : nullptr, cnt.data());
     const string err = rc ? clstm_last_error() : "";
     chk(clstm_net_set_overlap(net, train_overlap), "clstm_net_set_overlap");
-    if (rc) fail("clstm_net_predict_h: " + err);
+    if (rc) fail(string(on_host ? "clstm_net_predict_h: " : "clstm_net_predict: ") + err);
     int o = 0;
     for (int b = 0; b < bs; b++) {
       out.push_back(codec.decode(Classes(cls.begin() + o, cls.begin() + o + cnt[b])));
@@ -328,6 +338,45 @@ struct CLSTMOCR {
       o += batch_T[b];
     }
     T = batch_T.back();
+  }
+  // ---- raw line images normalised ON THE DEVICE (clstm_normalizer_*: the frames are the host normaliser's, bit for bit).  Main
+  // thread only: the call goes to the library's stream, which is per thread.
+  // measure + normalize of `raws` in one call; T: frames per line, *frames_d: DEVICE [sum T][target_height], valid until the next call
+  void normalize_device(const vector<const Image*>& raws, vector<int>& T_out, float** frames_d) {
+    if (!gpu_normalizer)
+      chk(clstm_normalizer_create(&gpu_normalizer, target_height, normalizer.smooth2d, normalizer.smooth1d, normalizer.range), "clstm_normalizer_create");
+    vector<int> w, h;
+    vector<float> pix;
+    for (const Image* r : raws) { w.push_back(r->w); h.push_back(r->h); pix.insert(pix.end(), r->d.begin(), r->d.end()); }
+    T_out.assign(raws.size(), 0);
+    chk(clstm_normalizer_run_h(gpu_normalizer, pix.data(), w.data(), h.data(), (int)raws.size(), T_out.data(), nullptr, frames_d), "clstm_normalizer_run_h");
+  }
+  // the same with the frames read back once into one Image per line (what a dataset cache keeps)
+  void normalize_batch_gpu(const vector<const Image*>& raws, vector<Image*>& frames) {
+    if (raws.empty()) return;
+    vector<int> Ts;
+    float* frames_d = nullptr;
+    normalize_device(raws, Ts, &frames_d);
+    size_t N = 0;
+    for (int t : Ts) N += t;
+    vector<float> all(N * target_height);
+    chk(clstm_normalizer_get_frames_h(gpu_normalizer, all.data()), "clstm_normalizer_get_frames_h");
+    size_t o = 0;
+    for (size_t b = 0; b < raws.size(); b++) {
+      frames[b]->resize(Ts[b], target_height);
+      std::copy(all.begin() + o, all.begin() + o + (size_t)Ts[b] * target_height, frames[b]->d.begin());
+      o += (size_t)Ts[b] * target_height;
+    }
+  }
+  // predict_batch with the normaliser on the device: pack the raw images, clstm_normalizer_run_h, clstm_net_predict on the frames
+  // where they lie.  Same overlap-mode bracket as predict_frames, so results do not depend on `batch`.
+  void predict_batch_gpu(const vector<const Image*>& raws, vector<ustring>& out, vector<vector<CharPrediction>>* preds = nullptr) {
+    out.clear();
+    if (preds) preds->clear();
+    if (raws.empty()) return;
+    float* frames_d = nullptr;
+    normalize_device(raws, batch_T, &frames_d);
+    predict_packed(frames_d, false, out, preds);
   }
   void predict_batch(const vector<Image>& raws, vector<ustring>& out, vector<vector<CharPrediction>>* preds = nullptr) {
     vector<Image> frames(raws.size());

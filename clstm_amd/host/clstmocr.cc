@@ -14,7 +14,8 @@ static float scaled_log(float x) {  // clstmocr.cc:33-40 (float arithmetic, clam
 static int main1(int argc, char** argv) {
   if (argc != 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
     std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " IMAGEFILE-LIST\n  Variables: load (required) conf output save_text\n"
-              << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)   (not in the reference)\n";
+              << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)\n"
+              << "             gpu_prep (1: lines are normalised on the device, helper threads only read PNGs; default 0)   (not in the reference)\n";
     return EXIT_FAILURE;
   }
   string load_name = getsenv("load", "");
@@ -29,7 +30,11 @@ static int main1(int argc, char** argv) {
   // before it -- and results are printed and written in input order, in the formats of the per-line loop.
   const int batch = std::max(1, getienv("batch", 1));
   const int prep_threads = std::max(1, std::min(std::min(getienv("prep_threads", 16), 16), std::max(1, (int)std::thread::hardware_concurrency())));
-  if (batch > 1) {
+  // gpu_prep=1 (default 0: nothing changes): the helper threads only read the PNGs and every chunk goes through
+  // CLSTMOCR::predict_batch_gpu -- CenterNormalizer on the device (clstm_normalizer_run_h), its frames handed to clstm_net_predict
+  // where they lie.  The frames are the host normaliser's bit for bit, so the output is the same bytes.
+  const bool gpu_prep = getienv("gpu_prep", 0) != 0;
+  if (batch > 1 || gpu_prep) {
     if (output != "text" && output != "logs" && output != "posteriors") fail("unknown output format");
     vector<string> names;
     read_lines(names, argv[1]);
@@ -42,7 +47,8 @@ static int main1(int argc, char** argv) {
           Image raw;
           read_png(raw, c.names[k]);
           for (float& v : raw.d) v = -v + 1.0f;
-          clstm.normalize_line(c.frames[k], raw);
+          if (gpu_prep) c.frames[k] = std::move(raw);   // (the raw line: normalised on the device, by the main thread)
+          else clstm.normalize_line(c.frames[k], raw);
         }
       };
       vector<std::future<void>> pool;
@@ -60,7 +66,8 @@ static int main1(int argc, char** argv) {
       for (auto& f : cur.frames) ptrs.push_back(&f);
       vector<ustring> outs;
       vector<vector<CharPrediction>> preds;
-      clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
+      if (gpu_prep) clstm.predict_batch_gpu(ptrs, outs, conf ? &preds : nullptr);
+      else clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
       vector<Image> posteriors;
       if (output != "text") clstm.get_outputs_batch(posteriors);
       for (size_t k = 0; k < cur.names.size(); k++) {

@@ -148,6 +148,7 @@ static int print_usage(char** argv) {
   std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " TRAININGLIST [TESTLIST]\n"
             << "  Variables: load save_name nhidden lrate momentum target_height ntrain start charsep\n"
             << "             report_time test_every report_every save_every params   (clstmocrtrain.cc:99-115)\n"
+            << "             gpu_prep (1: lines are normalised on the device, helper threads only decode PNGs; default 0)\n"
             << "             batch (lines per update, default 1)  test_batch (lines per recognition call of the test-set pass, default batch)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
   return EXIT_FAILURE;
 }
@@ -275,10 +276,66 @@ static int main1(int argc, char** argv) {
     for (int i : mine) ptrs.push_back(lines[i].get());
     clstm.pack(p, ptrs);
   };
+  // gpu_prep=1 (default 0: nothing below changes): CenterNormalizer runs on the device (clstm_normalizer_run_h; frames bit for bit the
+  // host's, so the run prints and saves the same bytes).  The library's stream belongs to the thread that calls it, so the device part
+  // runs on the MAIN thread: draw_host (helper task) draws the samples and decodes the PNGs of the lines not yet in the cache;
+  // draw_device (main thread, after the step that was enqueued meanwhile) normalises them in one call, reads their frames back once
+  // into the same Line cache entries and packs the minibatch.  That call is ordered on the library's stream behind the steps already
+  // queued -- accepted: it happens only for files seen for the first time; from the second visit of a file on the loop is the
+  // gpu_prep=0 loop.  The test-set pass goes through CLSTMOCR::predict_batch_gpu.
+  const bool gpu_prep = getienv("gpu_prep", 0) != 0;
+  struct Pending {
+    vector<int> samples, mine, todo;
+    vector<std::shared_ptr<CLSTMOCR::Line>> lines;
+    vector<Image> raws;   // raws[k]: the raw line of todo[k]
+  };
+  auto draw_host = [&](Pending& d) {
+    d.samples.assign(batch, 0);
+    for (int i = 0; i < batch; i++) d.samples[i] = lrand48() % trainingset.size();
+    d.lines.assign(batch, nullptr);
+    d.mine = deal(d.samples);
+    d.todo.clear();
+    for (int i : d.mine) {
+      if (use_cache && cache[d.samples[i]]) { d.lines[i] = cache[d.samples[i]]; continue; }
+      bool first = true;
+      for (int j : d.todo) if (d.samples[j] == d.samples[i]) first = false;
+      if (first) d.todo.push_back(i);
+    }
+    d.raws.assign(d.todo.size(), Image());
+    auto work = [&](int k0) {
+      for (size_t k = k0; k < d.todo.size(); k += prep_threads) {
+        const int i = d.todo[k];
+        ustring gt;
+        trainingset.readSample(d.raws[k], gt, d.samples[i]);
+        auto l = std::make_shared<CLSTMOCR::Line>();
+        clstm.codec.encode(l->labels, gt);
+        l->target = gt;
+        d.lines[i] = l;
+      }
+    };
+    vector<std::future<void>> pool;
+    for (int t = 1; t < prep_threads && t < (int)d.todo.size(); t++) pool.push_back(std::async(std::launch::async, work, t));
+    work(0);
+    for (auto& f : pool) f.get();
+  };
+  auto draw_device = [&](Pending& d, CLSTMOCR::Prepared& p) {
+    vector<const Image*> raws;
+    vector<Image*> frames;
+    for (size_t k = 0; k < d.todo.size(); k++) { raws.push_back(&d.raws[k]); frames.push_back(&d.lines[d.todo[k]]->frames); }
+    clstm.normalize_batch_gpu(raws, frames);
+    for (int i : d.todo) if (use_cache) cache[d.samples[i]] = d.lines[i];
+    for (int i : d.mine)
+      if (!d.lines[i]) for (int j : d.todo) if (d.samples[j] == d.samples[i]) d.lines[i] = d.lines[j];
+    vector<const CLSTMOCR::Line*> ptrs;
+    for (int i : d.mine) ptrs.push_back(d.lines[i].get());
+    clstm.pack(p, ptrs);
+  };
+  Pending pending;
   CLSTMOCR::Prepared cur, next;
   std::future<void> helper;
   const bool batched = batch > 1 || ngpu > 1;
-  if (batched) draw(next);
+  if (batched && gpu_prep) { draw_host(pending); draw_device(pending, next); }
+  else if (batched) draw(next);
   for (int trial = start; trial < ntrain; trial += batch) {
     // the last trial this update covers: the triggers look at it, so that the end-of-run save / test fire for any
     // batch size (Trigger fires for good at count >= upto - 1; with batch = 8 and ntrain = 1000 the loop ends at 992)
@@ -290,7 +347,7 @@ static int main1(int argc, char** argv) {
       pred = clstm.train(raw, gt);
     } else {
       std::swap(cur, next);
-      if (trial + batch < ntrain) helper = std::async(std::launch::async, [&] { draw(next); });
+      if (trial + batch < ntrain) helper = std::async(std::launch::async, [&] { if (gpu_prep) draw_host(pending); else draw(next); });
       // a minibatch whose result is printed reads decode + alignment back (synchronous); every other one is
       // enqueued without a host synchronisation and the loop goes straight on to the next
       if (report_trigger.peek(tend)) {
@@ -299,7 +356,7 @@ static int main1(int argc, char** argv) {
       } else {
         clstm.train_batch_async(cur);
       }
-      if (helper.valid()) helper.get();
+      if (helper.valid()) { helper.get(); if (gpu_prep) draw_device(pending, next); }
       gt = cur.targets.back();
     }
     if (report_trigger(tend)) {
@@ -330,7 +387,8 @@ static int main1(int argc, char** argv) {
           for (int k = k0; k < n; k += prep_threads) {
             Image traw;
             testset.readSample(traw, tgts[k], first + k);
-            clstm.normalize_line(frames[k], traw);
+            if (gpu_prep) frames[k] = std::move(traw);   // (the raw line: predict_batch_gpu normalises it on the device)
+            else clstm.normalize_line(frames[k], traw);
           }
         };
         vector<std::future<void>> pool;
@@ -339,7 +397,8 @@ static int main1(int argc, char** argv) {
         for (auto& f : pool) f.get();
         vector<const Image*> ptrs;
         for (auto& f : frames) ptrs.push_back(&f);
-        clstm.predict_frames(ptrs, tpreds);
+        if (gpu_prep) clstm.predict_batch_gpu(ptrs, tpreds);
+        else clstm.predict_frames(ptrs, tpreds);
         for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += levenshtein(tpreds[k], tgts[k]); }
       }
       test_error = errors / count;

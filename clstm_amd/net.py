@@ -268,6 +268,25 @@ class Network:
             o += tb
         return dec, locs, confs
 
+    def predict_images(self, images, normalizer):
+        """predict() for RAW line images (ink = 1, [w, h] arrays): normalised on the device by `normalizer` (Normalizer.run_device),
+        the frames handed to clstm_net_predict where they lie.  Returns what predict() returns."""
+        T, _, frames_d = normalizer.run_device(images)
+        self._declared = None
+        self.T = [int(t) for t in T]
+        self.N = int(sum(self.T))
+        cls, loc = np.zeros(self.N, np.int32), np.zeros(self.N, np.int32)
+        conf, cnt = np.zeros(self.N, np.float32), np.zeros(len(self.T), np.int32)
+        t = i32(self.T)
+        self.lib.call("clstm_net_predict", self.h, ptr(t), len(self.T), frames_d, ptr(cls), ptr(loc), ptr(conf), ptr(cnt))
+        dec, locs, confs, o = [], [], [], 0
+        for b, tb in enumerate(self.T):
+            dec.append(cls[o:o + cnt[b]].copy())
+            locs.append(loc[o:o + cnt[b]].copy())
+            confs.append(conf[o:o + cnt[b]].copy())
+            o += tb
+        return dec, locs, confs
+
     def device_bytes(self):
         """sum of this net's device allocations in bytes (clstm_net_device_bytes)"""
         n = C.c_longlong()
@@ -314,6 +333,69 @@ class Network:
 
     def reset_timing(self):
         self.lib.call("clstm_net_reset_timing", self.h)
+
+
+class Normalizer:
+    """CenterNormalizer (extras.cc:227-285) on the device (clstm_normalizer_*, csrc/normalize.h): raw line images in, input
+    frames out, bit for bit the host normaliser's.  images: [w, h] float arrays with ink = 1 -- image[x, y], the host Image
+    layout -- of any sizes."""
+
+    def __init__(self, target_height=48, smooth2d=1.0, smooth1d=0.3, range=4.0, lib=None):
+        self.lib = lib or abi.load()
+        self.target_height = int(target_height)
+        h = C.c_void_p()
+        self.lib.call("clstm_normalizer_create", C.byref(h), self.target_height, float(smooth2d), float(smooth1d), float(range))
+        self.h = h
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                self.lib.call("clstm_normalizer_destroy", self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    @staticmethod
+    def pack(images):
+        images = [f32(a) for a in images]
+        for a in images:
+            if a.ndim != 2:
+                raise ValueError("a line image is a [w, h] array")
+        w, h = i32([a.shape[0] for a in images]), i32([a.shape[1] for a in images])
+        pix = f32(np.concatenate([a.reshape(-1) for a in images])) if images else f32([])
+        return pix, w, h
+
+    def _run(self, name, pix, w, h):
+        bs = len(w)
+        T, r = np.zeros(bs, np.int32), np.zeros(bs, np.float32)
+        frames_d = C.c_void_p()
+        self.lib.call(name, self.h, ptr(pix), ptr(w), ptr(h), bs, ptr(T), ptr(r), C.byref(frames_d))
+        self.nframes = int(T.sum())
+        return T, r, frames_d.value
+
+    def run_device(self, images):
+        """-> (T, r, address of the DEVICE frames [sum T][target_height], valid until the next call on this normalizer)"""
+        return self._run("clstm_normalizer_run_h", *self.pack(images))
+
+    def run_device_pixels(self, pix_d, w, h):
+        """the same for pixels already on the device (packed back to back; a torch tensor or an address)"""
+        return self._run("clstm_normalizer_run_d", pix_d, i32(w), i32(h))
+
+    def frames(self):
+        """the last call's frames as a host array [sum T][target_height] (blocking)"""
+        out = np.empty((self.nframes, self.target_height), np.float32)
+        self.lib.call("clstm_normalizer_get_frames_h", self.h, ptr(out))
+        return out
+
+    def run(self, images):
+        """-> (T, r, frames ndarray [sum T][target_height])"""
+        T, r, _ = self.run_device(images)
+        return T, r, self.frames()
+
+    def device_bytes(self):
+        n = C.c_longlong()
+        self.lib.call("clstm_normalizer_device_bytes", self.h, C.byref(n))
+        return n.value
 
 
 class Comm:

@@ -220,6 +220,40 @@ int clstm_net_predict(clstm_net* net, const int* T_h, int bs, const float* x_d, 
                       int* counts_h);
 int clstm_net_predict_h(clstm_net* net, const int* T_h, int bs, const float* x_h, int* classes_h, int* locs_h, float* conf_h,
                         int* counts_h);
+/* ------------------------------------------------------------------------------------------
+ * Line normalisation on the device: CenterNormalizer::measure + normalize (extras.cc:53-131, 205-285; restated in
+ * clstm_amd/host/normalizer.h) for a minibatch of RAW line images, bit for bit what the host code gives (csrc/normalize.h): the
+ * frames are the bytes, T and r the values, of the host normaliser.  Everything is enqueued on the library's one stream.
+ *   Images: ink = 1 (1 - pixel of the PNG, clstmocrtrain.cc:73), float32 in the host Image layout -- pixel (x = i, y = j) of a
+ * w x h line at i*h + j -- packed back to back; w_h[bs], h_h[bs]: HOST.
+ *   Limit: the reach of every Gaussian mask, 1 + int(3 sigma) for sigma = h/2, h*smooth2d and h*smooth1d, must not exceed 800
+ * (any h <= 256 at the default parameters smooth2d = 1, smooth1d = 0.3; h <= 532 for smooth2d <= 0.5); a line beyond it is
+ * refused by name.  A line may have any width whose buffers fit in device memory (up to 2^30 pixels).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct clstm_normalizer clstm_normalizer;
+/* the reference's defaults: target_height 48, smooth2d 1.0, smooth1d 0.3, range 4.0.  target_height >= 1 */
+int clstm_normalizer_create(clstm_normalizer** out, int target_height, float smooth2d, float smooth1d, float range);
+int clstm_normalizer_destroy(clstm_normalizer* nz);
+/* measure + normalize of bs lines.  pix_h: HOST, packed as above; w_h / h_h[bs] HOST.  T_h[bs] out: frames per line; r_h[bs] out
+ * (CenterNormalizer::r), may be NULL.  Blocking only for the bs values of r / T (two floats per line are read back; mad, r and the
+ * target width are computed on the host).  *frames_d: library-owned DEVICE [sum T][target_height], line after line -- what
+ * clstm_net_set_inputs_d, clstm_net_predict and clstm_net_train_step take -- valid until the next call on this normalizer; the warp
+ * kernel is enqueued on the library's stream before the call returns.
+ *   bs > 0 and every w, h >= 1 (and the limit above) are checked before anything is touched.  A line without ink (the sum of its
+ * pixels is 0: the host's int(NaN) is undefined there) or with a non-finite mean absolute deviation is refused after the measure
+ * stage: clstm_last_error names the line index, no frames are produced for the call (T_h / r_h are not written), and the
+ * normalizer stays usable. */
+int clstm_normalizer_run_h(clstm_normalizer* nz, const float* pix_h, const int* w_h, const int* h_h, int bs, int* T_h, float* r_h,
+                           float** frames_d);
+/* the same with the pixels already on the device (pix_d DEVICE; not modified) */
+int clstm_normalizer_run_d(clstm_normalizer* nz, const float* pix_d, const int* w_h, const int* h_h, int bs, int* T_h, float* r_h,
+                           float** frames_d);
+/* blocking copy of the last call's frames, HOST [sum T][target_height]; refused if that call produced none */
+int clstm_normalizer_get_frames_h(clstm_normalizer* nz, float* frames_h);
+/* bytes of the normalizer's grow-only device buffers: the frames (sized after the T read-back; they grow and never shrink), the
+ * uploaded pixels, two intermediate images, the per-column arrays, masks and item lists */
+int clstm_normalizer_device_bytes(clstm_normalizer* nz, long long* bytes);
+
 /* sum of the net's device allocations in bytes (parameters, packed weights, every per-minibatch buffer, CTC / decode scratch) */
 int clstm_net_device_bytes(clstm_net* net, long long* bytes);
 /* internal NPLSTM state for parity tests: which = 0 gi,1 gf,2 go,3 ci,4 state,5 output h,
@@ -364,7 +398,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 22 / 23 / 15 the no-save forward
  * passes of clstm_net_predict (per-line recurrence launches, fused forward launches, batched MFMA launches; the training counters 5 /
  * 16 do not move for them), 7 training steps whose gradient exchange was the peer-read all-reduce fused with the update (either
- * form), 24 those of them that took the two-phase form, 21 minibatches whose forward pass the
+ * form), 24 those of them that took the two-phase form, 25 lines normalised on the device (clstm_normalizer_run_*), 21 minibatches whose forward pass the
  * batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255]; blocking).  Tests use it to make sure the
  * path they mean to cover is the one that ran. */
 int clstm_debug_path_count(int which, long long* out_h);
