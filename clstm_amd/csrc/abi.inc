@@ -453,7 +453,7 @@ int clstm_net_train_step_next(clstm_net* h, const int* T_h, int bs, const float*
   Net& n = h->net;
   if (n.next.matches(T_h, bs, x_d, labels_h, L_h) && n.src0_ready && !n.lo_pending) {
     n.next.valid = false;                  // declared and ingested by the previous call's tail
-    g_path_count[20]++;
+    g_path_count[PC_INGEST_TAIL_USED]++;
   } else {
     n.set_batch(T_h, bs);
     CtcMetaCopy meta;
@@ -902,8 +902,8 @@ int clstm_debug_set_option(const char* name, int value) {   // experiment switch
 }
 int clstm_debug_path_count(int which, long long* out_h) {
   ABI_BEGIN
-  REQUIRE(which >= 0 && which < 26 && out_h, "bad path index");
-  if (which == 21) {   // counted on the device: minibatches whose forward pass the batched recurrence handed to its routed per-line twins (lstm_mfma.h)
+  REQUIRE(which >= 0 && which < PC_COUNT && out_h, "bad path index");
+  if (which == PC_MFMA_ROUTED) {   // counted on the device: minibatches whose forward pass the batched recurrence handed to its routed per-line twins (lstm_mfma.h)
     int n = 0;
     HIPCHECK(hipStreamSynchronize(g_stream));
     HIPCHECK(hipMemcpy(&n, dev_err_words() + 8, sizeof(int), hipMemcpyDeviceToHost));

@@ -3,6 +3,8 @@
 // launches, which GEMM form), the chunk tables of the in-launch weight-gradient items, reductions, the gradient exchange.
 // The forward recurrence family of a layer is chosen in ONE place, Net::forward_family: forward() and predict() are the same
 // layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by the same answer.
+// Likewise the backward pass: Net::backward_family names a layer's family; backward() is backward_softmax, then per layer the
+// recurrence, the layer's BwdPlan (decided ONCE, behind the recurrence launch), the weight gradient, the input deltas.
 // Not a stand-alone header: included once by clstm_hip.hip behind runtime.inc.
 struct Layer {
   int ni, no, nk4, nthreads;
@@ -58,6 +60,18 @@ struct Layer {
 // the forward recurrence of one layer of the current minibatch (Net::forward_family): the whole forward half as one launch
 // (lstm_fwd_fused.h), batched over 16 lines on the MFMA (lstm_mfma.h), one workgroup per line (lstm_seq.h), lock-step (lstm_wide.h)
 enum class FwdFamily { Fused, Mfma, PerLine, Wide };
+// ... and its backward recurrence (Net::backward_family): with the chunked weight-gradient items of gemm_dw.h in or behind its launch
+// (backward_layer_overlapped), lock-step (lstm_wide.h), or the narrow layer's alone with the weight gradient as a product behind it
+enum class BwdFamily { Overlapped, Wide, Narrow };
+// what the weight-gradient and input-delta steps of a layer need to know: Net::backward_plan, once the recurrence has been launched
+struct BwdPlan {
+  BwdFamily family;
+  bool bwd_persistent;   // the recurrence ran as a persistent lock-step kernel (in bf16 mode: Dbf and dbias are this pass's)
+  bool dw_from_bf16;     // the weight-gradient product takes the bf16 rows their producers left (Sbf, Dbf)
+  bool dw_bias_out;      // ... in dw_rows < R rows (Net::dw_bf16_rows): without the bias row, which k_bias_rows lays from dbias
+  bool x3_big;           // exact-f32 mode, wide layer: the product as f32-grade bf16 x 3 on 128 x 128 tiles
+  int dw_rows, ns;       // ns: split-K slabs per direction the reduction will find
+};
 
 struct Net {
   clstm_net_desc desc;
@@ -570,7 +584,7 @@ struct Net {
     static const bool smem_set = (coop_set_smem(lstm_fwd_mfma_kernel<NO, NI, SAVE>, (size_t)Gm::SMEM), true);
     (void)smem_set; (void)fwd;
     CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI, SAVE>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
-    g_path_count[SAVE ? 16 : 15]++;
+    g_path_count[SAVE ? PC_MFMA_FWD : PC_MFMA_NOSAVE]++;
     if (l == 0) launch_routed_per_line(y, s, SAVE);
   }
   // the per-line forward pass of layer 0 (hoisted f32 W_x.x product + lstm_seq.h recurrence, as forward() launches them for
@@ -649,7 +663,7 @@ struct Net {
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
     (void)smem_set;
     CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
-    g_path_count[17]++;
+    g_path_count[PC_MFMA_BWD]++;
   }
   // ... and as ONE launch with the weight-gradient items (lstm_mfma_bwd_dw.h); false: not instantiated for this layer / arithmetic
   template <int NO>
@@ -661,7 +675,7 @@ struct Net {
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM), true);
     (void)smem_set;
     CLSTM_LAUNCH((lstm_bwd_mfma_dw_kernel<NO, NT, 3>), dim3((unsigned)nrec + ngemm), dim3(512), (size_t)Gr::SMEM, s, a, g, nrec, ngroups);
-    g_path_count[17]++; g_path_count[18]++;
+    g_path_count[PC_MFMA_BWD]++; g_path_count[PC_MFMA_BWD_DW]++;
     return true;
   }
   // (pays while the recurrence leaves most CUs idle -- same box, lines/s fused vs separate: 640 lines 368.1k vs 340.0k, 768: 395.7k
@@ -726,26 +740,22 @@ struct Net {
       // persistent kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) -- false if it did not run
       auto run_wide = [&](LstmWideArgs w, int fx_ngx) {
         timing.begin("lstm_fwd", s);
-        const bool ran = launch_lstm_wide(true, w, tmax, coop_sync, step_graphs, s, bf16_rec, fx_ngx);
+        const WideRan ran = launch_lstm_wide(true, w, tmax, coop_sync, step_graphs, s, bf16_rec, fx_ngx);
         timing.end(s);
-        if (!ran) return false;
-        y.fwd_persistent = g_wide_persistent && bf16_rec;
+        if (ran == WideRan::Nothing) return false;
+        y.fwd_persistent = ran == WideRan::Persistent && bf16_rec;
         y.h_f32_valid = !(y.fwd_persistent && w.skip_h);   // (the per-step kernels store everything)
         y.sh_valid = !(y.fwd_persistent && w.skip_s);
-        if (g_wide_persistent) g_path_count[0]++;
-        if (fx_ngx) g_path_count[6]++;
+        if (ran == WideRan::Persistent) g_path_count[PC_FWD_PERSISTENT]++;
+        if (fx_ngx) g_path_count[PC_FWD_FUSED_WX]++;
         y.sbf_ready = y.fwd_persistent && w.Sbf;
         if (y.sbf_ready) {   // the non-recurrent columns of the bf16 source rows (the recurrence stored the h columns)
           const bool from16 = l > 0 && L[l - 1].fwd_persistent && L[l - 1].Hbf.p && y.ni == ndir * L[l - 1].no;
           if (l > 0 && !from16) ensure_h_f32(l - 1);
           // x columns that fill whole tiles of the weight-gradient GEMM are not copied: the GEMM reads them from Hbf itself
+          // (for the row count the backward pass WILL launch that GEMM with: dw_bf16_rows)
           const int R_ = 1 + y.ni + y.no, Cn_ = 4 * y.no;
-          // (decided for the row count the backward pass WILL launch with -- R_ - 1 when the bias row is left out, the predicate of
-          //  `dw_bias_out` there -- with the same tile-height function; should the backward pass still come out with another tile
-          //  height, gemm_mc_check_a2 refuses the launch loudly instead of reading x rows nobody wrote.  Requiring BOTH R_ and
-          //  R_ - 1 to fit, the first form of this fix, switched the path off at configs[4]: 1537 rows pick 192-row tiles.)
-          const int R_bwd = wide_kp16_bwd(y.no) == 4 * y.no && gemm_bf16_big(R_ - 1, Cn_) ? R_ - 1 : R_;   // (= the backward's dbias condition)
-          y.sbf_x_external = from16 && y.ni % gemm_mc_rows_per_tile(R_bwd, Cn_) == 0;
+          y.sbf_x_external = from16 && y.ni % gemm_mc_rows_per_tile(dw_bf16_rows(y, R_, Cn_), Cn_) == 0;
           if (y.sbf_x_external) {
             if (y.sbf_one_key != (long long)N) {
               CLSTM_LAUNCH(k_source_one_bf16, dim3(nblocks((size_t)N)), dim3(256), 0, s, y.Sbf.p, (size_t)N, y.ni + y.no, w.sbf_ld, ndir, w.sbf_dir);
@@ -802,7 +812,7 @@ struct Net {
       if (x_from_hbf)
       {
         // the layer below left its outputs as a k-contiguous bf16 array: both operands go to LDS as they are
-        g_path_count[2]++;
+        g_path_count[PC_WX_FROM_BF16]++;
         gemm_b16kk(s, GemmOperand16{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni}, GemmOperand16{y.WtbT.p, y.ni, (long long)M * y.ni},
                    StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
       } else if (bf16_gemm && bf16_rec && l == 0 && y.wide && y.WtbT.p && (y.ni & 7) == 0 && gemm_tile256((int)N, M)) {
@@ -810,7 +820,7 @@ struct Net {
         // tiles and 16-byte stores for the product whose 4 M floats of pre-activations per frame-line are its whole cost
         xbf.reserve((size_t)N * y.ni + 64);
         CLSTM_LAUNCH(k_to_bf16, dim3(nblocks((size_t)N * y.ni)), dim3(256), 0, s, layer_input(0), xbf.p, (size_t)N * y.ni);
-        g_path_count[2]++;
+        g_path_count[PC_WX_FROM_BF16]++;
         gemm_b16kk(s, GemmOperand16{xbf.p, y.ni, (long long)N * y.ni}, GemmOperand16{y.WtbT.p, y.ni, (long long)M * y.ni},
                    StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
       } else if (bf16_gemm)
@@ -835,7 +845,7 @@ struct Net {
         timing.begin("lstm_fwd", s);
         launch_lstm(true, y.nk4, y.pd.ku, a, bs, y.nthreads, s, save);
         if (save) y.h_f32_valid = y.sh_valid = true;
-        else g_path_count[22]++;
+        else g_path_count[PC_LINE_NOSAVE]++;
         timing.end(s);
       }
       if (save && !y.sbf_ready) ensure_source_x(l);
@@ -939,7 +949,7 @@ struct Net {
     fw_prog_base += tmax + 64;
     if (fw_prog_base > (1 << 30)) fw_prog_base = 1024;
     fw_launches++;
-    g_path_count[save ? 5 : 23]++;
+    g_path_count[save ? PC_FWD_FUSED : PC_FUSED_NOSAVE]++;
     FwdFusedKernelArgs k{};
     LstmSeqArgs& a = k.a;
     a = seq_args(y, true, save);
@@ -964,17 +974,10 @@ struct Net {
     timing.begin("lstm_fwd", s);
     REQUIRE(launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s, save), "internal: no fused forward instantiation");
     timing.end(s);
-    if (trace_path) {
-      HIPCHECK(hipStreamSynchronize(s));
-      std::vector<long long> t(trace_rows * 4);
-      HIPCHECK(hipMemcpy(t.data(), dw_trace.p, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(trace_path, "w")) {
-        fprintf(f, "# %d recurrence rows (start - end -), %d producer items (start - done chunk), %d consumer items (start ready done ready_iteration); 100 MHz ticks\n",
-                h.nrec, fw_npitems, fw_ncitems);
-        for (size_t i = 0; i < trace_rows; i++) fprintf(f, "%lld %lld %lld %lld\n", t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
-        fclose(f);
-      }
-    }
+    if (trace_path)
+      dump_trace(trace_path, dw_trace.p, trace_rows, s,
+                 "# %d recurrence rows (start - end -), %d producer items (start - done chunk), %d consumer items (start ready done ready_iteration); 100 MHz ticks\n",
+                 h.nrec, fw_npitems, fw_ncitems);
   }
 
   // overlapped weight-gradient GEMM: true = bf16 MFMA on f32 operands split into bf16 terms (gemm_dw.h), false = f32 MFMA
@@ -996,38 +999,43 @@ struct Net {
     if (bf16_gemm || bf16_rec || !gemm_x3_on) return false;
     return dbg_opt("rec_x3") != 0;
   }
-  // split-K slabs for the weight-gradient GEMMs: enough workgroups to cover the 256 CUs
+  // split-K slabs for the weight-gradient GEMMs: enough workgroups to cover the 256 CUs, at least 64 frames per slab, 1..64 slabs
+  int clamp_split(long long want) const { return (int)std::max(1LL, std::min({want, (long long)(N + 63) / 64, 64LL})); }
   // big tiles of the contraction-major bf16 product (gemm_b16mc: 256 or 192 rows x 256 columns): one workgroup per CU, never a second round
   int pick_split_mc(int R, int Cn, int nbatch) const {
     const int th = gemm_mc_tile_rows(R);
     const long long tiles = (long long)((R + th - 1) / th) * ((Cn + 255) / 256) * nbatch;
-    long long want = device_cu_count() / tiles;
-    const long long maxs = (N + 63) / 64;
-    if (want > maxs) want = maxs;
-    if (want > 64) want = 64;
-    if (want < 1) want = 1;
-    return (int)want;
+    return clamp_split(device_cu_count() / tiles);
   }
   int pick_split(int R, int Cn, int nbatch = 1, int tile = GEMM_BT) const {
     const long long tiles = (long long)((R + tile - 1) / tile) * ((Cn + tile - 1) / tile) * nbatch;
     const long long target = tile == GEMM_BT ? 640 : 480;   // 64 x 64 tiles: 640 measured best (272: slower); 128 x 128 tiles: two workgroups per CU
     long long want = (target + tiles - 1) / tiles;
     if (tile == 256) want = device_cu_count() / tiles;          // 256 x 256 tiles: one workgroup per CU, never a second round
-    const long long maxs = (N + 63) / 64;   // at least 64 frames per slab
-    if (want > maxs) want = maxs;
-    if (want > 64) want = 64;
-    if (want < 1) want = 1;
-    return (int)want;
+    return clamp_split(want);
   }
 
   // ---- overlap machinery ---------------------------------------------------------------------------------------
-  bool overlap_eligible(const Layer& y) {
+  bool overlap_eligible(const Layer& y) const {
     if (!overlap || y.wide || y.no % 16 == 0) return false;          // the reporting lane must own no cell
     if (bs > PROG_LINES) return false;
     if ((overlap == 1) && (tmax < 64 || N < 2048)) return false;     // too small to profit
     if ((double)y.D.cap * 4.0 >= 2147483000.0) return false;         // 32-bit byte offsets inside one descriptor
     return overlap == 2 || y.nthreads >= 256;                        // one launch, two workgroup roles (lstm_bwd_dw.h)
   }
+  // THE launch rule of the backward pass: the layer loop, the slab count, the weight-gradient step and dwx_active all ask here.
+  // Overlapped: through backward_layer_overlapped, whatever launch form it picks (mfma_bwd_eligible / mfma_bwd_fused_ok choose a
+  // form INSIDE a family, as mfma_eligible does on the forward side).
+  BwdFamily backward_family(const Layer& y) const {
+    if (!bf16_gemm && overlap_eligible(y)) return BwdFamily::Overlapped;
+    return y.wide ? BwdFamily::Wide : BwdFamily::Narrow;
+  }
+  // Rows of the bf16-source weight-gradient product of an R x Cn gradient: R - 1 when the bias row is produced outside it
+  // (backward_dw_bf16), else R.  backward_plan launches with it and forward_pass PREDICTS it to decide sbf_x_external with the same
+  // tile-height function -- should the backward pass still come out with another tile height, gemm_mc_check_a2 refuses the launch
+  // loudly instead of reading x rows nobody wrote.  (Requiring BOTH R and R - 1 to fit, the first form of that fix, switched the
+  // path off at configs[4]: 1537 rows pick 192-row tiles.)  The first condition is wide_args' for reserving Dbf and dbias.
+  static int dw_bf16_rows(const Layer& y, int R, int Cn) { return wide_kp16_bwd(y.no) == 4 * y.no && gemm_bf16_big(R - 1, Cn) ? R - 1 : R; }
   // Slab geometry of the chunked weight-gradient GEMM (measured at the bench shape unless said otherwise):
   // - chunks of DW_CHUNK iterations (8: 0.407 ms per step, 16: 0.356, 32: 0.359, 48: 0.360, a decreasing plan 64..16: 0.3615);
   // - ~16 slabs per direction, at most DW_STAB_MAX k-tiles (of 16 frames) each: a slab's table must fit the items' LDS copy.  At
@@ -1161,16 +1169,9 @@ struct Net {
       g.done_target = (int)dw_done_total;
       REQUIRE(launch_lstm_bwd_dw(y.nk4, y.pd.ku, a, g, bs * ndir, nblk, y.nthreads, s), "internal: no fused instantiation");
       timing.end(s);
-      if (trace_path) {
-        HIPCHECK(hipStreamSynchronize(s));
-        std::vector<long long> h(trace_rows * 4);
-        HIPCHECK(hipMemcpy(h.data(), dw_trace.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(trace_path, "w")) {
-          fprintf(f, "# rows 0..%d: recurrence workgroups (start, -, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
-          for (size_t i = 0; i < trace_rows; i++) fprintf(f, "%lld %lld %lld %lld\n", h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]);
-          fclose(f);
-        }
-      }
+      if (trace_path)
+        dump_trace(trace_path, dw_trace.p, trace_rows, s,
+                   "# rows 0..%d: recurrence workgroups (start, -, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
       return;
     }
 #endif
@@ -1188,14 +1189,33 @@ struct Net {
     check_launch();
   }
 
+  // ... and of the softmax layer's W.d items in the top layer's launch (dwx_active): contiguous frames, entries of 16, slabs of
+  // 32 entries (512 frames: one short item each)
+  void build_dwx_table() {
+    if (dwx_N == N) return;
+    hipStream_t s = stream();
+    dwx_entries = (int)((N + 15) / 16);
+    const int eps = std::min(DW_STAB_MAX, std::max(32, (dwx_entries + 63) / 64));   // entries per slab: at most ~64 slabs to reduce
+    dwx_nslabs = (dwx_entries + eps - 1) / eps;
+    const size_t nsw = (size_t)dwx_nslabs * sizeof(DwSlab) / sizeof(int);
+    dwx_tab.reserve((size_t)2 * dwx_entries + nsw + 8);
+    int* stage = (int*)ring.acquire(((size_t)2 * dwx_entries + nsw) * sizeof(int));
+    for (int e = 0; e < dwx_entries; e++) { stage[2 * e] = 16 * e; stage[2 * e + 1] = (int)std::min<long long>(16, N - 16LL * e); }
+    DwSlab* sl = (DwSlab*)(stage + 2 * dwx_entries);
+    for (int i = 0; i < dwx_nslabs; i++) sl[i] = DwSlab{eps * i, std::min(eps, dwx_entries - eps * i), 0, 0, i, {0, 0, 0}};
+    for (int i = 0; i < dwx_nslabs; i++) REQUIRE(sl[i].ntiles <= DW_STAB_MAX, "internal: weight-gradient slab longer than its LDS table");
+    HIPCHECK(hipMemcpyAsync(dwx_tab.p, stage, ((size_t)2 * dwx_entries + nsw) * sizeof(int), hipMemcpyHostToDevice, s));
+    ring.commit(s);
+    dwx_N = N;
+  }
+  // of a pass's reductions: the update rides them (fuse) / they leave the gradient in the peer exchange's slot (peer, gdst)
+  struct ReduceTarget { bool fuse, peer; float* gdst; };
   void backward() {
     REQUIRE(N > 0, "set_batch first");
-    const bool fuse = fuse_update;   // consumed here: an exception below must not leave it set for a later pass
+    const bool fuse = fuse_update, peer = peer_step && comm;   // consumed here: an exception below must not leave them set for a later pass
     fuse_update = false;
-    const bool peer = peer_step && comm;
     peer_step = false; peer_pending = false;
-    float* const g_local = g;
-    float* const gdst = peer ? comm->peer.slot_ptr(comm->peer.seq + 1) : g_local;   // where the reductions leave the fresh gradient
+    const ReduceTarget rt{fuse, peer, peer ? comm->peer.slot_ptr(comm->peer.seq + 1) : g};
     nbackward++;
     RoctxRange range_("clstm:backward");
     update_applied = false;
@@ -1204,201 +1224,186 @@ struct Net {
     flush_line_off();
     repack();
     hipStream_t s = stream();
-    const int nc = desc.nclasses;
-    const float* W1 = v + sm_off;
     // every entry of g is assigned by exactly one reduce below: no clearing pass
-    // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T
-    Layer& top = L.back();
-    {  // (a side stream for this GEMM was measured on MI355X: no gain -- the recurrence workgroups it would
-       // overlap with slow down by as much -- so everything stays on one stream)
-      const int R = 1 + sm_ni, Cn = nc;
-      // (bf16 modes, shapes that fill 128 x 128 tiles: the two products as launches of the big-tile f32-grade kernel)
-      const bool sm_big = bf16_gemm && gemm_x3_on && gemm_bf16_big(R, Cn) && gemm_bf16_big((int)N, sm_ni);
-      int ns = sm_big ? pick_split(R, Cn, 1, GB2_BT) : pick_split(R, Cn);
-      // W.d depends on nothing the backward recurrence produces: when the top layer's backward runs as the fused launch
-      // (lstm_bwd_dw.h) its slabs are items of THAT launch -- they execute on the idle half of the chip during the ~14 us
-      // before the recurrence's first chunk is released -- and only x.d stays in front of the recurrence.
-      // (only while the recurrence leaves CUs idle: with 256 lines the same items cost the fused launch +42 us for 19 saved)
-      dwx_active = !bf16_gemm && dw_x3 && overlap_eligible(top) &&
-                   (long long)bs * ndir * 4 <= 3LL * device_cu_count();
-      if (dwx_active) {
-        if (dwx_N != N) {   // contiguous frames: entries of 16, slabs of 32 entries (512 frames: one short item each)
-          dwx_entries = (int)((N + 15) / 16);
-          const int eps = std::min(DW_STAB_MAX, std::max(32, (dwx_entries + 63) / 64));   // entries per slab: at most ~64 slabs to reduce
-          dwx_nslabs = (dwx_entries + eps - 1) / eps;
-          const size_t nsw = (size_t)dwx_nslabs * sizeof(DwSlab) / sizeof(int);
-          dwx_tab.reserve((size_t)2 * dwx_entries + nsw + 8);
-          int* stage = (int*)ring.acquire(((size_t)2 * dwx_entries + nsw) * sizeof(int));
-          for (int e = 0; e < dwx_entries; e++) { stage[2 * e] = 16 * e; stage[2 * e + 1] = (int)std::min<long long>(16, N - 16LL * e); }
-          DwSlab* sl = (DwSlab*)(stage + 2 * dwx_entries);
-          for (int i = 0; i < dwx_nslabs; i++) sl[i] = DwSlab{eps * i, std::min(eps, dwx_entries - eps * i), 0, 0, i, {0, 0, 0}};
-          for (int i = 0; i < dwx_nslabs; i++) REQUIRE(sl[i].ntiles <= DW_STAB_MAX, "internal: weight-gradient slab longer than its LDS table");
-          HIPCHECK(hipMemcpyAsync(dwx_tab.p, stage, ((size_t)2 * dwx_entries + nsw) * sizeof(int), hipMemcpyHostToDevice, s));
-          ring.commit(s);
-          dwx_N = N;
-        }
-        ns = dwx_nslabs;
-      }
-      partial_sm.reserve((size_t)ns * R * Cn);
-      // W.d (split-K slabs) and x.d in ONE launch: two small independent products, each mostly prologue and
-      // epilogue latency on its own (13.9 + 12.4 us back to back)
-      timing.begin("gemm_softmax_dw_dx", s);
-      if (dwx_active)
-        gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), gemm_kc(W1 + nc, nc, sm_ni, 0), StorePlain{top.dH.p, sm_ni}, (int)N, sm_ni, nc,
-                                  1, 1, split_terms);
-      else if (sm_big) {
-        gemm_x3_big<GEMM_MC, GEMM_MC>(s, gemm_mc(top.srow(), top.ldh, N, 32), gemm_mc(Dz.p, nc, N, 32), StorePartial{partial_sm.p, R, Cn}, R, Cn, (int)N, ns);
-        gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N, 32), gemm_kc(W1 + nc, nc, sm_ni, 0), StorePlain{top.dH.p, sm_ni}, (int)N, sm_ni, nc);
-      } else if (gemm_x3_on)
-        gemm_x3_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(
-            s, gemm_problem(gemm_mc(top.srow(), top.ldh, N), gemm_mc(Dz.p, nc, N), R, Cn, (int)N, ns),
-            StorePartial{partial_sm.p, R, Cn},
-            gemm_problem(gemm_kc(Dz.p, nc, N), gemm_kc(W1 + nc, nc, sm_ni, 0), (int)N, sm_ni, nc), StorePlain{top.dH.p, sm_ni},
-            split_terms);
-      else
-      gemm_f32_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(
-          s, gemm_problem(gemm_mc(top.srow(), top.ldh, N), gemm_mc(Dz.p, nc, N), R, Cn, (int)N, ns),
-          StorePartial{partial_sm.p, R, Cn},
-          gemm_problem(gemm_kc(Dz.p, nc, N), gemm_kc(W1 + nc, nc, sm_ni, 0), (int)N, sm_ni, nc), StorePlain{top.dH.p, sm_ni});
-      timing.end(s);
-      // the slabs are reduced together with the top layer's weight-gradient slabs below
-      sm_red = ReduceDesc{partial_sm.p, nullptr, (long long)sm_off, ns, 1, R, Cn, nc};
-    }
-    check_launch();
+    backward_softmax();
     for (int l = (int)L.size() - 1; l >= 0; l--) {
-      Layer& y = L[l];
-      const int M = ndir * 4 * y.no;
-      const LstmSeqArgs a = seq_args(y, false);   // (no progress words: backward_layer_overlapped sets them in its copy)
-      // W.d += delta [1; x_t; h_{t-1}]^T for the four gates of each direction
-      // (both directions in one batched launch: half the slabs per direction fill the chip)
-      const int R = 1 + y.ni + y.no, Cn = 4 * y.no;
-      int ns;
-      bool bwd_persistent = false;
-      if (!bf16_gemm && overlap_eligible(y)) {
-        // the recurrence and the weight-gradient GEMM run side by side (gemm_dw.h)
-        backward_layer_overlapped(y, a, R, Cn);
-        ns = dw_slabs_per_dir;
-        timing.begin("reduce_scatter", s);
-      } else {
-      timing.begin("lstm_bwd", s);
-      int skipped_d = 0;
-      if (y.wide) {
-        const LstmWideArgs w = wide_args(y, false);
-        launch_lstm_wide(false, w, tmax, coop_sync, step_graphs, s, bf16_rec, 0, rec_x3());
-        skipped_d = w.skip_d;
-      } else launch_bwd_narrow(y, a, s);
-      timing.end(s);
-      bwd_persistent = y.wide && g_wide_persistent;
-      y.d_f32_valid = !(bwd_persistent && bf16_rec && skipped_d);
-      if (bwd_persistent) g_path_count[1]++;
-      }
-      const bool dw_from_bf16 = bf16_gemm && bf16_rec && bwd_persistent && y.sbf_ready && y.Dbf.p && gemm_bf16_big(R, Cn);
-      const bool dw_bias_out = dw_from_bf16 && y.dbias.p && gemm_bf16_big(R - 1, Cn);
-      // exact-f32 mode, wide layer: the backward products as f32-grade bf16 x 3 on 128 x 128 tiles (gemm_x3_128_kernel) -- what
-      // narrow layers already do inside their fused backward launch; gemm_x3=0 (CLSTM_DEBUG) / clstm_net_set_strict_f32: the f32 MFMA
-      const bool x3_big = !bf16_gemm && y.wide && gemm_x3_on && gemm_bf16_big(R, Cn);
-      if (bf16_gemm || !overlap_eligible(y))
-        ns = dw_bias_out && gemm_tile256(R - 1, Cn) ? pick_split_mc(R - 1, Cn, ndir)
-             : dw_from_bf16 && gemm_tile256(R, Cn) ? pick_split_mc(R, Cn, ndir)
-             : (bf16_gemm || x3_big) && gemm_bf16_big(R, Cn) ? pick_split(R, Cn, ndir, GB2_BT) : pick_split(R, Cn, ndir);
-      if (!dw_from_bf16) { ensure_source(l); ensure_delta_f32(l); }   // the f32-source products below read S and D
-      DevBuf<float>& pbuf = layer_partial(y);
-      bool dx_done = false;   // the input deltas rode the weight-gradient launch (gemm_dw_dx)
-      auto do_dw = [&](hipStream_t q) {
-        if (bf16_gemm || !overlap_eligible(y)) {
-          pbuf.reserve((size_t)ndir * ns * R * Cn);
-          timing.begin("gemm_gates_dw", q);
-          if (dw_from_bf16) {
-            // both operands bf16 as their producers left them (deltas: the persistent backward recurrence; sources: the
-            // forward pass), transposed by the LDS on the way into the MFMA
-            const int ldsb = y.ni + y.no + 8;
-            g_path_count[4]++;
-            const GemmOperand16B a2 = y.sbf_x_external ? GemmOperand16B{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni, 0} : GemmOperand16B{nullptr, 0, 0, 0};
-            // ... and, where the layer also owes input deltas from the same bf16 delta array, BOTH products as one launch
-            // (gemm_bf16.h:gemm_dw_dx_kernel: apart, each leaves a quarter of the chip idle)
-            float* const dxp = l > 0 ? L[l - 1].dH.p : nullptr;
-            if (dw_bias_out && dxp && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p &&
-                gemm_dw_dx(q, GemmOperand16B{y.Sbf.p, ldsb, (long long)N * ndir * ldsb, (long long)N * ldsb}, GemmOperand16B{y.Dbf.p, M, (long long)N * M, 4LL * y.no},
-                           StorePartialShift{pbuf.p, R, Cn}, R - 1, Cn, (int)N, ns, ndir, a2, y.sbf_x_external ? y.ni : 0,
-                           GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dxp, y.ni}, (int)N, y.ni, M)) {
-              CLSTM_LAUNCH(k_bias_rows, dim3((unsigned)(((size_t)ndir * Cn + 63) / 64)), dim3(64), 0, q, (const float*)y.dbias.p, pbuf.p, bs, ndir, ns, R, Cn);
-              g_path_count[13]++; g_path_count[3]++; g_path_count[14]++;
-              dx_done = true;
-            } else if (dw_bias_out) {
-              // The bias row W.d[:,0] += sum_b y.d (clstm_compute.cc:301) is not a row of this product: 1 + ni + no rows are one
-              // more than a whole number of row panels at both configs[4] layers (1537 = 6 x 256 + 1: a seventh panel, 14 % of
-              // the product, for one row; 577 = 3 x 192 + 1) -- the persistent backward recurrence sums the deltas of a line while
-              // it produces them (LstmWideArgs::dbias) and k_bias_rows lays the sum over lines into row 0 of the first slab.
-              gemm_b16mc(q, GemmOperand16B{y.Sbf.p, ldsb, (long long)N * ndir * ldsb, (long long)N * ldsb},
-                         GemmOperand16B{y.Dbf.p, M, (long long)N * M, 4LL * y.no}, StorePartialShift{pbuf.p, R, Cn}, R - 1, Cn, (int)N, ns, ndir, a2,
-                         y.sbf_x_external ? y.ni : 0);
-              CLSTM_LAUNCH(k_bias_rows, dim3((unsigned)(((size_t)ndir * Cn + 63) / 64)), dim3(64), 0, q, (const float*)y.dbias.p, pbuf.p, bs, ndir, ns, R, Cn);
-              g_path_count[13]++;
-            } else
-            gemm_b16mc(q, GemmOperand16B{y.Sbf.p, ldsb, (long long)N * ndir * ldsb, (long long)N * ldsb},
-                       GemmOperand16B{y.Dbf.p, M, (long long)N * M, 4LL * y.no}, StorePartialRot{pbuf.p, R, Cn}, R, Cn, (int)N, ns, ndir, a2,
-                       y.sbf_x_external ? y.ni : 0);
-            if (y.sbf_x_external) g_path_count[8]++;
-          } else if (bf16_gemm)
-            gemm_bf16<GEMM_MC, GEMM_MC>(q, gemm_batched(gemm_mc(y.S.p, y.lds, N), (long long)N * y.lds, ndir),
-                                        gemm_batched(gemm_mc(y.D.p, M, N, 0), 4LL * y.no, 1),
-                                        StorePartial{pbuf.p, R, Cn}, R, Cn, (int)N, ns, ndir);
-          else if (x3_big)
-            gemm_x3_big<GEMM_MC, GEMM_MC>(q, gemm_batched(gemm_mc(y.S.p, y.lds, N), (long long)N * y.lds, ndir),
-                                          gemm_batched(gemm_mc(y.D.p, M, N, 0), 4LL * y.no, 1), StorePartial{pbuf.p, R, Cn}, R, Cn, (int)N, ns, ndir);
-          else
-            gemm_f32<GEMM_MC, GEMM_MC, StorePartial, GEMM_BK_DW>(q, gemm_batched(gemm_mc(y.S.p, y.lds, N), (long long)N * y.lds, ndir),
-                                                                 gemm_batched(gemm_mc(y.D.p, M, N, 0), 4LL * y.no, 1),
-                                                                 StorePartial{pbuf.p, R, Cn}, R, Cn, (int)N, ns, ndir);
-        }
-        const ReduceDesc gates{pbuf.p, y.moff, 0LL, ns, ndir, R, Cn, y.no};
-        ReduceDesc extra{};   // empty unless this is the top layer
-        if (l == (int)L.size() - 1) extra = sm_red;
-        if (L.size() > 1) {   // stacked net: every reduction behind the last recurrence of the pass (see reduce_layer)
-          pending_red.push_back(PendingReduce{gates, extra, l});
-          timing.end(q);
-          check_launch();
-          return;
-        }
-        reduce_layer(gates, extra, l, true, fuse, peer, gdst, q);
-        timing.end(q);
-        check_launch();
-      };
-      auto do_dx = [&]() {
-        // input deltas: x.d = sum_dir W_x^T delta (Parallel::backward sums both subs, clstm.cc:538-541)
-        float* dx = nullptr;
-        if (l > 0) dx = L[l - 1].dH.p;
-        else if (want_dx0) { dX0.reserve((size_t)N * y.ni); dx = dX0.p; }
-        if (!dx || dx_done) return;
-        timing.begin("gemm_gates_dx", s);
-        if (bf16_gemm && bf16_rec && bwd_persistent && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p && y.Dbf.p)
-        {
-          // the persistent recurrence left the deltas as a k-contiguous bf16 array: both operands go to LDS as they are
-          g_path_count[3]++;
-          gemm_b16kk(s, GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M},
-                     StorePlain{dx, y.ni}, (int)N, y.ni, M);
-        } else if (ensure_delta_f32(l), bf16_gemm)
-          gemm_bf16<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni},
-                                      (int)N, y.ni, M);
-        else if (y.wide && gemm_x3_on && gemm_bf16_big((int)N, y.ni))
-          gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni}, (int)N, y.ni, M);
-        else
-          gemm_f32<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N), gemm_kc(y.Wt, M, y.ni, 0), StorePlain{dx, y.ni}, (int)N,
-                                     y.ni, M);
-        timing.end(s);
-        check_launch();
-      };
-      do_dw(s);
-      do_dx();
+      const BwdFamily fam = backward_family(L[l]);
+      const bool bwd_persistent = backward_recurrence(l, fam);
+      const BwdPlan p = backward_plan(L[l], fam, bwd_persistent);
+      if (!p.dw_from_bf16) { ensure_source(l); ensure_delta_f32(l); }   // the f32-source products below read S and D
+      if (!backward_weight_gradient(l, p, rt)) backward_input_deltas(l, p);   // (true: the input deltas rode the weight-gradient launch)
     }
     if (!pending_red.empty()) {
       timing.begin("reduce_scatter", s);
-      for (size_t i = 0; i < pending_red.size(); i++)
-        reduce_layer(pending_red[i].gates, pending_red[i].extra, pending_red[i].l, i + 1 == pending_red.size(), fuse, peer, gdst, s);
+      for (size_t i = 0; i < pending_red.size(); i++) reduce_layer(pending_red[i].gates, pending_red[i].extra, i + 1 == pending_red.size(), rt);
       pending_red.clear();
       timing.end(s);
       check_launch();
     }
+  }
+  // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T.  (A side stream for these products was measured
+  // on MI355X: no gain -- the recurrence workgroups it would overlap with slow down by as much -- so everything stays on one stream.)
+  void backward_softmax() {
+    hipStream_t s = stream();
+    Layer& top = L.back();
+    const int nc = desc.nclasses, R = 1 + sm_ni, Cn = nc;
+    const float* W1 = v + sm_off;
+    // (bf16 modes, shapes that fill 128 x 128 tiles: the two products as launches of the big-tile f32-grade kernel)
+    const bool sm_big = bf16_gemm && gemm_x3_on && gemm_bf16_big(R, Cn) && gemm_bf16_big((int)N, sm_ni);
+    int ns = sm_big ? pick_split(R, Cn, 1, GB2_BT) : pick_split(R, Cn);
+    // W.d depends on nothing the backward recurrence produces: when the top layer's backward runs as the fused launch
+    // (lstm_bwd_dw.h) its slabs are items of THAT launch -- they execute on the idle half of the chip during the ~14 us
+    // before the recurrence's first chunk is released -- and only x.d stays in front of the recurrence.
+    // (only while the recurrence leaves CUs idle: with 256 lines the same items cost the fused launch +42 us for 19 saved)
+    dwx_active = dw_x3 && backward_family(top) == BwdFamily::Overlapped && (long long)bs * ndir * 4 <= 3LL * device_cu_count();
+    if (dwx_active) { build_dwx_table(); ns = dwx_nslabs; }
+    partial_sm.reserve((size_t)ns * R * Cn);
+    // W.d (split-K slabs) and x.d in ONE launch: two small independent products, each mostly prologue and
+    // epilogue latency on its own (13.9 + 12.4 us back to back)
+    const GemmOperand Wk = gemm_kc(W1 + nc, nc, sm_ni, 0);
+    const StorePartial wd_store{partial_sm.p, R, Cn};
+    const StorePlain xd_store{top.dH.p, sm_ni};
+    timing.begin("gemm_softmax_dw_dx", s);
+    if (dwx_active) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, split_terms);
+    else if (sm_big) {
+      gemm_x3_big<GEMM_MC, GEMM_MC>(s, gemm_mc(top.srow(), top.ldh, N, 32), gemm_mc(Dz.p, nc, N, 32), wd_store, R, Cn, (int)N, ns);
+      gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N, 32), Wk, xd_store, (int)N, sm_ni, nc);
+    } else {
+      const GemmProblem wd = gemm_problem(gemm_mc(top.srow(), top.ldh, N), gemm_mc(Dz.p, nc, N), R, Cn, (int)N, ns);
+      const GemmProblem xd = gemm_problem(gemm_kc(Dz.p, nc, N), Wk, (int)N, sm_ni, nc);
+      if (gemm_x3_on) gemm_x3_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store, split_terms);
+      else gemm_f32_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store);
+    }
+    timing.end(s);
+    // the slabs are reduced together with the top layer's weight-gradient slabs (backward_weight_gradient)
+    sm_red = ReduceDesc{partial_sm.p, nullptr, (long long)sm_off, ns, 1, R, Cn, nc};
+    check_launch();
+  }
+  // the backward recurrence of layer l in the family backward_family named; returns whether it ran as a persistent lock-step kernel
+  bool backward_recurrence(int l, BwdFamily fam) {
+    Layer& y = L[l];
+    hipStream_t s = stream();
+    const LstmSeqArgs a = seq_args(y, false);   // (no progress words: backward_layer_overlapped sets them in its copy)
+    if (fam == BwdFamily::Overlapped) {   // the recurrence and the weight-gradient GEMM run side by side (gemm_dw.h)
+      backward_layer_overlapped(y, a, 1 + y.ni + y.no, 4 * y.no);
+      return false;
+    }
+    timing.begin("lstm_bwd", s);
+    WideRan ran = WideRan::Nothing;
+    int skipped_d = 0;
+    if (fam == BwdFamily::Wide) {
+      const LstmWideArgs w = wide_args(y, false);
+      ran = launch_lstm_wide(false, w, tmax, coop_sync, step_graphs, s, bf16_rec, 0, rec_x3());
+      skipped_d = w.skip_d;
+    } else launch_bwd_narrow(y, a, s);
+    timing.end(s);
+    const bool persistent = ran == WideRan::Persistent;
+    y.d_f32_valid = !(persistent && bf16_rec && skipped_d);
+    if (persistent) g_path_count[PC_BWD_PERSISTENT]++;
+    return persistent;
+  }
+  BwdPlan backward_plan(const Layer& y, BwdFamily fam, bool bwd_persistent) const {
+    const int R = 1 + y.ni + y.no, Cn = 4 * y.no;
+    BwdPlan p{};
+    p.family = fam; p.bwd_persistent = bwd_persistent;
+    p.dw_from_bf16 = bf16_gemm && bf16_rec && bwd_persistent && y.sbf_ready && y.Dbf.p && gemm_bf16_big(R, Cn);
+    p.dw_rows = p.dw_from_bf16 ? dw_bf16_rows(y, R, Cn) : R;
+    p.dw_bias_out = p.dw_rows < R;
+    REQUIRE(!p.dw_bias_out || y.dbias.p, "internal: bias row left out of the weight-gradient product without the recurrence's per-line sums");
+    // exact-f32 mode, wide layer: the backward products as f32-grade bf16 x 3 on 128 x 128 tiles (gemm_x3_128_kernel) -- what
+    // narrow layers already do inside their fused backward launch; gemm_x3=0 (CLSTM_DEBUG) / clstm_net_set_strict_f32: the f32 MFMA
+    p.x3_big = !bf16_gemm && y.wide && gemm_x3_on && gemm_bf16_big(R, Cn);
+    p.ns = fam == BwdFamily::Overlapped ? dw_slabs_per_dir
+           : p.dw_bias_out && gemm_tile256(p.dw_rows, Cn) ? pick_split_mc(p.dw_rows, Cn, ndir)
+           : p.dw_from_bf16 && gemm_tile256(R, Cn) ? pick_split_mc(R, Cn, ndir)
+           : (bf16_gemm || p.x3_big) && gemm_bf16_big(R, Cn) ? pick_split(R, Cn, ndir, GB2_BT) : pick_split(R, Cn, ndir);
+    return p;
+  }
+  // W.d += delta [1; x_t; h_{t-1}]^T for the four gates of each direction (both directions in one batched launch: half the slabs per
+  // direction fill the chip) unless the recurrence launch's items have left the slabs already (Overlapped), and the slab reduction: queued
+  // in a stacked net (see reduce_layer), launched here, in this step's bracket, for a single layer.  true: x.d rode the launch (gemm_dw_dx).
+  bool backward_weight_gradient(int l, const BwdPlan& p, const ReduceTarget& rt) {
+    Layer& y = L[l];
+    hipStream_t s = stream();
+    const int M = ndir * 4 * y.no, R = 1 + y.ni + y.no, Cn = 4 * y.no;
+    const bool product = p.family != BwdFamily::Overlapped, stacked = L.size() > 1;
+    DevBuf<float>& pbuf = layer_partial(y);
+    // the bracket of this step: a product family reports its GEMM -- and, in a single-layer net, the reduction behind it -- as
+    // "gemm_gates_dw"; a single overlapped layer reports its reduction as "reduce_scatter"; a stacked overlapped layer launches
+    // nothing here (its reduction is queued) and opens none
+    const char* const bracket = product ? "gemm_gates_dw" : stacked ? nullptr : "reduce_scatter";
+    if (bracket) timing.begin(bracket, s);
+    bool dx_done = false;
+    if (product) {
+      pbuf.reserve((size_t)ndir * p.ns * R * Cn);
+      const GemmOperand src = gemm_batched(gemm_mc(y.S.p, y.lds, N), (long long)N * y.lds, ndir);
+      const GemmOperand dlt = gemm_batched(gemm_mc(y.D.p, M, N, 0), 4LL * y.no, 1);
+      const StorePartial store{pbuf.p, R, Cn};
+      if (p.dw_from_bf16) dx_done = backward_dw_bf16(l, p, pbuf.p);
+      else if (bf16_gemm) gemm_bf16<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
+      else if (p.x3_big) gemm_x3_big<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
+      else gemm_f32<GEMM_MC, GEMM_MC, StorePartial, GEMM_BK_DW>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
+    }
+    const ReduceDesc gates{pbuf.p, y.moff, 0LL, p.ns, ndir, R, Cn, y.no};
+    const ReduceDesc extra = l == (int)L.size() - 1 ? sm_red : ReduceDesc{};   // the softmax layer's slabs ride the top layer's
+    if (stacked) pending_red.push_back(PendingReduce{gates, extra});
+    else reduce_layer(gates, extra, true, rt);
+    if (bracket) timing.end(s);
+    check_launch();
+    return dx_done;
+  }
+  // ... from both operands in bf16 as their producers left them (deltas: the persistent backward recurrence; sources: the forward
+  // pass), transposed by the LDS on the way into the MFMA.  true: the layer's input deltas were computed by the same launch.
+  bool backward_dw_bf16(int l, const BwdPlan& p, float* slabs) {
+    Layer& y = L[l];
+    hipStream_t s = stream();
+    const int M = ndir * 4 * y.no, R = 1 + y.ni + y.no, Cn = 4 * y.no, ldsb = y.ni + y.no + 8;
+    g_path_count[PC_DW_FROM_BF16]++;
+    const GemmOperand16B src{y.Sbf.p, ldsb, (long long)N * ndir * ldsb, (long long)N * ldsb}, dlt{y.Dbf.p, M, (long long)N * M, 4LL * y.no};
+    const GemmOperand16B a2 = y.sbf_x_external ? GemmOperand16B{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni, 0} : GemmOperand16B{nullptr, 0, 0, 0};
+    const int a2_rows = y.sbf_x_external ? y.ni : 0;
+    bool dx_done = false;
+    if (!p.dw_bias_out) gemm_b16mc(s, src, dlt, StorePartialRot{slabs, R, Cn}, R, Cn, (int)N, p.ns, ndir, a2, a2_rows);
+    else {
+      // The bias row W.d[:,0] += sum_b y.d (clstm_compute.cc:301) is not a row of this product: 1 + ni + no rows are one more than a
+      // whole number of row panels at both configs[4] layers (1537 = 6 x 256 + 1: a seventh panel, 14 % of the product, for one row;
+      // 577 = 3 x 192 + 1) -- the persistent backward recurrence sums the deltas of a line while it produces them (LstmWideArgs::
+      // dbias) and k_bias_rows lays the sum over lines into row 0 of the first slab.  Where the layer also owes input deltas from the
+      // same bf16 delta array, BOTH products as one launch (gemm_bf16.h:gemm_dw_dx_kernel: apart, each leaves a quarter of the chip idle)
+      const StorePartialShift store{slabs, R, Cn};
+      float* const dxp = l > 0 ? L[l - 1].dH.p : nullptr;
+      dx_done = dxp && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p &&
+                gemm_dw_dx(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows, GemmOperand16{y.Dbf.p, M, (long long)N * M},
+                           GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dxp, y.ni}, (int)N, y.ni, M);
+      if (!dx_done) gemm_b16mc(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows);
+      CLSTM_LAUNCH(k_bias_rows, dim3((unsigned)(((size_t)ndir * Cn + 63) / 64)), dim3(64), 0, s, (const float*)y.dbias.p, slabs, bs, ndir, p.ns, R, Cn);
+      g_path_count[PC_DW_BIAS_OUT]++;
+      if (dx_done) { g_path_count[PC_DX_FROM_BF16]++; g_path_count[PC_DW_DX_ONE_LAUNCH]++; }
+    }
+    if (y.sbf_x_external) g_path_count[PC_DW_X_EXTERNAL]++;
+    return dx_done;
+  }
+  // input deltas: x.d = sum_dir W_x^T delta (Parallel::backward sums both subs, clstm.cc:538-541)
+  void backward_input_deltas(int l, const BwdPlan& p) {
+    Layer& y = L[l];
+    hipStream_t s = stream();
+    const int M = ndir * 4 * y.no;
+    if (l == 0 && want_dx0) dX0.reserve((size_t)N * y.ni);
+    float* const dx = l > 0 ? L[l - 1].dH.p : want_dx0 ? dX0.p : nullptr;   // the layer below's output deltas, or what the caller asked for
+    if (!dx) return;
+    timing.begin("gemm_gates_dx", s);
+    if (bf16_gemm && bf16_rec && p.bwd_persistent && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p && y.Dbf.p) {
+      // the persistent recurrence left the deltas as a k-contiguous bf16 array: both operands go to LDS as they are
+      g_path_count[PC_DX_FROM_BF16]++;
+      gemm_b16kk(s, GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    } else if (ensure_delta_f32(l), bf16_gemm)
+      gemm_bf16<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    else if (y.wide && gemm_x3_on && gemm_bf16_big((int)N, y.ni))
+      gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    else
+      gemm_f32<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N), gemm_kc(y.Wt, M, y.ni, 0), StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    timing.end(s);
+    check_launch();
   }
   // The slab reduction of one layer (+ the softmax layer's, riding the top layer's).  `last`: the last reduction launch of the
   // backward pass.  With the update riding the reductions (fuse: train_step without an exchange), ALL of them must see the final
@@ -1406,7 +1411,7 @@ struct Net {
   // would leave half a step applied -- so a stacked net keeps a slab buffer per layer (Layer::partial) and reduces every layer here,
   // behind the LAST recurrence; a single layer is reduced where it always was.  (What a reduction itself can still find is a
   // non-finite gradient ENTRY: skipped entry by entry, ops.h:k_update.)
-  struct PendingReduce { ReduceDesc gates, extra; int l; };
+  struct PendingReduce { ReduceDesc gates, extra; };
   std::vector<PendingReduce> pending_red;
   // ---- the NEXT minibatch's ingest behind this step's last reduction (abi.inc: clstm_net_train_step_next; ops.h: IngestTail) ----
   // defer_last_reduce (set by the caller around backward()): the last reduction launch of a fused-update step is described here
@@ -1424,7 +1429,7 @@ struct Net {
       t.nb_main = nb;
       const int ntrail = (t.lo_src ? 1 : 0) + (t.aux_src ? (t.aux_n + 255) / 256 : 0);
       CLSTM_LAUNCH(k_reduce_scatter_ingest, dim3(nb + t.nbi + ntrail), dim3(256), 0, deferred.q, deferred.gates, deferred.extra, deferred.gdst, (int*)nullptr, 0, deferred.uf, t);
-      g_path_count[19]++;
+      g_path_count[PC_INGEST_TAIL]++;
     } else {
       CLSTM_LAUNCH(k_reduce_scatter, dim3(nb), dim3(256), 0, deferred.q, deferred.gates, deferred.extra, deferred.gdst, (int*)nullptr, 0, deferred.uf);
     }
@@ -1452,11 +1457,12 @@ struct Net {
     }
   } next;
   DevBuf<float>& layer_partial(Layer& y) { return L.size() > 1 ? y.partial : partial; }
-  void reduce_layer(const ReduceDesc& gates, const ReduceDesc& extra, int l, bool last, bool fuse, bool peer, float* gdst, hipStream_t q) {
+  void reduce_layer(const ReduceDesc& gates, const ReduceDesc& extra, bool last, const ReduceTarget& rt) {
+    hipStream_t q = stream();
     const size_t work = (size_t)gates.nbatch * gates.R * gates.Cn + (size_t)extra.R * extra.Cn * extra.nbatch;
     UpdateFuse uf{};
     uf.nanflag = nanflag(); uf.step_no = step_no();
-    if (fuse) {   // (train_step without a communicator) this layer's parameters are updated by the reduction itself
+    if (rt.fuse) {   // (train_step without a communicator) this layer's parameters are updated by the reduction itself
       uf = UpdateFuse{v, d, lr, mom, gclip, (const int*)dev_err_words(), last ? update_step_word : nullptr, update_step_id, nanflag(), step_no(), PackDst{}};
       if (last) { update_step_word = nullptr; update_applied = true; }
       // a single narrow layer whose packed copies are current: the update keeps them current (ops.h: PackDst) and the next
@@ -1467,16 +1473,15 @@ struct Net {
         const size_t nr = (size_t)ndir * 4 * 4 * y.nk4 * y.nthreads;
         uf.pk = PackDst{y.pack_inv.p, PACK_KD, y.Wt, y.bias, y.Rf, y.Rb, y.pd, pack_fused_desc(y), (unsigned)((size_t)(1 + y.ni) * ndir * 4 * y.no), (unsigned)nr};
         packs_follow_update = true;
-        g_path_count[10]++;
+        g_path_count[PC_PACKS_FOLLOW_UPDATE]++;
       }
     }
-    if (defer_last_reduce && last && fuse) {   // enqueued by launch_deferred_reduce, the next minibatch's ingest behind it
-      deferred.armed = true; deferred.gates = gates; deferred.extra = extra; deferred.gdst = gdst; deferred.uf = uf; deferred.work = work; deferred.q = q;
+    if (defer_last_reduce && last && rt.fuse) {   // enqueued by launch_deferred_reduce, the next minibatch's ingest behind it
+      deferred.armed = true; deferred.gates = gates; deferred.extra = extra; deferred.gdst = rt.gdst; deferred.uf = uf; deferred.work = work; deferred.q = q;
       return;
     }
-    CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks(work)), dim3(256), 0, q, gates, extra, gdst, (int*)nullptr, 0, uf);
-    if (peer && last) peer_pending = true;
-    (void)l;
+    CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks(work)), dim3(256), 0, q, gates, extra, rt.gdst, (int*)nullptr, 0, uf);
+    if (rt.peer && last) peer_pending = true;
   }
 
   long long nbackward = 0;           // backward passes of this net so far = the number of the current training step (from 1)
@@ -1526,8 +1531,8 @@ struct Net {
       update_step_word = nullptr;
       timing.end(s);
       check_launch();
-      g_path_count[7]++;
-      if (two) g_path_count[24]++;
+      g_path_count[PC_PEER_EXCHANGE]++;
+      if (two) g_path_count[PC_PEER_TWO_PHASE]++;
       packed_dirty = true;
       maybe_replica_check(s);
       return;
@@ -1569,7 +1574,7 @@ struct Net {
     comm->allreduce(comm->chk.p + 4, 4, s, true);   // (four floats: one-shot whatever the rule says)
     CLSTM_LAUNCH(k_replica_verify, dim3(1), dim3(64), 0, s, (const float*)comm->chk.p, comm->nranks, dev_err_words() + 7, step_no());
     check_launch();
-    g_path_count[12]++;
+    g_path_count[PC_REPLICA_CHECK]++;
   }
 };
 

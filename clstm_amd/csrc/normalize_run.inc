@@ -167,6 +167,6 @@ struct Normalizer {
     }
     last_frames = (size_t)fo;
     *frames_d = frames.p;
-    g_path_count[25] += bs;
+    g_path_count[PC_NORMALIZED] += bs;
   }
 };

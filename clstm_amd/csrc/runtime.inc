@@ -137,7 +137,15 @@ struct StoreBias {  // out[r*ld + c] = val + bias[c]
     *reinterpret_cast<f32x4*>(out + (long long)r * ld + c) = o;
   }
 };
-static long long g_path_count[26];   // clstm_debug_path_count (diagnostics)
+// clstm_debug_path_count (diagnostics): the numbers are ABI -- tests and scripts pass them as integers, include/clstm_abi.h explains each
+enum PathCounter {
+  PC_FWD_PERSISTENT = 0, PC_BWD_PERSISTENT = 1, PC_WX_FROM_BF16 = 2, PC_DX_FROM_BF16 = 3, PC_DW_FROM_BF16 = 4, PC_FWD_FUSED = 5,
+  PC_FWD_FUSED_WX = 6, PC_PEER_EXCHANGE = 7, PC_DW_X_EXTERNAL = 8, PC_BWD_C32 = 9, PC_PACKS_FOLLOW_UPDATE = 10, PC_BWD_X3 = 11,
+  PC_REPLICA_CHECK = 12, PC_DW_BIAS_OUT = 13, PC_DW_DX_ONE_LAUNCH = 14, PC_MFMA_NOSAVE = 15, PC_MFMA_FWD = 16, PC_MFMA_BWD = 17,
+  PC_MFMA_BWD_DW = 18, PC_INGEST_TAIL = 19, PC_INGEST_TAIL_USED = 20, PC_MFMA_ROUTED = 21 /* counted on the device */,
+  PC_LINE_NOSAVE = 22, PC_FUSED_NOSAVE = 23, PC_PEER_TWO_PHASE = 24, PC_NORMALIZED = 25, PC_COUNT
+};
+static long long g_path_count[PC_COUNT];
 struct StorePlain {
   float* out; long long ld;
   DEVMFN void operator()(int r, int c, float v, int) const { out[(long long)r * ld + c] = v; }
@@ -418,16 +426,15 @@ static void check_device_errors() {
   throw Error("fused backward launch: " + std::to_string(w[1]) + " weight-gradient item(s) gave up waiting for the recurrence (watchdog); the "
               "minibatches since then were NOT applied -- set CLSTM_OVERLAP=0");
 }
-static bool g_wide_persistent = false;   // the last launch_lstm_wide call ran the persistent per-XCD kernels
 static int g_debug_fail_claims = 0;      // tests: this many upcoming persistent launches fail their placement check ...
 static int g_debug_fail_skip = 0;        // ... after this many that do not
 
-// fx_ngx > 0 (forward, bf16): try ONLY the persistent kernel with the input projection folded in (lstm_xcd_fwd_bf16_fx<fx_ngx>);
-// returns false -- nothing launched or nothing written -- if it does not apply or its placement check failed: the caller then
-// runs the hoisted product and calls again with fx_ngx = 0.
+// What launch_lstm_wide ran: persistent per-XCD kernels or a launch per step.  Nothing only with fx_ngx > 0 (forward, bf16): ONLY the
+// persistent kernel with the input projection folded in (lstm_xcd_fwd_bf16_fx<fx_ngx>) is tried, and if it does not apply or its placement
+// check failed nothing was launched or nothing written: the caller then runs the hoisted product and calls again with fx_ngx = 0.
+enum class WideRan { Nothing, Steps, Persistent };
 static std::map<const void*, int> g_stamp_base;   // per sync buffer: where the group-barrier stamps of its next persistent launch start
-static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sync, StepGraphCache& graphs, hipStream_t s, bool bf16 = false, int fx_ngx = 0, bool x3 = false) {
-  g_wide_persistent = false;
+static WideRan launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sync, StepGraphCache& graphs, hipStream_t s, bool bf16 = false, int fx_ngx = 0, bool x3 = false) {
   REQUIRE((double)a.N * a.ndir * 4 * a.no * 4 < 2147483000.0,
           "minibatch too large for the lock-step recurrence (frames x 4 x nhidden x ndir x 4 B must stay below 2 GiB)");
   const int no = a.no, ncu = device_cu_count();
@@ -480,7 +487,7 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
       ok = g_xcd_outcome.after_launch(sync.p + XcdSyncLayout::LAST_ERROR, s);
       REQUIRE(ok || zb0 == 0, "persistent recurrence: placement failed after the first chunk had run; set CLSTM_XCD_REC=0");
     }
-    if (ok) g_wide_persistent = true; else g_xcd_failed = true;
+    if (!ok) g_xcd_failed = true;
     return ok;
   };
   // (the persistent bf16 kernels address their per-frame arrays through 32-bit buffer offsets: G / C / D / Dbf are covered by the check
@@ -490,16 +497,15 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
                                (a.skip_s || (double)a.ndir * a.N * a.lds * 4 < 2147483000.0) && (double)a.N * a.ldh * 4 < 2147483000.0);
   const bool fits = xcd_on && !g_xcd_failed && off32 && tmax > 1 && ntile <= 32 && 8 * ntile <= std::max(ncu, 16);
   if (fx_ngx > 0) {
-    if (!(fwd && bf16 && fits && mt == 1 && a.kp16 <= 512 && (no & 3) == 0 && a.x_ni <= 128 * fx_ngx && a.x_ni <= 2048)) return false;
-    const size_t smem = (size_t)xcd_fwd_lds_bytes(1);
-    return fx_ngx == 1 ? persistent(lstm_xcd_fwd_bf16_fx<1>, smem) : fx_ngx == 4 ? persistent(lstm_xcd_fwd_bf16_fx<4>, smem)
-         : fx_ngx == 8 ? persistent(lstm_xcd_fwd_bf16_fx<8>, smem) : false;
+    if (!(fwd && bf16 && fits && mt == 1 && a.kp16 <= 512 && (no & 3) == 0 && a.x_ni <= 128 * fx_ngx && a.x_ni <= 2048)) return WideRan::Nothing;
+    auto fx = [&](auto kernel) { return persistent(kernel, (size_t)xcd_fwd_lds_bytes(1)) ? WideRan::Persistent : WideRan::Nothing; };
+    return fx_ngx == 1 ? fx(lstm_xcd_fwd_bf16_fx<1>) : fx_ngx == 4 ? fx(lstm_xcd_fwd_bf16_fx<4>) : fx_ngx == 8 ? fx(lstm_xcd_fwd_bf16_fx<8>) : WideRan::Nothing;
   }
   if (fwd) {
-    if (fits && !bf16 && (size_t)xcd_fwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_fwd_f32, (size_t)xcd_fwd_f32_lds_bytes(a.kp))) return true;
+    if (fits && !bf16 && (size_t)xcd_fwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_fwd_f32, (size_t)xcd_fwd_f32_lds_bytes(a.kp))) return WideRan::Persistent;
     if (fits && bf16 && a.kp16 <= 512 &&
         (mt == 4 ? persistent(lstm_xcd_fwd_bf16<4>, (size_t)xcd_fwd_lds_bytes(4))
-         : mt == 2 ? persistent(lstm_xcd_fwd_bf16<2>, (size_t)xcd_fwd_lds_bytes(2)) : persistent(lstm_xcd_fwd_bf16<1>, (size_t)xcd_fwd_lds_bytes(1)))) return true;
+         : mt == 2 ? persistent(lstm_xcd_fwd_bf16<2>, (size_t)xcd_fwd_lds_bytes(2)) : persistent(lstm_xcd_fwd_bf16<1>, (size_t)xcd_fwd_lds_bytes(1)))) return WideRan::Persistent;
     const int mts = a.bs > 32 ? 4 : a.bs > 16 ? 2 : 1;
     const dim3 grid((no + 3) / 4, a.ndir, (a.bs + 16 * mts - 1) / (16 * mts));
     const dim3 grid16(ntile * a.ndir * nzb16);
@@ -515,9 +521,9 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
     });
   } else {
     if (fits && !bf16 && x3 && a.Rw16 && a.kp16 <= 2048) {
-      if (persistent(lstm_xcd_bwd_x3, (size_t)xcd_bwd_lds_bytes(1))) { g_path_count[11]++; return true; }
+      if (persistent(lstm_xcd_bwd_x3, (size_t)xcd_bwd_lds_bytes(1))) { g_path_count[PC_BWD_X3]++; return WideRan::Persistent; }
     } else
-    if (fits && !bf16 && (size_t)xcd_bwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_bwd_f32, (size_t)xcd_bwd_f32_lds_bytes(a.kp))) return true;
+    if (fits && !bf16 && (size_t)xcd_bwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_bwd_f32, (size_t)xcd_bwd_f32_lds_bytes(a.kp))) return WideRan::Persistent;
     // 32 cells per workgroup, two groups per XCD, groups of 8 / 16 / 32 lines (lstm_wide.h:lstm_xcd_bwd_bf16_c32): half the
     // delta block per step and CU of the 16-cell kernel below, which stays for hidden sizes that are not multiples of 32
     const bool c32_on = dbg_opt("bwd_c32") != 0;   // (read per pass: tests compare both kernels in one process)
@@ -530,13 +536,13 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
       auto go = [&](auto k_full, auto k_any) { return fullk ? persistent(k_full, smem, WIDE_THREADS, ng, per) : persistent(k_any, smem, WIDE_THREADS, ng, per); };
       if (ept == 1 ? go(lstm_xcd_bwd_bf16_c32<1, true>, lstm_xcd_bwd_bf16_c32<1, false>)
           : ept == 2 ? go(lstm_xcd_bwd_bf16_c32<2, true>, lstm_xcd_bwd_bf16_c32<2, false>) : go(lstm_xcd_bwd_bf16_c32<4, true>, lstm_xcd_bwd_bf16_c32<4, false>)) {
-        g_path_count[9]++;
-        return true;
+        g_path_count[PC_BWD_C32]++;
+        return WideRan::Persistent;
       }
     } else
     if (fits && bf16 && a.kp16 <= 2048 &&
         (mt == 4 ? persistent(lstm_xcd_bwd_bf16<4>, (size_t)xcd_bwd_lds_bytes(4))
-         : mt == 2 ? persistent(lstm_xcd_bwd_bf16<2>, (size_t)xcd_bwd_lds_bytes(2)) : persistent(lstm_xcd_bwd_bf16<1>, (size_t)xcd_bwd_lds_bytes(1)))) return true;
+         : mt == 2 ? persistent(lstm_xcd_bwd_bf16<2>, (size_t)xcd_bwd_lds_bytes(2)) : persistent(lstm_xcd_bwd_bf16<1>, (size_t)xcd_bwd_lds_bytes(1)))) return WideRan::Persistent;
     const dim3 grid(ntile, a.ndir, nzb16);
     const dim3 grid16(ntile * a.ndir * nzb16);
     launch_steps(graphs, bf16 ? 3 : 1, a, tmax, s, [&]() {
@@ -549,7 +555,19 @@ static bool launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sy
     });
   }
   check_launch();
-  return true;
+  return WideRan::Steps;
+}
+// diagnostics (CLSTM_FW_TRACE / CLSTM_DW_TRACE): the stamp rows a launch left on the device, four per line, under the caller's header
+template <class... A>
+static void dump_trace(const char* path, const long long* rows_d, size_t rows, hipStream_t s, const char* header_fmt, A... header_args) {
+  HIPCHECK(hipStreamSynchronize(s));
+  std::vector<long long> t(rows * 4);
+  HIPCHECK(hipMemcpy(t.data(), rows_d, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  FILE* f = fopen(path, "w");
+  if (!f) return;
+  fprintf(f, header_fmt, header_args...);
+  for (size_t i = 0; i < rows; i++) fprintf(f, "%lld %lld %lld %lld\n", t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
+  fclose(f);
 }
 
 // ---- per-kernel device timing (bench.py roofline) ---------------------------------------------
@@ -598,7 +616,6 @@ struct Timing {
   void collect(hipStream_t) {}
 };
 #endif
-
 
 // ---- roctx ranges (SURVEY 5: a rocprofv3 --marker-trace of a drop-in run should read ingest / forward / ctc / backward /
 // allreduce / update) ----------------------------------------------------------------------------------------------------

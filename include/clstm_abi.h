@@ -391,16 +391,28 @@ int clstm_debug_lane_ops(float* out);
  * [6..15] sub-phase stamps of the short-line path (see scripts/gpu_ctcprof.py) */
 int clstm_debug_ctc_cycles(long long* out_h);
 int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, int Cn, int K, int nsplit);
-/* how often this process has taken an optional fast path (HOST out): which = 0 persistent per-XCD forward recurrence,
- * 1 persistent backward recurrence, 2 W_x.x from the lower layer's bf16 outputs, 3 x.d from the bf16 delta array,
- * 4 weight-gradient product from contraction-major bf16 operands (LDS transpose reads), 5 the forward half as one
- * launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h), 16 / 17 / 18 the recurrences batched over 16 lines on the
- * MFMA (forward launch, backward launch, backward as one launch with the weight-gradient items), 22 / 23 / 15 the no-save forward
- * passes of clstm_net_predict (per-line recurrence launches, fused forward launches, batched MFMA launches; the training counters 5 /
- * 16 do not move for them), 7 training steps whose gradient exchange was the peer-read all-reduce fused with the update (either
- * form), 24 those of them that took the two-phase form, 25 lines normalised on the device (clstm_normalizer_run_*), 21 minibatches whose forward pass the
- * batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255]; blocking).  Tests use it to make sure the
- * path they mean to cover is the one that ran. */
+/* how often this process has taken an optional fast path (HOST out).  The numbers are fixed (csrc/runtime.inc: enum PathCounter); which =
+ *  0 / 1  persistent per-XCD forward / backward recurrence passes of a wide layer;
+ *  2  W_x.x from bf16 operands (the lower layer's bf16 outputs, or a bf16 copy of the input frames);  3  x.d from the bf16 delta array;
+ *  4  weight-gradient products from contraction-major bf16 operands (LDS transpose reads);  8  those of them that read their x rows from
+ *     the layer below's bf16 outputs instead of a copy;  13  those that left the bias row to the recurrence's per-line sums;  14  those
+ *     that computed the layer's x.d in the same launch (3 moves with it);
+ *  5  the forward half as one launch (W_x producers + recurrence + softmax consumers, lstm_fwd_fused.h);
+ *  6  persistent forward recurrences with the input projection folded in;
+ *  9  persistent bf16 backward recurrences on the 32-cells-per-workgroup kernel;  11  persistent f32-grade (bf16 x 3) backward recurrences;
+ *  10  fused updates that kept the packed parameter copies of a single narrow layer current;
+ *  16 / 17 / 18  the recurrences batched over 16 lines on the MFMA (forward launch, backward launch, backward as one launch with the
+ *     weight-gradient items: 17 moves with 18);
+ *  22 / 23 / 15  the no-save forward passes of clstm_net_predict (per-line recurrence launches, fused forward launches, batched MFMA
+ *     launches; the training counters 5 / 16 do not move for them);
+ *  19  steps whose last reduction carried the next minibatch's ingest (clstm_net_train_step_next);  20  calls that found their minibatch
+ *     declared by such a step;
+ *  7  training steps whose gradient exchange was the peer-read all-reduce fused with the update (either form);  24  those of them that
+ *     took the two-phase form;  12  replica consistency checks enqueued;
+ *  25  lines normalised on the device (clstm_normalizer_run_*);
+ *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
+ *     counted on the device: blocking).
+ * Tests use it to make sure the path they mean to cover is the one that ran. */
 int clstm_debug_path_count(int which, long long* out_h);
 /* Experiment switches of the library (clstm_amd/csrc/dbgopt.h: the table of names and defaults, e.g. "gemm_stag", "bwd_c32",
  * "rec_x3", "pack_tiles"): tests compare the two sides bit for bit within one process.  A name not in the table is an error.
