@@ -27,6 +27,16 @@ struct DwSlab {
   int pad[3];
 };
 
+// The softmax layer's x.d = z.d . W as a PROLOGUE of the recurrence role (lstm_xd_prologue.h): workgroup (line, direction) computes
+// the rows of its own line and the columns of its own direction -- the only part of the top layer's dH it ever reads -- in front
+// of its first step.  A.p == nullptr: the product was a launch of its own (gemm_x3), dH is complete.
+struct XdArgs {
+  GemmOperand A;            // z.d, gemm_kc(Dz, nc, N): rows = frames
+  GemmOperand B;            // gemm_kc(W1 + nc, nc, sm_ni, 0): rows = columns of the softmax layer's input
+  float* out; int ld;       // the top layer's dH [frame][ld], ld = ndir * no
+  int K;                    // classes (contraction length), <= XD_MAX_K
+};
+
 struct GemmDwArgs {
   const float* S; long long sdir; int lds; long long s_elems;   // A: S[dir][frame][col]
   const float* D; int M; int no4; long long d_elems;            // B: D[frame][dir*no4 + c]  (written concurrently: system-scope loads)
@@ -57,6 +67,7 @@ struct GemmDwArgs {
   float* xpartial; int xR, xCn; unsigned xgx, xgy;
   int x3;                   // 1: products on the bf16 MFMA with both operands split into bf16 terms (gemm_dw_item_x3), 0: f32 MFMA
   int terms;                // x3: 3 = hi + mid + lo, six products, operand-exact (default); 2 = hi + lo, three products
+  XdArgs xd;                // fused launch, top layer: the recurrence role's x.d prologue (x3 only)
 };
 
 // blocks of the x3 item in flight in registers (6 and 8 were measured: the fused launch then needs > 168 registers,

@@ -11,6 +11,7 @@
 #pragma once
 #include "gemm_dw.h"
 #include "lstm_seq.h"
+#include "lstm_xd_prologue.h"
 
 namespace clstm {
 
@@ -19,6 +20,7 @@ namespace clstm {
 // it (three interleaved runs, 0.2866 vs 0.2861 ms)
 constexpr int DW_FUSED_STAB_ENTRIES = 1024;
 static_assert(DW_FUSED_STAB_ENTRIES >= DW_STAB_MAX, "the items' k-tile table fits");
+static_assert(xd_smem_floats(2) <= dw_img_floats(2) && xd_smem_floats(3) <= dw_img_floats(3), "the recurrence role's x.d prologue stages in the items' carve");
 
 // NT: the weight-gradient items' arithmetic (gemm_dw_body): 0 f32 MFMA, 2 / 3 bf16 terms per operand
 template <int NK4, int KU, int NT>
@@ -30,7 +32,13 @@ __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_bwd_dw
 #endif
     const long long t0 = g.trace ? wall_clock() : 0;
     const int bl = (int)blockIdx.x % a.bs;
-    lstm_bwd_body<NK4, KU>(a, a.order ? a.order[bl] : bl, (int)blockIdx.x / a.bs);
+    const int b = a.order ? a.order[bl] : bl, dir = (int)blockIdx.x / a.bs;
+    // top layer: the workgroup first computes its own slice of dH (the recurrence role has no other use for gsm); this sits in
+    // front of the body's recurrent-weight loads, so the two register populations are never live together
+    if constexpr (NT >= 2) {
+      if (g.xd.A.p) xd_prologue<NT, xd_maxu(NK4)>(gsm, g.xd, a.line_off, b, dir, a.no);
+    }
+    lstm_bwd_body<NK4, KU>(a, b, dir);
     if (g.done && threadIdx.x == 0) atomic_add_i32(g.done, 1);   // (the body ended with drain + barrier: this line's deltas are in memory)
     if (g.trace && threadIdx.x == 0) { g.trace[blockIdx.x * 4] = t0; g.trace[blockIdx.x * 4 + 2] = wall_clock(); }
   } else {

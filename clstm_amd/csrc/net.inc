@@ -687,7 +687,12 @@ struct Net {
   }
 #endif
   // the narrow layer's backward recurrence: batched over lines on the MFMA where that pays, else one workgroup per line
-  void launch_bwd_narrow(Layer& y, const LstmSeqArgs& a, hipStream_t s) {
+  // xd: the softmax layer's x.d as the prologue of every workgroup (top layer, xd_in_launch)
+  void launch_bwd_narrow(Layer& y, const LstmSeqArgs& a, hipStream_t s, const XdArgs* xd = nullptr) {
+    if (xd) {
+      REQUIRE(launch_lstm_bwd_xd(y.nk4, y.pd.ku, a, *xd, split_terms, bs, y.nthreads, s), "internal: no per-line backward instantiation");
+      return;
+    }
 #ifndef CLSTM_HIP_EMU
     if (mfma_bwd_eligible(y)) {
       if (y.no == 64) launch_mfma_bwd_no<64>(y, a, s);
@@ -1030,6 +1035,27 @@ struct Net {
     if (!bf16_gemm && overlap_eligible(y)) return BwdFamily::Overlapped;
     return y.wide ? BwdFamily::Wide : BwdFamily::Narrow;
   }
+  // Does the top layer's backward launch compute the softmax layer's x.d itself (lstm_xd_prologue.h)?  backward_softmax (which
+  // then launches nothing) and backward_layer_overlapped (which hands the prologue its operands) both ask here.  All of:
+  //  * dwx_active -- this pass's condition for the lone x.d launch: top layer Overlapped, dw_x3, bs * ndir * 4 <= 3 * CUs;
+  //  * the per-line recurrence kernel runs it (fused launch or, below four waves / on the host emulator, the two-launch form):
+  //    the batched-MFMA backward recurrence keeps the separate launch;
+  //  * the split is two or three bf16 terms (dw_x3 says so: the launch rounds split_terms to one of the two, as gemm_x3 does);
+  //  * nc <= XD_MAX_K = 96: three k-blocks of W fragments (3 x NT x 4 VGPRs) stay in registers for the whole prologue, and three
+  //    blocks are what the launch it replaces runs for such nc, zero blocks included (bit-identity);
+  //  * experiment option xd_prologue (default 1).
+  // Lines: inherits dwx_active's bound (bs * ndir <= 192 on 256 CUs); measured 64 / 96 bidirectional lines, EXPERIMENTS 15.
+  bool xd_in_launch() const {
+    const Layer& top = L.back();
+    return dwx_active && !mfma_bwd_eligible(top) && desc.nclasses <= XD_MAX_K && top.nthreads >= 64 * ((top.no + 15) / 16) &&
+           top.nthreads * xd_maxu(top.nk4) >= XD_UNITS &&   // (always: the smallest workgroup of an instantiation covers a staging round)
+           dbg_opt("xd_prologue") != 0;
+  }
+  XdArgs xd_args() const {
+    const Layer& top = L.back();
+    const int nc = desc.nclasses;
+    return XdArgs{gemm_kc(Dz.p, nc, N), gemm_kc(v + sm_off + nc, nc, sm_ni, 0), top.dH.p, sm_ni, nc};
+  }
   // Rows of the bf16-source weight-gradient product of an R x Cn gradient: R - 1 when the bias row is produced outside it
   // (backward_dw_bf16), else R.  backward_plan launches with it and forward_pass PREDICTS it to decide sbf_x_external with the same
   // tile-height function -- should the backward pass still come out with another tile height, gemm_mc_check_a2 refuses the launch
@@ -1140,6 +1166,8 @@ struct Net {
     g.x3 = dw_x3;
     g.terms = split_terms;
     unsigned nextra = 0;
+    const bool xd = &y == &L.back() && xd_in_launch();   // (only the top layer's dH comes from the softmax layer)
+    if (xd) { g.xd = xd_args(); g_path_count[PC_XD_PROLOGUE]++; }
     if (dwx_active && &y == &L.back()) {
       const int xR = 1 + sm_ni, xCn = desc.nclasses;
       g.xS = y.srow(); g.xlds = y.ldh; g.xs_elems = (long long)N * y.ldh + 3;
@@ -1179,7 +1207,7 @@ struct Net {
     // tests force the path): the items find every progress word complete
     // (... and minibatches whose backward recurrence runs batched on the MFMA, lstm_mfma_bwd.h: it marks its lines complete)
     timing.begin("lstm_bwd", s);
-    launch_bwd_narrow(y, a, s);
+    launch_bwd_narrow(y, a, s, xd ? &g.xd : nullptr);
     timing.end(s);
     timing.begin("gemm_gates_dw", s);
     if (g.x3 && g.terms >= 3) CLSTM_LAUNCH(gemm_dw_kernel<3>, dim3(nblk), dim3(256), 0, s, g);
@@ -1263,9 +1291,11 @@ struct Net {
     const GemmOperand Wk = gemm_kc(W1 + nc, nc, sm_ni, 0);
     const StorePartial wd_store{partial_sm.p, R, Cn};
     const StorePlain xd_store{top.dH.p, sm_ni};
-    timing.begin("gemm_softmax_dw_dx", s);
-    if (dwx_active) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, split_terms);
-    else if (sm_big) {
+    const bool launches = !xd_in_launch();   // (else nothing is launched here: the top layer's backward launch computes x.d)
+    if (launches) timing.begin("gemm_softmax_dw_dx", s);
+    if (dwx_active) {
+      if (launches) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, split_terms);
+    } else if (sm_big) {
       gemm_x3_big<GEMM_MC, GEMM_MC>(s, gemm_mc(top.srow(), top.ldh, N, 32), gemm_mc(Dz.p, nc, N, 32), wd_store, R, Cn, (int)N, ns);
       gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N, 32), Wk, xd_store, (int)N, sm_ni, nc);
     } else {
@@ -1274,7 +1304,7 @@ struct Net {
       if (gemm_x3_on) gemm_x3_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store, split_terms);
       else gemm_f32_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store);
     }
-    timing.end(s);
+    if (launches) timing.end(s);
     // the slabs are reduced together with the top layer's weight-gradient slabs (backward_weight_gradient)
     sm_red = ReduceDesc{partial_sm.p, nullptr, (long long)sm_off, ns, 1, R, Cn, nc};
     check_launch();

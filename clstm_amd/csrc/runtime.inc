@@ -143,7 +143,7 @@ enum PathCounter {
   PC_FWD_FUSED_WX = 6, PC_PEER_EXCHANGE = 7, PC_DW_X_EXTERNAL = 8, PC_BWD_C32 = 9, PC_PACKS_FOLLOW_UPDATE = 10, PC_BWD_X3 = 11,
   PC_REPLICA_CHECK = 12, PC_DW_BIAS_OUT = 13, PC_DW_DX_ONE_LAUNCH = 14, PC_MFMA_NOSAVE = 15, PC_MFMA_FWD = 16, PC_MFMA_BWD = 17,
   PC_MFMA_BWD_DW = 18, PC_INGEST_TAIL = 19, PC_INGEST_TAIL_USED = 20, PC_MFMA_ROUTED = 21 /* counted on the device */,
-  PC_LINE_NOSAVE = 22, PC_FUSED_NOSAVE = 23, PC_PEER_TWO_PHASE = 24, PC_NORMALIZED = 25, PC_COUNT
+  PC_LINE_NOSAVE = 22, PC_FUSED_NOSAVE = 23, PC_PEER_TWO_PHASE = 24, PC_NORMALIZED = 25, PC_XD_PROLOGUE = 26, PC_COUNT
 };
 static long long g_path_count[PC_COUNT];
 struct StorePlain {
@@ -220,6 +220,18 @@ static void launch_lstm(bool fwd, int nk4, int ku, LstmSeqArgs a, int bs, int nt
   CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
 #undef CASE_
   throw Error("unsupported nhidden for the register-resident recurrence");
+}
+
+// the per-line backward recurrence with the softmax layer's x.d as its prologue (lstm_xd_prologue.h); terms as gemm_x3
+static bool launch_lstm_bwd_xd(int nk4, int ku, const LstmSeqArgs& a, const XdArgs& x, int terms, int bs, int nthreads, hipStream_t s) {
+#define CASE_(N, K) if (nk4 == N && ku == K) { \
+    const size_t smem = (2 * 16 * (size_t)lstm_qstride(N) + 4) * sizeof(float); \
+    if (terms >= 3) CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 3>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x); \
+    else CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 2>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x); \
+    check_launch(); return true; }
+  CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
+#undef CASE_
+  return false;
 }
 
 template <int NK4, int KU>

@@ -410,6 +410,8 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *  7  training steps whose gradient exchange was the peer-read all-reduce fused with the update (either form);  24  those of them that
  *     took the two-phase form;  12  replica consistency checks enqueued;
  *  25  lines normalised on the device (clstm_normalizer_run_*);
+ *  26  backward passes whose top layer's recurrence workgroups computed the softmax layer's input deltas themselves, in front of
+ *     their first step (lstm_xd_prologue.h), instead of a product launch of its own (experiment option xd_prologue=0);
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
