@@ -25,7 +25,10 @@ inline constexpr DbgOptDef DBG_OPTS[] = {
     {"dw_x3", 1},            // 0: the f32 MFMA for the fused launch's weight-gradient items ...
     {"gemm_x3", 1},          // 0: ... / for the softmax layer's backward pair (what clstm_net_set_strict_f32 selects per net)
     {"split_terms", 3},      // 2: two-term split of the backward products
-    {"xd_prologue", 1},      // 0: the softmax layer's x.d as a launch of its own in front of the top layer's fused backward launch
+    {"xd_prologue", 2},      // the softmax layer's x.d: 2 the recurrence workgroups of the top layer's fused backward launch compute
+                             //   only the 32 frames they visit first, helper items of the launch the rest (where Net::xd_mode
+                             //   admits it, else as 1); 1 every recurrence workgroup computes its whole slice in front of its
+                             //   first step; 0 a launch of its own in front of the backward launch
     {"fwd_mfma", 1},         // the batched-MFMA narrow forward recurrence: 0 never, 1 from 640 lines, 2 always
     {"bwd_mfma", 1},         // ... and backward recurrence: the same
     {"bwd_mfma_fused", 1},   // the batched backward recurrence and its weight-gradient items as one launch: 0 never,

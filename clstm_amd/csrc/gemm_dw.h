@@ -35,6 +35,10 @@ struct XdArgs {
   GemmOperand B;            // gemm_kc(W1 + nc, nc, sm_ni, 0): rows = columns of the softmax layer's input
   float* out; int ld;       // the top layer's dH [frame][ld], ld = ndir * no
   int K;                    // classes (contraction length), <= XD_MAX_K
+  // producer form (fused launch, experiment option xd_prologue=2): the recurrence workgroup computes only the 32 frames it visits
+  // first, helper items the rest; ready[(dir * bs + line) * PROG_STRIDE] = ready0 + rounds of that line and direction the item
+  // has completed (ready0 = the launch's prog_base).  nullptr: the whole prologue in the recurrence workgroup.
+  int* ready; int ready0;
 };
 
 struct GemmDwArgs {

@@ -34,16 +34,36 @@ __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_bwd_dw
     const int bl = (int)blockIdx.x % a.bs;
     const int b = a.order ? a.order[bl] : bl, dir = (int)blockIdx.x / a.bs;
     // top layer: the workgroup first computes its own slice of dH (the recurrence role has no other use for gsm); this sits in
-    // front of the body's recurrent-weight loads, so the two register populations are never live together
+    // front of the body's recurrent-weight loads, so the two register populations are never live together.  Producer form
+    // (g.xd.ready): only the 32 frames it visits first; the helper items behind the monitor compute the rest and the body checks
+    // their word before its prefetch enters a round it did not make.
+    bool producers = false;
     if constexpr (NT >= 2) {
-      if (g.xd.A.p) xd_prologue<NT, xd_maxu(NK4)>(gsm, g.xd, a.line_off, b, dir, a.no);
+      if (g.xd.A.p) {
+        producers = g.xd.ready != nullptr;   // (kernel argument: uniform)
+        if (producers) xd_own_round<NT, xd_maxu(NK4)>(gsm, g.xd, a.line_off, b, dir, a.no);
+        else xd_prologue<NT, xd_maxu(NK4)>(gsm, g.xd, a.line_off, b, dir, a.no);
+      }
     }
-    lstm_bwd_body<NK4, KU>(a, b, dir);
+    const long long t1 = g.trace ? wall_clock() : 0;
+    if constexpr (NT >= 2) {
+      if (producers) lstm_bwd_body<NK4, KU, true>(a, b, dir, g.xd.ready + ((size_t)dir * a.bs + b) * PROG_STRIDE, g.xd.ready0);
+      else lstm_bwd_body<NK4, KU>(a, b, dir);
+    } else lstm_bwd_body<NK4, KU>(a, b, dir);
     if (g.done && threadIdx.x == 0) atomic_add_i32(g.done, 1);   // (the body ended with drain + barrier: this line's deltas are in memory)
-    if (g.trace && threadIdx.x == 0) { g.trace[blockIdx.x * 4] = t0; g.trace[blockIdx.x * 4 + 2] = wall_clock(); }
+    if (g.trace && threadIdx.x == 0) { g.trace[blockIdx.x * 4] = t0; g.trace[blockIdx.x * 4 + 1] = t1; g.trace[blockIdx.x * 4 + 2] = wall_clock(); }
   } else {
+    unsigned blk = blockIdx.x - (unsigned)nrec;
+    if constexpr (NT >= 2) {
+      // producer form: the dH items sit behind the monitor and in front of everything that waits -- one per recurrence workgroup,
+      // in the same (longest line first) order; they never wait, and all waves of the launch stay for them
+      if (g.xd.ready) {
+        if (blk >= 1u && blk <= (unsigned)nrec) { xd_item<NT, xd_maxu(NK4)>(gsm, g.xd, a.line_off, a.order, a.bs, (int)blk - 1, a.no); return; }
+        if (blk > (unsigned)nrec) blk -= (unsigned)nrec;
+      }
+    }
     if (threadIdx.x >= 256) return;   // the GEMM role is four waves; the others retire (a barrier counts live waves only)
-    gemm_dw_body<NT>(g, gsm, blockIdx.x - (unsigned)nrec);   // the monitor, then one item per workgroup in dispatch order
+    gemm_dw_body<NT>(g, gsm, blk);   // the monitor, then one item per workgroup in dispatch order
   }
 }
 

@@ -413,8 +413,17 @@ __global__ __launch_bounds__(64 * NK4) CLSTM_TWO_WAVES_PER_SIMD void lstm_fwd_ke
   lstm_fwd_body<NK4, KU, false, SAVE>(a, a.order ? a.order[blockIdx.x] : (int)blockIdx.x, blockIdx.y, nullptr);
 }
 
-template <int NK4, int KU>
-DEVFN void lstm_bwd_body(const LstmSeqArgs& a, const int b, const int dir) {
+// XDP (fused launch, top layer, producer form of the softmax layer's x.d; lstm_xd_prologue.h): dH beyond the workgroup's first 32
+// iterations is made by a helper workgroup of the same launch, which publishes xdw = xd0 + rounds complete (round k = iterations
+// 32 k .. 32 k + 31, k >= 1).  Two things change, neither on the step's dependent chain:
+//  * every dH load asks at system scope (the rows were written through on another XCD; each is read once, nothing to reuse);
+//  * wave 0 runs a copy of the loop that requests the word with every step's prefetches and, in front of each barrier, compares
+//    the value requested two steps earlier (in memory order behind operands the step has already waited for) with the round the
+//    NEXT step's prefetch reaches; short of it, the wave polls and so holds the barrier, as wave 3 of the fused forward launch
+//    does for its pre-activations.  The wait is bounded and counted in a.timeouts (the step is then dropped as a whole).
+// Without XDP nothing of this is instantiated.
+template <int NK4, int KU, bool XDP = false>
+DEVFN void lstm_bwd_body(const LstmSeqArgs& a, const int b, const int dir, const int* xdw = nullptr, const int xd0 = 0) {
   constexpr int SLP = 4 * NK4;
   constexpr int QS = SLP + ((NK4 & 1) ? 0 : 4);
   constexpr int DB = 16 * QS;
@@ -481,21 +490,27 @@ DEVFN void lstm_bwd_body(const LstmSeqArgs& a, const int b, const int dir) {
   // registers anyway and copied them back at the loop back-edge behind an s_waitcnt vmcnt(1) -- a stall on
   // prefetches issued a few hundred cycles earlier, every second step.  Now whatever the compiler copies at
   // the back-edge was requested at least a full step before.  c_{s-1} is the NEXT set's c (no extra load).
-  struct Ops { float act, dh, cc; };
+  struct Ops { float act, dh, cc; int rdy; };
+  auto hload = [&](unsigned o) -> float { return XDP ? buf_load_wt(hbuf, o) : buf_load(hbuf, o); };
   Ops X0, X1, X2;
   X0.act = buf_load(gbuf, gl + fr(T - 1) * gstride4); X1.act = buf_load(gbuf, gl + fr(T - 2) * gstride4);
-  X0.dh = buf_load(hbuf, cl + fr(T - 1) * cstride4);  X1.dh = buf_load(hbuf, cl + fr(T - 2) * cstride4);
+  X0.dh = hload(cl + fr(T - 1) * cstride4);           X1.dh = hload(cl + fr(T - 2) * cstride4);
   X0.cc = buf_load(cbuf, cl + fr(T - 1) * cstride4);  X1.cc = buf_load(cbuf, T >= 2 ? cl + fr(T - 2) * cstride4 : BUF_OOB);
   X2.act = X2.dh = X2.cc = 0.0f;
+  X0.rdy = X1.rdy = X2.rdy = xd0;          // (XDP: nothing known yet; the first 32 iterations are the workgroup's own)
   float dc_carry = 0.0f;
   float ka0 = 0.f, ka1 = 0.f, ka2 = 0.f;  // store-data pins (see KEEP_ALIVE)
+  bool xd_gave_up = false;                 // (XDP: the watchdog fired once -- the pass is lost, finish it without further waits)
   __syncthreads();
+  auto run = [&](auto chk_t) {
+  constexpr bool CHK = decltype(chk_t)::value;   // this wave watches the producers' word
   // cur: operands of step s; nxt: operands of step s-1 (its c is c_{s-1}); ld: set to refill for step s-2
   auto step = [&](const int s, Ops& cur, const Ops& nxt, Ops& ld, const float* dq, float* dw, float& ka, float& kprev) {
     KEEP_ALIVE(ka);
     ld.act = buf_load(gbuf, gl + fr(s - 2) * gstride4);
-    ld.dh = buf_load(hbuf, cl + fr(s - 2) * cstride4);
+    ld.dh = hload(cl + fr(s - 2) * cstride4);
     ld.cc = buf_load(cbuf, s >= 2 ? cl + fr(s - 2) * cstride4 : BUF_OOB);   // before the first step: 0 = c_{-1}
+    if constexpr (CHK) ld.rdy = load_i32_wt(xdw);
     // Everything that does not depend on this step's mat-vec is computed BEFORE it (its operands were
     // requested two steps ago): tanh(c), the gate broadcasts, the derivative factor and the second factor
     // of this lane's gate delta.  The dependent tail behind the reduction is then five VALU operations.
@@ -557,6 +572,19 @@ DEVFN void lstm_bwd_body(const LstmSeqArgs& a, const int b, const int dir) {
     const float sdat = tagl ? __builtin_bit_cast(float, a.prog_base + (T - 1 - s) - 3) : delta;
     *dw = delta;
     ka = sdat;
+    if constexpr (CHK) {
+      // behind this barrier the workgroup issues, at the top of step s - 1, the dH load of step s - 3 = iteration T + 2 - s
+      // (clamped to the last): its round must be there.  Round 0 is the workgroup's own: no word.
+      const int itn = T + 2 - s < T ? T + 2 - s : T - 1;
+      const int need = itn >> 5;
+      if (need > 0 && !xd_gave_up && __builtin_expect(wave_uniform(cur.rdy) - xd0 < need, 0)) {
+        int polls = 0;
+        while (wave_uniform(load_i32_wt(xdw)) - xd0 < need) {
+          poll_pause();
+          if (++polls > (1 << 20)) { if (lane == 0) atomic_add_i32(a.timeouts, 1); xd_gave_up = true; break; }   // never hang the device
+        }
+      }
+    }
     __syncthreads();
   };
   // 3 operand sets x 2 LDS phases: the pattern repeats every 6 steps
@@ -574,6 +602,10 @@ DEVFN void lstm_bwd_body(const LstmSeqArgs& a, const int b, const int dir) {
   if (s >= 2) step(s - 2, X2, X0, X1, rdA, wrA, ka2, ka1);
   if (s >= 3) step(s - 3, X0, X1, X2, rdB, wrB, ka0, ka2);
   if (s >= 4) step(s - 4, X1, X2, X0, rdA, wrA, ka1, ka0);
+  };
+  if constexpr (XDP) {
+    if (wave_uniform(wave) == 0) run(std::true_type{}); else run(std::false_type{});
+  } else run(std::false_type{});
   {   // the last step's deltas (own step 0): the store data sits in slot (T - 1) mod 3
     const int r = (T - 1) % 3;
     const float last = r == 0 ? ka0 : r == 1 ? ka1 : ka2;

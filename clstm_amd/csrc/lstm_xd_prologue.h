@@ -4,6 +4,8 @@
 // launch of its own that product (12800 x 200 x 83 at the bench shape) pays ~12 us for well under 2 us of MFMA work.  Here every
 // recurrence workgroup computes its own T x no x nc slice in front of its first step, on the matrix cores its CU leaves idle,
 // stores it, meets at ONE barrier and starts the time loop.  Producer and consumer are the same workgroup: no flag, no poll.
+// (Producer form, further down: only the 32 frames the workgroup visits first are computed here, helper workgroups of the fused
+// launch compute the others while the time loop already runs.)
 //
 // Arithmetic: gemm_x3_body<GEMM_KC, GEMM_KC, StorePlain, NT> (gemm_bf16.h), expression for expression -- the same term split
 // (bf16_pack8, then the exact remainder), contraction indices >= nc zeroed, accumulators from zero, k-blocks ascending, inside a
@@ -32,8 +34,17 @@ constexpr int XD_RING = 3;               // rounds of z.d in flight in registers
 constexpr int xd_maxu(int nk4) { return nk4 <= 1 ? 6 : nk4 == 2 ? 3 : nk4 <= 7 ? 2 : 1; }
 constexpr int xd_smem_floats(int nt) { return 2 * nt * XD_KB * XD_ROWS * 32 / 2; }   // 24 KB (NT = 2) / 36 KB (NT = 3)
 
-template <int NT, int MAXU>
-DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const int b, const int dir, const int no) {
+// xd_rounds: `nr` rounds of one (line, direction) -- round p is the 32 frames from row0 + p * rstep on; frames outside [0, T)
+// are neither read nor stored, so a round may hang over either end of the line.  Both callers of the producer form share this
+// body with the whole prologue: the recurrence role computes the round it visits first, a helper item the others in the order the
+// recurrence reaches them.  A row of dH depends on nothing but its own row of z.d, so which round (and which workgroup) computes a
+// frame does not change its bytes.
+// WT: the rows leave write-through (sc0 sc1), for readers on another XCD.  word != nullptr (WT only): after every round each wave
+// drains its stores, the workgroup meets at the round's barrier, and one lane publishes word0 + rounds complete at system scope --
+// word0 is the launch's prog_base, so a word left by an earlier pass is below every value this one waits for.
+template <int NT, int MAXU, bool WT = false>
+DEVFN void xd_rounds(float* smem, const XdArgs& x, const int* line_off, const int b, const int dir, const int no,
+                     const int row0, const int rstep, const int nr, int* word = nullptr, const int word0 = 0) {
   static_assert(NT == 2 || NT == 3, "two or three bf16 terms per operand");
   unsigned short* img = reinterpret_cast<unsigned short*>(smem);
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
@@ -55,8 +66,8 @@ DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const 
     for (int i = 0; i < MAXU; i++) {
       if (i * nthreads + (tid & ~63) >= XD_UNITS) break;   // (wave-uniform)
       const int u = i * nthreads + tid;
-      const int row = r * XD_ROWS + u / (XD_KB * 4), ku = u % (XD_KB * 4);   // (r * XD_ROWS <= T + 95)
-      const unsigned o = u < XD_UNITS && row < T ? ((unsigned)row * (unsigned)x.A.ld + (unsigned)((ku >> 2) * 32 + (ku & 3) * 8)) * 4u : BUF_OOB_BASE;
+      const int row = row0 + r * rstep + u / (XD_KB * 4), ku = u % (XD_KB * 4);
+      const unsigned o = u < XD_UNITS && r < nr && (unsigned)row < (unsigned)T ? ((unsigned)row * (unsigned)x.A.ld + (unsigned)((ku >> 2) * 32 + (ku & 3) * 8)) * 4u : BUF_OOB_BASE;
       ra[i][0] = buf_load4(abuf, o);
       ra[i][1] = buf_load4(abuf, o + 16u);
     }
@@ -122,7 +133,6 @@ DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const 
     }
   }
 
-  const int nrounds = (T + XD_ROWS - 1) / XD_ROWS;
   const int fofs = fi * 32 + ((fk ^ gb2_sw(fi)) << 3);   // (rows 16 apart share the swizzle)
   const unsigned ocol = n < no ? (unsigned)(dir * no + n) * 4u : BUF_OOB_BASE;
   auto round = [&](const int r, f32x4 (&ra)[MAXU][2]) {
@@ -130,8 +140,14 @@ DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const 
     stage_round(cur, ra);
     // every wave's images of this round are in LDS (the other buffer's readers passed the barrier of the round before)
     wait_lgkmcnt0();
+    if constexpr (WT) {
+      if (word) drain_vmem();                  // this wave's rows of the rounds before are in memory ...
+    }
     wg_barrier();
     COMPILER_MEMORY_BARRIER();
+    if constexpr (WT) {
+      if (word && r > 0 && tid == 0) store_i32_wt(word, word0 + r);   // ... and now every wave's: rounds < r are complete
+    }
     load_round(r + XD_RING, ra);   // into the set this round has just staged from: in flight for XD_RING rounds
     SCHED_FENCE();
     if (has_tile) {
@@ -159,19 +175,57 @@ DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const 
       for (int m = 0; m < 2; m++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-          const int row = r * XD_ROWS + m * 16 + fk * 4 + q;
-          buf_store(obuf, row < T ? (unsigned)row * (unsigned)x.ld * 4u + ocol : BUF_OOB_BASE, acc[m][q]);
+          const int row = row0 + r * rstep + m * 16 + fk * 4 + q;
+          const unsigned o = (unsigned)row < (unsigned)T ? (unsigned)row * (unsigned)x.ld * 4u + ocol : BUF_OOB_BASE;
+          if constexpr (WT) buf_store_wt(obuf, o, acc[m][q]);
+          else buf_store(obuf, o, acc[m][q]);
         }
     }
   };
-  for (int r = 0; r < nrounds; r += XD_RING) {
+  for (int r = 0; r < nr; r += XD_RING) {
 #pragma unroll
     for (int p = 0; p < XD_RING; p++)
-      if (r + p < nrounds) round(r + p, ring[p]);
+      if (r + p < nr) round(r + p, ring[p]);
   }
-  // every dH store of every wave acknowledged, then one barrier, then the recurrence's first loads
+  // every dH store of every wave acknowledged, then one barrier, then the recurrence's first loads / the last publication
   drain_vmem();
   __syncthreads();
+  if constexpr (WT) {
+    if (word && tid == 0) store_i32_wt(word, word0 + nr);
+  }
+}
+
+// the whole prologue: every round of the line, in frame order
+template <int NT, int MAXU>
+DEVFN void xd_prologue(float* smem, const XdArgs& x, const int* line_off, const int b, const int dir, const int no) {
+  const int T = line_off[b + 1] - line_off[b];
+  xd_rounds<NT, MAXU>(smem, x, line_off, b, dir, no, 0, XD_ROWS, (T + XD_ROWS - 1) / XD_ROWS);
+}
+
+// ---- the producer form (experiment option xd_prologue=2, fused launch only) ------------------------------------------------------
+// The recurrence reads dH[t] two steps before it uses it and reaches the frames of its k-th 32 iterations only ~15 k us into its
+// time loop: only the round it visits FIRST has to exist before step 0.  Rounds are counted in visit order -- visit round j is
+// iterations 32 j .. 32 j + 31: frames 32 j .. for direction 1, frames T - 32 (j + 1) .. T - 32 j - 1 for direction 0, which
+// walks the line backwards (so the short round of a line whose length is no multiple of 32 is the LAST visited in both).
+// The recurrence workgroup computes visit round 0; item (line, direction) of the helper role computes rounds 1 .. in visit order
+// and publishes after each (xd_rounds); lstm_bwd_body<.., XDP> checks the word before its prefetch enters a round.
+DEVFN int xd_visit_rounds(const int T) { return (T + XD_ROWS - 1) / XD_ROWS; }
+template <int NT, int MAXU>
+DEVFN void xd_own_round(float* smem, const XdArgs& x, const int* line_off, const int b, const int dir, const int no) {
+  const int T = line_off[b + 1] - line_off[b];
+  xd_rounds<NT, MAXU, true>(smem, x, line_off, b, dir, no, dir == 0 ? T - XD_ROWS : 0, 0, 1);
+}
+// helper item i: the rounds of the line and direction that recurrence workgroup i walks (every wave of the launch stays: one
+// per column tile, as in the recurrence role).  Lines of at most 32 frames have nothing left to compute.
+template <int NT, int MAXU>
+DEVFN void xd_item(float* smem, const XdArgs& x, const int* line_off, const int* order, const int bs, const int i, const int no) {
+  const int bl = i % bs, dir = i / bs;
+  const int b = order ? order[bl] : bl;
+  const int T = line_off[b + 1] - line_off[b];
+  const int nv = xd_visit_rounds(T);
+  if (nv <= 1) return;
+  xd_rounds<NT, MAXU, true>(smem, x, line_off, b, dir, no, dir == 0 ? T - 2 * XD_ROWS : XD_ROWS, dir == 0 ? -XD_ROWS : XD_ROWS, nv - 1,
+                            x.ready + ((size_t)dir * bs + b) * PROG_STRIDE, x.ready0);
 }
 
 // the per-line backward kernel with the prologue in front: the two-launch form of the overlapped backward pass

@@ -126,6 +126,7 @@ struct Net {
   int overlap = getenv("CLSTM_OVERLAP") ? atoi(getenv("CLSTM_OVERLAP")) : 1;
   unsigned dw_done_total = 0;     // recurrence workgroups launched so far through the fused launch (GemmDwArgs::done)
   DevBuf<long long> dw_trace;
+  DevBuf<int> xd_ready;           // producer form of the top layer's x.d (xd_mode 2): rounds-complete words of the dH items
   DevBuf<int> dw_ktab, dw_slabs, dw_queue;   // dw_queue: the monitor's published minima and the `done` counter, each on its own 128-byte line
   std::vector<int> dw_key;        // line offsets the tables were built for
   // the softmax layer's W.d as independent items of the top layer's fused backward launch (gemm_dw.h, GemmDwArgs::x*)
@@ -1043,18 +1044,33 @@ struct Net {
   //  * the split is two or three bf16 terms (dw_x3 says so: the launch rounds split_terms to one of the two, as gemm_x3 does);
   //  * nc <= XD_MAX_K = 96: three k-blocks of W fragments (3 x NT x 4 VGPRs) stay in registers for the whole prologue, and three
   //    blocks are what the launch it replaces runs for such nc, zero blocks included (bit-identity);
-  //  * experiment option xd_prologue (default 1).
+  //  * experiment option xd_prologue (default 2: the producer form where xd_mode admits it, else as 1; 1 the whole prologue; 0 the separate launch).
   // Lines: inherits dwx_active's bound (bs * ndir <= 192 on 256 CUs); measured 64 / 96 bidirectional lines, EXPERIMENTS 15.
-  bool xd_in_launch() const {
+  // xd_mode is THE decision: 0 the separate launch, 1 the whole prologue in every recurrence workgroup, 2 (experiment option
+  // xd_prologue=2, the default) the producer form -- the recurrence workgroup computes only the 32 frames it visits first, helper items of the
+  // same launch the rest (lstm_xd_prologue.h).  Form 2 needs the one-launch form of the overlapped pass (four or more waves, not the
+  // host emulator: backward_layer_overlapped's rule) and recurrence workgroups on at most half of the CUs -- the items are workgroups of its helper role, one wave per column tile like
+  // the recurrence role -- and whatever is eligible for 1 but not for 2 runs 1 unchanged.
+  int xd_mode() const {
     const Layer& top = L.back();
-    return dwx_active && !mfma_bwd_eligible(top) && desc.nclasses <= XD_MAX_K && top.nthreads >= 64 * ((top.no + 15) / 16) &&
-           top.nthreads * xd_maxu(top.nk4) >= XD_UNITS &&   // (always: the smallest workgroup of an instantiation covers a staging round)
-           dbg_opt("xd_prologue") != 0;
+    const int opt = dbg_opt("xd_prologue");
+    const bool ok = dwx_active && !mfma_bwd_eligible(top) && desc.nclasses <= XD_MAX_K && top.nthreads >= 64 * ((top.no + 15) / 16) &&
+                    top.nthreads * xd_maxu(top.nk4) >= XD_UNITS &&   // (always: the smallest workgroup of an instantiation covers a staging round)
+                    opt != 0;
+    if (!ok) return 0;
+#ifndef CLSTM_HIP_EMU
+    // ... and a CU of its own for every item: an item that shares a CU with a recurrence workgroup takes issue slots from the
+    // latency-bound time loop (96 bidirectional lines, 192 + 192 workgroups on 256 CUs: form 2 measured 5.5 us per step SLOWER than
+    // form 1; 64 lines, 128 + 128: 4.1 us faster -- profiles/ab_xd_producers.txt)
+    if (opt >= 2 && top.nthreads >= 256 && (long long)bs * ndir * 2 <= device_cu_count()) return 2;
+#endif
+    return 1;
   }
+  bool xd_in_launch() const { return xd_mode() != 0; }
   XdArgs xd_args() const {
     const Layer& top = L.back();
     const int nc = desc.nclasses;
-    return XdArgs{gemm_kc(Dz.p, nc, N), gemm_kc(v + sm_off + nc, nc, sm_ni, 0), top.dH.p, sm_ni, nc};
+    return XdArgs{gemm_kc(Dz.p, nc, N), gemm_kc(v + sm_off + nc, nc, sm_ni, 0), top.dH.p, sm_ni, nc, nullptr, 0};
   }
   // Rows of the bf16-source weight-gradient product of an R x Cn gradient: R - 1 when the bias row is produced outside it
   // (backward_dw_bf16), else R.  backward_plan launches with it and forward_pass PREDICTS it to decide sbf_x_external with the same
@@ -1145,7 +1161,8 @@ struct Net {
     REQUIRE(prog_off >= (long long)N * M, "internal: progress words overlap the deltas");
     prog_base += tmax + 64;
     dw_launches++;
-    if (prog_base > (1 << 30)) prog_base = 1024;   // (words left from ~5 million launches ago could look complete: harmless in practice, D is rewritten)
+    const bool prog_base_wrapped = prog_base > (1 << 30);
+    if (prog_base_wrapped) prog_base = 1024;   // (words left from ~5 million launches ago could look complete: harmless in practice, D is rewritten)
     a.prog_off = prog_off;
     a.prog_base = prog_base;
     DevBuf<float>& partial = layer_partial(y);
@@ -1167,7 +1184,17 @@ struct Net {
     g.terms = split_terms;
     unsigned nextra = 0;
     const bool xd = &y == &L.back() && xd_in_launch();   // (only the top layer's dH comes from the softmax layer)
-    if (xd) { g.xd = xd_args(); g_path_count[PC_XD_PROLOGUE]++; }
+    const int xdm = &y == &L.back() ? xd_mode() : 0;
+    if (xd) { g.xd = xd_args(); g_path_count[xdm == 2 ? PC_XD_PRODUCERS : PC_XD_PROLOGUE]++; }
+    if (xdm == 2) {   // the items' rounds-complete words: [ndir][bs], one per 128 bytes; zero is below every prog_base
+      const size_t nw = (size_t)ndir * bs * PROG_STRIDE;
+      if (nw > xd_ready.cap || prog_base_wrapped) {
+        xd_ready.reserve(nw);
+        HIPCHECK(hipMemsetAsync(xd_ready.p, 0, xd_ready.cap * sizeof(int), s));
+      }
+      g.xd.ready = xd_ready.p; g.xd.ready0 = prog_base;
+      a.timeouts = g.timeouts;   // (the recurrence role's bounded wait for a round)
+    }
     if (dwx_active && &y == &L.back()) {
       const int xR = 1 + sm_ni, xCn = desc.nclasses;
       g.xS = y.srow(); g.xlds = y.ldh; g.xs_elems = (long long)N * y.ldh + 3;
@@ -1180,7 +1207,8 @@ struct Net {
     static const char* trace_path = getenv("CLSTM_DW_TRACE");   // diagnostics: wall-clock stamps of every workgroup of the fused launch
     const size_t trace_rows = (size_t)bs * ndir + (size_t)((dw_nslabs + 7) / 8) * 8 * g.gx * g.gy + 8;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); g.trace = dw_trace.p; g.trace_base = bs * ndir; }
-    const unsigned nblk = 1u + nextra + (unsigned)((dw_nslabs + 7) / 8) * 8u * g.gx * g.gy;   // the monitor + the independent items + one per item
+    // the monitor + (producer form) one dH item per recurrence workgroup + the independent items + one per item
+    const unsigned nblk = 1u + (xdm == 2 ? (unsigned)(bs * ndir) : 0u) + nextra + (unsigned)((dw_nslabs + 7) / 8) * 8u * g.gx * g.gy;
 #ifndef CLSTM_HIP_EMU
     if (mfma_bwd_fused_ok(y, g)) {   // chip-filling minibatch: the batched-MFMA recurrence and the items as one launch
       timing.begin("lstm_bwd", s);
@@ -1199,13 +1227,14 @@ struct Net {
       timing.end(s);
       if (trace_path)
         dump_trace(trace_path, dw_trace.p, trace_rows, s,
-                   "# rows 0..%d: recurrence workgroups (start, -, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
+                   "# rows 0..%d: recurrence workgroups (start, x.d prologue returned, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
       return;
     }
 #endif
     // two launches one after the other (host emulator; layers too narrow for the GEMM role's 256 threads when the
     // tests force the path): the items find every progress word complete
     // (... and minibatches whose backward recurrence runs batched on the MFMA, lstm_mfma_bwd.h: it marks its lines complete)
+    REQUIRE(xdm != 2, "internal: the producer form of x.d outside the one-launch form");
     timing.begin("lstm_bwd", s);
     launch_bwd_narrow(y, a, s, xd ? &g.xd : nullptr);
     timing.end(s);

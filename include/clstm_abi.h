@@ -412,6 +412,8 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *  25  lines normalised on the device (clstm_normalizer_run_*);
  *  26  backward passes whose top layer's recurrence workgroups computed the softmax layer's input deltas themselves, in front of
  *     their first step (lstm_xd_prologue.h), instead of a product launch of its own (experiment option xd_prologue=0);
+ *  27  backward passes that took the producer form of the same instead (the default where Net::xd_mode admits it; xd_prologue=1: never): every recurrence workgroup
+ *     computed only the 32 frames it visits first, helper workgroups of the launch the rest (26 does not move for them);
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
