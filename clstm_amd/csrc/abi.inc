@@ -8,6 +8,7 @@ struct clstm_net {
   Net net;
   CtcWorkspace ctc;
   DecodeWorkspace dec;
+  ScoreWorkspace score;
 };
 
 #define EW(kernel, len, ...) \
@@ -137,6 +138,13 @@ int clstm_ctc_align_batch(const float* probs, float* deltas, float* aligned, int
   ABI_BEGIN
   if (!g_ctc_ws) g_ctc_ws = new CtcWorkspace();
   run_ctc(*g_ctc_ws, probs, deltas, aligned, nc, line_off_h, states_h, state_off_h, bs, g_stream);
+  ABI_END
+}
+int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int bs, const int* states_h, const int* state_off_h,
+                          const int* cand_line_h, int ncand, float* score_h, float* vscore_h, int* path_h) {
+  ABI_BEGIN
+  if (!g_score_ws) g_score_ws = new ScoreWorkspace();
+  run_ctc_score(*g_score_ws, probs, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, score_h, vscore_h, path_h, g_stream);
   ABI_END
 }
 int clstm_trivial_decode_batch(const float* probs, int nc, const int* line_off_h, int bs, int* classes_h,
@@ -301,6 +309,35 @@ int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* alig
   REQUIRE_CURRENT(h);
   REFUSE_NOSAVE(h, "clstm_net_ctc");
   net_ctc(h, labels_h, L_h, aligned_h);
+  ABI_END
+}
+// score / forced alignment of candidate transcripts against the current minibatch: reads Z only (so it also follows clstm_net_predict),
+// writes nothing of the net's -- no Dz, no error words, not the prepared alignment of a declared next minibatch (ScoreWorkspace)
+int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int* cand_line_h, int ncand, float* score_h,
+                    float* vscore_h, int* path_h) {
+  ABI_BEGIN
+  REQUIRE(h, "null argument");
+  REQUIRE_CURRENT(h);
+  Net& n = h->net;
+  REQUIRE(n.N > 0, "set_batch first");
+  REQUIRE(score_h || vscore_h || path_h, "clstm_net_score: score_h, vscore_h and path_h are all NULL");
+  REQUIRE(labels_h && L_h && ncand > 0, "null argument / no candidates");
+  std::vector<int> soff(ncand + 1, 0), states;
+  int lpos = 0;
+  for (int c = 0; c < ncand; c++) {
+    const int L = L_h[c];
+    REQUIRE(L >= 0, "negative transcript length");
+    states.resize(soff[c] + 2 * L + 1);
+    clstm_mktargets(states.data() + soff[c], labels_h + lpos, L);
+    for (int i = 0; i < L; i++) REQUIRE(labels_h[lpos + i] != 0, "transcript contains the blank class (Codec::encode asserts c != 0, clstm.cc:232)");
+    lpos += L;
+    soff[c + 1] = soff[c] + 2 * L + 1;
+  }
+  RoctxRange range_("clstm:score");
+  n.timing.begin("ctc_score", g_stream);
+  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  run_ctc_score(h->score, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, states.data(), soff.data(), cand_line_h, ncand,
+                score_h, vscore_h, path_h, g_stream);
   ABI_END
 }
 int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }

@@ -14,6 +14,7 @@
 #include "../../include/clstm_abi.h"
 #include "dbgopt.h"
 #include "ctc.h"
+#include "ctc_score.h"
 #include "devintrin.h"
 #include "gemm_mfma.h"
 #include "gemm_bf16.h"

@@ -140,6 +140,180 @@ static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int
   if (conf_h) memcpy(conf_h, w.host + bs + 2 * (size_t)N, (size_t)N * sizeof(float));
 }
 
+// ---- scores and forced alignments (ctc_score.h) ------------------------------------------------------------------------
+// A workspace of its own: meta block, pinned ring slot, rolling rows / back-pointer words, result block.  Nothing here touches a
+// CtcWorkspace: an alignment that clstm_net_train_step_next prepared and has not launched survives a score call.
+struct ScoreWorkspace {
+  PinnedRing ring;
+  DevBuf<double> tables;
+  DevBuf<char> meta;
+  DevBuf<unsigned long long> ws;
+  DevBuf<int> out;            // [score ncand | vscore ncand (float bits) | paths]: ONE copy brings the results back
+  int* host = nullptr;        // pinned landing buffer of that copy
+  size_t host_cap = 0;
+  ~ScoreWorkspace() { if (host) (void)hipHostFree(host); }
+};
+// what the launch will be, decided on the host from the arguments alone (nothing is enqueued while this can still refuse)
+struct ScorePlan {
+  std::vector<ScoreGroup> groups;
+  std::vector<ScoreItem> items;
+  std::vector<long long> path_off;   // per candidate, in ints
+  long long npath = 0, ws_words = 0;
+  int tmax = 1, tile = 0;
+};
+static void plan_ctc_score(ScorePlan& pl, int nc, const int* line_off_h, int bs, const int* states_h, const int* state_off_h,
+                           const int* cand_line_h, int ncand, bool any_out, bool maxplus) {
+  REQUIRE(any_out, "clstm_ctc_score: score_h, vscore_h and path_h are all NULL");
+  REQUIRE(bs > 0 && ncand > 0 && nc >= 1 && line_off_h && states_h && state_off_h, "empty batch / null argument");
+  REQUIRE(cand_line_h || ncand == bs, "cand_line_h is NULL: one candidate per line expected (ncand == bs)");
+  for (int b = 0; b < bs; b++) {
+    const long long T = (long long)line_off_h[b + 1] - line_off_h[b];
+    REQUIRE(T >= 0 && line_off_h[b] >= 0, "bad offsets");
+    REQUIRE(T * nc * 4 < 0x7FFFFFF0ll, "a line's posteriors exceed 2 GB");
+  }
+  for (int c = 0; c < ncand; c++) {
+    REQUIRE(state_off_h[c] >= 0 && state_off_h[c + 1] - state_off_h[c] >= 1, "bad offsets (a candidate has at least one state)");
+    if (cand_line_h) REQUIRE(cand_line_h[c] >= 0 && cand_line_h[c] < bs, "cand_line out of range");
+  }
+  const int ns = state_off_h[ncand];
+  for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+  // items in candidate order first; T = 0 lines have no lattice (the caller fills -inf)
+  pl.path_off.assign(ncand + 1, 0);
+  struct Cand { int c, b, T, S, form; };
+  std::vector<Cand> small, big;
+  for (int c = 0; c < ncand; c++) {
+    const int b = cand_line_h ? cand_line_h[c] : c;
+    const int T = line_off_h[b + 1] - line_off_h[b], S = state_off_h[c + 1] - state_off_h[c];
+    pl.path_off[c + 1] = pl.path_off[c] + T;
+    if (T == 0) continue;
+    const int form = (S <= 64 && T <= SCORE_TMAX) ? 0 : (S <= CTC_SMAX_LDS ? 1 : 2);
+    (form == 0 ? small : big).push_back(Cand{c, b, T, S, form});
+    if (form == 0) pl.tmax = std::max(pl.tmax, T);
+  }
+  pl.npath = pl.path_off[ncand];
+  {   // frames of the LDS tile: what SCORE_ROW_WORDS hold, one thread per frame at most, no more than the longest line
+    int tall = 1;
+    for (int b = 0; b < bs; b++) tall = std::max(tall, line_off_h[b + 1] - line_off_h[b]);
+    pl.tile = std::min(std::min(SCORE_THREADS, SCORE_ROW_WORDS / (nc | 1)), tall);
+  }
+  // one-wave items: a line's candidates side by side, largest first, four to a workgroup
+  std::stable_sort(small.begin(), small.end(), [](const Cand& x, const Cand& y) { return x.b != y.b ? x.b < y.b : x.S > y.S; });
+  auto item_of = [&](const Cand& k, long long ws_off) {
+    return ScoreItem{ws_off, line_off_h[k.b], k.T, state_off_h[k.c], k.S, k.c, (int)pl.path_off[k.c]};
+  };
+  struct G { ScoreGroup g; long long cost; std::vector<ScoreItem> it; };
+  std::vector<G> gs;
+  for (size_t i = 0; i < small.size();) {
+    G g{ScoreGroup{0, 0, 0, 0}, 0, {}};
+    const int b = small[i].b;
+    while (i < small.size() && small[i].b == b && g.g.n < SCORE_WAVES) { g.it.push_back(item_of(small[i], 0)); g.g.n++; i++; }
+    g.g.lml = g.it[0].T <= pl.tile;   // the line fits the LDS tile whole: its match scores are made there once, for all candidates
+    g.cost = (long long)g.it[0].T * 64;
+    gs.push_back(g);
+  }
+  for (const Cand& k : big) {
+    G g{ScoreGroup{0, 1, k.form, 0}, (long long)k.T * k.S, {}};
+    g.it.push_back(item_of(k, pl.ws_words));
+    pl.ws_words += (long long)k.T + k.S + (maxplus ? (long long)k.T * score_frame_words(k.S) : 0);
+    gs.push_back(g);
+  }
+  REQUIRE(pl.npath < 0x7FFFFFFFll, "paths exceed 2^31 entries");
+  std::stable_sort(gs.begin(), gs.end(), [](const G& x, const G& y) { return x.cost > y.cost; });   // workgroups largest first
+  for (G& g : gs) {
+    g.g.first = (int)pl.items.size();
+    pl.groups.push_back(g.g);
+    pl.items.insert(pl.items.end(), g.it.begin(), g.it.end());
+  }
+}
+#ifndef CLSTM_HIP_EMU
+// the dynamic-LDS ceiling of a kernel is a property of the function ON A DEVICE: remembered per device, per calling thread
+static void score_allow_smem(const void* kernel, int which, size_t smem) {
+  static thread_local std::map<int, size_t> allowed[2];
+  int dev = 0;
+  HIPCHECK(hipGetDevice(&dev));
+  size_t& have = allowed[which][dev];
+  if (smem > have) {
+    HIPCHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    have = smem;
+  }
+}
+#endif
+static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, const int* states_h,
+                          const int* state_off_h, const int* cand_line_h, int ncand, float* score_h, float* vscore_h,
+                          int* path_h, hipStream_t s) {
+  const bool sum = score_h != nullptr, maxplus = vscore_h != nullptr || path_h != nullptr;
+  ScorePlan pl;
+  plan_ctc_score(pl, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, sum || maxplus, maxplus);
+  REQUIRE(probs, "null argument");
+  const size_t nout = 2 * (size_t)ncand + (path_h ? (size_t)pl.npath : 0);
+  if (!pl.groups.empty()) {
+    const int ns = state_off_h[ncand];
+    const size_t ngr = pl.groups.size() * sizeof(ScoreGroup), nit = pl.items.size() * sizeof(ScoreItem), nst = (size_t)ns * sizeof(int);
+    w.meta.reserve(ngr + nit + nst);
+    w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
+    w.out.reserve(nout);
+    if (w.host_cap < nout) {
+      if (w.host) HIPCHECK(hipHostFree(w.host));
+      w.host = nullptr; w.host_cap = 0;
+      HIPCHECK(hipHostMalloc((void**)&w.host, (nout + nout / 4 + 64) * sizeof(int)));
+      w.host_cap = nout + nout / 4 + 64;
+    }
+    if (!w.tables.p) {
+      w.tables.reserve(CTC_TABLE_DOUBLES);
+      std::vector<double> tb(CTC_TABLE_DOUBLES);
+      for (int i = 0; i < 32; i++) tb[i] = CTC_EXP2_32[i];
+      for (int i = 0; i < 64; i++) { tb[32 + i] = CTC_LOG_INVC[i]; tb[96 + i] = CTC_LOG_LOGC[i]; }
+      for (int k = 0; k < 2 * CTC_SP_KMAX + 1; k++)
+        for (int c = 0; c < 4; c++) tb[160 + 4 * k + c] = CTC_SOFTPLUS[k][c];
+      HIPCHECK(hipMemcpy(w.tables.p, tb.data(), CTC_TABLE_DOUBLES * sizeof(double), hipMemcpyHostToDevice));
+    }
+    char* stage = (char*)w.ring.acquire(ngr + nit + nst);   // one pinned slot, one copy: [groups | items | states]
+    memcpy(stage, pl.groups.data(), ngr);
+    memcpy(stage + ngr, pl.items.data(), nit);
+    memcpy(stage + ngr + nit, states_h, nst);
+    HIPCHECK(hipMemcpyAsync(w.meta.p, stage, ngr + nit + nst, hipMemcpyHostToDevice, s));
+    w.ring.commit(s);
+    ScoreArgs a{};
+    a.groups = (const ScoreGroup*)w.meta.p;
+    a.items = (const ScoreItem*)(w.meta.p + ngr);
+    a.states = (const int*)(w.meta.p + ngr + nit);
+    a.P = probs; a.tables = w.tables.p; a.ws = w.ws.p;
+    a.nc = nc; a.ncp = nc | 1; a.tile = pl.tile; a.tmax = pl.tmax; a.ncand = ncand; a.npath = (int)pl.npath;
+    const int ng = (int)pl.groups.size();
+    if (sum) {
+      const size_t smem = (size_t)score_lds_layout(a.tmax, a.tile, a.ncp, false).words * sizeof(float);
+#ifndef CLSTM_HIP_EMU
+      score_allow_smem((const void*)ctc_score_kernel<false>, 0, smem);
+#endif
+      a.score = reinterpret_cast<float*>(w.out.p); a.path = nullptr;
+      CLSTM_LAUNCH(ctc_score_kernel<false>, dim3(ng), dim3(SCORE_THREADS), smem, s, a);
+      check_launch();
+      g_path_count[PC_SCORE]++;
+    }
+    if (maxplus) {
+      const size_t smem = (size_t)score_lds_layout(a.tmax, a.tile, a.ncp, true).words * sizeof(float);
+#ifndef CLSTM_HIP_EMU
+      score_allow_smem((const void*)ctc_score_kernel<true>, 1, smem);
+#endif
+      a.score = reinterpret_cast<float*>(w.out.p) + ncand; a.path = path_h ? w.out.p + 2 * (size_t)ncand : nullptr;
+      CLSTM_LAUNCH(ctc_score_kernel<true>, dim3(ng), dim3(SCORE_THREADS), smem, s, a);
+      check_launch();
+      g_path_count[PC_SCORE]++;
+    }
+    HIPCHECK(hipMemcpyAsync(w.host, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (score_h) memcpy(score_h, w.host, (size_t)ncand * sizeof(float));
+    if (vscore_h) memcpy(vscore_h, w.host + ncand, (size_t)ncand * sizeof(float));
+    if (path_h) memcpy(path_h, w.host + 2 * (size_t)ncand, (size_t)pl.npath * sizeof(int));
+  }
+  for (int c = 0; c < ncand; c++) {   // a line without frames has no lattice
+    if (pl.path_off[c + 1] != pl.path_off[c]) continue;
+    if (score_h) score_h[c] = -INFINITY;
+    if (vscore_h) vscore_h[c] = -INFINITY;
+  }
+}
+
 static thread_local CtcWorkspace* g_ctc_ws = nullptr;
 static thread_local DecodeWorkspace* g_dec_ws = nullptr;
+static thread_local ScoreWorkspace* g_score_ws = nullptr;
 

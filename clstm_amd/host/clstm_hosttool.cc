@@ -103,8 +103,12 @@ int main(int argc, char** argv) {
       m.load(argv[2]);
       std::ofstream f(argv[3], std::ios::binary);
       f.write((const char*)m.params.data(), m.params.size() * 4);
+    } else if (cmd == "codec" && argc == 3) {  // the code point of every class of a model file, one per line
+      Model m;
+      m.load(argv[2]);
+      for (int c : m.codec) std::cout << c << std::endl;
     } else {
-      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params ...\n";
+      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params|codec ...\n";
       return 2;
     }
     return 0;

@@ -83,6 +83,8 @@ inline void trivial_decode_host(Classes& cs, const float* out, int T, int nc) {
 }
 
 struct CharPrediction { int i, x; char32_t c; float p; };
+// forced alignment: the frame columns x0 .. x1 a transcript's i-th character occupies on a best path (-1, -1: the path never visits it)
+struct CharSpan { int i, x0, x1; char32_t c; };
 
 // predict(): the forward pass belongs to no training step -- a non-finite logit there must not arm the device flag that blocks
 // updates (clstm_net_set_training; the reference only asserts in backward, clstm.cc:630-649)
@@ -383,6 +385,63 @@ struct CLSTMOCR {
     vector<const Image*> ptrs;
     for (size_t b = 0; b < raws.size(); b++) { normalize_line(frames[b], raws[b]); ptrs.push_back(&frames[b]); }
     predict_frames(ptrs, out, preds);
+  }
+  // ---- scores and forced alignments of known transcripts (clstm_net_score: the reference's forward_algorithm, ctc.cc:24-40, and its
+  // max-plus twin with a back-trace; include/clstm_abi.h states the semantics).  score_current works on the net's CURRENT
+  // minibatch, one transcript per line -- the lines of the last predict_frames() / predict_batch_gpu() (Ts = batch_T) or the line of
+  // the last predict() (Ts = {T}); either result may be null.  lines (optional): the line of each transcript, for several candidates
+  // per line or transcripts for some of the lines only.
+  void score_current(const vector<int>& Ts, const vector<ustring>& transcripts, vector<float>* scores, vector<vector<CharSpan>>* spans,
+                     const vector<int>* lines = nullptr) {
+    const int n = (int)transcripts.size();
+    if (n != (int)(lines ? lines->size() : Ts.size())) fail("score: one transcript per line expected");
+    if (n == 0) return;
+    vector<int> Tc;   // frames of each candidate's line
+    for (int c = 0; c < n; c++) {
+      const int b = lines ? (*lines)[c] : c;
+      if (b < 0 || b >= (int)Ts.size()) fail("score: no such line");
+      Tc.push_back(Ts[b]);
+    }
+    Classes labels, one;
+    vector<int> L;
+    for (const ustring& t : transcripts) {
+      codec.encode(one, t);
+      L.push_back((int)one.size());
+      labels.insert(labels.end(), one.begin(), one.end());
+    }
+    Classes dummy(1, 1);
+    size_t N = 0;
+    for (int t : Tc) N += t;
+    vector<int> path(spans ? std::max<size_t>(N, 1) : 0);
+    if (scores) scores->assign(n, 0.0f);
+    chk(clstm_net_score(net, labels.empty() ? dummy.data() : labels.data(), L.data(), lines ? lines->data() : nullptr, n, scores ? scores->data() : nullptr,
+                        nullptr, spans ? path.data() : nullptr), "clstm_net_score");
+    if (!spans) return;
+    spans->assign(n, vector<CharSpan>());
+    size_t o = 0;
+    for (int b = 0; b < n; b++) {
+      vector<CharSpan>& sp = (*spans)[b];
+      for (int k = 0; k < L[b]; k++) sp.push_back(CharSpan{k, -1, -1, transcripts[b][k]});
+      for (int t = 0; t < Tc[b]; t++) {
+        const int st = path[o + t];
+        if (st < 0 || st % 2 == 0) continue;   // a late start's prefix / a blank state; label k is state 2 k + 1
+        CharSpan& c = sp[st / 2];
+        if (c.x0 < 0) c.x0 = t;
+        c.x1 = t;
+      }
+      o += Tc[b];
+    }
+  }
+  // normalised lines (the frames path of predict_frames) against one transcript each
+  void score(const vector<const Image*>& lines, const vector<ustring>& transcripts, vector<float>& scores) {
+    vector<ustring> texts;
+    predict_frames(lines, texts);
+    score_current(batch_T, transcripts, &scores, nullptr);
+  }
+  void align(const vector<const Image*>& lines, const vector<ustring>& transcripts, vector<vector<CharSpan>>& spans) {
+    vector<ustring> texts;
+    predict_frames(lines, texts);
+    score_current(batch_T, transcripts, nullptr, &spans);
   }
   void get_outputs_batch(vector<Image>& outs) {   // [T_b][nclasses] of every line of the last predict_frames() minibatch
     int N = 0;

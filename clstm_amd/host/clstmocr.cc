@@ -34,6 +34,34 @@ static int main1(int argc, char** argv) {
   // CLSTMOCR::predict_batch_gpu -- CenterNormalizer on the device (clstm_normalizer_run_h), its frames handed to clstm_net_predict
   // where they lie.  The frames are the host normaliser's bit for bit, so the output is the same bytes.
   const bool gpu_prep = getienv("gpu_prep", 0) != 0;
+  // align=1 (default 0: nothing changes): for every input line with a ground truth beside it (<name up to its first '.'>.gt.txt) the
+  // forced alignment follows the line's ordinary output: "align <file>", then per ground-truth character "<char>\t<x0>\t<x1>" --
+  // the first and last frame column it occupies on the best path (-1 -1: never visited) --, then "end <score>" with the ground
+  // truth's CTC score on the line (CLSTMOCR::score)
+  const bool do_align = getienv("align", 0) != 0;
+  auto print_alignment = [&](const string& name, const vector<CharSpan>& spans, float score) {
+    std::cout << "align " << name << std::endl;
+    for (const CharSpan& c : spans) std::cout << utf32_to_utf8(ustring(1, c.c)) << "\t" << c.x0 << "\t" << c.x1 << std::endl;
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.9g", (double)score);
+    std::cout << "end " << buf << std::endl;
+  };
+  // false: no ground truth beside the line, or one the model's codec cannot encode (then "noalign <file>\t<reason>" is printed where
+  // the alignment would have stood, and recognition goes on)
+  vector<string> noalign;   // notes of the current chunk, by line index
+  auto ground_truth = [&](const string& name, ustring& gt, string* note) -> bool {
+    const string gtname = basename_noext(name) + ".gt.txt";
+    if (!std::ifstream(gtname)) return false;
+    gt = utf8_to_utf32(read_text(gtname));
+    try {
+      Classes cs;
+      clstm.codec.encode(cs, gt);
+    } catch (const std::exception& e) {
+      *note = "noalign " + name + "\t" + e.what();
+      return false;
+    }
+    return true;
+  };
   if (batch > 1 || gpu_prep) {
     if (output != "text" && output != "logs" && output != "posteriors") fail("unknown output format");
     vector<string> names;
@@ -70,6 +98,21 @@ static int main1(int argc, char** argv) {
       else clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
       vector<Image> posteriors;
       if (output != "text") clstm.get_outputs_batch(posteriors);
+      vector<vector<CharSpan>> spans;   // of the lines that have a ground truth, in input order
+      vector<int> gt_line;
+      vector<float> gt_score;
+      if (do_align) {
+        vector<ustring> gts;
+        noalign.assign(cur.names.size(), "");
+        for (size_t k = 0; k < cur.names.size(); k++) {
+          ustring gt;
+          if (!ground_truth(cur.names[k], gt, &noalign[k])) continue;
+          gt_line.push_back((int)k);
+          gts.push_back(gt);
+        }
+        clstm.score_current(clstm.batch_T, gts, &gt_score, &spans, &gt_line);
+      }
+      size_t next_gt = 0;
       for (size_t k = 0; k < cur.names.size(); k++) {
         const string& name = cur.names[k];
         string basename = name.substr(0, name.find_last_of("."));
@@ -89,6 +132,8 @@ static int main1(int argc, char** argv) {
             for (float& v : posteriors[k].d) v = scaled_log(v);
           write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), posteriors[k]);
         }
+        if (next_gt < gt_line.size() && gt_line[next_gt] == (int)k) { print_alignment(name, spans[next_gt], gt_score[next_gt]); next_gt++; }
+        else if (do_align && !noalign[k].empty()) std::cout << noalign[k] << std::endl;
       }
       if (helper.valid()) helper.get();
     }
@@ -122,6 +167,16 @@ static int main1(int argc, char** argv) {
         for (float& v : outputs.d) v = scaled_log(v);
       write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), outputs);
     } else fail("unknown output format");
+    ustring gt;
+    string note;
+    if (do_align && !ground_truth(line, gt, &note)) {
+      if (!note.empty()) std::cout << note << std::endl;
+    } else if (do_align) {
+      vector<vector<CharSpan>> spans;
+      vector<float> sc;
+      clstm.score_current(vector<int>(1, clstm.T), vector<ustring>(1, gt), &sc, &spans);
+      print_alignment(line, spans[0], sc[0]);
+    }
   }
   return 0;
 }

@@ -240,6 +240,7 @@ static int main1(int argc, char** argv) {
   // is trained on.
   const bool use_cache = getienv("cache", 1) != 0;
   const int test_batch = std::max(1, getienv("test_batch", batch));
+  const bool test_loss = getienv("test_loss", 0) != 0;   // (not in the reference) TESTLOSS line after every ERROR line
   const int prep_threads = std::max(1, std::min(getienv("prep_threads", 16), (int)std::thread::hardware_concurrency()));
   vector<std::shared_ptr<CLSTMOCR::Line>> cache(use_cache ? trainingset.size() : 0);
   auto draw = [&](CLSTMOCR::Prepared& p) {
@@ -368,7 +369,23 @@ static int main1(int argc, char** argv) {
       start_time = now();
     }
     if (test_trigger(tend) && testset.size() > 0 && lead) {
-      double count = 0.0, errors = 0.0;
+      double count = 0.0, errors = 0.0, loss = 0.0;
+      int loss_lines = 0;
+      // test_loss=1: every test line is also scored against its ground truth (clstm_net_score on the minibatch the recognition call
+      // left); a line whose ground truth the codec cannot encode is left out of the mean
+      auto add_loss = [&](const vector<int>& Ts, const vector<ustring>& tgts) {
+        vector<int> lines;
+        vector<ustring> known;
+        for (size_t k = 0; k < tgts.size(); k++) {
+          Classes cs;
+          try { clstm.codec.encode(cs, tgts[k]); } catch (const std::exception&) { continue; }
+          lines.push_back((int)k);
+          known.push_back(tgts[k]);
+        }
+        vector<float> sc;
+        clstm.score_current(Ts, known, &sc, nullptr, &lines);
+        for (float v : sc) { loss -= v; loss_lines++; }
+      };
       // test_batch=N (default: batch): the test set through clstm_net_predict_h in chunks of N lines (CLSTMOCR::predict_frames;
       // read + normalised on the preparation threads) instead of testset.size() single-line launches; 1: the reference's loop
       for (int test = 0; test_batch <= 1 && test < testset.size(); test++) {
@@ -376,6 +393,7 @@ static int main1(int argc, char** argv) {
         ustring tgt;
         testset.readSample(traw, tgt, test);
         ustring tpred = clstm.predict(traw);
+        if (test_loss) add_loss(vector<int>(1, clstm.T), vector<ustring>(1, tgt));
         count += tgt.size();
         errors += levenshtein(tpred, tgt);
       }
@@ -399,10 +417,12 @@ static int main1(int argc, char** argv) {
         for (auto& f : frames) ptrs.push_back(&f);
         if (gpu_prep) clstm.predict_batch_gpu(ptrs, tpreds);
         else clstm.predict_frames(ptrs, tpreds);
+        if (test_loss) add_loss(clstm.batch_T, tgts);
         for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += levenshtein(tpreds[k], tgts[k]); }
       }
       test_error = errors / count;
       std::cout << "ERROR " << trial << " " << test_error << "     " << errors << " " << count << std::endl;
+      if (test_loss) std::cout << "TESTLOSS " << trial << " " << (loss_lines ? loss / loss_lines : 0.0) << " " << loss_lines << std::endl;
       if (test_error < best_error) {
         best_error = test_error;
         string fname = save_name + ".clstm";

@@ -152,6 +152,44 @@ class Network:
         self.lib.call("clstm_net_ctc", self.h, ptr(labels), ptr(L), ptr(al))
         return al
 
+    def _score(self, transcripts, lines, want_score, want_vscore, want_path):
+        """clstm_net_score: candidate k is scored against line lines[k] of the current minibatch (None: one per line)."""
+        if lines is None:
+            assert len(transcripts) == len(self.T)
+            cl = None
+            T = self.T
+        else:
+            assert len(lines) == len(transcripts)
+            cl = i32(lines)
+            T = [self.T[b] if 0 <= b < len(self.T) else 0 for b in cl.tolist()]   # (the library refuses a bad index)
+        n = len(transcripts)
+        L = i32([len(t) for t in transcripts])
+        flat = [int(c) for t in transcripts for c in t]
+        labels = i32(flat if flat else [0])
+        score = np.empty(n, np.float32) if want_score else None
+        vscore = np.empty(n, np.float32) if want_vscore else None
+        path = np.empty(max(1, int(sum(T))), np.int32) if want_path else None
+        self.lib.call("clstm_net_score", self.h, ptr(labels), ptr(L), ptr(cl), n, ptr(score), ptr(vscore), ptr(path))
+        paths = None
+        if want_path:
+            paths, o = [], 0
+            for t in T:
+                paths.append(path[o:o + t].copy())
+                o += t
+        return score, vscore, paths
+
+    def score(self, transcripts, lines=None, viterbi=False):
+        """Per-candidate CTC score of `transcripts` against the current minibatch's outputs: the last cell of the reference's
+        forward_algorithm (ctc.cc:24-40; unnormalised, see include/clstm_abi.h).  lines: the line of each candidate (None: one
+        transcript per line).  viterbi=True: -> (score, vscore), vscore the best single path's score."""
+        s, v, _ = self._score(transcripts, lines, True, viterbi, False)
+        return (s, v) if viterbi else s
+
+    def align(self, transcripts, lines=None):
+        """Forced alignment: per candidate the state index occupied at every frame of its line on a best path (label k is
+        state 2k + 1, blanks the even states; -1 on frames before a late start).  See spans()."""
+        return self._score(transcripts, lines, False, False, True)[2]
+
     def backward(self):
         self.lib.call("clstm_net_backward", self.h)
 
@@ -444,6 +482,17 @@ def make_net(kind, ninput, noutput, nhidden, nhidden2=None, lib=None, **bufs):
 
 def sgd_update(net):
     net.update()
+
+
+def spans(path, L):
+    """Per label k < L of a transcript the (first_frame, last_frame) it occupies on `path` (Network.align): label k is state
+    2k + 1.  A label the path never visits gives (-1, -1)."""
+    path = np.asarray(path)
+    out = []
+    for k in range(int(L)):
+        f = np.flatnonzero(path == 2 * k + 1)
+        out.append((int(f[0]), int(f[-1])) if f.size else (-1, -1))
+    return out
 
 
 def mktargets(transcript):

@@ -102,6 +102,22 @@ int clstm_sgd_update(float* v, float* d, int len, float lr, float mom);
  * state_off_h[bs+1]: HOST.  Synchronous with respect to the host arrays (they are copied). */
 int clstm_ctc_align_batch(const float* probs, float* deltas, float* aligned, int nc,
                           const int* line_off_h, const int* states_h, const int* state_off_h, int bs);
+/* Score and force-align candidate transcripts: forward_algorithm (ctc.cc:24-40) over the match scores of ctc_align_targets
+ * (ctc.cc:66-77), per (line, candidate) item -- clstm_amd/csrc/ctc_score.h.  probs DEVICE [N][nc]; candidate c has the states
+ * [state_off_h[c], state_off_h[c+1]) (one class each, at least one) and belongs to line cand_line_h[c] (NULL: ncand == bs,
+ * candidate c <-> line c).  Results, HOST, each may be NULL (at least one must not be):
+ *   score_h  [ncand]  lr(T-1, S-1) of the recursion with skip = -5 and the reference's log_add (cut-off at 10).  This is the
+ *                     reference's UNNORMALISED score, not the textbook CTC likelihood: every state and frame carries a skip term
+ *                     and frame 0 of state 0 counts `same` and `next` both, so a good fit can score slightly above 0.
+ *   vscore_h [ncand]  the same recursion with max(same, next) in place of log_add: the score of a best path
+ *   path_h   packed   candidate c owns T(line of c) ints, in candidate order: the state occupied at each frame on a best path
+ *                     (back-trace from (T-1, S-1): advance iff next > same, ties stay); nondecreasing in steps of 0 or 1, ends in
+ *                     S-1; a path that enters state 0 late, at frame i0 > 0, carries -1 on the frames before i0.
+ * A line without frames: score = vscore = -INFINITY, no path entries.  A non-finite posterior: non-finite scores for that line's
+ * candidates, path entries still in [-1, S).  Everything is validated before anything is enqueued.  Blocking. */
+int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int bs, const int* states_h,
+                          const int* state_off_h, const int* cand_line_h, int ncand,
+                          float* score_h, float* vscore_h, int* path_h);
 /* mktargets  ctc.cc:148-157: 2L+1 state classes, blank (0) on even positions.  HOST arrays. */
 int clstm_mktargets(int* states_h, const int* transcript_h, int L);
 /* trivial_decode  ctc.cc:159-190 (+ argmax tensor.h:357-366), batched.  probs DEVICE [N][nc];
@@ -185,6 +201,13 @@ int clstm_net_set_output_deltas_h(clstm_net* net, const float* deltas_h);
  * every line of the batch.  labels_h packed transcripts, L_h[bs] lengths (HOST).
  * aligned_h (HOST, [N][nc]) may be NULL. */
 int clstm_net_ctc(clstm_net* net, const int* labels_h, const int* L_h, float* aligned_h);
+/* clstm_ctc_score_batch on the outputs of the net's current minibatch: labels_h packed transcripts, L_h[ncand]; mktargets is
+ * applied per candidate; cand_line_h[ncand] names each candidate's line (NULL: one per line, ncand == bs).  Needs a current
+ * minibatch; reads the outputs only, so it works after clstm_net_forward, after a training step and after clstm_net_predict.
+ * Rank-local with a communicator attached.  Deltas, gradients, parameters, the step count, the device error words and a declared
+ * next minibatch are untouched.  Kernel time under "ctc_score" (clstm_net_kernel_time_ms). */
+int clstm_net_score(clstm_net* net, const int* labels_h, const int* L_h, const int* cand_line_h, int ncand,
+                    float* score_h, float* vscore_h, int* path_h);
 /* net->backward(): accumulates this minibatch's gradient sum into grads (zeroed first). */
 int clstm_net_backward(clstm_net* net);
 /* input deltas of the first layer are only computed if enabled (nothing on the OCR path reads
@@ -414,6 +437,8 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *     their first step (lstm_xd_prologue.h), instead of a product launch of its own (experiment option xd_prologue=0);
  *  27  backward passes that took the producer form of the same instead (the default where Net::xd_mode admits it; xd_prologue=1: never): every recurrence workgroup
  *     computed only the 32 frames it visits first, helper workgroups of the launch the rest (26 does not move for them);
+ *  28  score launches (clstm_ctc_score_batch / clstm_net_score): one per form a call launched -- the sum form for score_h, the
+ *     max-plus form for vscore_h / path_h;
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
