@@ -1,5 +1,6 @@
 // abi.inc -- part of clstm_hip.hip: the extern "C" entry points of include/clstm_abi.h (per-op, CTC, fused network, one-call
-// training step, communicator, debug hooks).  Included once by clstm_hip.hip behind the namespace.
+// training step, communicator, debug hooks): argument checks and the call into net.inc / ctc_run.inc / step.inc -- the step sequence and
+// its launches are step.inc's.  Included once by clstm_hip.hip behind the namespace.
 using namespace clstm;
 struct clstm_net {
   // bytes held by the grow-only buffers of the members below (runtime.inc: AcctScope).  Declared first = destroyed last: the buffers
@@ -188,15 +189,6 @@ int clstm_net_buffers(clstm_net* h, float** v, float** d, float** g) {
   if (g) *g = h->net.g;
   return 0;
 }
-static void copy_h2d(float* dst, const float* src, size_t n) {
-  HIPCHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, g_stream));
-  HIPCHECK(hipStreamSynchronize(g_stream));
-}
-static void copy_d2h(float* dst, const float* src, size_t n) {
-  HIPCHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, g_stream));
-  HIPCHECK(hipStreamSynchronize(g_stream));
-  check_device_errors();   // whatever is read back was produced by launches whose outcome is known now
-}
 int clstm_net_set_params_h(clstm_net* h, const float* p) { ABI_BEGIN copy_h2d(h->net.v, p, h->net.nparams); h->net.packed_dirty = true; h->net.params_epoch++; ABI_END }
 int clstm_net_get_params_h(clstm_net* h, float* p) { ABI_BEGIN copy_d2h(p, h->net.v, h->net.nparams); ABI_END }
 int clstm_net_set_derivs_h(clstm_net* h, const float* p) { ABI_BEGIN copy_h2d(h->net.d, p, h->net.nparams); ABI_END }
@@ -217,48 +209,10 @@ int clstm_net_set_inputs_h(clstm_net* h, const float* x) {
   h->net.src0_ready = false;
   ABI_END
 }
-static void net_set_inputs_d(clstm_net* h, const float* x, const CtcMetaCopy* aux = nullptr) {
-  Net& n = h->net;
-  REQUIRE(n.N > 0, "set_batch first");
-  n.ensure_training_buffers();   // (the ingest writes layer 0's source rows)
-  RoctxRange range_("clstm:ingest");
-  Layer& y = n.L[0];
-  bool aux_done = false;
-  const bool with_pack = n.packed_dirty && n.L.size() == 1 && !y.wide;   // the training step of a narrow net: ingest + weight repack in one launch
-  if (with_pack || n.lo_pending || (aux && aux->nwords > 0)) {
-    // (any net: the small host arrays of the step ride the ingest launch -- a separate copy of the CTC metadata cost a
-    // configs[4] step ~25 us of DMA set-up in front of its first kernel)
-    const int M = n.ndir * 4 * y.no, KQP = 4 * y.nk4;
-    const size_t nr = (size_t)n.ndir * 4 * KQP * y.nthreads;
-    // (the ingest blocks' 16-byte form -- ops.h:k_ingest_pack -- has one item per four input floats: launching a thread per float
-    //  there dispatched 1,800 workgroups that found nothing to do)
-    const bool vec16 = (y.ni & 3) == 0 && (y.lds & 3) == 0 && ((size_t)x & 15) == 0;
-    const int nbi = nblocks(vec16 ? (size_t)n.N * (y.ni / 4 + 1) : (size_t)n.N * (1 + y.ni)), nbp = with_pack ? nblocks((size_t)(1 + y.ni) * M + 2 * nr) : 0;
-    const bool lo = n.lo_pending, ax = aux && aux->nwords > 0;
-    // optional trailing blocks read small host arrays straight from their pinned slots: the line offsets and -- in a
-    // training step -- the CTC metadata (no DMA launches, no event records on the stream's critical path)
-    CLSTM_LAUNCH(k_ingest_pack, dim3(nbi + nbp + (lo ? 1 : 0) + (ax ? (aux->nwords + 255) / 256 : 0)), dim3(256), 0, g_stream, x, n.X.p, y.S.p, (size_t)n.N, y.ni, y.lds,
-                 n.ndir, (long long)n.N * y.lds, nbi, nbp, (const float*)n.v, y.Wt, y.bias, y.Rf, y.Rb, y.pd, n.pack_fused_desc(y),
-                 lo ? n.lo_stage : nullptr, n.line_off.p, 2 * n.bs + 1, ax ? aux->src : nullptr, ax ? aux->dst : nullptr, ax ? aux->nwords : 0,
-                 with_pack ? (const int*)n.pack_table(y) : (const int*)nullptr);
-    if (lo) { n.ring.commit(g_stream); n.lo_pending = false; }
-    if (ax) { h->ctc.ring.commit(g_stream); aux_done = true; }
-    if (with_pack) n.packed_dirty = false;
-  } else {
-    CLSTM_LAUNCH(k_ingest, dim3(nblocks((size_t)n.N * (1 + y.ni))), dim3(256), 0, g_stream, x, n.X.p, y.S.p, (size_t)n.N, y.ni,
-                 y.lds, n.ndir, (long long)n.N * y.lds);
-  }
-  check_launch();
-  if (aux && aux->nwords > 0 && !aux_done) {   // not the fused launch: a plain asynchronous copy
-    HIPCHECK(hipMemcpyAsync(aux->dst, aux->src, (size_t)aux->nwords * sizeof(int), hipMemcpyHostToDevice, g_stream));
-    h->ctc.ring.commit(g_stream);
-  }
-  n.src0_ready = true;
-}
 int clstm_net_set_inputs_d(clstm_net* h, const float* x) {
   ABI_BEGIN
   h->net.next.valid = false;
-  net_set_inputs_d(h, x);
+  net_ingest(h->net, h->ctc, x);
   ABI_END
 }
 // (after clstm_net_train_step_next: the declared minibatch becomes the current one -- its outputs are addressable, and a later step
@@ -271,44 +225,11 @@ int clstm_net_outputs(clstm_net* h, float** p, float** d) {
 }
 int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN REQUIRE_CURRENT(h); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
 int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN REFUSE_NOSAVE(h, "clstm_net_set_output_deltas_h"); copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
-static void net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h, CtcMetaCopy* defer = nullptr,
-                    bool launch = true) {
-  Net& n = h->net;
-  REQUIRE(n.N > 0, "set_batch first");
-  std::vector<int> soff(n.bs + 1, 0), states;
-  int lpos = 0;
-  for (int b = 0; b < n.bs; b++) {
-    const int L = L_h[b];
-    REQUIRE(L >= 0, "negative transcript length");
-    states.resize(soff[b] + 2 * L + 1);
-    clstm_mktargets(states.data() + soff[b], labels_h + lpos, L);
-    for (int i = 0; i < L; i++) REQUIRE(labels_h[lpos + i] != 0, "transcript contains the blank class (Codec::encode asserts c != 0, clstm.cc:232)");
-    lpos += L;
-    soff[b + 1] = soff[b] + 2 * L + 1;
-  }
-  float* al = nullptr;
-  if (aligned_h) { n.aligned.reserve((size_t)n.N * n.desc.nclasses); al = n.aligned.p; }
-  RoctxRange range_(launch ? "clstm:ctc" : "clstm:ctc_prepare");
-  if (launch) n.timing.begin("ctc_align", g_stream);
-  run_ctc(h->ctc, n.Z.p, n.Dz.p, al, n.desc.nclasses, n.line_off_h.data(), states.data(), soff.data(), n.bs, g_stream, defer, launch);
-  if (launch) n.timing.end(g_stream);
-  if (aligned_h && launch) copy_d2h(aligned_h, al, (size_t)n.N * n.desc.nclasses);
-}
-// the alignment prepared by net_ctc(..., launch = false)
-static void net_ctc_launch(clstm_net* h) {
-  Net& n = h->net;
-  RoctxRange range_("clstm:ctc");
-  n.timing.begin("ctc_align", g_stream);
-  if (h->ctc.pending.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<true>, dim3(h->ctc.pending_bs), dim3(CTC_THREADS), h->ctc.pending_smem, g_stream, h->ctc.pending);
-  else CLSTM_LAUNCH(ctc_align_kernel<false>, dim3(h->ctc.pending_bs), dim3(CTC_THREADS), h->ctc.pending_smem, g_stream, h->ctc.pending);
-  check_launch();
-  n.timing.end(g_stream);
-}
 int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h) {
   ABI_BEGIN
   REQUIRE_CURRENT(h);
   REFUSE_NOSAVE(h, "clstm_net_ctc");
-  net_ctc(h, labels_h, L_h, aligned_h);
+  net_ctc(h->net, h->ctc, Minibatch{nullptr, h->net.bs, nullptr, labels_h, L_h}, aligned_h);
   ABI_END
 }
 // score / forced alignment of candidate transcripts against the current minibatch: reads Z only (so it also follows clstm_net_predict),
@@ -322,17 +243,8 @@ int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int
   REQUIRE(n.N > 0, "set_batch first");
   REQUIRE(score_h || vscore_h || path_h, "clstm_net_score: score_h, vscore_h and path_h are all NULL");
   REQUIRE(labels_h && L_h && ncand > 0, "null argument / no candidates");
-  std::vector<int> soff(ncand + 1, 0), states;
-  int lpos = 0;
-  for (int c = 0; c < ncand; c++) {
-    const int L = L_h[c];
-    REQUIRE(L >= 0, "negative transcript length");
-    states.resize(soff[c] + 2 * L + 1);
-    clstm_mktargets(states.data() + soff[c], labels_h + lpos, L);
-    for (int i = 0; i < L; i++) REQUIRE(labels_h[lpos + i] != 0, "transcript contains the blank class (Codec::encode asserts c != 0, clstm.cc:232)");
-    lpos += L;
-    soff[c + 1] = soff[c] + 2 * L + 1;
-  }
+  std::vector<int> soff, states;
+  expand_transcripts(labels_h, L_h, ncand, states, soff);
   RoctxRange range_("clstm:score");
   n.timing.begin("ctc_score", g_stream);
   struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
@@ -340,7 +252,7 @@ int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int
                 score_h, vscore_h, path_h, g_stream);
   ABI_END
 }
-int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.fuse_update = false; h->net.peer_step = false; h->net.backward(); ABI_END }
+int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.backward(); ABI_END }
 int clstm_net_enable_input_deltas(clstm_net* h, int on) { h->net.want_dx0 = on != 0; return 0; }
 int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
   ABI_BEGIN
@@ -349,7 +261,8 @@ int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
   copy_d2h(dx, h->net.dX0.p, (size_t)h->net.N * h->net.desc.ninput);
   ABI_END
 }
-int clstm_net_update(clstm_net* h) { ABI_BEGIN h->net.update(); ABI_END }
+// (a backward pass of its own call ran the default plan: it left nothing for the update -- net.inc: StepPlan, PassLeft)
+int clstm_net_update(clstm_net* h) { ABI_BEGIN PassLeft nothing; h->net.update(nothing); ABI_END }
 int clstm_net_decode(clstm_net* h, int* cls, int* locs, int* cnt) {
   ABI_BEGIN
   REQUIRE_CURRENT(h);
@@ -457,10 +370,7 @@ int clstm_net_set_gemm_precision(clstm_net* h, int mode) {
   n.bf16_rec = rec;
   if (n.N > 0 && rec)   // a batch is already declared: make room for the bf16 operand copies
     for (auto& y : n.L)
-      if (y.wide) {
-        y.Hb.reserve((size_t)std::max<long long>(n.N, 4LL * n.bs + 32) * n.ndir * wide_kp16_fwd(y.no) + 64);
-        y.Db.reserve((size_t)std::max<long long>(n.N, 2LL * n.bs + 32) * n.ndir * wide_kp16_bwd(y.no) + 64);
-      }
+      if (y.wide) n.reserve_wide_rings(y);
   ABI_END
 }
 int clstm_net_enable_timing(clstm_net* h, int on) { h->net.timing.on = on != 0; return 0; }
@@ -474,148 +384,29 @@ int clstm_net_kernel_time_ms(clstm_net* h, const char* name, double* total_ms, i
 }
 int clstm_net_reset_timing(clstm_net* h) { ABI_BEGIN h->net.timing.collect(g_stream); h->net.timing.acc.clear(); ABI_END }
 
-// ---- one-call training step ---------------------------------------------------------------------------
-// The same step for a loop that knows its NEXT minibatch (all of the `n` arguments NULL / 0: exactly clstm_net_train_step).  The front
-// half of the next step -- batch geometry, the host half of its alignment, the ingest of its frames, the copies of its line offsets
-// and CTC metadata -- is done HERE: on the host while this step's launches run, on the device by extra workgroups of this step's last
-// launch (the slab reduction + fused update; ops.h: k_reduce_scatter_ingest), whose CUs are mostly idle.  The next call finds its
-// minibatch declared (same x pointer, same T / transcripts: compared by content) and starts with the forward launch; anything
-// else -- another minibatch, clstm_net_set_batch in between, a communicator of several ranks, a net whose update does not keep
-// its packed weights current -- takes the ordinary path.  Between the two calls the net's per-batch accessors (outputs,
-// decode, states) have no valid batch to refer to and refuse.
+// ---- one-call training step (step.inc: train_step) -------------------------------------------------------
+// The same step for a loop that knows its NEXT minibatch (all of the `n` arguments NULL / 0: exactly clstm_net_train_step): its front
+// half rides this step's last launch, and the next call -- which must bring that very minibatch -- starts with the forward launch.
+// Between the two calls the net's per-batch accessors (outputs, decode, states) have no valid batch to refer to and refuse.
 int clstm_net_train_step_next(clstm_net* h, const int* T_h, int bs, const float* x_d, const int* labels_h, const int* L_h,
                               const int* Tn_h, int bsn, const float* xn_d, const int* labels_n_h, const int* Ln_h) {
   ABI_BEGIN
   REQUIRE(h && T_h && x_d && labels_h && L_h, "null argument");
-  Net& n = h->net;
-  if (n.next.matches(T_h, bs, x_d, labels_h, L_h) && n.src0_ready && !n.lo_pending) {
-    n.next.valid = false;                  // declared and ingested by the previous call's tail
-    g_path_count[PC_INGEST_TAIL_USED]++;
-  } else {
-    n.set_batch(T_h, bs);
-    CtcMetaCopy meta;
-    net_ctc(h, labels_h, L_h, nullptr, &meta, false);
-    net_set_inputs_d(h, x_d, &meta);
-  }
-  n.forward();
-  net_ctc_launch(h);
-  n.fuse_update = n.fuse_eligible();
-  n.peer_step = n.comm && n.comm->nranks > 1 && n.comm->peer_ready((size_t)n.nparams, g_stream);
-  const bool want_next = Tn_h && xn_d && labels_n_h && Ln_h && bsn > 0 && n.fuse_update;
-  n.defer_last_reduce = want_next;
-  try { n.backward(); } catch (...) { n.defer_last_reduce = false; n.deferred.armed = false; throw; }
-  n.defer_last_reduce = false;
-  if (n.deferred.armed) {
-    // (a single narrow layer whose update does not keep the packed weights current: its ingest launch also repacks -- not the tail's job)
-    bool tail = !(n.L.size() == 1 && !n.L[0].wide && !n.packs_follow_update);
-    if (tail) {
-      try {
-        n.set_batch(Tn_h, bsn);
-        CtcMetaCopy meta;
-        net_ctc(h, labels_n_h, Ln_h, nullptr, &meta, false);
-        Layer& y = n.L[0];
-        const bool vec16 = (y.ni & 3) == 0 && (y.lds & 3) == 0 && ((size_t)xn_d & 15) == 0;
-        IngestTail t{};
-        t.x = xn_d; t.X = n.X.p; t.S = y.S.p; t.N = (unsigned long long)n.N; t.ni = y.ni; t.lds = y.lds; t.ndir = n.ndir; t.sdir = (long long)n.N * y.lds;
-        t.nbi = nblocks(vec16 ? (size_t)n.N * (y.ni / 4 + 1) : (size_t)n.N * (1 + y.ni));
-        t.lo_src = n.lo_pending ? n.lo_stage : nullptr; t.lo_dst = n.line_off.p; t.lo_n = 2 * n.bs + 1;
-        t.aux_src = meta.nwords > 0 ? meta.src : nullptr; t.aux_dst = meta.dst; t.aux_n = meta.nwords;
-        n.launch_deferred_reduce(&t);
-        if (t.lo_src) { n.ring.commit(g_stream); n.lo_pending = false; }
-        if (t.aux_src) h->ctc.ring.commit(g_stream);
-        n.src0_ready = true;
-        n.next.remember(Tn_h, bsn, xn_d, labels_n_h, Ln_h);
-      } catch (...) {
-        // the NEXT minibatch is at fault (a bad label, a size): this step still completes; the next call declares its minibatch
-        // itself and reports the error where it belongs
-        n.next.valid = false;
-        tail = false;
-      }
-    }
-    if (!tail) n.launch_deferred_reduce(nullptr);
-  }
-  n.update();
+  train_step(h->net, h->ctc, Minibatch{T_h, bs, x_d, labels_h, L_h}, Minibatch{Tn_h, bsn, xn_d, labels_n_h, Ln_h}, nullptr);
   ABI_END
 }
-// (no exchange between backward pass and update -- no communicator, or one of a single rank: the reductions of the backward pass
-//  apply the update themselves; a communicator of several ranks: the peer-read all-reduce fused into the update where the ranks
-//  could map each other, else ncclAllReduce + k_update)
 int clstm_net_train_step(clstm_net* h, const int* T_h, int bs, const float* x_d, const int* labels_h, const int* L_h) {
   return clstm_net_train_step_next(h, T_h, bs, x_d, labels_h, L_h, nullptr, 0, nullptr, nullptr, nullptr);
 }
-
 // host frames in, no host synchronisation: see Net::HostFeed
 int clstm_net_train_step_h(clstm_net* h, const int* T_h, int bs, const float* x_h, const int* labels_h, const int* L_h) {
   ABI_BEGIN
   REQUIRE(h && T_h && x_h && labels_h && L_h && bs > 0, "null argument");
   Net& n = h->net;
-  Net::HostFeed& f = n.hf;
-  long long N = 0;
-  for (int b = 0; b < bs; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); N += T_h[b]; }
-  REQUIRE(N > 0, "batch has no frames");
-  const size_t bytes = (size_t)N * n.desc.ninput * sizeof(float);
-  if (!f.ready) {
-    f.ready = true;
-    HIPCHECK(hipStreamCreateWithFlags(&f.cs, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) HIPCHECK(hipEventCreateWithFlags(&f.copied[i], hipEventDisableTiming));
-    HIPCHECK(hipHostMalloc((void**)&f.step_done, 64));
-    *f.step_done = 0;
-  }
-  // This step's number (1, 2, ...) is COMMITTED only when its last kernel -- the one that publishes it in the pinned word --
-  // has been enqueued: a call that fails on the way (a bad label, a launch error) leaves f.steps where it was, so the next
-  // call reuses number and slot and never waits for a step that was not enqueued (two failed calls in a row used to spin
-  // here for ever).
-  const long long k = f.steps + 1;
-  const int slot = (int)(k & 1);
-  // the slot was read by step k - 2: its update kernel has run when the pinned word says so (the host is at most a few
-  // steps ahead of the GPU, so this rarely waits).  Bounded: after ~2 s of yielding the stream is drained instead --
-  // everything enqueued has then run, whatever the word says.
-  {
-    const auto t0 = std::chrono::steady_clock::now();
-    int spins = 0;
-    while (k > 2 && (int)((unsigned)(k - 2) - (unsigned)__atomic_load_n(f.step_done, __ATOMIC_ACQUIRE)) > 0) {   // (wrap-safe)
-      sched_yield();
-      if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-        HIPCHECK(hipStreamSynchronize(g_stream));
-        check_device_errors();
-        break;
-      }
-    }
-  }
-  f.xin[slot].reserve((size_t)N * n.desc.ninput + 64);
-  const void* src = x_h;
-#ifndef CLSTM_HIP_EMU
-  hipPointerAttribute_t attr;
-  const bool pinned = hipPointerGetAttributes(&attr, x_h) == hipSuccess && attr.type == hipMemoryTypeHost;
-  if (!pinned) {   // pageable memory: one host copy into the slot's pinned staging buffer, then the same DMA
-    (void)hipGetLastError();
-    if (f.pin_cap[slot] < bytes) {
-      if (f.pin[slot]) HIPCHECK(hipHostFree(f.pin[slot]));
-      f.pin_cap[slot] = bytes + bytes / 4;
-      HIPCHECK(hipHostMalloc(&f.pin[slot], f.pin_cap[slot]));
-    }
-    memcpy(f.pin[slot], x_h, bytes);
-    src = f.pin[slot];
-  }
-#endif
-  HIPCHECK(hipMemcpyAsync(f.xin[slot].p, src, bytes, hipMemcpyHostToDevice, f.cs));
-  HIPCHECK(hipEventRecord(f.copied[slot], f.cs));
-  HIPCHECK(hipStreamWaitEvent(g_stream, f.copied[slot], 0));
-  n.set_batch(T_h, bs);
-  CtcMetaCopy meta;
-  net_ctc(h, labels_h, L_h, nullptr, &meta, false);
-  net_set_inputs_d(h, f.xin[slot].p, &meta);
-  n.forward();
-  net_ctc_launch(h);
-  n.update_step_word = f.step_done; n.update_step_id = (int)(unsigned)k;
-  n.fuse_update = n.fuse_eligible();
-  n.peer_step = n.comm && n.comm->nranks > 1 && n.comm->peer_ready((size_t)n.nparams, g_stream);
-  try {
-    n.backward();
-    n.update();
-  } catch (...) { n.update_step_word = nullptr; throw; }
-  REQUIRE(n.update_step_word == nullptr, "internal: no kernel of the step took the step word");
-  f.steps = k;
+  const long long N = batch_frames(T_h, bs);
+  HostTicket ticket;
+  const float* x_d = n.hf.stage(x_h, (size_t)N * n.desc.ninput, ticket);
+  train_step(n, h->ctc, Minibatch{T_h, bs, x_d, labels_h, L_h}, Minibatch{}, &ticket);
   ABI_END
 }
 int clstm_host_alloc(void** p, size_t bytes) { ABI_BEGIN REQUIRE(p, "null argument"); HIPCHECK(hipHostMalloc(p, bytes ? bytes : 1)); ABI_END }

@@ -11,6 +11,8 @@
 //             dX = W_x^T.delta (MFMA GEMM, only where a consumer exists)
 //   update  : k_update on the flat reference-layout buffers, then re-pack kernel weights.
 // Stacked/Parallel/Reversed never copy: they are pointer hand-offs and index arithmetic.
+// The host side is the .inc files below: net.inc decides (one scheduler each for the forward pass, the backward pass and the
+// plan of a step), step.inc is the one training-step sequence, abi.inc is the boundary: argument checks and calls.
 #include "../../include/clstm_abi.h"
 #include "dbgopt.h"
 #include "ctc.h"
@@ -44,8 +46,9 @@
 
 namespace clstm {
 #include "runtime.inc"   // errors, buffers, launch helpers, timing
-#include "net.inc"       // Layer / Net: the step scheduler
-#include "ctc_run.inc"   // CTC / decode launches, host side
+#include "net.inc"       // Layer / Net: the schedulers of the forward pass, the backward pass and the step plan
+#include "ctc_run.inc"   // CTC / score / decode launches, host side
+#include "step.inc"      // one training step: the sequence, its ingest and alignment launches
 #include "normalize_run.inc"   // the line normaliser (normalize.h), host side
 }  // namespace clstm
 

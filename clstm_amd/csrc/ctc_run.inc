@@ -1,4 +1,5 @@
-// ctc_run.inc -- part of clstm_hip.hip (namespace clstm): host side of the CTC and decode launches (workspaces, metadata staging).
+// ctc_run.inc -- part of clstm_hip.hip (namespace clstm): host side of the CTC, score and decode launches (workspaces, metadata staging,
+// the table upload, transcript expansion and the one alignment launch site).
 static thread_local long long* g_last_ctc_prof = nullptr;
 // CTC on an arbitrary packed batch (used by the net and by the stand-alone ABI entry)
 struct CtcWorkspace {
@@ -11,6 +12,38 @@ struct CtcWorkspace {
   DevBuf<char> meta;
   DevBuf<float> lat;
 };
+// the ctc_tables.h block (ctc.h: CTC_TABLE_DOUBLES) in a workspace's own device buffer, uploaded when the workspace first needs it
+static void upload_ctc_tables(DevBuf<double>& tables) {
+  if (tables.p) return;
+  tables.reserve(CTC_TABLE_DOUBLES);
+  std::vector<double> tb(CTC_TABLE_DOUBLES);
+  for (int i = 0; i < 32; i++) tb[i] = CTC_EXP2_32[i];
+  for (int i = 0; i < 64; i++) { tb[32 + i] = CTC_LOG_INVC[i]; tb[96 + i] = CTC_LOG_LOGC[i]; }
+  for (int k = 0; k < 2 * CTC_SP_KMAX + 1; k++)
+    for (int c = 0; c < 4; c++) tb[160 + 4 * k + c] = CTC_SOFTPLUS[k][c];
+  HIPCHECK(hipMemcpy(tables.p, tb.data(), CTC_TABLE_DOUBLES * sizeof(double), hipMemcpyHostToDevice));
+}
+// the alignment run_ctc prepared (w.pending): at once, or -- in a training step -- behind the forward pass (step.inc)
+static void launch_ctc_align(const CtcWorkspace& w, hipStream_t s) {
+  if (!w.pending.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<false>, dim3(w.pending_bs), dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  else CLSTM_LAUNCH(ctc_align_kernel<true>, dim3(w.pending_bs), dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  check_launch();
+}
+// n transcripts (packed labels, lengths) as blank-interleaved target states (clstm_mktargets) with their offsets: what the alignment
+// and the score take
+static void expand_transcripts(const int* labels_h, const int* L_h, int n, std::vector<int>& states, std::vector<int>& soff) {
+  soff.assign(n + 1, 0);
+  int lpos = 0;
+  for (int b = 0; b < n; b++) {
+    const int L = L_h[b];
+    REQUIRE(L >= 0, "negative transcript length");
+    states.resize(soff[b] + 2 * L + 1);
+    clstm_mktargets(states.data() + soff[b], labels_h + lpos, L);
+    for (int i = 0; i < L; i++) REQUIRE(labels_h[lpos + i] != 0, "transcript contains the blank class (Codec::encode asserts c != 0, clstm.cc:232)");
+    lpos += L;
+    soff[b + 1] = soff[b] + 2 * L + 1;
+  }
+}
 // The per-minibatch metadata block [line records | states] is staged in a pinned slot;
 // `defer` (non-null): do not enqueue its copy -- the caller folds it into a kernel it launches anyway before the CTC
 // kernel (the input-ingest launch of a training step) and receives source, destination and size here.
@@ -59,15 +92,7 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   a.lat = w.lat.p; a.nc = nc;
   w.prof.reserve(16); a.prof = w.prof.p; g_last_ctc_prof = w.prof.p;
   a.float_logadd = dbg_opt("ctc_float") != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
-  if (!w.tables.p) {
-    w.tables.reserve(CTC_TABLE_DOUBLES);
-    std::vector<double> tb(CTC_TABLE_DOUBLES);
-    for (int i = 0; i < 32; i++) tb[i] = CTC_EXP2_32[i];
-    for (int i = 0; i < 64; i++) { tb[32 + i] = CTC_LOG_INVC[i]; tb[96 + i] = CTC_LOG_LOGC[i]; }
-    for (int k = 0; k < 2 * CTC_SP_KMAX + 1; k++)
-      for (int c = 0; c < 4; c++) tb[160 + 4 * k + c] = CTC_SOFTPLUS[k][c];
-    HIPCHECK(hipMemcpy(w.tables.p, tb.data(), CTC_TABLE_DOUBLES * sizeof(double), hipMemcpyHostToDevice));
-  }
+  upload_ctc_tables(w.tables);
   a.tables = w.tables.p;
   int smax = 1, tmax = 1;
   for (int b = 0; b < bs; b++) {
@@ -95,19 +120,13 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   }
 #endif
   w.pending = a; w.pending_smem = smem; w.pending_bs = bs;
-  if (launch) {
-    if (a.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<true>, dim3(bs), dim3(CTC_THREADS), smem, s, a);
-    else CLSTM_LAUNCH(ctc_align_kernel<false>, dim3(bs), dim3(CTC_THREADS), smem, s, a);
-    check_launch();
-  }
+  if (launch) launch_ctc_align(w, s);
 }
 struct DecodeWorkspace {
   DevBuf<int> line_off, idx;
   DevBuf<float> val;
   DevBuf<int> out;            // [counts bs | classes N | locs N | peak values N (float bits)]: ONE copy brings the results back
-  int* host = nullptr;        // pinned landing buffer of that copy
-  size_t host_cap = 0;
-  ~DecodeWorkspace() { if (host) (void)hipHostFree(host); }
+  PinnedBuf<int> host;       // pinned landing buffer of that copy
 };
 // conf_h (may be null): the peak value of every emitted class (decode_kernel: out_val)
 static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs,
@@ -116,12 +135,7 @@ static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int
   REQUIRE(bs > 0 && N > 0, "empty batch");
   const size_t nout = (size_t)bs + 3 * (size_t)N;
   w.line_off.reserve(bs + 1); w.idx.reserve(N); w.val.reserve(N); w.out.reserve(nout);
-  if (w.host_cap < nout) {
-    if (w.host) HIPCHECK(hipHostFree(w.host));
-    w.host = nullptr; w.host_cap = 0;
-    HIPCHECK(hipHostMalloc((void**)&w.host, (nout + nout / 4 + 64) * sizeof(int)));
-    w.host_cap = nout + nout / 4 + 64;
-  }
+  w.host.reserve(nout);
   int* cnt_d = w.out.p; int* cls_d = cnt_d + bs; int* loc_d = cls_d + N; float* conf_d = reinterpret_cast<float*>(loc_d + N);
   HIPCHECK(hipMemcpyAsync(w.line_off.p, line_off_h, (bs + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   CLSTM_LAUNCH(argmax_kernel, dim3((N + 255) / 256), dim3(256), 0, s, probs, w.idx.p, w.val.p, N, nc);
@@ -132,12 +146,12 @@ static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int
   //  predict's one-launch ingest: set_batch + set_inputs_d + forward + decode 199 -> 172 us per call, clstm_net_predict with conf 210 ->
   //  172 us; EXPERIMENTS 13.4)
   const size_t ncopy = (size_t)bs + (conf_h ? 3 : locs_h ? 2 : classes_h ? 1 : 0) * (size_t)N;
-  HIPCHECK(hipMemcpyAsync(w.host, w.out.p, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  memcpy(counts_h, w.host, (size_t)bs * sizeof(int));
-  if (classes_h) memcpy(classes_h, w.host + bs, (size_t)N * sizeof(int));
-  if (locs_h) memcpy(locs_h, w.host + bs + N, (size_t)N * sizeof(int));
-  if (conf_h) memcpy(conf_h, w.host + bs + 2 * (size_t)N, (size_t)N * sizeof(float));
+  memcpy(counts_h, w.host.p, (size_t)bs * sizeof(int));
+  if (classes_h) memcpy(classes_h, w.host.p + bs, (size_t)N * sizeof(int));
+  if (locs_h) memcpy(locs_h, w.host.p + bs + N, (size_t)N * sizeof(int));
+  if (conf_h) memcpy(conf_h, w.host.p + bs + 2 * (size_t)N, (size_t)N * sizeof(float));
 }
 
 // ---- scores and forced alignments (ctc_score.h) ------------------------------------------------------------------------
@@ -149,9 +163,7 @@ struct ScoreWorkspace {
   DevBuf<char> meta;
   DevBuf<unsigned long long> ws;
   DevBuf<int> out;            // [score ncand | vscore ncand (float bits) | paths]: ONE copy brings the results back
-  int* host = nullptr;        // pinned landing buffer of that copy
-  size_t host_cap = 0;
-  ~ScoreWorkspace() { if (host) (void)hipHostFree(host); }
+  PinnedBuf<int> host;       // pinned landing buffer of that copy
 };
 // what the launch will be, decided on the host from the arguments alone (nothing is enqueued while this can still refuse)
 struct ScorePlan {
@@ -252,21 +264,8 @@ static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const i
     w.meta.reserve(ngr + nit + nst);
     w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
     w.out.reserve(nout);
-    if (w.host_cap < nout) {
-      if (w.host) HIPCHECK(hipHostFree(w.host));
-      w.host = nullptr; w.host_cap = 0;
-      HIPCHECK(hipHostMalloc((void**)&w.host, (nout + nout / 4 + 64) * sizeof(int)));
-      w.host_cap = nout + nout / 4 + 64;
-    }
-    if (!w.tables.p) {
-      w.tables.reserve(CTC_TABLE_DOUBLES);
-      std::vector<double> tb(CTC_TABLE_DOUBLES);
-      for (int i = 0; i < 32; i++) tb[i] = CTC_EXP2_32[i];
-      for (int i = 0; i < 64; i++) { tb[32 + i] = CTC_LOG_INVC[i]; tb[96 + i] = CTC_LOG_LOGC[i]; }
-      for (int k = 0; k < 2 * CTC_SP_KMAX + 1; k++)
-        for (int c = 0; c < 4; c++) tb[160 + 4 * k + c] = CTC_SOFTPLUS[k][c];
-      HIPCHECK(hipMemcpy(w.tables.p, tb.data(), CTC_TABLE_DOUBLES * sizeof(double), hipMemcpyHostToDevice));
-    }
+    w.host.reserve(nout);
+    upload_ctc_tables(w.tables);
     char* stage = (char*)w.ring.acquire(ngr + nit + nst);   // one pinned slot, one copy: [groups | items | states]
     memcpy(stage, pl.groups.data(), ngr);
     memcpy(stage + ngr, pl.items.data(), nit);
@@ -300,11 +299,11 @@ static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const i
       check_launch();
       g_path_count[PC_SCORE]++;
     }
-    HIPCHECK(hipMemcpyAsync(w.host, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
-    if (score_h) memcpy(score_h, w.host, (size_t)ncand * sizeof(float));
-    if (vscore_h) memcpy(vscore_h, w.host + ncand, (size_t)ncand * sizeof(float));
-    if (path_h) memcpy(path_h, w.host + 2 * (size_t)ncand, (size_t)pl.npath * sizeof(int));
+    if (score_h) memcpy(score_h, w.host.p, (size_t)ncand * sizeof(float));
+    if (vscore_h) memcpy(vscore_h, w.host.p + ncand, (size_t)ncand * sizeof(float));
+    if (path_h) memcpy(path_h, w.host.p + 2 * (size_t)ncand, (size_t)pl.npath * sizeof(int));
   }
   for (int c = 0; c < ncand; c++) {   // a line without frames has no lattice
     if (pl.path_off[c + 1] != pl.path_off[c]) continue;

@@ -5,6 +5,8 @@
 // layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by the same answer.
 // Likewise the backward pass: Net::backward_family names a layer's family; backward() is backward_softmax, then per layer the
 // recurrence, the layer's BwdPlan (decided ONCE, behind the recurrence launch), the weight gradient, the input deltas.
+// And the step: Net::step_plan decides a StepPlan ONCE per training step; backward(plan) returns what the pass left (PassLeft) and
+// update(left) consumes it -- nothing of a step's plan is a member of Net.  The step sequence itself is step.inc.
 // Not a stand-alone header: included once by clstm_hip.hip behind runtime.inc.
 struct Layer {
   int ni, no, nk4, nthreads;
@@ -73,6 +75,39 @@ struct BwdPlan {
   int dw_rows, ns;       // ns: split-K slabs per direction the reduction will find
 };
 
+// host-side view of one minibatch as the step entries take it: line lengths, frames, packed transcripts and their lengths
+struct Minibatch {
+  const int* T; int bs; const float* x; const int* labels; const int* L;
+  bool given() const { return T && x && labels && L && bs > 0; }
+};
+// frames of a minibatch whose line lengths are acceptable
+static long long batch_frames(const int* T_h, int nb) {
+  long long n = 0;
+  for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
+  REQUIRE(n > 0, "batch has no frames");
+  return n;
+}
+// (host-fed steps) the pinned word the step's last kernel writes `id` into, and that number: Net::HostFeed::stage
+struct HostTicket { int* word = nullptr; int id = 0; };
+// The plan of one training step, decided once (Net::step_plan) and passed by value.  The default is the plan of separate calls:
+// clstm_net_backward leaves the gradient in g, clstm_net_update exchanges it if there are ranks and launches k_update.
+struct StepPlan {
+  bool fuse = false;         // the update rides the slab reductions of the backward pass
+  bool peer = false;         // the gradient goes into the communicator's exchange slot: update() runs the peer-read all-reduce fused with the update
+  bool defer_last = false;   // the last reduction is described instead of enqueued: the next minibatch's ingest goes behind it (step.inc)
+  HostTicket ticket;         // host-fed step: its last kernel publishes the step number
+};
+// the last reduction launch of a fused-update step, described (gates ... q) and not yet enqueued: Net::launch_deferred_reduce
+struct DeferredReduce { bool armed = false; ReduceDesc gates, extra; float* gdst = nullptr; UpdateFuse uf; size_t work = 0; hipStream_t q = nullptr; };
+// what a backward pass left behind for update()
+struct PassLeft {
+  bool update_applied = false;        // the reductions applied the update: update() has nothing left to launch
+  bool packs_follow_update = false;   // ... and rewrote the packed copies of the parameters they moved
+  bool peer_pending = false;          // the gradient is in the exchange slot
+  DeferredReduce deferred;
+  HostTicket ticket;                  // word: null once a kernel of the step has taken it
+};
+
 struct Net {
   clstm_net_desc desc;
   int ndir;
@@ -111,10 +146,6 @@ struct Net {
   DevBuf<long long> lstm_prof;  // diagnostics build only
   StepGraphCache step_graphs;   // captured per-step launch sequences of the lock-step recurrence
   DevBuf<int> coop_sync;      // grid-barrier ticket counter + watchdog flag of the cooperative recurrence
-  // ctc / decode
-  DevBuf<int> states, state_off, dec_idx, dec_cls, dec_loc, dec_cnt;
-  DevBuf<float> dec_val, lat;
-  DevBuf<long long> lat_off;
   Timing timing;
   // --- weight-gradient GEMM beside the backward recurrence (gemm_dw.h) ---
   static const int PROG_LINES = 2048;                          // overlap only for minibatches up to this many lines
@@ -146,11 +177,61 @@ struct Net {
     hipStream_t cs = nullptr;
     hipEvent_t copied[2] = {};
     DevBuf<float> xin[2];
-    void* pin[2] = {nullptr, nullptr};     // staging for pageable sources
-    size_t pin_cap[2] = {0, 0};
+    PinnedBuf<char> pin[2];                // staging for pageable sources
     int* step_done = nullptr;              // pinned: number of the last step whose update kernel has run
     long long steps = 0;
     bool ready = false;
+    // The slot for the next step's `nfloats` frames at x_h: waits until the step that last read it has ended, copies the frames in
+    // on the copy stream and makes the compute stream wait for them.  Returns the device frames and the step's ticket.
+    // The step's number (1, 2, ...) is COMMITTED (commit) only when its last kernel -- the one that publishes it in the pinned
+    // word -- has been enqueued: a call that fails on the way (a bad label, a launch error) leaves `steps` where it was, so the
+    // next call reuses number and slot and never waits for a step that was not enqueued (two failed calls in a row used to spin
+    // here for ever).
+    const float* stage(const float* x_h, size_t nfloats, HostTicket& ticket) {
+      if (!ready) {
+        ready = true;
+        HIPCHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        for (int i = 0; i < 2; i++) HIPCHECK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
+        HIPCHECK(hipHostMalloc((void**)&step_done, 64));
+        *step_done = 0;
+      }
+      const long long k = steps + 1;
+      const int slot = (int)(k & 1);
+      // the slot was read by step k - 2: its update kernel has run when the pinned word says so (the host is at most a few
+      // steps ahead of the GPU, so this rarely waits).  Bounded: after ~2 s of yielding the stream is drained instead --
+      // everything enqueued has then run, whatever the word says.
+      {
+        const auto t0 = std::chrono::steady_clock::now();
+        int spins = 0;
+        while (k > 2 && (int)((unsigned)(k - 2) - (unsigned)__atomic_load_n(step_done, __ATOMIC_ACQUIRE)) > 0) {   // (wrap-safe)
+          sched_yield();
+          if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
+            HIPCHECK(hipStreamSynchronize(g_stream));
+            check_device_errors();
+            break;
+          }
+        }
+      }
+      const size_t bytes = nfloats * sizeof(float);
+      xin[slot].reserve(nfloats + 64);
+      const void* src = x_h;
+#ifndef CLSTM_HIP_EMU
+      hipPointerAttribute_t attr;
+      const bool pinned = hipPointerGetAttributes(&attr, x_h) == hipSuccess && attr.type == hipMemoryTypeHost;
+      if (!pinned) {   // pageable memory: one host copy into the slot's pinned staging buffer, then the same DMA
+        (void)hipGetLastError();
+        pin[slot].reserve(bytes);
+        memcpy(pin[slot].p, x_h, bytes);
+        src = pin[slot].p;
+      }
+#endif
+      HIPCHECK(hipMemcpyAsync(xin[slot].p, src, bytes, hipMemcpyHostToDevice, cs));
+      HIPCHECK(hipEventRecord(copied[slot], cs));
+      HIPCHECK(hipStreamWaitEvent(g_stream, copied[slot], 0));
+      ticket = HostTicket{step_done, (int)(unsigned)k};
+      return xin[slot].p;
+    }
+    void commit() { steps++; }
   } hf;
   // --- fused forward launch (lstm_fwd_fused.h): W_x GEMM producers + recurrence + softmax consumers ---
   float* W1k = nullptr;         // k-contiguous softmax rows (PackFused)
@@ -296,16 +377,14 @@ struct Net {
       y.G.release(); y.C.release(); y.H.release(); y.D.release(); y.dH.release(); y.S.release(); y.Sbf.release(); y.sbf_ready = false; y.pack_tab.release(); y.pack_inv.release(); y.Wmf.release(); y.mf_scale.release(); y.mf_xmax.release(); y.Wmfb.release(); y.pack_inv_state = 0; y.partial.release(); y.dbias.release();
     }
     (void)hipFree(W1k); fw_items.release(); fw_flags.release();
-    for (int i = 0; i < 2; i++) { hf.xin[i].release(); if (hf.pin[i]) (void)hipHostFree(hf.pin[i]); if (hf.copied[i]) (void)hipEventDestroy(hf.copied[i]); }
+    for (int i = 0; i < 2; i++) { hf.xin[i].release(); if (hf.copied[i]) (void)hipEventDestroy(hf.copied[i]); }
     if (hf.step_done) (void)hipHostFree(hf.step_done);
     if (hf.cs) (void)hipStreamDestroy(hf.cs);
     if (own_v) (void)hipFree(v);
     if (own_d) (void)hipFree(d);
     if (own_g) (void)hipFree(g);
     line_off.release(); X.release(); Z.release(); Dz.release();
-    dX0.release(); partial.release(); partial_sm.release(); coop_sync.release(); lstm_prof.release(); aligned.release(); tmp.release(); states.release();
-    state_off.release(); dec_idx.release(); dec_cls.release(); dec_loc.release(); dec_cnt.release();
-    dec_val.release(); lat.release(); lat_off.release();
+    dX0.release(); partial.release(); partial_sm.release(); coop_sync.release(); lstm_prof.release(); aligned.release(); tmp.release();
   }
 
   void repack() {
@@ -368,9 +447,7 @@ struct Net {
   // T_h / nb are validated BEFORE the net is touched: a refused declaration leaves the previous minibatch the current one
   void declare_batch(const int* T_h, int nb) {
     REQUIRE(T_h && nb > 0, "empty batch");
-    long long n = 0;
-    for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
-    REQUIRE(n > 0, "batch has no frames");
+    const long long n = batch_frames(T_h, nb);
     REQUIRE(n < 2147483000LL, "batch has too many frames");   // (the line offsets are ints)
     next.valid = false;   // (whatever a step's tail had prepared is replaced by this declaration)
     nosave = false;
@@ -421,15 +498,26 @@ struct Net {
       if (predict) continue;
       y.D.reserve((size_t)N * ndir * 4 * y.no + (y.wide ? 0 : PROG_WORDS + 64));
       y.dH.reserve((size_t)N * ndir * y.no);
-      if (y.wide && bf16_rec) {
-        // lock-step rings [step parity][dir][line][k] (lstm_wide.h); never smaller than the per-frame layout of the first version
-        y.Hb.reserve((size_t)std::max<long long>(N, 4LL * bs + 32) * ndir * wide_kp16_fwd(y.no) + 64);   // (2 x whole 16-line blocks: the tiled ring of the persistent kernels)
-        y.Db.reserve((size_t)std::max<long long>(N, 2LL * bs + 32) * ndir * wide_kp16_bwd(y.no) + 64);
-      }
+      if (y.wide && bf16_rec) reserve_wide_rings(y);
       y.S.reserve((size_t)N * ndir * y.lds + 64);
     }
     Z.reserve((size_t)N * desc.nclasses);
     if (!predict) Dz.reserve((size_t)N * desc.nclasses);
+  }
+
+  // bf16 operand copies of a wide layer in precision mode 2: the lock-step rings [step parity][dir][line][k] (lstm_wide.h); never
+  // smaller than the per-frame layout of the first version
+  void reserve_wide_rings(Layer& y) {
+    y.Hb.reserve((size_t)std::max<long long>(N, 4LL * bs + 32) * ndir * wide_kp16_fwd(y.no) + 64);   // (2 x whole 16-line blocks: the tiled ring of the persistent kernels)
+    y.Db.reserve((size_t)std::max<long long>(N, 2LL * bs + 32) * ndir * wide_kp16_bwd(y.no) + 64);
+  }
+  // workgroups of the ingest of frames at x -- k_ingest_pack's leading blocks, the IngestTail's.  (The 16-byte form -- ops.h:
+  // k_ingest_pack -- has one item per four input floats: launching a thread per float there dispatched 1,800 workgroups that found
+  // nothing to do)
+  int ingest_blocks(const float* x) const {
+    const Layer& y = L[0];
+    const bool vec16 = (y.ni & 3) == 0 && (y.lds & 3) == 0 && ((size_t)x & 15) == 0;
+    return nblocks(vec16 ? (size_t)N * (y.ni / 4 + 1) : (size_t)N * (1 + y.ni));
   }
 
   const float* layer_input(int l) const { return l == 0 ? X.p : L[l - 1].hrow(); }
@@ -1265,19 +1353,17 @@ struct Net {
     ring.commit(s);
     dwx_N = N;
   }
-  // of a pass's reductions: the update rides them (fuse) / they leave the gradient in the peer exchange's slot (peer, gdst)
-  struct ReduceTarget { bool fuse, peer; float* gdst; };
-  void backward() {
+  // of a pass's reductions: the step's plan (the update rides them / they leave the gradient in the peer exchange's slot), where
+  // the gradient goes, and what they leave for update()
+  struct ReduceTarget { const StepPlan& plan; float* gdst; PassLeft& left; };
+  PassLeft backward(const StepPlan& plan = StepPlan{}) {
     REQUIRE(N > 0, "set_batch first");
-    const bool fuse = fuse_update, peer = peer_step && comm;   // consumed here: an exception below must not leave them set for a later pass
-    fuse_update = false;
-    peer_step = false; peer_pending = false;
-    const ReduceTarget rt{fuse, peer, peer ? comm->peer.slot_ptr(comm->peer.seq + 1) : g};
+    PassLeft left;
+    left.ticket = plan.ticket;
+    const ReduceTarget rt{plan, plan.peer ? comm->peer.slot_ptr(comm->peer.seq + 1) : g, left};
     nbackward++;
     RoctxRange range_("clstm:backward");
-    update_applied = false;
     pending_red.clear();   // (entries a throwing pass left behind must not be reduced -- or, with the update fused in, APPLIED -- by this one)
-    deferred.armed = false;
     flush_line_off();
     repack();
     hipStream_t s = stream();
@@ -1297,6 +1383,7 @@ struct Net {
       timing.end(s);
       check_launch();
     }
+    return left;
   }
   // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T.  (A side stream for these products was measured
   // on MI355X: no gain -- the recurrence workgroups it would overlap with slow down by as much -- so everything stays on one stream.)
@@ -1472,13 +1559,11 @@ struct Net {
   // non-finite gradient ENTRY: skipped entry by entry, ops.h:k_update.)
   struct PendingReduce { ReduceDesc gates, extra; };
   std::vector<PendingReduce> pending_red;
-  // ---- the NEXT minibatch's ingest behind this step's last reduction (abi.inc: clstm_net_train_step_next; ops.h: IngestTail) ----
-  // defer_last_reduce (set by the caller around backward()): the last reduction launch of a fused-update step is described here
-  // instead of enqueued; the caller declares the next minibatch (set_batch + the host half of its alignment: neither touches
-  // anything the described launch reads) and enqueues it with the ingest blocks behind its own.
-  bool defer_last_reduce = false;
-  struct DeferredReduce { bool armed = false; ReduceDesc gates, extra; float* gdst = nullptr; UpdateFuse uf; size_t work = 0; hipStream_t q = nullptr; } deferred;
-  void launch_deferred_reduce(const IngestTail* tail) {
+  // ---- the NEXT minibatch's ingest behind this step's last reduction (step.inc: train_step; ops.h: IngestTail) ----
+  // StepPlan::defer_last: the last reduction launch of a fused-update step is described in PassLeft::deferred instead of enqueued;
+  // the step declares the next minibatch (set_batch + the host half of its alignment: neither touches anything the described
+  // launch reads) and enqueues it with the ingest blocks behind its own.
+  void launch_deferred_reduce(DeferredReduce& deferred, const IngestTail* tail) {
     if (!deferred.armed) return;
     deferred.armed = false;
     const int nb = nblocks(deferred.work);
@@ -1500,18 +1585,20 @@ struct Net {
     bool valid = false;
     const float* x = nullptr;
     std::vector<int> T, labels, L;
-    bool matches(const int* T_h, int bs, const float* x_d, const int* labels_h, const int* L_h) const {
-      if (!valid || x != x_d || (int)T.size() != bs) return false;
-      if (memcmp(T.data(), T_h, (size_t)bs * sizeof(int)) || memcmp(L.data(), L_h, (size_t)bs * sizeof(int))) return false;
+    static size_t nlabels(const Minibatch& m) {
       size_t nl = 0;
-      for (int b = 0; b < bs; b++) nl += (size_t)L_h[b];
-      return nl == labels.size() && (nl == 0 || !memcmp(labels.data(), labels_h, nl * sizeof(int)));
+      for (int b = 0; b < m.bs; b++) nl += (size_t)m.L[b];
+      return nl;
     }
-    void remember(const int* T_h, int bs, const float* x_d, const int* labels_h, const int* L_h) {
-      x = x_d; T.assign(T_h, T_h + bs); L.assign(L_h, L_h + bs);
-      size_t nl = 0;
-      for (int b = 0; b < bs; b++) nl += (size_t)L_h[b];
-      labels.assign(labels_h, labels_h + nl);
+    bool matches(const Minibatch& m) const {
+      if (!valid || x != m.x || (int)T.size() != m.bs) return false;
+      if (memcmp(T.data(), m.T, (size_t)m.bs * sizeof(int)) || memcmp(L.data(), m.L, (size_t)m.bs * sizeof(int))) return false;
+      const size_t nl = nlabels(m);
+      return nl == labels.size() && (nl == 0 || !memcmp(labels.data(), m.labels, nl * sizeof(int)));
+    }
+    void remember(const Minibatch& m) {
+      x = m.x; T.assign(m.T, m.T + m.bs); L.assign(m.L, m.L + m.bs);
+      labels.assign(m.labels, m.labels + nlabels(m));
       valid = true;
     }
   } next;
@@ -1521,26 +1608,27 @@ struct Net {
     const size_t work = (size_t)gates.nbatch * gates.R * gates.Cn + (size_t)extra.R * extra.Cn * extra.nbatch;
     UpdateFuse uf{};
     uf.nanflag = nanflag(); uf.step_no = step_no();
-    if (rt.fuse) {   // (train_step without a communicator) this layer's parameters are updated by the reduction itself
-      uf = UpdateFuse{v, d, lr, mom, gclip, (const int*)dev_err_words(), last ? update_step_word : nullptr, update_step_id, nanflag(), step_no(), PackDst{}};
-      if (last) { update_step_word = nullptr; update_applied = true; }
+    PassLeft& left = rt.left;
+    if (rt.plan.fuse) {   // (train_step without a communicator) this layer's parameters are updated by the reduction itself
+      uf = UpdateFuse{v, d, lr, mom, gclip, (const int*)dev_err_words(), last ? left.ticket.word : nullptr, left.ticket.id, nanflag(), step_no(), PackDst{}};
+      if (last) { left.ticket.word = nullptr; left.update_applied = true; }
       // a single narrow layer whose packed copies are current: the update keeps them current (ops.h: PackDst) and the next
       // step's ingest launch has nothing to repack
-      packs_follow_update = false;
+      left.packs_follow_update = false;
       if (L.size() == 1 && !L[0].wide && !packed_dirty && pack_inverse(L[0])) {
         Layer& y = L[0];
         const size_t nr = (size_t)ndir * 4 * 4 * y.nk4 * y.nthreads;
         uf.pk = PackDst{y.pack_inv.p, PACK_KD, y.Wt, y.bias, y.Rf, y.Rb, y.pd, pack_fused_desc(y), (unsigned)((size_t)(1 + y.ni) * ndir * 4 * y.no), (unsigned)nr};
-        packs_follow_update = true;
+        left.packs_follow_update = true;
         g_path_count[PC_PACKS_FOLLOW_UPDATE]++;
       }
     }
-    if (defer_last_reduce && last && rt.fuse) {   // enqueued by launch_deferred_reduce, the next minibatch's ingest behind it
-      deferred.armed = true; deferred.gates = gates; deferred.extra = extra; deferred.gdst = rt.gdst; deferred.uf = uf; deferred.work = work; deferred.q = q;
+    if (rt.plan.defer_last && last && rt.plan.fuse) {   // enqueued by launch_deferred_reduce, the next minibatch's ingest behind it
+      left.deferred = DeferredReduce{true, gates, extra, rt.gdst, uf, work, q};
       return;
     }
     CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks(work)), dim3(256), 0, q, gates, extra, rt.gdst, (int*)nullptr, 0, uf);
-    if (rt.peer && last) peer_pending = true;
+    if (rt.plan.peer && last) left.peer_pending = true;
   }
 
   long long nbackward = 0;           // backward passes of this net so far = the number of the current training step (from 1)
@@ -1554,30 +1642,32 @@ struct Net {
     static const bool on = !(getenv("CLSTM_NANCHECK") && atoi(getenv("CLSTM_NANCHECK")) == 0);
     return on ? dev_err_words() + 3 : nullptr;
   }
-  int* update_step_word = nullptr;   // (host-fed steps) pinned word the update kernel writes update_step_id into
-  int update_step_id = 0;
-  bool peer_step = false;     // the NEXT backward pass writes its gradient into the communicator's exchange slot and update() runs the
-                              //   peer-read all-reduce fused with the update (set by train_step when a communicator of > 1 ranks is attached)
-  bool peer_pending = false;  // ... this backward pass did so
-  bool fuse_update = false;   // the NEXT backward pass applies the update inside its reductions (set by train_step)
   // The update rides the slab reductions (train_step without an exchange).  All or nothing: every reduction of a pass runs behind
   // its last recurrence (reduce_layer) -- in a stacked net the layers' reductions used to sit between the recurrences, top down, and
   // an error word raised by a lower layer found the upper layers' parameters already updated: half a step.
   bool fuse_eligible() const { return !comm || comm->nranks == 1; }
-  bool update_applied = false; // ... and has done so: update() has nothing left to launch
-  bool packs_follow_update = false;   // ... and rewrote the packed copies of the parameters it moved
-  void update() {
+  // the plan of a one-call step: no exchange between backward pass and update -> the update rides the reductions; several ranks that
+  // could map each other -> the peer exchange; a next minibatch to ingest behind the last reduction only where that one carries the update
+  StepPlan step_plan(bool next_given, const HostTicket* ticket) {
+    StepPlan p;
+    p.fuse = fuse_eligible();
+    p.peer = comm && comm->nranks > 1 && comm->peer_ready((size_t)nparams, stream());
+    p.defer_last = next_given && p.fuse;
+    if (ticket) p.ticket = *ticket;
+    return p;
+  }
+  // `left`: what the backward pass just enqueued returned.  Of a backward pass and an update made by separate calls nothing has to
+  // reach this function: that pass ran the default plan, which leaves a default PassLeft -- the last branch below.
+  void update(PassLeft& left) {
     hipStream_t s = stream();
     RoctxRange range_("clstm:update");
     params_epoch++;
-    if (update_applied) {   // done by the reductions of the backward pass just enqueued
-      update_applied = false;
-      packed_dirty = !packs_follow_update;
-      packs_follow_update = false;
+    if (left.update_applied) {   // done by the reductions of the backward pass just enqueued
+      packed_dirty = !left.packs_follow_update;
       return;
     }
-    if (peer_pending && comm) {   // peer all-reduce fused into the update, one-shot or two-phase (comm.h: peer_use_two_phase; ops.h)
-      peer_pending = false;
+    HostTicket& tk = left.ticket;
+    if (left.peer_pending) {   // peer all-reduce fused into the update, one-shot or two-phase (comm.h: peer_use_two_phase; ops.h)
       RoctxRange range2_("clstm:allreduce+update");
       const int sq = ++comm->peer.seq;
       const bool two = peer_use_two_phase((size_t)nparams, comm->nranks);
@@ -1585,9 +1675,9 @@ struct Net {
       peer_exchange_begin(*comm, sq, two, (size_t)nparams, s);   // (the hosts announce the exchange to each other first: Comm::peer_barrier)
       timing.end(s);
       timing.begin("sgd_update", s);
-      peer_exchange_finish(*comm, sq, two, v, d, g, (size_t)nparams, lr, mom, gclip, (const int*)dev_err_words(), update_step_word, update_step_id, nanflag(),
+      peer_exchange_finish(*comm, sq, two, v, d, g, (size_t)nparams, lr, mom, gclip, (const int*)dev_err_words(), tk.word, tk.id, nanflag(),
                            step_no(), s);
-      update_step_word = nullptr;
+      tk.word = nullptr;
       timing.end(s);
       check_launch();
       g_path_count[PC_PEER_EXCHANGE]++;
@@ -1603,9 +1693,9 @@ struct Net {
       timing.end(s);
     }
     timing.begin("sgd_update", s);
-    CLSTM_LAUNCH(k_update, dim3(nblocks(nparams)), dim3(256), 0, s, v, d, (const float*)g, (size_t)nparams, lr, mom, gclip, (const int*)dev_err_words(), update_step_word, update_step_id,
+    CLSTM_LAUNCH(k_update, dim3(nblocks(nparams)), dim3(256), 0, s, v, d, (const float*)g, (size_t)nparams, lr, mom, gclip, (const int*)dev_err_words(), tk.word, tk.id,
                  nanflag(), step_no());
-    update_step_word = nullptr;
+    tk.word = nullptr;
     timing.end(s);
     check_launch();
     packed_dirty = true;

@@ -122,6 +122,22 @@ struct PinnedRing {
       if (h[i]) (void)hipHostFree(h[i]);
   }
 };
+// Grow-only pinned host buffer: the landing buffer of a results copy (decode, score), the staging of pageable frames (HostFeed)
+template <class T>
+struct PinnedBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  void reserve(size_t n) {
+    if (n <= cap) return;
+    if (p) HIPCHECK(hipHostFree(p));
+    p = nullptr; cap = 0;
+    HIPCHECK(hipHostMalloc((void**)&p, (n + n / 4 + 64) * sizeof(T)));
+    cap = n + n / 4 + 64;
+  }
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
 
 // ---- GEMM operand functors ---------------------------------------------------------------------
 // operator(): one element; row4(): four consecutive columns of one row (c % 4 == 0) when vec4() says the
@@ -437,6 +453,16 @@ static void check_device_errors() {
                         "); the minibatches enqueued since then were NOT applied (layers above the failing one may have taken their update of that one minibatch) -- set CLSTM_XCD_REC=0");
   throw Error("fused backward launch: " + std::to_string(w[1]) + " weight-gradient item(s) gave up waiting for the recurrence (watchdog); the "
               "minibatches since then were NOT applied -- set CLSTM_OVERLAP=0");
+}
+// synchronous float copies of the accessors (set / get of parameters, outputs, states)
+static void copy_h2d(float* dst, const float* src, size_t n) {
+  HIPCHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, g_stream));
+  HIPCHECK(hipStreamSynchronize(g_stream));
+}
+static void copy_d2h(float* dst, const float* src, size_t n) {
+  HIPCHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, g_stream));
+  HIPCHECK(hipStreamSynchronize(g_stream));
+  check_device_errors();   // whatever is read back was produced by launches whose outcome is known now
 }
 static int g_debug_fail_claims = 0;      // tests: this many upcoming persistent launches fail their placement check ...
 static int g_debug_fail_skip = 0;        // ... after this many that do not
