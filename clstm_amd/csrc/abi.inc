@@ -741,6 +741,17 @@ int clstm_debug_path_count(int which, long long* out_h) {
   *out_h = g_path_count[which];
   ABI_END
 }
+int clstm_debug_wide_plan(const int* shape, int* plan) {   // host arithmetic only: no net, no device (runtime.inc:wide_plan)
+  ABI_BEGIN
+  REQUIRE(shape && plan, "null argument");
+  static_assert(sizeof(WideShape) == 20 * sizeof(int) && sizeof(WidePlan) == 14 * sizeof(int), "include/clstm_abi.h documents the int layout");
+  WideShape h;
+  memcpy(&h, shape, sizeof(h));
+  REQUIRE(h.no > 0 && h.ndir >= 1 && h.bs > 0 && h.ncu >= 0, "bad shape");
+  const WidePlan p = wide_plan(h);
+  memcpy(plan, &p, sizeof(p));
+  ABI_END
+}
 int clstm_debug_lane_ops(float* out) {
   ABI_BEGIN
   CLSTM_LAUNCH(k_debug_lane_ops, dim3(1), dim3(64), 0, g_stream, out);

@@ -12,6 +12,10 @@ struct Layer {
   int ni, no, nk4, nthreads;
   bool wide = false;          // lock-step recurrence (lstm_wide.h) instead of the register-resident one
   int kpf = 0, kpb = 0;
+  // padded contraction lengths of the bf16 rows and the rows of the packed bf16 weights per direction, forward | backward; bwd_exact: the
+  // backward rows are exactly the 4 no gate columns (no % 32 == 0), so per-frame bf16 deltas (Dbf) can be a GEMM operand as they are
+  int kp16f = 0, kp16b = 0, rowsf = 0, rowsb = 0;
+  bool bwd_exact = false;
   long long nwf = 0, nwb = 0;
   PackDesc pd;
   float *Wt = nullptr, *bias = nullptr, *Rf = nullptr, *Rb = nullptr, *Rwf = nullptr, *Rwb = nullptr;
@@ -145,7 +149,7 @@ struct Net {
   ReduceDesc sm_red{};
   DevBuf<long long> lstm_prof;  // diagnostics build only
   StepGraphCache step_graphs;   // captured per-step launch sequences of the lock-step recurrence
-  DevBuf<int> coop_sync;      // grid-barrier ticket counter + watchdog flag of the cooperative recurrence
+  XcdSync coop_sync;          // sync words of the persistent lock-step kernels + the stamp base of their next launch
   Timing timing;
   // --- weight-gradient GEMM beside the backward recurrence (gemm_dw.h) ---
   static const int PROG_LINES = 2048;                          // overlap only for minibatches up to this many lines
@@ -313,6 +317,9 @@ struct Net {
       y.wide = y.nk4 < 0 || force_wide;
       if (y.wide) y.nk4 = 1;
       y.nthreads = y.wide ? 64 : 64 * ((y.no + 15) / 16);
+      y.kp16f = wide_kp16_fwd(y.no); y.kp16b = wide_kp16_bwd(y.no);
+      y.rowsf = (y.no + 3) / 4 * 16; y.rowsb = (y.no + 15) / 16 * 16;
+      y.bwd_exact = y.kp16b == 4 * y.no;
       y.lds = ((1 + y.ni + y.no + 15) / 16) * 16;   // source rows [1 | x | h_prev], padded to 64-byte rows
       y.ldh = ((y.hofs + ndir * y.no + 15) / 16) * 16;   // 64-byte aligned rows
       const long long blk = (long long)y.no * (1 + y.ni + y.no);
@@ -344,12 +351,12 @@ struct Net {
       dev_malloc((void**)&y.bias, (size_t)M * sizeof(float));
       if (y.wide) {
         y.kpf = wide_kp_fwd(y.no); y.kpb = wide_kp_bwd(y.no);
-        y.nwf = (long long)ndir * ((y.no + 3) / 4) * 16 * y.kpf;
-        y.nwb = (long long)ndir * ((y.no + 15) / 16) * 16 * y.kpb;
+        y.nwf = (long long)ndir * y.rowsf * y.kpf;
+        y.nwb = (long long)ndir * y.rowsb * y.kpb;
         dev_malloc((void**)&y.Rwf, (size_t)(y.nwf + 4) * sizeof(float));
         dev_malloc((void**)&y.Rwb, (size_t)(y.nwb + 4) * sizeof(float));
-        dev_malloc((void**)&y.Rbf, ((size_t)ndir * ((y.no + 3) / 4) * 16 * wide_kp16_fwd(y.no) + 8) * sizeof(unsigned short));
-        dev_malloc((void**)&y.Rbb, ((size_t)ndir * ((y.no + 15) / 16) * 16 * wide_kp16_bwd(y.no) + 8) * sizeof(unsigned short));
+        dev_malloc((void**)&y.Rbf, ((size_t)ndir * y.rowsf * y.kp16f + 8) * sizeof(unsigned short));
+        dev_malloc((void**)&y.Rbb, ((size_t)ndir * y.rowsb * y.kp16b + 8) * sizeof(unsigned short));
       } else {
         dev_malloc((void**)&y.Rf, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float));
         dev_malloc((void**)&y.Rb, (size_t)ndir * 4 * KQP * y.nthreads * sizeof(float));
@@ -384,7 +391,7 @@ struct Net {
     if (own_d) (void)hipFree(d);
     if (own_g) (void)hipFree(g);
     line_off.release(); X.release(); Z.release(); Dz.release();
-    dX0.release(); partial.release(); partial_sm.release(); coop_sync.release(); lstm_prof.release(); aligned.release(); tmp.release();
+    dX0.release(); partial.release(); partial_sm.release(); coop_sync.words.release(); lstm_prof.release(); aligned.release(); tmp.release();
   }
 
   void repack() {
@@ -393,20 +400,18 @@ struct Net {
     for (auto& y : L) {
       const int M = ndir * 4 * y.no, KQP = 4 * y.nk4;
       const size_t nr = y.wide ? 0 : (size_t)ndir * 4 * KQP * y.nthreads;
-      if (y.wide && bf16_rec && y.no % 128 == 0 && y.ni % 32 == 0 && wide_kp16_fwd(y.no) == y.no && wide_kp16_bwd(y.no) == 4 * y.no &&
+      if (y.wide && bf16_rec && y.no % 128 == 0 && y.ni % 32 == 0 && y.kp16f == y.no && y.bwd_exact &&
           dbg_opt("pack_tiles") != 0) {
         // every bf16-mode copy of the layer in one tiled pass (ops.h:k_pack_wide_tiles)
-        const int rf = (y.no + 3) / 4 * 16, kf = wide_kp16_fwd(y.no), rb = (y.no + 15) / 16 * 16, kb = wide_kp16_bwd(y.no);
         y.Wtb.reserve((size_t)y.ni * M + 64);
         y.WtbT.reserve((size_t)y.ni * M + 64);
         const unsigned nblk = (unsigned)ndir * (unsigned)((y.ni + y.no) / 32) * (unsigned)(y.no / 32);
-        CLSTM_LAUNCH(k_pack_wide_tiles, dim3(nblk), dim3(256), 0, s, (const float*)v, y.pd, y.Wt, y.bias, y.Wtb.p, y.WtbT.p, y.Rbf, y.Rbb, kf, kb, rf, rb);
+        CLSTM_LAUNCH(k_pack_wide_tiles, dim3(nblk), dim3(256), 0, s, (const float*)v, y.pd, y.Wt, y.bias, y.Wtb.p, y.WtbT.p, y.Rbf, y.Rbb, y.kp16f, y.kp16b, y.rowsf, y.rowsb);
         continue;
       }
       if (y.wide && bf16_rec) {
-        const int rf = (y.no + 3) / 4 * 16, kf = wide_kp16_fwd(y.no), rb = (y.no + 15) / 16 * 16, kb = wide_kp16_bwd(y.no);
-        CLSTM_LAUNCH(k_pack_wide_bf16, dim3(nblocks((size_t)ndir * ((size_t)rf * kf + (size_t)rb * kb))), dim3(256), 0, s,
-                     (const float*)v, y.Rbf, y.Rbb, y.pd, rf, kf, rb, kb);
+        CLSTM_LAUNCH(k_pack_wide_bf16, dim3(nblocks((size_t)ndir * ((size_t)y.rowsf * y.kp16f + (size_t)y.rowsb * y.kp16b))), dim3(256), 0, s,
+                     (const float*)v, y.Rbf, y.Rbb, y.pd, y.rowsf, y.kp16f, y.rowsb, y.kp16b);
       }
       else if (y.wide) {
         CLSTM_LAUNCH(k_pack_wide, dim3(nblocks((size_t)(y.nwf + y.nwb))), dim3(256), 0, s, (const float*)v, y.Rwf, y.Rwb,
@@ -414,10 +419,9 @@ struct Net {
         y.r2b_ready = false;
         if (rec_x3()) {   // hi | lo planes of the backward recurrence's weights
           y.r2b_ready = true;
-          const int rb = (y.no + 15) / 16 * 16, kb = wide_kp16_bwd(y.no);
-          const long long pb = (long long)ndir * rb * kb;
+          const long long pb = (long long)ndir * y.rowsb * y.kp16b;
           y.R2b.reserve((size_t)2 * pb + 64);
-          CLSTM_LAUNCH(k_pack_wide_split, dim3(nblocks((size_t)pb)), dim3(256), 0, s, (const float*)v, y.R2b.p, y.pd, rb, kb, pb);
+          CLSTM_LAUNCH(k_pack_wide_split, dim3(nblocks((size_t)pb)), dim3(256), 0, s, (const float*)v, y.R2b.p, y.pd, y.rowsb, y.kp16b, pb);
         }
       }
       CLSTM_LAUNCH(k_pack_layer, dim3(nblocks((size_t)(1 + y.ni) * M + 2 * nr)), dim3(256), 0, s, (const float*)v, y.Wt,
@@ -508,8 +512,8 @@ struct Net {
   // bf16 operand copies of a wide layer in precision mode 2: the lock-step rings [step parity][dir][line][k] (lstm_wide.h); never
   // smaller than the per-frame layout of the first version
   void reserve_wide_rings(Layer& y) {
-    y.Hb.reserve((size_t)std::max<long long>(N, 4LL * bs + 32) * ndir * wide_kp16_fwd(y.no) + 64);   // (2 x whole 16-line blocks: the tiled ring of the persistent kernels)
-    y.Db.reserve((size_t)std::max<long long>(N, 2LL * bs + 32) * ndir * wide_kp16_bwd(y.no) + 64);
+    y.Hb.reserve((size_t)std::max<long long>(N, 4LL * bs + 32) * ndir * y.kp16f + 64);   // (2 x whole 16-line blocks: the tiled ring of the persistent kernels)
+    y.Db.reserve((size_t)std::max<long long>(N, 2LL * bs + 32) * ndir * y.kp16b + 64);
   }
   // workgroups of the ingest of frames at x -- k_ingest_pack's leading blocks, the IngestTail's.  (The 16-byte form -- ops.h:
   // k_ingest_pack -- has one item per four input floats: launching a thread per float there dispatched 1,800 workgroups that found
@@ -524,36 +528,59 @@ struct Net {
   int layer_input_ld(int l) const { return l == 0 ? desc.ninput : L[l - 1].ldh; }
   int layer_input_slack(int l) const { return 32; }   // X and H are over-allocated by >= 64 floats
 
+  // Layer l can take the bf16 rows (Hbf) the layer below leaves as they are -- the A operand of its W_x product, the x columns of its
+  // bf16 source rows: the half of that question that the net's build and mode answer.  The other half is whether the layer below RAN
+  // its persistent forward kernel, which alone writes Hbf: a fact once it has run (forward_pass: x_from_hbf), a prediction while its
+  // own arguments are made (wide_args: next_takes_hbf -- only the persistent kernel reads skip_h, so a wrong prediction costs nothing)
+  bool hbf_feeds(int l) const {
+    return bf16_gemm && bf16_rec && l > 0 && l < (int)L.size() && L[l - 1].Hbf.p && L[l].WtbT.p && L[l].ni == ndir * L[l - 1].no && (L[l].ni & 1) == 0;
+  }
+  // the forward pass of a wide layer leaves bf16 source rows [x | h_{t-1} | 1] for the weight-gradient product (gemm_b16mc)
+  bool wants_sbf(const Layer& y) const { return bf16_rec && dbg_opt("gemm_b16mc") != 0 && bf16_gemm && (y.ni & 7) == 0 && (y.no & 7) == 0 && y.bwd_exact; }
+  // what wide_plan decides from, read here: the device, the environment, the options (each per pass: tests switch them inside one process)
+  WideShape wide_shape(const Layer& y, bool fwd, int fx_mode = 0) const {
+    WideShape h{};
+    h.fwd = fwd; h.no = y.no; h.x_ni = y.ni; h.ndir = ndir; h.bs = bs; h.tmax = tmax; h.N = (int)N;
+    h.kp = fwd ? y.kpf : y.kpb; h.kp16 = fwd ? y.kp16f : y.kp16b;
+    h.bf16 = bf16_rec; h.x3 = !fwd && rec_x3() && y.r2b_ready; h.fx_mode = fx_mode;
+    h.ncu = device_cu_count();
+    h.xcd_on = !(getenv("CLSTM_XCD_REC") && atoi(getenv("CLSTM_XCD_REC")) == 0);
+    h.xcd_failed = g_xcd_failed;
+    h.c32_on = dbg_opt("bwd_c32") != 0;
+    h.sbf = fwd && wants_sbf(y); h.sbf_ld = y.ni + y.no + 8; h.lds = y.lds; h.ldh = y.ldh;
+    return h;
+  }
   LstmWideArgs wide_args(Layer& y, bool fwd) {
+    REQUIRE((double)N * ndir * 4 * y.no * 4 < 2147483000.0,
+            "minibatch too large for the lock-step recurrence (frames x 4 x nhidden x ndir x 4 B must stay below 2 GiB)");
     LstmWideArgs w{};
     w.Rw = fwd ? y.Rwf : y.Rwb; w.rw_elems = fwd ? y.nwf : y.nwb;
     w.G = y.G.p; w.C = y.C.p; w.H = y.H.p; w.dH = y.dH.p; w.D = y.D.p;
     y.dCc.reserve((size_t)bs * ndir * y.no);
     w.dC = y.dCc.p; w.line_off = line_off.p; w.S = y.S.p; w.sdir = (long long)N * y.lds; w.N = N;
     w.lds = y.lds; w.sofs = 1 + y.ni; w.ldh = y.ldh; w.hofs = y.hofs; w.no = y.no; w.ndir = ndir; w.bs = bs;
-    w.kp = fwd ? y.kpf : y.kpb;
+    w.kp = fwd ? y.kpf : y.kpb; w.tmax = tmax;
     if (!bf16_rec) { y.Rf32.reserve(ring32_floats(ndir, bs, std::max(y.kpf, y.kpb)) + 64); w.Rf = y.Rf32.p; }
-    if (!bf16_rec && !fwd && rec_x3() && y.r2b_ready) {   // (tried first by launch_lstm_wide; the f32 kernel stays as the fallback)
+    if (!bf16_rec && !fwd && rec_x3() && y.r2b_ready) {   // (wide_plan's x3: planned instead of the f32 kernel)
       const int nblk = (bs + 15) / 16;
-      w.kp16 = wide_kp16_bwd(y.no);
+      w.kp16 = y.kp16b;
       w.ring_plane = 2LL * ndir * nblk * 16 * w.kp16;
       y.D2.reserve((size_t)2 * w.ring_plane + 64);
-      w.Db = y.D2.p; w.Rw16 = y.R2b.p; w.rw_plane = (long long)ndir * ((y.no + 15) / 16 * 16) * w.kp16;
+      w.Db = y.D2.p; w.Rw16 = y.R2b.p; w.rw_plane = (long long)ndir * y.rowsb * w.kp16;
     }
     if (bf16_rec) {
       w.Rw16 = fwd ? y.Rbf : y.Rbb;
-      w.kp16 = fwd ? wide_kp16_fwd(y.no) : wide_kp16_bwd(y.no);
-      w.rw_elems = (long long)ndir * (fwd ? (y.no + 3) / 4 : (y.no + 15) / 16) * 16 * w.kp16;
+      w.kp16 = fwd ? y.kp16f : y.kp16b;
+      w.rw_elems = (long long)ndir * (fwd ? y.rowsf : y.rowsb) * w.kp16;
       w.Hb = y.Hb.p; w.Db = y.Db.p;
-      if (!fwd && wide_kp16_bwd(y.no) == 4 * y.no) {
+      if (!fwd && y.bwd_exact) {
         y.Dbf.reserve((size_t)N * ndir * w.kp16 + 64); w.Dbf = y.Dbf.p;
         // with bf16 GEMMs behind it, nobody reads the f32 deltas of a persistent pass (16 bytes per lane and step, 0.17 ms
         // per configs[4] minibatch); ensure_delta_f32() expands Dbf for a fallback product
         w.skip_d = bf16_gemm;
         y.dbias.reserve((size_t)bs * ndir * 4 * y.no + 64); w.dbias = y.dbias.p;   // per-line bias-gradient sums (lstm_wide.h: LstmWideArgs::dbias)
       }
-      const bool b16mc_on = dbg_opt("gemm_b16mc") != 0;
-      if (fwd && b16mc_on && bf16_gemm && (y.ni & 7) == 0 && (y.no & 7) == 0 && wide_kp16_bwd(y.no) == 4 * y.no) {
+      if (fwd && wants_sbf(y)) {
         const int ldsb = y.ni + y.no + 8;
         { const size_t cap0 = y.Sbf.cap; y.Sbf.reserve((size_t)N * ndir * ldsb + 64); if (y.Sbf.cap != cap0) y.sbf_one_key = -1; }
         w.Sbf = y.Sbf.p; w.sbf_ld = ldsb; w.sbf_ofs = y.ni; w.sbf_dir = (long long)N * ldsb;
@@ -564,8 +591,7 @@ struct Net {
       // f32 h_{t-1} source columns when the weight gradient takes Sbf.  ensure_h_f32 / ensure_source rebuild them exactly.
       if (fwd) {   // (measured at configs[4]: forward passes 1.647 -> 1.580 ms per minibatch)
         const int l = (int)(&y - L.data());
-        const bool next_takes_hbf = w.Hbf && l + 1 < (int)L.size() && bf16_gemm && L[l + 1].WtbT.p &&
-                                    L[l + 1].ni == ndir * y.no && (L[l + 1].ni & 1) == 0;
+        const bool next_takes_hbf = w.Hbf && hbf_feeds(l + 1);
         w.skip_h = next_takes_hbf;
         w.skip_s = w.Sbf != nullptr;
       }
@@ -573,6 +599,7 @@ struct Net {
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); w.prof = lstm_prof.p;    // (the last pass launched before clstm_debug_lstm_cycles is what it reads)
 #endif
+    w.sync = coop_sync.reserve();
     return w;
   }
 
@@ -829,27 +856,25 @@ struct Net {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
       const FwdFamily fam = forward_family(y);
-      const bool x_from_hbf = bf16_gemm && bf16_rec && l > 0 && L[l - 1].fwd_persistent && L[l - 1].Hbf.p && y.WtbT.p && y.ni == ndir * L[l - 1].no && (y.ni & 1) == 0;
-      // the lock-step recurrence of a wide layer + what follows it (bf16 source rows for the weight gradient); fx_ngx > 0: the
-      // persistent kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) -- false if it did not run
-      auto run_wide = [&](LstmWideArgs w, int fx_ngx) {
+      const bool x_from_hbf = hbf_feeds(l) && L[l - 1].fwd_persistent;   // (a fact: the layer below has run)
+      // the lock-step recurrence of a wide layer as planned + what follows it (bf16 source rows for the weight gradient); false: the
+      // plan was the kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) and it did not run
+      auto run_wide = [&](const WidePlan& plan, const LstmWideArgs& w) {
         timing.begin("lstm_fwd", s);
-        const WideRan ran = launch_lstm_wide(true, w, tmax, coop_sync, step_graphs, s, bf16_rec, fx_ngx);
+        const WideRan ran = launch_lstm_wide(plan, w, coop_sync, step_graphs, s);
         timing.end(s);
         if (ran == WideRan::Nothing) return false;
         y.fwd_persistent = ran == WideRan::Persistent && bf16_rec;
         y.h_f32_valid = !(y.fwd_persistent && w.skip_h);   // (the per-step kernels store everything)
         y.sh_valid = !(y.fwd_persistent && w.skip_s);
-        if (ran == WideRan::Persistent) g_path_count[PC_FWD_PERSISTENT]++;
-        if (fx_ngx) g_path_count[PC_FWD_FUSED_WX]++;
         y.sbf_ready = y.fwd_persistent && w.Sbf;
         if (y.sbf_ready) {   // the non-recurrent columns of the bf16 source rows (the recurrence stored the h columns)
-          const bool from16 = l > 0 && L[l - 1].fwd_persistent && L[l - 1].Hbf.p && y.ni == ndir * L[l - 1].no;
-          if (l > 0 && !from16) ensure_h_f32(l - 1);
+          // (x_from_hbf: with Sbf written -- bf16 GEMMs, ni % 8 == 0, the bf16 packs made -- it is no more than "the layer below left Hbf of this width")
+          if (l > 0 && !x_from_hbf) ensure_h_f32(l - 1);
           // x columns that fill whole tiles of the weight-gradient GEMM are not copied: the GEMM reads them from Hbf itself
           // (for the row count the backward pass WILL launch that GEMM with: dw_bf16_rows)
           const int R_ = 1 + y.ni + y.no, Cn_ = 4 * y.no;
-          y.sbf_x_external = from16 && y.ni % gemm_mc_rows_per_tile(dw_bf16_rows(y, R_, Cn_), Cn_) == 0;
+          y.sbf_x_external = x_from_hbf && y.ni % gemm_mc_rows_per_tile(dw_bf16_rows(y, R_, Cn_), Cn_) == 0;
           if (y.sbf_x_external) {
             if (y.sbf_one_key != (long long)N) {
               CLSTM_LAUNCH(k_source_one_bf16, dim3(nblocks((size_t)N)), dim3(256), 0, s, y.Sbf.p, (size_t)N, y.ni + y.no, w.sbf_ld, ndir, w.sbf_dir);
@@ -857,14 +882,15 @@ struct Net {
             }
           } else {
             y.sbf_one_key = -1;
-            CLSTM_LAUNCH(k_source_x_bf16, dim3(nblocks((size_t)N * ((y.ni >> 3) + 1))), dim3(256), 0, s, y.Sbf.p, from16 ? nullptr : layer_input(l),
-                         from16 ? L[l - 1].Hbf.p : nullptr, from16 ? y.ni : layer_input_ld(l), (size_t)N, y.ni, y.ni + y.no, w.sbf_ld, ndir, w.sbf_dir);
+            CLSTM_LAUNCH(k_source_x_bf16, dim3(nblocks((size_t)N * ((y.ni >> 3) + 1))), dim3(256), 0, s, y.Sbf.p, x_from_hbf ? nullptr : layer_input(l),
+                         x_from_hbf ? L[l - 1].Hbf.p : nullptr, x_from_hbf ? y.ni : layer_input_ld(l), (size_t)N, y.ni, y.ni + y.no, w.sbf_ld, ndir, w.sbf_dir);
           }
         }
         return true;
       };
       // bf16 mode, wide layer: no hoisted product at all when the persistent recurrence can take the input projection with it
       // (its operands are the bf16 rows the layer below left, or a bf16 copy of the input frames)
+      // (its gate is wide_plan's: here only whether its operands exist.)
       bool fx_done = false;
       // experiment option fuse_wx (CLSTM_DEBUG): 0 never, 1 (default) layers of up to 128 inputs, 2 every eligible layer.  Measured at configs[4]
       // (profiles/r04_xcd_phase_cycles_fused_wx.txt): there is no idle shadow to hide the x-part in -- a step's "group wait" is
@@ -872,9 +898,9 @@ struct Net {
       // for 64 inputs (67 us per pass against the 121 us of product + bf16 copy it replaces: kept), +2,950 for 1024 inputs
       // (490 us against 321: not kept).  (read per pass: tests switch it inside one process)
       const int fx_mode = dbg_opt("fuse_wx");
-      if (fx_mode > 0 && (fx_mode > 1 || y.ni <= 128) && y.wide && bf16_gemm && bf16_rec && y.WtbT.p && (y.ni & 31) == 0 && (l == 0 || x_from_hbf)) {
-        const int ngx = y.ni <= 128 ? 1 : y.ni <= 512 ? 4 : y.ni <= 1024 ? 8 : 0;
-        if (ngx) {
+      if (y.wide && bf16_gemm && bf16_rec && y.WtbT.p && (l == 0 || x_from_hbf)) {
+        const WidePlan plan = wide_plan(wide_shape(y, true, fx_mode));
+        if (plan.fx_ngx) {   // asked for: the bf16 input frames are made before the rest of the gate is looked at (as ever; the hoisted product makes them again)
           const unsigned short* xb = l > 0 ? L[l - 1].Hbf.p : nullptr;
           if (l == 0) {
             xbf.reserve((size_t)N * y.ni + 64);
@@ -884,7 +910,7 @@ struct Net {
           LstmWideArgs w = wide_args(y, true);
           w.Xb = xb; w.x_ld = y.ni; w.x_ni = y.ni; w.Wxb = y.WtbT.p; w.bias = y.bias;
           y.sx_valid = l == 0 && src0_ready;
-          fx_done = run_wide(w, ngx);
+          fx_done = plan.kernel == WK_XCD_FWD_BF16_FX && run_wide(plan, w);
         }
       }
       if (fx_done) { if (!y.sbf_ready) ensure_source_x(l); continue; }
@@ -930,7 +956,7 @@ struct Net {
       // only if something still asks for them: a fallback path or the state API)
       if (save) y.sx_valid = l == 0 && src0_ready;
       if (save && (l == 0 || !y.wide)) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
-      if (fam == FwdFamily::Wide) run_wide(wide_args(y, true), 0);
+      if (fam == FwdFamily::Wide) run_wide(wide_plan(wide_shape(y, true)), wide_args(y, true));
       else {
         LstmSeqArgs a = seq_args(y, true, save);
 #ifdef CLSTM_LSTM_PROF
@@ -1165,7 +1191,7 @@ struct Net {
   // tile-height function -- should the backward pass still come out with another tile height, gemm_mc_check_a2 refuses the launch
   // loudly instead of reading x rows nobody wrote.  (Requiring BOTH R and R - 1 to fit, the first form of that fix, switched the
   // path off at configs[4]: 1537 rows pick 192-row tiles.)  The first condition is wide_args' for reserving Dbf and dbias.
-  static int dw_bf16_rows(const Layer& y, int R, int Cn) { return wide_kp16_bwd(y.no) == 4 * y.no && gemm_bf16_big(R - 1, Cn) ? R - 1 : R; }
+  static int dw_bf16_rows(const Layer& y, int R, int Cn) { return y.bwd_exact && gemm_bf16_big(R - 1, Cn) ? R - 1 : R; }
   // Slab geometry of the chunked weight-gradient GEMM (measured at the bench shape unless said otherwise):
   // - chunks of DW_CHUNK iterations (8: 0.407 ms per step, 16: 0.356, 32: 0.359, 48: 0.360, a decreasing plan 64..16: 0.3615);
   // - ~16 slabs per direction, at most DW_STAB_MAX k-tiles (of 16 frames) each: a slab's table must fit the items' LDS copy.  At
@@ -1439,13 +1465,12 @@ struct Net {
     int skipped_d = 0;
     if (fam == BwdFamily::Wide) {
       const LstmWideArgs w = wide_args(y, false);
-      ran = launch_lstm_wide(false, w, tmax, coop_sync, step_graphs, s, bf16_rec, 0, rec_x3());
+      ran = launch_lstm_wide(wide_plan(wide_shape(y, false)), w, coop_sync, step_graphs, s);
       skipped_d = w.skip_d;
     } else launch_bwd_narrow(y, a, s);
     timing.end(s);
     const bool persistent = ran == WideRan::Persistent;
-    y.d_f32_valid = !(persistent && bf16_rec && skipped_d);
-    if (persistent) g_path_count[PC_BWD_PERSISTENT]++;
+    y.d_f32_valid = !(persistent && bf16_rec && skipped_d);   // (launch_lstm_wide moved the plan's path counters)
     return persistent;
   }
   BwdPlan backward_plan(const Layer& y, BwdFamily fam, bool bwd_persistent) const {
@@ -1518,7 +1543,7 @@ struct Net {
       // same bf16 delta array, BOTH products as one launch (gemm_bf16.h:gemm_dw_dx_kernel: apart, each leaves a quarter of the chip idle)
       const StorePartialShift store{slabs, R, Cn};
       float* const dxp = l > 0 ? L[l - 1].dH.p : nullptr;
-      dx_done = dxp && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p &&
+      dx_done = dxp && y.bwd_exact && y.Wtb.p &&
                 gemm_dw_dx(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows, GemmOperand16{y.Dbf.p, M, (long long)N * M},
                            GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dxp, y.ni}, (int)N, y.ni, M);
       if (!dx_done) gemm_b16mc(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows);
@@ -1538,7 +1563,7 @@ struct Net {
     float* const dx = l > 0 ? L[l - 1].dH.p : want_dx0 ? dX0.p : nullptr;   // the layer below's output deltas, or what the caller asked for
     if (!dx) return;
     timing.begin("gemm_gates_dx", s);
-    if (bf16_gemm && bf16_rec && p.bwd_persistent && wide_kp16_bwd(y.no) == 4 * y.no && y.Wtb.p && y.Dbf.p) {
+    if (bf16_gemm && bf16_rec && p.bwd_persistent && y.bwd_exact && y.Wtb.p && y.Dbf.p) {
       // the persistent recurrence left the deltas as a k-contiguous bf16 array: both operands go to LDS as they are
       g_path_count[PC_DX_FROM_BF16]++;
       gemm_b16kk(s, GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dx, y.ni}, (int)N, y.ni, M);

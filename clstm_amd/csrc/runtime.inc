@@ -1,5 +1,6 @@
 // runtime.inc -- part of clstm_hip.hip (namespace clstm): errors, device buffers and the pinned staging ring, GEMM store functors,
-// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), device error words, per-kernel timing, roctx.
+// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), the lock-step layer's kernel choice (wide_plan),
+// device error words, per-kernel timing, roctx.
 // Not a stand-alone header: included once, inside the namespace, by clstm_hip.hip.
 
 static thread_local std::string g_err;
@@ -467,132 +468,183 @@ static void copy_d2h(float* dst, const float* src, size_t n) {
 static int g_debug_fail_claims = 0;      // tests: this many upcoming persistent launches fail their placement check ...
 static int g_debug_fail_skip = 0;        // ... after this many that do not
 
-// What launch_lstm_wide ran: persistent per-XCD kernels or a launch per step.  Nothing only with fx_ngx > 0 (forward, bf16): ONLY the
-// persistent kernel with the input projection folded in (lstm_xcd_fwd_bf16_fx<fx_ngx>) is tried, and if it does not apply or its placement
-// check failed nothing was launched or nothing written: the caller then runs the hoisted product and calls again with fx_ngx = 0.
-enum class WideRan { Nothing, Steps, Persistent };
-static std::map<const void*, int> g_stamp_base;   // per sync buffer: where the group-barrier stamps of its next persistent launch start
-static WideRan launch_lstm_wide(bool fwd, LstmWideArgs a, int tmax, DevBuf<int>& sync, StepGraphCache& graphs, hipStream_t s, bool bf16 = false, int fx_ngx = 0, bool x3 = false) {
-  REQUIRE((double)a.N * a.ndir * 4 * a.no * 4 < 2147483000.0,
-          "minibatch too large for the lock-step recurrence (frames x 4 x nhidden x ndir x 4 B must stay below 2 GiB)");
-  const int no = a.no, ncu = device_cu_count();
-  const int ntile = (no + 15) / 16, nzb16 = (a.bs + 15) / 16;
+// ---- the lock-step layer (lstm_wide.h): WHICH of its eleven kernels runs is decided once per pass by wide_plan, a pure function of a
+// WideShape (no device, no global, no environment: the caller reads those into the shape -- Net::wide_shape); launch_lstm_wide only
+// executes the plan.  clstm_debug_wide_plan asks wide_plan without a net: both structs are plain ints in the order documented there.
+enum WideKernel {
+  WK_NONE = 0, WK_XCD_FWD_F32, WK_XCD_FWD_BF16 /* <MT> */, WK_XCD_FWD_BF16_FX /* <NGX> */, WK_XCD_BWD_X3, WK_XCD_BWD_F32, WK_XCD_BWD_BF16_C32 /* <EPT, FULLK> */,
+  WK_XCD_BWD_BF16 /* <MT> */, WK_FWD_STEP /* <MT> */, WK_FWD_STEP16_BF16, WK_BWD_STEP, WK_BWD_STEP16_BF16
+};
+struct WideShape {
+  int fwd, no, x_ni, ndir, bs, tmax, N;   // the pass, the layer (x_ni: its inputs), the minibatch (N frames)
+  int kp, kp16;                           // padded contraction lengths of this pass: f32 rows (Layer::kpf / kpb), bf16 rows (kp16f / kp16b)
+  int bf16;                               // bf16 MFMA operands in the recurrence (precision mode 2)
+  int x3;                                 // backward, exact-f32 mode: the x3 kernel is asked for (Net::rec_x3) and R2b holds the current weights
+  int fx_mode;                            // forward: option fuse_wx where the operands of the folded input projection exist, else 0
+  int ncu, xcd_on, xcd_failed, c32_on;    // CUs of the device, CLSTM_XCD_REC, g_xcd_failed, option bwd_c32
+  int sbf, sbf_ld, lds, ldh;              // what the 32-bit offsets of the persistent bf16 kernels must cover: the bf16 source rows (sbf: written by
+                                          // this pass -- the f32 h_{t-1} columns of S are then skipped: Net::wide_args), the f32 source and output rows
+};
+struct WidePlan {
+  int kernel, param, fullk;               // the persistent kernel to try (WK_NONE: none applies) and its template parameter MT / NGX / EPT
+  int nzb, zb_per, launches, lds_bytes;   // its line blocks, how many of them one launch walks, hence the launches; dynamic LDS
+  int step_kernel, step_param;            // the per-step kernel that runs if none applies or chunk 0 failed its placement check (WK_NONE behind
+  int step_grid[3];                       // WK_XCD_FWD_BF16_FX: the caller runs the hoisted product first and asks again without fx) and its grid
+  int moves;                              // bit c: a successful persistent pass moves path counter c
+  int fx_ngx;                             // the folded input projection was ASKED for (fuse_wx and the input width admit it): its NGX, else 0
+};
+static WidePlan wide_plan(const WideShape& h) {
+  WidePlan p{};
+  const bool fwd = h.fwd != 0, bf16 = h.bf16 != 0;
+  const int no = h.no, ntile = (no + 15) / 16, nzb16 = (h.bs + 15) / 16;
   // persistent bf16 kernels: 32-line groups (two 16-line MFMA tiles per workgroup) once 16-line groups would need more than
   // one launch of 8 groups -- a step's barrier and ring round trip are then paid once for twice the lines
-  const int mt = !bf16 ? 1 : nzb16 * a.ndir > 16 ? 4 : nzb16 * a.ndir > 8 ? 2 : 1;
-  const int nzb_default = (a.bs + 16 * mt - 1) / (16 * mt);
-  a.tmax = tmax;
-  sync.reserve(XcdSyncLayout::WORDS);
-  a.sync = sync.p;
-  // ONE launch per pass, a workgroup group per XCD with its weight rows resident in LDS (lstm_xcd_*: the default).
-  // CLSTM_XCD_REC=0 selects the per-step launches below; they are also the fallback when the placement check of the
-  // first launch fails (workgroups not spread evenly over the XCDs: nothing has been written at that point).
-  const bool xcd_on = !(getenv("CLSTM_XCD_REC") && atoi(getenv("CLSTM_XCD_REC")) == 0);
-  // (minibatches of more than 8 / ndir line blocks: one launch per chunk of line blocks)
-  const int zb_per_default = std::max(1, 8 / a.ndir);
-  auto persistent = [&](auto kernel, size_t smem, int nthreads = WIDE_THREADS, int nzb_ = -1, int zb_per_ = -1) {
-    bool ok = true;
-    const int nzb = nzb_ > 0 ? nzb_ : nzb_default, zb_per = zb_per_ > 0 ? zb_per_ : zb_per_default;
-    for (int zb0 = 0; zb0 < nzb && ok; zb0 += zb_per) {
-      a.zb0 = zb0; a.zbn = std::min(zb_per, nzb - zb0);
-      a.debug_fail_claim = g_debug_fail_skip > 0 ? (g_debug_fail_skip--, 0) : g_debug_fail_claims > 0 ? (g_debug_fail_claims--, 1) : 0;
-      // (the counter words are zero: DevBuf zero-fills, and every persistent launch returns them to zero as its last act;
-      // the stamps of the group barriers keep counting up: lstm_wide.h:xcd_finish)
-      {
-        int& base = g_stamp_base[(const void*)sync.p];
-        if (base > (1 << 30)) {   // (once per ~2 million launches)
-          HIPCHECK(hipMemsetAsync(sync.p, 0, XcdSyncLayout::WORDS * sizeof(int), s));
-          base = 0;
-        }
-        a.stamp_base = base;
-        base += tmax + 2;
-      }
-      a.out_sticky = dev_err_words();
-      a.out_host = g_xcd_outcome.prepare();
-      coop_set_smem(kernel, smem);
-      // An ORDINARY launch: one workgroup per CU (LDS), at most as many workgroups as CUs, the stream's previous kernel complete --
-      // they are all resident, and if they ever were not, the placement check of xcd_claim times out with error 1 before anything
-      // has been written.  The first four launches of a process are checked synchronously and the per-step path redoes such a pass;
-      // a later failure is found asynchronously (XcdOutcome): the updates since then are skipped on the device, the host reports it
-      // at its next check and uses the per-step launches from then on.  hipLaunchCooperativeKernel cost ~20 us of gaps around every
-      // one of the four launches of a configs[4] step.  (The host emulator needs its "all workgroups live" launch.)
-#ifdef CLSTM_HIP_EMU
-      CLSTM_LAUNCH_COOP(kernel, dim3(8 * ntile), dim3(nthreads), smem, s, a);
-#else
-      CLSTM_LAUNCH(kernel, dim3(8 * ntile), dim3(nthreads), smem, s, a);
-#endif
-      check_launch();
-      ok = g_xcd_outcome.after_launch(sync.p + XcdSyncLayout::LAST_ERROR, s);
-      REQUIRE(ok || zb0 == 0, "persistent recurrence: placement failed after the first chunk had run; set CLSTM_XCD_REC=0");
-    }
-    if (!ok) g_xcd_failed = true;
-    return ok;
-  };
-  // (the persistent bf16 kernels address their per-frame arrays through 32-bit buffer offsets: G / C / D / Dbf are covered by the check
-  // above, the bf16 and f32 source rows -- ndir x N x (ni + no + 8) halfs / (1 + ni + no) floats -- and the output rows must stay below 2 GiB
-  // too, or the per-step launches run)
-  const bool off32 = !bf16 || ((!a.Sbf || (double)a.ndir * a.N * a.sbf_ld * 2 < 2147483000.0) &&
-                               (a.skip_s || (double)a.ndir * a.N * a.lds * 4 < 2147483000.0) && (double)a.N * a.ldh * 4 < 2147483000.0);
-  const bool fits = xcd_on && !g_xcd_failed && off32 && tmax > 1 && ntile <= 32 && 8 * ntile <= std::max(ncu, 16);
-  if (fx_ngx > 0) {
-    if (!(fwd && bf16 && fits && mt == 1 && a.kp16 <= 512 && (no & 3) == 0 && a.x_ni <= 128 * fx_ngx && a.x_ni <= 2048)) return WideRan::Nothing;
-    auto fx = [&](auto kernel) { return persistent(kernel, (size_t)xcd_fwd_lds_bytes(1)) ? WideRan::Persistent : WideRan::Nothing; };
-    return fx_ngx == 1 ? fx(lstm_xcd_fwd_bf16_fx<1>) : fx_ngx == 4 ? fx(lstm_xcd_fwd_bf16_fx<4>) : fx_ngx == 8 ? fx(lstm_xcd_fwd_bf16_fx<8>) : WideRan::Nothing;
-  }
-  if (fwd) {
-    if (fits && !bf16 && (size_t)xcd_fwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_fwd_f32, (size_t)xcd_fwd_f32_lds_bytes(a.kp))) return WideRan::Persistent;
-    if (fits && bf16 && a.kp16 <= 512 &&
-        (mt == 4 ? persistent(lstm_xcd_fwd_bf16<4>, (size_t)xcd_fwd_lds_bytes(4))
-         : mt == 2 ? persistent(lstm_xcd_fwd_bf16<2>, (size_t)xcd_fwd_lds_bytes(2)) : persistent(lstm_xcd_fwd_bf16<1>, (size_t)xcd_fwd_lds_bytes(1)))) return WideRan::Persistent;
-    const int mts = a.bs > 32 ? 4 : a.bs > 16 ? 2 : 1;
-    const dim3 grid((no + 3) / 4, a.ndir, (a.bs + 16 * mts - 1) / (16 * mts));
-    const dim3 grid16(ntile * a.ndir * nzb16);
-    launch_steps(graphs, bf16 ? 2 : 0, a, tmax, s, [&]() {
-      LstmWideArgs w = a;
-      for (int t = 0; t < tmax; t++) {
-        w.step = t;
-        if (bf16) CLSTM_LAUNCH(lstm_wide_fwd_step16_bf16, grid16, dim3(WIDE_THREADS), 0, s, w);
-        else if (mts == 4) CLSTM_LAUNCH(lstm_wide_fwd_step<4>, grid, dim3(WIDE_THREADS), 0, s, w);
-        else if (mts == 2) CLSTM_LAUNCH(lstm_wide_fwd_step<2>, grid, dim3(WIDE_THREADS), 0, s, w);
-        else CLSTM_LAUNCH(lstm_wide_fwd_step<1>, grid, dim3(WIDE_THREADS), 0, s, w);
-      }
-    });
+  const int mt = !bf16 ? 1 : nzb16 * h.ndir > 16 ? 4 : nzb16 * h.ndir > 8 ? 2 : 1;
+  // the fallback, and the rule where no persistent kernel applies: one launch per time step
+  if (fwd && !bf16) {
+    const int mts = h.bs > 32 ? 4 : h.bs > 16 ? 2 : 1;
+    p.step_kernel = WK_FWD_STEP; p.step_param = mts;
+    p.step_grid[0] = (no + 3) / 4; p.step_grid[1] = h.ndir; p.step_grid[2] = (h.bs + 16 * mts - 1) / (16 * mts);
+  } else if (!bf16) {
+    p.step_kernel = WK_BWD_STEP;
+    p.step_grid[0] = ntile; p.step_grid[1] = h.ndir; p.step_grid[2] = nzb16;
   } else {
-    if (fits && !bf16 && x3 && a.Rw16 && a.kp16 <= 2048) {
-      if (persistent(lstm_xcd_bwd_x3, (size_t)xcd_bwd_lds_bytes(1))) { g_path_count[PC_BWD_X3]++; return WideRan::Persistent; }
-    } else
-    if (fits && !bf16 && (size_t)xcd_bwd_f32_lds_bytes(a.kp) <= 160 * 1024 && persistent(lstm_xcd_bwd_f32, (size_t)xcd_bwd_f32_lds_bytes(a.kp))) return WideRan::Persistent;
-    // 32 cells per workgroup, two groups per XCD, groups of 8 / 16 / 32 lines (lstm_wide.h:lstm_xcd_bwd_bf16_c32): half the
-    // delta block per step and CU of the 16-cell kernel below, which stays for hidden sizes that are not multiples of 32
-    const bool c32_on = dbg_opt("bwd_c32") != 0;   // (read per pass: tests compare both kernels in one process)
-    if (fits && bf16 && a.kp16 <= 2048 && c32_on && no % 32 == 0 && a.ndir <= 2) {
-      const int per = 16 / a.ndir;   // line groups per launch
-      const int ept = a.bs <= 8 * per ? 1 : a.bs <= 16 * per ? 2 : 4;
-      const int ng = (a.bs + 8 * ept - 1) / (8 * ept);
-      const size_t smem = (size_t)xcd_bwd_c32_lds_bytes(ept);
-      const bool fullk = a.kp16 == 2048;
-      auto go = [&](auto k_full, auto k_any) { return fullk ? persistent(k_full, smem, WIDE_THREADS, ng, per) : persistent(k_any, smem, WIDE_THREADS, ng, per); };
-      if (ept == 1 ? go(lstm_xcd_bwd_bf16_c32<1, true>, lstm_xcd_bwd_bf16_c32<1, false>)
-          : ept == 2 ? go(lstm_xcd_bwd_bf16_c32<2, true>, lstm_xcd_bwd_bf16_c32<2, false>) : go(lstm_xcd_bwd_bf16_c32<4, true>, lstm_xcd_bwd_bf16_c32<4, false>)) {
-        g_path_count[PC_BWD_C32]++;
-        return WideRan::Persistent;
-      }
-    } else
-    if (fits && bf16 && a.kp16 <= 2048 &&
-        (mt == 4 ? persistent(lstm_xcd_bwd_bf16<4>, (size_t)xcd_bwd_lds_bytes(4))
-         : mt == 2 ? persistent(lstm_xcd_bwd_bf16<2>, (size_t)xcd_bwd_lds_bytes(2)) : persistent(lstm_xcd_bwd_bf16<1>, (size_t)xcd_bwd_lds_bytes(1)))) return WideRan::Persistent;
-    const dim3 grid(ntile, a.ndir, nzb16);
-    const dim3 grid16(ntile * a.ndir * nzb16);
-    launch_steps(graphs, bf16 ? 3 : 1, a, tmax, s, [&]() {
-      LstmWideArgs w = a;
-      for (int t = 0; t < tmax; t++) {
-        w.step = t;
-        if (bf16) CLSTM_LAUNCH(lstm_wide_bwd_step16_bf16, grid16, dim3(WIDE_THREADS), 0, s, w);
-        else CLSTM_LAUNCH(lstm_wide_bwd_step, grid, dim3(WIDE_THREADS), 0, s, w);
-      }
-    });
+    p.step_kernel = fwd ? WK_FWD_STEP16_BF16 : WK_BWD_STEP16_BF16;
+    p.step_grid[0] = ntile * h.ndir * nzb16; p.step_grid[1] = p.step_grid[2] = 1;
   }
+  // ONE launch per pass, a workgroup group per XCD with its weight rows resident in LDS (lstm_xcd_*: the default); minibatches of
+  // more than 8 / ndir line blocks: one launch per chunk of line blocks.  CLSTM_XCD_REC=0 selects the per-step launches.
+  // (The persistent bf16 kernels address their per-frame arrays through 32-bit buffer offsets: G / C / D / Dbf are covered by
+  // Net::wide_args' check, the bf16 and f32 source rows -- ndir x N x (ni + no + 8) halfs / (1 + ni + no) floats -- and the output rows
+  // must stay below 2 GiB too, or the per-step launches run)
+  const double lim = 2147483000.0;
+  const bool off32 = !bf16 || ((!h.sbf || (double)h.ndir * h.N * h.sbf_ld * 2 < lim) && (h.sbf || (double)h.ndir * h.N * h.lds * 4 < lim) && (double)h.N * h.ldh * 4 < lim);
+  const bool fits = h.xcd_on && !h.xcd_failed && off32 && h.tmax > 1 && ntile <= 32 && 8 * ntile <= std::max(h.ncu, 16);
+  p.nzb = (h.bs + 16 * mt - 1) / (16 * mt);
+  p.zb_per = std::max(1, 8 / h.ndir);
+  // The input projection folded into the persistent bf16 forward kernel (lstm_xcd_fwd_bf16_fx; measurements: Net::forward_pass).  fuse_wx:
+  // 0 never, 1 (default) layers of up to 128 inputs, 2 every eligible layer; whole 32-k groups of inputs, NGX x 128 of them at most.
+  // ONLY that kernel is planned then: where it does not apply, kernel names what runs behind the hoisted product.
+  if (fwd && h.fx_mode > 0 && (h.fx_mode > 1 || h.x_ni <= 128) && (h.x_ni & 31) == 0)
+    p.fx_ngx = h.x_ni <= 128 ? 1 : h.x_ni <= 512 ? 4 : h.x_ni <= 1024 ? 8 : 0;
+  auto take = [&](int kernel, int param, int lds_bytes, int moves = 0) { p.kernel = kernel; p.param = param; p.lds_bytes = lds_bytes; p.moves = moves; };
+  if (fits && p.fx_ngx && bf16 && mt == 1 && h.kp16 <= 512 && (no & 3) == 0 && h.x_ni <= 128 * p.fx_ngx && h.x_ni <= 2048) {
+    take(WK_XCD_FWD_BF16_FX, p.fx_ngx, xcd_fwd_lds_bytes(1), 1 << PC_FWD_FUSED_WX);
+    p.step_kernel = WK_NONE;
+  } else if (fits && fwd) {
+    if (!bf16 && xcd_fwd_f32_lds_bytes(h.kp) <= 160 * 1024) take(WK_XCD_FWD_F32, 0, xcd_fwd_f32_lds_bytes(h.kp));
+    else if (bf16 && h.kp16 <= 512) take(WK_XCD_FWD_BF16, mt, xcd_fwd_lds_bytes(mt));
+  } else if (fits && !bf16) {   // (an x3 pass whose placement failed does not try the f32 kernel: one persistent kernel per plan)
+    if (h.x3 && h.kp16 <= 2048) take(WK_XCD_BWD_X3, 0, xcd_bwd_lds_bytes(1), 1 << PC_BWD_X3);
+    else if (xcd_bwd_f32_lds_bytes(h.kp) <= 160 * 1024) take(WK_XCD_BWD_F32, 0, xcd_bwd_f32_lds_bytes(h.kp));
+  } else if (fits && h.kp16 <= 2048) {
+    // 32 cells per workgroup, two groups per XCD, groups of 8 / 16 / 32 lines (lstm_wide.h:lstm_xcd_bwd_bf16_c32): half the
+    // delta block per step and CU of the 16-cell kernel, which stays for hidden sizes that are not multiples of 32
+    if (h.c32_on && no % 32 == 0 && h.ndir <= 2) {
+      p.zb_per = 16 / h.ndir;   // line groups per launch
+      const int ept = h.bs <= 8 * p.zb_per ? 1 : h.bs <= 16 * p.zb_per ? 2 : 4;
+      take(WK_XCD_BWD_BF16_C32, ept, xcd_bwd_c32_lds_bytes(ept), 1 << PC_BWD_C32);
+      p.fullk = h.kp16 == 2048;
+      p.nzb = (h.bs + 8 * ept - 1) / (8 * ept);
+    } else take(WK_XCD_BWD_BF16, mt, xcd_bwd_lds_bytes(mt));
+  }
+  if (p.kernel != WK_NONE) {
+    p.moves |= 1 << (fwd ? PC_FWD_PERSISTENT : PC_BWD_PERSISTENT);
+    p.launches = (p.nzb + p.zb_per - 1) / p.zb_per;
+  } else p.launches = h.tmax;
+  return p;
+}
+// every instantiation of the lock-step kernels: the ONE place that names them (in the order of their first use so far: the
+// order of the instantiations in the code object)
+using WideFn = void (*)(LstmWideArgs);
+static WideFn wide_kernel_fn(int kernel, int param, int fullk) {
+  static const struct { int kernel, param, fullk; WideFn fn; } table[] = {
+      {WK_XCD_FWD_BF16_FX, 1, 0, lstm_xcd_fwd_bf16_fx<1>}, {WK_XCD_FWD_BF16_FX, 4, 0, lstm_xcd_fwd_bf16_fx<4>}, {WK_XCD_FWD_BF16_FX, 8, 0, lstm_xcd_fwd_bf16_fx<8>},
+      {WK_XCD_FWD_F32, 0, 0, lstm_xcd_fwd_f32},
+      {WK_XCD_FWD_BF16, 4, 0, lstm_xcd_fwd_bf16<4>}, {WK_XCD_FWD_BF16, 2, 0, lstm_xcd_fwd_bf16<2>}, {WK_XCD_FWD_BF16, 1, 0, lstm_xcd_fwd_bf16<1>},
+      {WK_FWD_STEP16_BF16, 0, 0, lstm_wide_fwd_step16_bf16},
+      {WK_FWD_STEP, 4, 0, lstm_wide_fwd_step<4>}, {WK_FWD_STEP, 2, 0, lstm_wide_fwd_step<2>}, {WK_FWD_STEP, 1, 0, lstm_wide_fwd_step<1>},
+      {WK_XCD_BWD_X3, 0, 0, lstm_xcd_bwd_x3}, {WK_XCD_BWD_F32, 0, 0, lstm_xcd_bwd_f32},
+      {WK_XCD_BWD_BF16_C32, 1, 1, lstm_xcd_bwd_bf16_c32<1, true>}, {WK_XCD_BWD_BF16_C32, 1, 0, lstm_xcd_bwd_bf16_c32<1, false>},
+      {WK_XCD_BWD_BF16_C32, 2, 1, lstm_xcd_bwd_bf16_c32<2, true>}, {WK_XCD_BWD_BF16_C32, 2, 0, lstm_xcd_bwd_bf16_c32<2, false>},
+      {WK_XCD_BWD_BF16_C32, 4, 1, lstm_xcd_bwd_bf16_c32<4, true>}, {WK_XCD_BWD_BF16_C32, 4, 0, lstm_xcd_bwd_bf16_c32<4, false>},
+      {WK_XCD_BWD_BF16, 4, 0, lstm_xcd_bwd_bf16<4>}, {WK_XCD_BWD_BF16, 2, 0, lstm_xcd_bwd_bf16<2>}, {WK_XCD_BWD_BF16, 1, 0, lstm_xcd_bwd_bf16<1>},
+      {WK_BWD_STEP16_BF16, 0, 0, lstm_wide_bwd_step16_bf16}, {WK_BWD_STEP, 0, 0, lstm_wide_bwd_step}};
+  for (const auto& e : table)
+    if (e.kernel == kernel && e.param == param && e.fullk == fullk) return e.fn;
+  throw Error("internal: no lock-step kernel for this plan");
+}
+// The sync words of the persistent kernels and where the group-barrier stamps of the buffer's next launch start.  (The counter words are
+// zero: DevBuf zero-fills, and every persistent launch returns them to zero as its last act; the stamps keep counting up: lstm_wide.h:xcd_finish)
+struct XcdSync {
+  DevBuf<int> words;
+  int base = 0;
+  int* reserve() { words.reserve(XcdSyncLayout::WORDS); return words.p; }
+  int take_stamps(int tmax, hipStream_t s) {
+    if (base > (1 << 30)) {   // (once per ~2 million launches)
+      HIPCHECK(hipMemsetAsync(words.p, 0, XcdSyncLayout::WORDS * sizeof(int), s));
+      base = 0;
+    }
+    const int b = base;
+    base += tmax + 2;
+    return b;
+  }
+};
+// the persistent kernel of the plan over its chunks of line blocks; false: chunk 0 failed its placement check and nothing was written
+static bool launch_wide_persistent(const WidePlan& p, LstmWideArgs& a, XcdSync& sync, hipStream_t s) {
+  const WideFn kernel = wide_kernel_fn(p.kernel, p.param, p.fullk);
+  const int ntile = (a.no + 15) / 16;
+  bool ok = true;
+  for (int zb0 = 0; zb0 < p.nzb && ok; zb0 += p.zb_per) {
+    a.zb0 = zb0; a.zbn = std::min(p.zb_per, p.nzb - zb0);
+    a.debug_fail_claim = g_debug_fail_skip > 0 ? (g_debug_fail_skip--, 0) : g_debug_fail_claims > 0 ? (g_debug_fail_claims--, 1) : 0;
+    a.stamp_base = sync.take_stamps(a.tmax, s);
+    a.out_sticky = dev_err_words();
+    a.out_host = g_xcd_outcome.prepare();
+    coop_set_smem(kernel, (size_t)p.lds_bytes);
+    // An ORDINARY launch: one workgroup per CU (LDS), at most as many workgroups as CUs, the stream's previous kernel complete --
+    // they are all resident, and if they ever were not, the placement check of xcd_claim times out with error 1 before anything
+    // has been written.  The first four launches of a process are checked synchronously and the per-step path redoes such a pass;
+    // a later failure is found asynchronously (XcdOutcome): the updates since then are skipped on the device, the host reports it
+    // at its next check and uses the per-step launches from then on.  hipLaunchCooperativeKernel cost ~20 us of gaps around every
+    // one of the four launches of a configs[4] step.  (The host emulator needs its "all workgroups live" launch.)
+#ifdef CLSTM_HIP_EMU
+    CLSTM_LAUNCH_COOP(kernel, dim3(8 * ntile), dim3(WIDE_THREADS), (size_t)p.lds_bytes, s, a);
+#else
+    CLSTM_LAUNCH(kernel, dim3(8 * ntile), dim3(WIDE_THREADS), (size_t)p.lds_bytes, s, a);
+#endif
+    check_launch();
+    ok = g_xcd_outcome.after_launch(sync.words.p + XcdSyncLayout::LAST_ERROR, s);
+    REQUIRE(ok || zb0 == 0, "persistent recurrence: placement failed after the first chunk had run; set CLSTM_XCD_REC=0");
+  }
+  if (!ok) g_xcd_failed = true;
+  return ok;
+}
+// ... and its per-step kernel, one launch per time step (a replayed graph from 8 steps on: launch_steps)
+static void launch_wide_steps(const WidePlan& p, const LstmWideArgs& a, StepGraphCache& graphs, hipStream_t s) {
+  const WideFn kernel = wide_kernel_fn(p.step_kernel, p.step_param, 0);
+  const int kind = p.step_kernel == WK_FWD_STEP ? 0 : p.step_kernel == WK_BWD_STEP ? 1 : p.step_kernel == WK_FWD_STEP16_BF16 ? 2 : 3;
+  const dim3 grid(p.step_grid[0], p.step_grid[1], p.step_grid[2]);
+  launch_steps(graphs, kind, a, a.tmax, s, [&]() {
+    LstmWideArgs w = a;
+    for (int t = 0; t < a.tmax; t++) {
+      w.step = t;
+      CLSTM_LAUNCH(kernel, grid, dim3(WIDE_THREADS), 0, s, w);
+    }
+  });
   check_launch();
+}
+// What launch_lstm_wide ran.  The persistent kernel is tried first; a placement failure in chunk 0 (nothing written) falls back to the
+// per-step launches, a later one is fatal.  Nothing: the plan was the fx kernel alone and it failed its placement check.
+enum class WideRan { Nothing, Steps, Persistent };
+static WideRan launch_lstm_wide(const WidePlan& p, LstmWideArgs a, XcdSync& sync, StepGraphCache& graphs, hipStream_t s) {
+  if (p.kernel != WK_NONE && launch_wide_persistent(p, a, sync, s)) {
+    for (int c = 0; c < PC_COUNT; c++)
+      if (p.moves >> c & 1) g_path_count[c]++;
+    return WideRan::Persistent;
+  }
+  if (p.step_kernel == WK_NONE) return WideRan::Nothing;
+  launch_wide_steps(p, a, graphs, s);
   return WideRan::Steps;
 }
 // diagnostics (CLSTM_FW_TRACE / CLSTM_DW_TRACE): the stamp rows a launch left on the device, four per line, under the caller's header

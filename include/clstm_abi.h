@@ -451,6 +451,19 @@ int clstm_debug_set_option(const char* name, int value);
  * items that gave up waiting.  While either is non-zero clstm_net_update() applies nothing; the next synchronisation
  * point (clstm_synchronize, any *_h read-back) reports the error and clears the words. */
 int clstm_debug_set_device_error(int which, int value);
+/* Which lock-step kernel a wide layer's pass runs (csrc/runtime.inc: wide_plan, the one place that decides): host arithmetic, no net, no device.
+ * shape (20 ints, HOST in): fwd, no, x_ni (the layer's inputs), ndir, bs, tmax, N (frames), kp, kp16 (padded contraction lengths of the
+ *   pass: f32 rows, multiple of 64 / bf16 rows, multiple of 128), bf16 (precision mode 2), x3 (backward: the x3 kernel asked for and its
+ *   weights packed), fx_mode (forward: option fuse_wx where the folded input projection has its operands, else 0), ncu, xcd_on
+ *   (CLSTM_XCD_REC), xcd_failed (a placement check has failed in this process), c32_on (option bwd_c32), sbf (the pass writes bf16 source
+ *   rows), sbf_ld, lds, ldh (row strides of the bf16 source, f32 source and output rows).
+ * plan (14 ints, HOST out): kernel, param, fullk -- the persistent kernel tried first, 0 none, 1 xcd_fwd_f32, 2 xcd_fwd_bf16<MT>,
+ *   3 xcd_fwd_bf16_fx<NGX>, 4 xcd_bwd_x3, 5 xcd_bwd_f32, 6 xcd_bwd_bf16_c32<EPT, FULLK>, 7 xcd_bwd_bf16<MT>; nzb, zb_per (line blocks, and
+ *   how many one launch walks), launches (of what runs if every placement check holds: chunks, or tmax per-step launches), lds_bytes;
+ *   step_kernel, step_param -- what runs per time step otherwise: 8 wide_fwd_step<MT>, 9 wide_fwd_step16_bf16, 10 wide_bwd_step,
+ *   11 wide_bwd_step16_bf16, 0 none (behind kernel 3 the caller runs the hoisted product and asks again with fx_mode 0); step_grid[3];
+ *   moves (bit c: a successful persistent pass moves clstm_debug_path_count(c)); fx_ngx (the folded projection was asked for). */
+int clstm_debug_wide_plan(const int* shape, int* plan);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,8 @@
 """Parity sweep over the hidden sizes, line counts, input widths and precisions of wide layers (lstm_wide.h: every layer of more than
 128 cells, BASELINE configs[4]).
 
-Seven persistent and four per-step kernels carry these layers; which one runs is decided on the host (runtime.inc:launch_lstm_wide,
-net.inc:wide_args / Net::repack / Net::forward_pass) from the cell count -- the padded contraction lengths wide_kp_fwd / wide_kp_bwd
+Seven persistent and four per-step kernels carry these layers; which one runs is decided on the host (runtime.inc:wide_plan from
+net.inc:Net::wide_shape; the weight packs: Net::repack) from the cell count -- the padded contraction lengths wide_kp_fwd / wide_kp_bwd
 (multiples of 64) and wide_kp16_fwd / wide_kp16_bwd (multiples of 128), the cell tiles (4 forward, 16 backward, 32 for
 lstm_xcd_bwd_bf16_c32), no % 32, no % 128, no % 4, ntile <= 32 -- and from the line count: 16-line blocks, mt = 1 / 2 / 4 and ept =
 1 / 2 / 4 at 8 / 16 line-block x direction groups, chunks of 8 / ndir blocks per launch, mts of the per-step forward at 16 / 32 lines.
@@ -30,6 +30,7 @@ Each case prints `SWEEP <case> class=(kp_fwd, kp16_fwd, persistent) fwd=<kernel>
 and `worst=<largest error / bar>` (f32) or `ratio=<largest kernel error / D_q>` (bf16) with the per-quantity figures.
 `python tests/test_wide_layer_sweep.py [pytest output of a GPU run]` prints the table of DESIGN.md 4.6 from wide_geometry()."""
 import contextlib
+import ctypes
 import os
 import re
 import subprocess
@@ -92,13 +93,14 @@ def tiled_pack(no, ni, precision):
     return precision == 2 and no % 128 == 0 and ni % 32 == 0 and kp16_fwd(no) == no and kp16_bwd(no) == 4 * no
 
 
-def wide_geometry(no, ni, ndir, nlines, tmax, precision, strict, kind, xcd_rec=True):
+def wide_geometry(no, ni, ndir, nlines, tmax, precision, strict, kind, xcd_rec=True, ncu=None):
     """What the C++ derives for the first (wide) layer of a net in one forward + backward: the cell tiles, the padded contraction
-    lengths, whether the persistent kernels may run, per pass the kernel and its number of launches, and the path-counter moves."""
+    lengths, whether the persistent kernels may run, per pass the kernel and its number of launches, and the path-counter moves.
+    ncu: a chip of that many CUs instead of the backend's."""
     assert no > 128 and precision in (0, 2) and not (strict and precision)
     bf16 = precision == 2
-    ncu = cus(kind)
-    ntile, nzb16 = (no + 15) // 16, (nlines + 15) // 16                           # runtime.inc:launch_lstm_wide
+    ncu = cus(kind) if ncu is None else ncu
+    ntile, nzb16 = (no + 15) // 16, (nlines + 15) // 16                           # runtime.inc:wide_plan
     mt = 1 if not bf16 else 4 if nzb16 * ndir > 16 else 2 if nzb16 * ndir > 8 else 1
     nzb, zb_per = (nlines + 16 * mt - 1) // (16 * mt), max(1, 8 // ndir)
     chunks = (nzb + zb_per - 1) // zb_per
@@ -140,6 +142,41 @@ def wide_geometry(no, ni, ndir, nlines, tmax, precision, strict, kind, xcd_rec=T
         g["bwd"], g["bwd_launches"] = "bwd_step16_bf16" if bf16 else "bwd_step", tmax
     g["moves"] = moves
     return g
+
+
+# clstm_debug_wide_plan (include/clstm_abi.h): what the library's own rule (runtime.inc:wide_plan) answers for the same shape.  The shape is
+# laid out here as net.inc:Net::wide_shape fills it for the first layer of a net in its default options.
+PLAN_KERNELS = {1: "xcd_fwd_f32", 2: "xcd_fwd_bf16<%d>", 3: "xcd_fwd_bf16_fx<%d>", 4: "xcd_bwd_x3", 5: "xcd_bwd_f32", 6: "xcd_bwd_bf16_c32<%d>",
+                7: "xcd_bwd_bf16<%d>", 8: "fwd_step<%d>", 9: "fwd_step16_bf16", 10: "bwd_step", 11: "bwd_step16_bf16"}
+
+
+def library_plan(lib, no, ni, ndir, nlines, tmax, precision, strict, ncu, xcd_rec=True, frames=None):
+    """{fwd, fwd_launches, bwd, bwd_launches, moves} as wide_geometry names them, from the library's plans of the two passes"""
+    bf16, out, moves = precision == 2, {}, 0
+    sbf = bf16 and ni % 8 == 0 and no % 8 == 0 and kp16_bwd(no) == 4 * no                     # net.inc:Net::wants_sbf
+    for fwd in (1, 0):
+        shape = (ctypes.c_int * 20)(fwd, no, ni, ndir, nlines, tmax, nlines * tmax if frames is None else frames,
+                                    kp_fwd(no) if fwd else kp_bwd(no), kp16_fwd(no) if fwd else kp16_bwd(no), bf16,
+                                    not fwd and not bf16 and not strict,                       # x3: net.inc:Net::rec_x3, R2b packed with it
+                                    1 if fwd and bf16 else 0,                                  # fuse_wx = 1: a first layer in precision 2 has the operands
+                                    ncu, xcd_rec, 0, 1, fwd and sbf, ni + no + 8, (1 + ni + no + 15) // 16 * 16, (4 + ndir * no + 15) // 16 * 16)
+        plan = (ctypes.c_int * 14)()
+        lib.call("clstm_debug_wide_plan", ctypes.addressof(shape), ctypes.addressof(plan))
+        kernel, param, launches, step_kernel, step_param = plan[0], plan[1], plan[5], plan[7], plan[8]
+        name = PLAN_KERNELS[kernel or step_kernel]
+        side = "fwd" if fwd else "bwd"
+        out[side] = name % (param if kernel else step_param) if "%" in name else name
+        out[side + "_launches"] = launches
+        assert launches == ((plan[3] + plan[4] - 1) // plan[4] if kernel else tmax), list(plan)
+        if kernel:
+            moves |= plan[12]
+    out["moves"] = {c: 1 for c in range(31) if moves >> c & 1}
+    return out
+
+
+def assert_plan_agrees(lib, geo, *shape, **kw):
+    got = library_plan(lib, *shape, **kw)
+    assert got == {k: geo[k] for k in got}, (shape, kw, got, {k: geo[k] for k in got})
 
 
 def klass(no):
@@ -273,7 +310,7 @@ def oracle_from(want, params):
 
 @contextlib.contextmanager
 def xcd_rec_env(on):
-    """CLSTM_XCD_REC is read per pass (runtime.inc:launch_lstm_wide)"""
+    """CLSTM_XCD_REC is read per pass (net.inc:Net::wide_shape)"""
     old = os.environ.get("CLSTM_XCD_REC")
     os.environ["CLSTM_XCD_REC"] = "1" if on else "0"
     try:
@@ -339,6 +376,7 @@ def f32_case(backend, ora32, name, no, mode, uni=False, check_dx=False, **shape_
     m = MODES[mode]
     ni, nc, T, scale, lr = shape(backend, no, **shape_kw)
     geo = wide_geometry(no, ni, 1 if uni else 2, len(T), max(T), 0, m.get("strict", False), backend.kind, m.get("rec", True))
+    assert_plan_agrees(backend.lib, geo, no, ni, 1 if uni else 2, len(T), max(T), 0, m.get("strict", False), cus(backend.kind), m.get("rec", True), frames=sum(T))
     params, lines, trs = case_inputs(ora32, ni, no, nc, T, uni, scale)
     want = reference(ora32, ora32, ni, no, nc, T, uni, scale, lr, dx=check_dx)
     before, moved = counters(backend), None
@@ -378,6 +416,7 @@ def bf16_case(backend, ora32, name, no, mode, uni=False, **shape_kw):
     m = MODES[mode]
     ni, nc, T, scale, lr = shape(backend, no, **shape_kw)
     geo = wide_geometry(no, ni, 1 if uni else 2, len(T), max(T), 2, False, backend.kind, m.get("rec", True))
+    assert_plan_agrees(backend.lib, geo, no, ni, 1 if uni else 2, len(T), max(T), 2, False, cus(backend.kind), m.get("rec", True), frames=sum(T))
     params, lines, trs = case_inputs(ora32, ni, no, nc, T, uni, scale)
     want, dq = gauge(ora32, ni, no, nc, T, uni, scale, lr)
     assert all(v > 0 for v in dq.values()), dq
