@@ -752,6 +752,12 @@ int clstm_debug_wide_plan(const int* shape, int* plan) {   // host arithmetic on
   memcpy(plan, &p, sizeof(p));
   ABI_END
 }
+int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
+                         int* line_plan_h) {   // host arithmetic only: no net, no device (ctc.h: ctc_batch_plan / ctc_line_plan)
+  ABI_BEGIN
+  describe_ctc_plan(nc, line_off_h, states_h, state_off_h, bs, batch_plan_h, line_plan_h);
+  ABI_END
+}
 int clstm_debug_lane_ops(float* out) {
   ABI_BEGIN
   CLSTM_LAUNCH(k_debug_lane_ops, dim3(1), dim3(64), 0, g_stream, out);

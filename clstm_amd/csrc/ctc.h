@@ -47,11 +47,19 @@ constexpr int CTC_MAX_TILE = 256;  // frames per LDS tile (phases A and E)
 #define CLSTM_CTC_PD 8
 #endif
 constexpr int CTC_PD = CLSTM_CTC_PD;   // frames the one-wave lattice recursions request their match scores ahead
+constexpr int CTC_PREG = 34;    // posteriors per thread held in registers across the state classification
+constexpr int CTC_NB = 12;      // items a thread of the short-line path takes per round in the match-score and write-out loops
+constexpr int CTC_CLANE = 32;   // frames per wave of the lane = state form of phases C / D (lines of up to 64 states and 256 frames)
+constexpr int CTC_CCACHE = 26;  // lattice cells per thread kept in registers between the two passes of phase C (26 x 512 = 13312
+                                // cells: lines of up to 261 frames x 51 states -- a ragged OCR minibatch, T ~ U{150..250} -- stay on the short-line path;
+                                // at 24 the 10 % of such lines beyond 240 frames took the tiled path and the launch 107 us instead of 75)
 
 // what a workgroup needs to know about its line, in ONE 32-byte record indexed by the workgroup: the kernel used to walk
 // order[] -> line_off[] / state_off[] / lat_off[] -> states / posteriors, three dependent trips to memory before its first
 // useful load; with the record it is two
-struct CtcLine { long long lat_off; int b, off, T, soff, S, pad; };
+// nu: the distinct classes among the line's states, counted by the host (the short-line rule needs them before the workgroup has classified
+// its states; the classification arrives at the same number)
+struct CtcLine { long long lat_off; int b, off, T, soff, S, nu; };
 struct CtcArgs {
   const CtcLine* lines;  // [bs] per workgroup (largest lattice first)
   const float* P;        // [N][nc] softmax outputs
@@ -92,6 +100,74 @@ inline __host__ __device__ CtcLds ctc_lds_layout(int tile, int ncp, int smax) {
   l.dump = o;   o += 2;      // target of masked-off LDS stores (branch-free guards)
   l.words = o;
   return l;
+}
+// words of the region the short-line path re-uses phase by phase (row buffer + lattice tile + row sums)
+inline __host__ __device__ int ctc_region_words(const CtcLds& l, int tile) { return l.asum + tile - l.rowbuf; }
+
+// ---- WHICH path a line takes: the one statement of the rule.  ctc_batch_plan is the host's arithmetic, once per minibatch; ctc_line_plan
+// what a workgroup decides from it and from its own line; ctc_scores_in_lds the one decision that has to wait for the line's number of
+// distinct classes.  The kernel branches on these and nowhere re-derives them; clstm_debug_ctc_plan (include/clstm_abi.h) answers with
+// the same functions on the host, so a test can assert the path it means to cover (tests/test_ctc_path_sweep.py).
+struct CtcBatchPlan { int tile, smax, ncp, smem; };   // frames per LDS tile (< 1: the carve has no room for one), capped states, row stride, LDS bytes
+// smax_lines, tmax: the most states / frames of any line of the minibatch
+inline CtcBatchPlan ctc_batch_plan(int nc, int smax_lines, int tmax) {
+  CtcBatchPlan p;
+  p.smax = smax_lines < 1 ? 1 : (smax_lines > CTC_SMAX_LDS ? CTC_SMAX_LDS : smax_lines);   // (longer lines do not use the per-state LDS arrays)
+  if (tmax < 1) tmax = 1;
+  p.ncp = nc | 1;                                   // odd row stride: conflict-free row-per-lane access
+  // frames per LDS tile: what the 160 KiB carve leaves after the tables and the per-state vectors
+  const long fixed = (long)ctc_lds_layout(0, p.ncp, p.smax).words * (long)sizeof(float);
+  int tile = (int)((160 * 1024 - fixed) / (long)((p.ncp + (p.smax | 1) + 1) * sizeof(float)));
+  if (tile > CTC_MAX_TILE) tile = CTC_MAX_TILE;
+  if (tile > tmax) tile = tmax;
+  p.tile = tile;
+  p.smem = (int)((size_t)ctc_lds_layout(tile < 1 ? 1 : tile, p.ncp, p.smax).words * sizeof(float));
+  return p;
+}
+enum CtcForm { CTC_FORM_SHORT = 0, CTC_FORM_TILED = 1, CTC_FORM_HUGE = 2, CTC_FORM_NONE = 3 };   // (none: no frames or no states, the workgroup returns)
+// the recursion of phase B: one wave per direction with one state per lane / with two; groups of 256 lanes holding up to 2 / up to
+// CTC_RMAX states each; rounds over the label axis (ctc_lattice_huge)
+enum CtcRec { CTC_REC_WAVE = 0, CTC_REC_PAIR = 1, CTC_REC_RM2 = 2, CTC_REC_RM8 = 3, CTC_REC_ROUNDS = 4 };
+struct CtcLinePlan {
+  int form, rec;
+  int flat, lds_lat, lanemap;                        // short-line path (0 elsewhere); its fourth decision is ctc_scores_in_lds
+  int flat_stage, c_in_regs, d_per_state, ntiles;    // tiled and huge paths (0 on the short-line path)
+};
+// cap = ctc_region_words of the minibatch's carve; nu = CtcLine::nu
+inline __host__ __device__ CtcLinePlan ctc_line_plan(int T, int S, int nu, int nc, int ncp, int tile, int cap) {
+  CtcLinePlan p{CTC_FORM_NONE, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (T <= 0 || S <= 0) return p;
+  // (the short-line path classifies ONE target state per thread: transcripts of more than 255 labels take the tiled path)
+  // (the region the short-line path re-uses phase by phase must hold the line: always true for T <= tile)
+  // nub: the line's class columns.  A blank-interleaved target has at most (S + 1) / 2 distinct classes, and the rule reserves that many
+  // whatever the labels are; a plain class list (the Classes overload) can have up to S, and then its own count holds -- the rule used
+  // to reserve (S + 1) / 2 for those too, and the class columns of such a line ran over the region into the per-state arrays behind it
+  const int nub_mk = ((S + 1) / 2 < nc ? (S + 1) / 2 : nc) | 1;
+  const int nub = (nu | 1) > nub_mk ? (nu | 1) : nub_mk;
+  const bool short_line = T <= CTC_THREADS && (long)T * (ncp + nub) <= cap && (long)T * ((S | 1) + nub) <= cap &&
+                          S <= CTC_THREADS && T * S <= CTC_THREADS * CTC_CCACHE && nc <= CTC_THREADS;
+  // lines of more than CTC_SMAX_LDS states: the per-state arrays do not fit the LDS carve
+  p.form = short_line ? CTC_FORM_SHORT : (S > CTC_SMAX_LDS ? CTC_FORM_HUGE : CTC_FORM_TILED);
+  // RM: states a lane can hold (2 for S <= 512, else CTC_RMAX)
+  p.rec = S <= 64 ? CTC_REC_WAVE : S <= 128 ? CTC_REC_PAIR : S > CTC_SMAX_LDS ? CTC_REC_ROUNDS
+        : (S + CTC_GROUP - 1) / CTC_GROUP <= 2 ? CTC_REC_RM2 : CTC_REC_RM8;
+  if (short_line) {
+    p.flat = ncp == nc && T * nc <= CTC_PREG * CTC_THREADS;   // rows back to back in LDS too: flat copy through registers
+    p.lds_lat = S <= 64 && 2 * T * S <= cap;                  // both lattices of phase B in LDS
+    p.lanemap = S <= 64 && T <= (CTC_THREADS / 64) * CTC_CLANE;   // phases C / D with lane = state
+  } else {
+    p.flat_stage = ncp == nc;                                 // rows are back to back in LDS too: flat coalesced copy
+    p.c_in_regs = (long)T * S <= CTC_THREADS * CTC_CCACHE;    // phase C keeps the cells in registers between its passes
+    p.d_per_state = S > CTC_THREADS;                          // phase D: one thread per state, states in rounds
+    p.ntiles = (T + tile - 1) / tile;                         // phases A and E walk the line in tiles of `tile` frames
+  }
+  return p;
+}
+// short-line path: first word of the match scores per distinct class when they sit behind the LDS lattices of phase B
+inline __host__ __device__ int ctc_scores_behind(int T, int S, int ncp) { return 2 * T * S > T * ncp ? 2 * T * S : T * ncp; }
+// ... and whether they do: the recursion then reads them where they are (ctc_lattice: LDS_SRC).  nu: distinct classes of the line
+inline __host__ __device__ bool ctc_scores_in_lds(const CtcLinePlan& p, int T, int S, int ncp, int nu, int cap) {
+  return p.lds_lat && ctc_scores_behind(T, S, ncp) + T * (nu | 1) <= cap;
 }
 
 // Float-only form of log(exp(d) + 1) (experiment option ctc_float=1; NOT the default): exp as in ctc_limexp
@@ -142,14 +218,16 @@ DEVFN float ctc_limexp(float x) {
 // recursion, and the first frames arrive in an LDS latency.  (With the scores requested two frames ahead an LDS source had
 // measured 100 cycles per frame slower than HBM -- its reads share lgkmcnt with the table reads of log_add; CTC_PD frames
 // ahead a score has long arrived when the step that uses it waits for its table entry.)
-template <bool LDS_OUT, bool LDS_SRC = false, bool FLA = false>
+// REC_MAX: the widest recursion class the call site's lines can have -- what the caller's own plan rules out is not instantiated there
+// (LDS_OUT: lds_lat holds for one-wave lines only; the short-line path: at most CTC_THREADS = 2 CTC_GROUP states)
+template <bool LDS_OUT, bool LDS_SRC = false, bool FLA = false, int REC_MAX = (LDS_OUT ? CTC_REC_WAVE : CTC_REC_RM8)>
 DEVFN void ctc_lattice(const float* lm, float* al, float* be, float* vx, float* dump, const CrTables tb, const int T,
-                       const int S, const float* lml = nullptr, const int nup = 0, const int* ucol = nullptr) {
-  // (= forwardbackward(), ctc.cc:42-55); serial in t, parallel over the label axis
+                       const int S, const int rec, const float* lml = nullptr, const int nup = 0, const int* ucol = nullptr) {
+  // (= forwardbackward(), ctc.cc:42-55); serial in t, parallel over the label axis.  rec: ctc_line_plan's recursion class of the line
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const size_t latbytes = (size_t)T * S * 4;
   const BufF32 lmb = make_buf(lm, latbytes);
-  if (S <= 64) {
+  if (REC_MAX == CTC_REC_WAVE || rec == CTC_REC_WAVE) {
     // one wave per direction: the j-1 neighbour arrives by a DPP wave shift, no barrier per frame
     __syncthreads();  // lattice rows of phase A visible
     if (wave < 2) {
@@ -210,7 +288,7 @@ DEVFN void ctc_lattice(const float* lm, float* al, float* be, float* vx, float* 
       for (int q = 0; q < 2 * CTC_PD - 1; q++)
         if (i + q < T) step(lmq[q % CTC_PD], kaq[q % CTC_PD], i + q + CTC_PD < T);
     }
-  } else if (S <= 128) {
+  } else if (REC_MAX == CTC_REC_PAIR || rec == CTC_REC_PAIR) {
     // 65..128 states (transcripts of 33..63 labels: configs[4]'s 50 labels = 101 states): still ONE wave per direction and no
     // barrier per frame -- lane u holds states 2u and 2u + 1; state 2u + 1 takes its j-1 neighbour from the lane's own other
     // register, state 2u from lane u - 1's odd state by the DPP wave shift.  The two log_adds of a lane are independent, so a
@@ -266,6 +344,8 @@ DEVFN void ctc_lattice(const float* lm, float* al, float* be, float* vx, float* 
     // RM: states a lane can hold (2 for S <= 512, else CTC_RMAX): every frame issues RM prefetches and RM guarded updates
     auto run = [&](auto rm_tag) {
     constexpr int RM = decltype(rm_tag)::value;
+    // (RM 2: 129..512 states, RM 8: 513..2048 -- the plan's class says so; the compiler no longer sees the comparisons that picked RM)
+    if (R > RM || R < (RM == 2 ? 1 : 3)) __builtin_unreachable();
     const int grp = wave >> 2, u = tid & (CTC_GROUP - 1);
     float* vxg = vx + grp * 2 * (CTC_GROUP + 2);
     vxg[u] = (float)(-5.0 * (u * R + R - 1));
@@ -322,7 +402,7 @@ DEVFN void ctc_lattice(const float* lm, float* al, float* be, float* vx, float* 
     }
     if (i < T) step(i, lmA, kaA);
     };
-    if (R <= 2) run(std::integral_constant<int, 2>{}); else run(std::integral_constant<int, CTC_RMAX>{});
+    if (REC_MAX == CTC_REC_RM2 || rec == CTC_REC_RM2) run(std::integral_constant<int, 2>{}); else run(std::integral_constant<int, CTC_RMAX>{});
   }
 }
 
@@ -355,12 +435,6 @@ DEVFN void ctc_lattice_huge(const float* lm, float* al, float* be, const CrTable
 
 #define CTC_STAMP(k) do { if (a.prof && b == 0 && threadIdx.x == 0) a.prof[k] = dev_clock(); } while (0)
 constexpr int CTC_TREG = (CTC_TABLE_DOUBLES + CTC_THREADS - 1) / CTC_THREADS;
-constexpr int CTC_PREG = 34;    // posteriors per thread held in registers across the state classification
-constexpr int CTC_NB = 12;      // items a thread of the short-line path takes per round in the match-score and write-out loops
-constexpr int CTC_CLANE = 32;   // frames per wave of the lane = state form of phases C / D (lines of up to 64 states and 256 frames)
-constexpr int CTC_CCACHE = 26;  // lattice cells per thread kept in registers between the two passes of phase C (26 x 512 = 13312
-                                // cells: lines of up to 261 frames x 51 states -- a ragged OCR minibatch, T ~ U{150..250} -- stay on the short-line path;
-                                // at 24 the 10 % of such lines beyond 240 frames took the tiled path and the launch 107 us instead of 75)
 
 // ---- lines whose lattice fits in LDS: phases A..E on one CU, see the header ------------------------------
 // Guards are branch-free throughout: reads use a clamped index and a select, masked-off stores go to `dump`,
@@ -369,7 +443,7 @@ constexpr int CTC_CCACHE = 26;  // lattice cells per thread kept in registers be
 template <bool FLA>
 DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const CrTables tb, const int b, float* lm,
                           const int off, const int T, const int S, const double (&treg)[CTC_TREG],
-                          const float (&preg)[CTC_PREG], const bool flat) {
+                          const float (&preg)[CTC_PREG], const CtcLinePlan& pl) {
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int nc = a.nc, ncp = a.ncp;
   double* part = reinterpret_cast<double*>(lds + L.part);   // 512 doubles, reused phase by phase
@@ -380,7 +454,8 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   //   C..E: lattice tile [T][sp] | class columns [T][nup]
   float* rowbuf = lds + L.rowbuf;
   float* etile = rowbuf;
-  const int cap = L.asum + a.tile - L.rowbuf;
+  const int cap = ctc_region_words(L, a.tile);
+  const bool flat = pl.flat;
   int* stl = reinterpret_cast<int*>(lds + L.states);
   int* lists = reinterpret_cast<int*>(lds + L.lists);
   int* ucol = reinterpret_cast<int*>(lds + L.ucol);
@@ -442,10 +517,9 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   CTC_STAMP(12);
   // the match scores per distinct class, [T][nup]: behind the posteriors -- and, where the region has the room, behind the two
   // LDS lattices of phase B as well, which then reads them where they are (ctc_lattice: LDS_SRC)
-  const bool lds_lat = S <= 64 && 2 * TS <= cap;
-  const int lmu_hi = 2 * TS > T * ncp ? 2 * TS : T * ncp;
-  const bool lm_lds = lds_lat && lmu_hi + T * nup <= cap;   // uniform per workgroup
-  float* lmu = rowbuf + (lm_lds ? lmu_hi : T * ncp);
+  const bool lds_lat = pl.lds_lat;
+  const bool lm_lds = ctc_scores_in_lds(pl, T, S, ncp, nu, cap);   // uniform per workgroup
+  float* lmu = rowbuf + (lm_lds ? ctc_scores_behind(T, S, ncp) : T * ncp);
   // the posteriors the write-out at the very end subtracts (first round of its loop: (frame, present class) items tid,
   // tid + 512, ..): requested HERE, a whole kernel ahead -- inside a training step such a load is a microsecond on the tail
   float pw[CTC_NB];
@@ -570,13 +644,14 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   //         depend on the lattice: a class without a target state has aligned = 0, delta = -p.
   float* all = rowbuf;            // alpha / reversed alpha in LDS (row buffer + lattice tile are both free here)
   float* bel = rowbuf + TS;
-  if (lm_lds) ctc_lattice<true, true, FLA>(lm, all, bel, lds + L.vx, dump, tb, T, S, lmu, nup, ucol);
-  else if (lds_lat) ctc_lattice<true, false, FLA>(lm, all, bel, lds + L.vx, dump, tb, T, S);
-  else ctc_lattice<false, false, FLA>(lm, al, be, lds + L.vx, dump, tb, T, S);
+  if (lm_lds) ctc_lattice<true, true, FLA>(lm, all, bel, lds + L.vx, dump, tb, T, S, pl.rec, lmu, nup, ucol);
+  else if (lds_lat) ctc_lattice<true, false, FLA>(lm, all, bel, lds + L.vx, dump, tb, T, S, pl.rec);
+  else ctc_lattice<false, false, FLA, CTC_REC_RM2>(lm, al, be, lds + L.vx, dump, tb, T, S, pl.rec);
   const BufF32 dzb = make_buf(a.Dz + (size_t)off * nc, (size_t)T * nc * 4);
   const BufF32 agb = make_buf(a.aligned ? a.aligned + (size_t)off * nc : a.Dz, a.aligned ? (size_t)T * nc * 4 : 0);
-  if (S > 64 || (wave & 2)) {   // waves 2, 3, 6, 7: not on the SIMDs of the two lattice waves (w mod 4 = 0, 1)
-    const int w0 = S > 64 ? wave : (wave & 1) + ((wave >> 2) << 1), nw = S > 64 ? CTC_THREADS / 64 : 4;
+  const bool one_wave = pl.rec == CTC_REC_WAVE;
+  if (!one_wave || (wave & 2)) {   // waves 2, 3, 6, 7: not on the SIMDs of the two lattice waves (w mod 4 = 0, 1)
+    const int w0 = !one_wave ? wave : (wave & 1) + ((wave >> 2) << 1), nw = !one_wave ? CTC_THREADS / 64 : 4;
     for (int cb = 0; cb < nc; cb += 64) {   // one wave per frame, lanes over classes
       const int c = cb + lane;
       const bool absent = c < nc && ccol[c < nc ? c : 0] < 0;
@@ -605,7 +680,7 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   // the load to the normalised store, and the per-state sums over a wave's frames ARE the time chunks of the generic phase D
   // (thread q of a state took the frames q, q + 8, ..; Q = 8 for S <= 64), so every sum has the operands and the order it had.
   // The tile then holds the NORMALISED cells (float)((double)e * 1/total), which phase E otherwise forms on the fly.
-  const bool lanemap = S <= 64 && T <= (CTC_THREADS / 64) * CTC_CLANE;   // uniform per workgroup
+  const bool lanemap = pl.lanemap;   // uniform per workgroup
   if (lanemap) {
     const BufF32 alb = make_buf(al, latbytes), beb = make_buf(be, latbytes);
     const bool sok = lane < S;
@@ -922,7 +997,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   const int nc = a.nc, ncp = a.ncp, TT = a.tile;
   const int off = ln.off, T = ln.T;
   const int soff = ln.soff, S = ln.S;
-  if (T <= 0 || S <= 0) return;
+  const CtcLinePlan pl = ctc_line_plan(T, S, ln.nu, nc, ncp, TT, ctc_region_words(L, TT));   // uniform per workgroup
+  if (pl.form == CTC_FORM_NONE) return;
   const float* P = a.P + (size_t)off * nc;
   float* Dz = a.Dz + (size_t)off * nc;
   float* lm = a.lat + ln.lat_off;
@@ -931,11 +1007,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   CTC_STAMP(0);
   // Request order = completion order (vmcnt counts in order): the target states first (needed at once), then the
   // tables and -- short lines -- the posteriors, whose latency overlaps the state classification.
-  // (the short-line path classifies ONE target state per thread: transcripts of more than 255 labels take the tiled path)
-  // (the region the short-line path re-uses phase by phase must hold the line: always true for T <= tile)
-  const int sl_cap = L.asum + TT - L.rowbuf, sl_nub = ((S + 1) / 2 < nc ? (S + 1) / 2 : nc) | 1;   // nub: bound of its class columns
-  const bool short_line = T <= CTC_THREADS && (long)T * (ncp + sl_nub) <= sl_cap && (long)T * ((S | 1) + sl_nub) <= sl_cap &&
-                          S <= CTC_THREADS && T * S <= CTC_THREADS * CTC_CCACHE && nc <= CTC_THREADS;   // uniform per workgroup
+  const bool short_line = pl.form == CTC_FORM_SHORT;
   const int st0 = a.states[soff + (tid < S ? tid : 0)];
   double treg[CTC_TREG];
 #pragma unroll
@@ -945,21 +1017,20 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   }
   if (short_line) {
     const BufF32 pb = make_buf(P, (size_t)T * nc * 4);
-    const bool flat = ncp == nc && T * nc <= CTC_PREG * CTC_THREADS;   // rows back to back in LDS too: flat copy
     float preg[CTC_PREG];
-    if (flat) {
+    if (pl.flat) {
 #pragma unroll
       for (int k = 0; k < CTC_PREG; k++) preg[k] = buf_load(pb, (unsigned)(tid + k * CTC_THREADS) * 4u);   // past the end: 0
     }
     if (tid < S) stl[tid] = st0;
     for (int s = tid + CTC_THREADS; s < S; s += CTC_THREADS) stl[s] = a.states[soff + s];
     __syncthreads();
-    ctc_short_line<FLA>(a, lds, L, tb, b, lm, off, T, S, treg, preg, flat);
+    ctc_short_line<FLA>(a, lds, L, tb, b, lm, off, T, S, treg, preg, pl);
     return;
   }
   // lines of more than CTC_SMAX_LDS states: the per-state arrays do not fit the LDS carve -- target states are read from
   // memory, the per-state totals live behind the line's lattice, the projection reads the lattice directly
-  const bool huge = S > CTC_SMAX_LDS;
+  const bool huge = pl.form == CTC_FORM_HUGE;
   const int* stg = a.states + soff;
   double* totg = reinterpret_cast<double*>(lm + (((size_t)3 * T * S + 1) & ~(size_t)1));   // (8-byte aligned: lat_off is even)
   if (!huge) {
@@ -999,7 +1070,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   for (int t0 = 0; t0 < T; t0 += TT) {
     const int nt = (T - t0) < TT ? (T - t0) : TT;
     __syncthreads();
-    if (ncp == nc) {  // rows are back to back in LDS too: flat coalesced copy, CTC_MLP loads in flight
+    if (pl.flat_stage) {  // rows are back to back in LDS too: flat coalesced copy, CTC_MLP loads in flight
       const float* src = P + (size_t)t0 * nc;
       const int n = nt * nc;
       for (int i0 = tid; i0 < n; i0 += CTC_MLP * CTC_THREADS) {
@@ -1053,14 +1124,14 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
 
   // ---- B: forward recursion and the same recursion on the (t,s)-reversed lattice
   if (huge) ctc_lattice_huge<FLA>(lm, al, be, tb, T, S);
-  else ctc_lattice<false, false, FLA>(lm, al, be, vx, nullptr, tb, T, S);
+  else ctc_lattice<false, false, FLA>(lm, al, be, vx, nullptr, tb, T, S, pl.rec);
   __syncthreads();
   CTC_STAMP(2);
 
   // ---- C: epath = limexp(both - amax2(both)) ---------------------------------------------
   const int TS = T * S;
   constexpr int CCACHE = CTC_CCACHE;
-  if (TS <= CTC_THREADS * CCACHE) {
+  if (pl.c_in_regs) {
     float bo[CCACHE];
     float mx = -3.0e38f;
 #pragma unroll
@@ -1121,7 +1192,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   // ---- D: per-state totals over time (double accumulator, floor 1e-9); x/total is evaluated as
   //         (float)((double)x * (1/total)): equal to the reference's (Float)(x/total) except for
   //         ~1e-8 of the values (1 ulp of double before the rounding to float) -----------------------
-  if (S > CTC_THREADS) {   // long transcripts (more states than threads): one thread per state, states in rounds
+  if (pl.d_per_state) {   // long transcripts (more states than threads): one thread per state, states in rounds
     double* td = huge ? totg : tot;
     for (int s = tid; s < S; s += CTC_THREADS) {
       double acc = 0.0;

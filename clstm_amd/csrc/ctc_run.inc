@@ -11,6 +11,7 @@ struct CtcWorkspace {
   DevBuf<double> tables;
   DevBuf<char> meta;
   DevBuf<float> lat;
+  std::vector<int> nu, seen;    // host scratch of ctc_distinct_classes, kept across calls
 };
 // the ctc_tables.h block (ctc.h: CTC_TABLE_DOUBLES) in a workspace's own device buffer, uploaded when the workspace first needs it
 static void upload_ctc_tables(DevBuf<double>& tables) {
@@ -44,6 +45,48 @@ static void expand_transcripts(const int* labels_h, const int* L_h, int n, std::
     soff[b + 1] = soff[b] + 2 * L + 1;
   }
 }
+// the batch arithmetic of a minibatch (ctc.h: ctc_batch_plan) from its offsets, with the refusals run_ctc has always made
+static CtcBatchPlan ctc_minibatch_plan(int nc, const int* line_off_h, const int* state_off_h, int bs) {
+  int smax = 1, tmax = 1;
+  for (int b = 0; b < bs; b++) {
+    smax = std::max(smax, state_off_h[b + 1] - state_off_h[b]);
+    tmax = std::max(tmax, line_off_h[b + 1] - line_off_h[b]);
+  }
+  const CtcBatchPlan bp = ctc_batch_plan(nc, smax, tmax);
+  REQUIRE(bp.tile >= 1, "too many classes / target states for the CTC row tile");
+  REQUIRE(bp.smem <= 160 * 1024, "CTC LDS carve exceeds 160 KiB");
+  return bp;
+}
+// distinct classes of every line (CtcLine::nu) into nu[0 .. bs); the states are known to lie in [0, nc).  seen: scratch of the caller's
+static void ctc_distinct_classes(int nc, const int* states_h, const int* state_off_h, int bs, std::vector<int>& nu, std::vector<int>& seen) {
+  nu.assign(bs, 0);
+  seen.assign(nc, -1);
+  for (int b = 0; b < bs; b++)
+    for (int i = state_off_h[b]; i < state_off_h[b + 1]; i++)
+      if (seen[states_h[i]] != b) { seen[states_h[i]] = b; nu[b]++; }
+}
+// clstm_debug_ctc_plan: what run_ctc and the workgroups of its launch decide for this minibatch, without a device
+constexpr int CTC_PLAN_INTS = 13;   // include/clstm_abi.h documents the record
+static void describe_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
+                              int* line_plan_h) {
+  REQUIRE(bs > 0 && nc >= 1 && line_off_h && states_h && state_off_h && batch_plan_h && line_plan_h, "empty batch / null argument");
+  for (int b = 0; b < bs; b++)
+    REQUIRE(line_off_h[b + 1] >= line_off_h[b] && state_off_h[b + 1] >= state_off_h[b], "bad offsets");
+  for (int i = 0; i < state_off_h[bs]; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+  const CtcBatchPlan bp = ctc_minibatch_plan(nc, line_off_h, state_off_h, bs);
+  batch_plan_h[0] = bp.tile; batch_plan_h[1] = bp.smax; batch_plan_h[2] = bp.ncp; batch_plan_h[3] = bp.smem;
+  const int cap = ctc_region_words(ctc_lds_layout(bp.tile, bp.ncp, bp.smax), bp.tile);
+  std::vector<int> nus, seen;
+  ctc_distinct_classes(nc, states_h, state_off_h, bs, nus, seen);
+  for (int b = 0; b < bs; b++) {
+    const int T = line_off_h[b + 1] - line_off_h[b], S = state_off_h[b + 1] - state_off_h[b];
+    const int nu = nus[b];
+    const CtcLinePlan p = ctc_line_plan(T, S, nu, nc, bp.ncp, bp.tile, cap);
+    const int rec[CTC_PLAN_INTS] = {T, S, nu, p.form, p.rec, p.flat, p.lds_lat, (int)ctc_scores_in_lds(p, T, S, bp.ncp, nu, cap), p.lanemap,
+                                    p.flat_stage, p.c_in_regs, p.d_per_state, p.ntiles};
+    memcpy(line_plan_h + (size_t)b * CTC_PLAN_INTS, rec, sizeof(rec));
+  }
+}
 // The per-minibatch metadata block [line records | states] is staged in a pinned slot;
 // `defer` (non-null): do not enqueue its copy -- the caller folds it into a kernel it launches anyway before the CTC
 // kernel (the input-ingest launch of a training step) and receives source, destination and size here.
@@ -63,6 +106,8 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   const int ns = state_off_h[bs];
   for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
   w.lat.reserve((size_t)(lo[bs] > 0 ? lo[bs] : 1));
+  ctc_distinct_classes(nc, states_h, state_off_h, bs, w.nu, w.seen);
+  const std::vector<int>& nus = w.nu;
   // one pinned slot, one device block, one copy: [line records (bs x 32 bytes, in workgroup order) | states]
   const size_t nln = (size_t)bs * sizeof(CtcLine), nst = (size_t)(ns > 0 ? ns : 1) * sizeof(int);
   w.meta.reserve(nln + nst);
@@ -75,7 +120,7 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
     CtcLine* ln = (CtcLine*)stage;
     for (int i = 0; i < bs; i++) {
       const int b = order[i];
-      ln[i] = CtcLine{lo[b], b, line_off_h[b], line_off_h[b + 1] - line_off_h[b], state_off_h[b], state_off_h[b + 1] - state_off_h[b], 0};
+      ln[i] = CtcLine{lo[b], b, line_off_h[b], line_off_h[b + 1] - line_off_h[b], state_off_h[b], state_off_h[b + 1] - state_off_h[b], nus[b]};
     }
     if (ns > 0) memcpy(stage + nln, states_h, (size_t)ns * sizeof(int));
     if (defer) {
@@ -94,23 +139,9 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   a.float_logadd = dbg_opt("ctc_float") != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
   upload_ctc_tables(w.tables);
   a.tables = w.tables.p;
-  int smax = 1, tmax = 1;
-  for (int b = 0; b < bs; b++) {
-    smax = std::max(smax, state_off_h[b + 1] - state_off_h[b]);
-    tmax = std::max(tmax, line_off_h[b + 1] - line_off_h[b]);
-  }
-  if (smax > CTC_SMAX_LDS) smax = CTC_SMAX_LDS;     // (longer lines do not use the per-state LDS arrays)
-  a.smax = smax;
-  a.ncp = nc | 1;                                   // odd row stride: conflict-free row-per-lane access
-  // frames per LDS tile: what the 160 KiB carve leaves after the tables and the per-state vectors
-  const long fixed = (long)ctc_lds_layout(0, a.ncp, smax).words * (long)sizeof(float);
-  int tile = (int)((160 * 1024 - fixed) / (long)((a.ncp + (smax | 1) + 1) * sizeof(float)));
-  if (tile > CTC_MAX_TILE) tile = CTC_MAX_TILE;
-  if (tile > tmax) tile = tmax;
-  REQUIRE(tile >= 1, "too many classes / target states for the CTC row tile");
-  a.tile = tile;
-  const size_t smem = (size_t)ctc_lds_layout(a.tile, a.ncp, a.smax).words * sizeof(float);
-  REQUIRE(smem <= 160 * 1024, "CTC LDS carve exceeds 160 KiB");
+  const CtcBatchPlan bp = ctc_minibatch_plan(nc, line_off_h, state_off_h, bs);   // (ctc.h: the one statement of the batch arithmetic)
+  a.smax = bp.smax; a.ncp = bp.ncp; a.tile = bp.tile;
+  const size_t smem = (size_t)bp.smem;
 #ifndef CLSTM_HIP_EMU
   static size_t smem_set = 0;
   if (smem > smem_set) {

@@ -464,6 +464,25 @@ int clstm_debug_set_device_error(int which, int value);
  *   11 wide_bwd_step16_bf16, 0 none (behind kernel 3 the caller runs the hoisted product and asks again with fx_mode 0); step_grid[3];
  *   moves (bit c: a successful persistent pass moves clstm_debug_path_count(c)); fx_ngx (the folded projection was asked for). */
 int clstm_debug_wide_plan(const int* shape, int* plan);
+/* Which path of the alignment kernel every line of a minibatch takes (csrc/ctc.h: ctc_batch_plan, ctc_line_plan, ctc_scores_in_lds -- the
+ * functions clstm_ctc_align_batch and the kernel's workgroups themselves decide with): host arithmetic, no net, no device.  Arguments as
+ * clstm_ctc_align_batch's.  A line's path depends on the other lines of its minibatch through tile and smax.
+ * batch_plan_h (4 ints, HOST out): tile (frames per LDS tile), smax (the most states of a line, capped at 2048), ncp (LDS row stride of the
+ *   class tile: nc | 1), LDS bytes of the launch.
+ * line_plan_h (13 ints per line, in line order, HOST out):
+ *   0 T, 1 S, 2 nu (distinct classes among the line's states);
+ *   3 form: 0 short line (every phase in one LDS region), 1 tiled (lattices in memory, phases A and E tile by tile), 2 huge (more than
+ *     2048 states: per-state arrays in memory), 3 none (no frames or no states: nothing is written);
+ *   4 recursion: 0 one wave per direction, one state per lane (S <= 64), 1 two states per lane (S <= 128), 2 / 3 groups of 256 lanes
+ *     holding up to 2 / up to 8 states each, 4 rounds over the label axis;
+ *   short lines (0 otherwise): 5 flat (posteriors held in registers across the classification, copied flat into LDS), 6 lds_lat (both
+ *     lattices of the recursion in LDS), 7 lm_lds (the recursion reads its match scores from LDS), 8 lanemap (phases C / D with lane =
+ *     state);
+ *   tiled and huge lines (0 otherwise): 9 flat_stage (posterior tiles copied flat), 10 c_in_regs (phase C keeps the cells in registers
+ *     between its passes), 11 d_per_state (phase D one thread per state), 12 ntiles (tiles phases A and E walk).
+ * Tests use it to make sure the path they mean to cover is the one that runs (tests/test_ctc_path_sweep.py). */
+int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
+                         int* line_plan_h);
 
 #ifdef __cplusplus
 }

@@ -303,6 +303,23 @@ def ctc_via_abi(backend, probs_list, states_list, want_aligned=True):
     return backend.down(A_), backend.down(D_), loff
 
 
+CTC_PLAN_FIELDS = ("T", "S", "nu", "form", "rec", "flat", "lds_lat", "lm_lds", "lanemap", "flat_stage", "c_in_regs", "d_per_state", "ntiles")
+CTC_SHORT, CTC_TILED, CTC_HUGE = 0, 1, 2                  # form;  rec: 0 one wave, 1 two states per lane, 2 / 3 groups of 256 lanes, 4 rounds
+CTC_WAVE, CTC_PAIR, CTC_RM2, CTC_RM8, CTC_ROUNDS = range(5)
+
+
+def ctc_plan(backend, probs_list, states_list):
+    """(batch plan, one record per line) of the minibatch ctc_via_abi would launch: the library's own rule (clstm_debug_ctc_plan,
+    include/clstm_abi.h) -- which path a line takes is asserted from it, never claimed in a comment"""
+    nc = probs_list[0].shape[1]
+    loff = np.concatenate([[0], np.cumsum([len(p) for p in probs_list])]).astype(np.int32)
+    soff = np.concatenate([[0], np.cumsum([len(s) for s in states_list])]).astype(np.int32)
+    states = np.concatenate(states_list).astype(np.int32)
+    bp = np.zeros(4, np.int32); lp = np.zeros((len(probs_list), len(CTC_PLAN_FIELDS)), np.int32)
+    backend.lib.call("clstm_debug_ctc_plan", nc, ptr(loff), ptr(states), ptr(soff), len(probs_list), ptr(bp), ptr(lp))
+    return dict(zip(("tile", "smax", "ncp", "smem"), bp.tolist())), [dict(zip(CTC_PLAN_FIELDS, row)) for row in lp.tolist()]
+
+
 def test_ctc_reference_known_answers(backend):
     """test-ctc.cc:47-74 and :76-109 through the device kernel (tolerance 1e-4 as asserted there)."""
     o1 = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 1]], np.float32).T
@@ -318,14 +335,21 @@ def test_ctc_reference_known_answers(backend):
     assert np.allclose(d2, a2 - o2, atol=1e-7)
 
 
-@pytest.mark.parametrize("T,L,nc", [(12, 3, 6), (40, 12, 30), (7, 3, 5), (3, 1, 83), (60, 40, 30), (100, 62, 70), (200, 70, 90), (256, 25, 83),
+# the path of each case's first line: (form, recursion, both lattices in LDS)
+CTC_VS_ORACLE_PATHS = {(12, 3, 6): (CTC_SHORT, CTC_WAVE, 1), (40, 12, 30): (CTC_SHORT, CTC_WAVE, 1), (7, 3, 5): (CTC_SHORT, CTC_WAVE, 0),
+                       (3, 1, 83): (CTC_SHORT, CTC_WAVE, 1), (60, 40, 30): (CTC_SHORT, CTC_PAIR, 0), (100, 62, 70): (CTC_SHORT, CTC_PAIR, 0),
+                       (110, 62, 70): (CTC_TILED, CTC_PAIR, 0), (200, 70, 90): (CTC_TILED, CTC_RM2, 0), (256, 25, 83): (CTC_SHORT, CTC_WAVE, 1),
+                       (400, 50, 100): (CTC_TILED, CTC_PAIR, 0), (90, 32, 40): (CTC_SHORT, CTC_PAIR, 0), (150, 63, 70): (CTC_TILED, CTC_PAIR, 0)}
+
+
+@pytest.mark.parametrize("T,L,nc", [(12, 3, 6), (40, 12, 30), (7, 3, 5), (3, 1, 83), (60, 40, 30), (100, 62, 70), (110, 62, 70), (200, 70, 90), (256, 25, 83),
                                     # 65..128 states: one wave per direction, two states per lane (round 4) -- the configs[4] transcript length
                                     # (101 / 99 / 97 states) on the tiled path, 65 states (the smallest), 127 / 125 / 123 (the largest)
                                     (400, 50, 100), (90, 32, 40), (150, 63, 70)])
 def test_ctc_vs_oracle(backend, ora32, T, L, nc):
-    # (12..40: short-line path, lattice resident in LDS; 60 x 81 states: the same with the wide recursion;
-    #  100 x 125 states and 200 x 141: the tiled path through HBM; 256 x 51 = 13056 cells: the largest OCR-shaped lattice of
-    #  the short-line path, 26 cells per thread)
+    # (12..40: short-line path, lattices resident in LDS; 60 x 81 and 100 x 125 states: the short-line path with two states per lane --
+    #  100 x 125 = 12500 cells used to be claimed for the tiled path here, which begins beyond 13312: 110 x 125 states takes it, as do
+    #  200 x 141; 256 x 51 = 13056 cells: the largest OCR-shaped lattice of the short-line path.  CTC_VS_ORACLE_PATHS, asserted below)
     rng = np.random.default_rng(T)
     probs, states = [], []
     for b in range(3):
@@ -335,6 +359,8 @@ def test_ctc_vs_oracle(backend, ora32, T, L, nc):
         p[0, 1] = 0.0                                     # exercises the 1e-5 floor (ctc.cc:68)
         tr = rng.integers(1, nc, max(1, L - b))
         probs.append(p.astype(np.float32)); states.append(ora32.mktargets(tr))
+    first = ctc_plan(backend, probs, states)[1][0]
+    assert (first["form"], first["rec"], first["lds_lat"]) == CTC_VS_ORACLE_PATHS[(T, L, nc)], first
     al, dz, loff = ctc_via_abi(backend, probs, states)
     for b in range(3):
         want = ora32.ctc_align_classes(probs[b], states[b])
@@ -379,9 +405,12 @@ def test_ctc_float_logadd_option(backend, ora32, T, L, nc):
 def test_ctc_recursion_ring_boundaries(backend, ora32, L, nc):
     """The one-wave lattice recursions request their match scores CTC_PD = 8 frames ahead through a register ring: line lengths
     around the ring size and its multiples (the loop's rounds, its unrolled tail of up to 15 steps, lines shorter than the ring).
-    (L, nc) pick the source of the scores: 3 / 51 / 63 states with the scores in LDS (ctc_lattice<true, true>), 51 states over
-    60 classes with LDS lattices but the scores from HBM (the carve has no room behind the lattices), 81 / 127 states on two
-    states per lane with everything in HBM."""
+    (L, nc) pick the source of the scores: 3 / 51 / 63 states with the scores in LDS (ctc_lattice<true, true>; 63 states: up to 24
+    frames -- at 25 frames the scores no longer fit behind the LDS lattices, at 33 the lattices themselves no longer fit),
+    51 states over 60 classes with LDS lattices but the scores from HBM (the carve has no room behind the lattices -- true of a line
+    that sizes the carve itself: in one minibatch with a 33-frame line every shorter line's scores fit, so these lines are launched
+    one by one as well as together), 81 / 127 states on two states per lane with everything in HBM.  Each claim is asserted from
+    the plan."""
     rng = np.random.default_rng(100 * L + nc)
     probs, states = [], []
     for T in (1, 2, 3, 7, 8, 9, 15, 16, 17, 23, 24, 25, 33):
@@ -390,16 +419,31 @@ def test_ctc_recursion_ring_boundaries(backend, ora32, L, nc):
         tr = rng.integers(1, nc, L)
         tr[::3] = tr[0]                                   # repeated labels: the read-modify-write columns of phase E
         probs.append(p.astype(np.float32)); states.append(ora32.mktargets(tr))
-    al, dz, loff = ctc_via_abi(backend, probs, states)
-    for b in range(len(probs)):
-        want = ora32.ctc_align_classes(probs[b], states[b])
-        assert_close(al[loff[b]:loff[b + 1]], want, rtol=1e-4, atol=1e-6, what="aligned, T = %d" % len(probs[b]))
-        assert_close(dz[loff[b]:loff[b + 1]], want - probs[b], rtol=1e-4, atol=2e-6, what="delta, T = %d" % len(probs[b]))
+    launches = [list(range(len(probs)))] + ([[b] for b in range(len(probs))] if (L, nc) == (25, 60) else [])
+    for lines in launches:
+        ps, sts = [probs[b] for b in lines], [states[b] for b in lines]
+        for rec in ctc_plan(backend, ps, sts)[1]:
+            assert rec["form"] == CTC_SHORT
+            if (L, nc) in ((1, 5), (25, 83)):
+                assert rec["rec"] == CTC_WAVE and rec["lm_lds"], rec
+            elif (L, nc) == (31, 40):
+                assert rec["rec"] == CTC_WAVE and (rec["lds_lat"], rec["lm_lds"]) == (rec["T"] < 33, rec["T"] <= 24), rec
+            elif (L, nc) == (25, 60) and len(lines) > 1:       # together: only the 33-frame line, which sizes the carve, reads from HBM
+                assert rec["rec"] == CTC_WAVE and rec["lds_lat"] and rec["lm_lds"] == (rec["T"] < 33), rec
+            elif (L, nc) == (25, 60):
+                assert rec["rec"] == CTC_WAVE and rec["lds_lat"] and not rec["lm_lds"], rec
+            else:
+                assert rec["rec"] == CTC_PAIR and not rec["lds_lat"], rec
+        al, dz, loff = ctc_via_abi(backend, ps, sts)
+        for i, b in enumerate(lines):
+            want = ora32.ctc_align_classes(probs[b], states[b])
+            assert_close(al[loff[i]:loff[i + 1]], want, rtol=1e-4, atol=1e-6, what="aligned, T = %d" % len(probs[b]))
+            assert_close(dz[loff[i]:loff[i + 1]], want - probs[b], rtol=1e-4, atol=2e-6, what="delta, T = %d" % len(probs[b]))
 
 
 def test_ctc_ragged_ocr_minibatch(backend, ora32):
     """One launch over lines as a ragged OCR minibatch has them (83 classes): 256 frames -- the longest line whose phases C / D run
-    with lane = state --, 257 and 261 frames (generic phases C / D, match scores still in LDS), lines around the bench length with
+    with lane = state --, 257 and 261 frames (generic phases C / D, both lattices still in LDS), lines around the bench length with
     25 / 31 / 10 labels, short lines, a one-label line; every line against the oracle."""
     rng = np.random.default_rng(83)
     nc = 83
@@ -411,6 +455,8 @@ def test_ctc_ragged_ocr_minibatch(backend, ora32):
         p = rng.random((T, nc)).astype(np.float32) ** 4
         p /= p.sum(1, keepdims=True)
         probs.append(p.astype(np.float32)); states.append(ora32.mktargets(rng.integers(1, nc, L)))
+    for rec in ctc_plan(backend, probs, states)[1]:
+        assert rec["form"] == CTC_SHORT and rec["lds_lat"] and rec["lanemap"] == (rec["T"] <= 256), rec
     al, dz, loff = ctc_via_abi(backend, probs, states)
     for b in range(len(probs)):
         want = ora32.ctc_align_classes(probs[b], states[b])
@@ -440,6 +486,10 @@ def test_ctc_target_shapes(backend, ora32, case):
         st = ora32.mktargets([7, 24999])
     p = rng.random((T, nc)).astype(np.float32) ** 3
     p /= p.sum(1, keepdims=True)
+    batch, (rec,) = ctc_plan(backend, [p.astype(np.float32)], [st])
+    assert rec["form"] == (CTC_TILED if nc > 512 else CTC_SHORT), rec
+    if case == "huge_classes":
+        assert batch["tile"] == 1 and rec["ntiles"] == T
     al, dz, _ = ctc_via_abi(backend, [p.astype(np.float32)], [st])
     want = ora32.ctc_align_classes(p.astype(np.float32), st)
     assert_close(al, want, rtol=1e-4, atol=1e-6, what="aligned " + case)
@@ -473,6 +523,8 @@ def test_ctc_many_states_on_a_short_lattice(backend, ora32, T, L):
     p /= p.sum(1, keepdims=True)
     st = ora32.mktargets(rng.integers(1, nc, L))
     assert T * st.size <= 12288 and st.size > 512
+    rec = ctc_plan(backend, [p.astype(np.float32)], [st])[1][0]
+    assert rec["form"] == CTC_TILED and rec["d_per_state"] and rec["c_in_regs"], rec
     al, dz, _ = ctc_via_abi(backend, [p.astype(np.float32)], [st])
     want = ora32.ctc_align_classes(p.astype(np.float32), st)
     assert_close(al, want, rtol=1e-4, atol=1e-6, what="aligned, %d states on %d frames" % (st.size, T))
@@ -494,6 +546,8 @@ def test_ctc_unbounded_label_axis(backend, ora32, T, L):
         p /= p.sum(1, keepdims=True)
         ps.append(p.astype(np.float32)); sts.append(ora32.mktargets(rng.integers(1, nc, l)))
     assert sts[0].size > 2048
+    recs = ctc_plan(backend, ps, sts)[1]
+    assert (recs[0]["form"], recs[0]["rec"]) == (CTC_HUGE, CTC_ROUNDS) and recs[1]["form"] == CTC_SHORT, recs
     al, dz, _ = ctc_via_abi(backend, ps, sts)
     want = np.concatenate([ora32.ctc_align_classes(p, st) for p, st in zip(ps, sts)], 0)
     assert_close(al, want, rtol=1e-4, atol=1e-6, what="aligned, %d states" % sts[0].size)
