@@ -62,6 +62,7 @@ _SIGS = {
     "clstm_sgd_update": [_P, _P, _I, _F, _F],
     "clstm_ctc_align_batch": [_P, _P, _P, _I, _P, _P, _P, _I],
     "clstm_ctc_score_batch": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
+    "clstm_ctc_beam_batch": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
     "clstm_mktargets": [_P, _P, _I],
     "clstm_trivial_decode_batch": [_P, _I, _P, _I, _P, _P, _P],
     "clstm_net_nparams_for": [_P],
@@ -87,6 +88,7 @@ _SIGS = {
     "clstm_net_set_output_deltas_h": [_P, _P],
     "clstm_net_ctc": [_P, _P, _P, _P],
     "clstm_net_score": [_P, _P, _P, _P, _I, _P, _P, _P],
+    "clstm_net_beam": [_P, _I, _I, _P, _P, _P, _P],
     "clstm_net_backward": [_P],
     "clstm_net_enable_input_deltas": [_P, _I],
     "clstm_net_get_input_deltas_h": [_P, _P],

@@ -10,6 +10,7 @@ struct clstm_net {
   CtcWorkspace ctc;
   DecodeWorkspace dec;
   ScoreWorkspace score;
+  BeamWorkspace beam;
 };
 
 #define EW(kernel, len, ...) \
@@ -17,6 +18,11 @@ struct clstm_net {
 
 #define REQUIRE_CURRENT(h) REQUIRE(!(h)->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)")
 #define REFUSE_NOSAVE(h, what) REQUIRE(!(h)->net.nosave, what ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)")
+// what clstm_net_score and clstm_net_beam ask of the net: a current minibatch whose outputs stand (they read Z and nothing else)
+#define REQUIRE_OUTPUTS(h) \
+  REQUIRE(h, "null argument"); \
+  REQUIRE_CURRENT(h); \
+  REQUIRE((h)->net.N > 0, "set_batch first")
 struct clstm_normalizer {
   std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
   Normalizer nz;
@@ -148,6 +154,13 @@ int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int
   run_ctc_score(*g_score_ws, probs, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, score_h, vscore_h, path_h, g_stream);
   ABI_END
 }
+int clstm_ctc_beam_batch(const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest, int* nhyp_h, int* len_h,
+                         float* score_h, int* labels_h) {
+  ABI_BEGIN
+  if (!g_beam_ws) g_beam_ws = new BeamWorkspace();
+  run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
+  ABI_END
+}
 int clstm_trivial_decode_batch(const float* probs, int nc, const int* line_off_h, int bs, int* classes_h,
                                int* locs_h, int* counts_h) {
   ABI_BEGIN
@@ -237,10 +250,8 @@ int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* alig
 int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int* cand_line_h, int ncand, float* score_h,
                     float* vscore_h, int* path_h) {
   ABI_BEGIN
-  REQUIRE(h, "null argument");
-  REQUIRE_CURRENT(h);
+  REQUIRE_OUTPUTS(h);
   Net& n = h->net;
-  REQUIRE(n.N > 0, "set_batch first");
   REQUIRE(score_h || vscore_h || path_h, "clstm_net_score: score_h, vscore_h and path_h are all NULL");
   REQUIRE(labels_h && L_h && ncand > 0, "null argument / no candidates");
   std::vector<int> soff, states;
@@ -250,6 +261,19 @@ int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int
   struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
   run_ctc_score(h->score, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, states.data(), soff.data(), cand_line_h, ncand,
                 score_h, vscore_h, path_h, g_stream);
+  ABI_END
+}
+// n-best transcripts of the current minibatch's lines: the guards and guarantees of clstm_net_score (reads Z only, BeamWorkspace)
+int clstm_net_beam(clstm_net* h, int beam, int nbest, int* nhyp_h, int* len_h, float* score_h, int* labels_h) {
+  ABI_BEGIN
+  REQUIRE_OUTPUTS(h);
+  Net& n = h->net;
+  REQUIRE(nhyp_h && score_h, "clstm_net_beam: nhyp_h and score_h are required");
+  REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam: 1 <= nbest <= beam <= 32");
+  RoctxRange range_("clstm:beam");
+  n.timing.begin("ctc_beam", g_stream);
+  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
   ABI_END
 }
 int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.backward(); ABI_END }

@@ -17,6 +17,7 @@
 #include "dbgopt.h"
 #include "ctc.h"
 #include "ctc_score.h"
+#include "ctc_beam.h"
 #include "devintrin.h"
 #include "gemm_mfma.h"
 #include "gemm_bf16.h"

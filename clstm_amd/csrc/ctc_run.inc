@@ -271,7 +271,7 @@ static void plan_ctc_score(ScorePlan& pl, int nc, const int* line_off_h, int bs,
 #ifndef CLSTM_HIP_EMU
 // the dynamic-LDS ceiling of a kernel is a property of the function ON A DEVICE: remembered per device, per calling thread
 static void score_allow_smem(const void* kernel, int which, size_t smem) {
-  static thread_local std::map<int, size_t> allowed[2];
+  static thread_local std::map<int, size_t> allowed[4];   // score sum, score max-plus, beam (all in LDS), beam
   int dev = 0;
   HIPCHECK(hipGetDevice(&dev));
   size_t& have = allowed[which][dev];
@@ -343,7 +343,112 @@ static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const i
   }
 }
 
+// ---- n-best transcripts by prefix beam search (ctc_beam.h) -------------------------------------------------------------
+// A workspace of its own, as the score's: a beam call touches neither a prepared alignment nor a score in flight.
+struct BeamWorkspace {
+  PinnedRing ring;
+  DevBuf<char> meta;
+  DevBuf<int> ws;
+  DevBuf<int> out;            // [nhyp bs | len bs nbest | score bs nbest (float bits) | labels nbest N]: ONE copy brings the results back
+  PinnedBuf<int> host;
+};
+// what the launch will be, from the arguments alone; every section of a line goes to LDS while the line's sections still fit
+struct BeamPlan {
+  std::vector<BeamLine> lines;
+  long long ws_words = 0;
+  int K = 1, lds_words = 0;
+  bool all_lds = true;        // every section of every line in LDS: ctc_beam_kernel<true>
+};
+static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, int beam, int nbest) {
+  REQUIRE(bs > 0 && line_off_h, "empty batch / null argument");
+  REQUIRE(nc >= 2 && nc < (1 << 26), "clstm_ctc_beam: the class count must lie in [2, 2^26)");
+  REQUIRE(beam >= 1 && beam <= BEAM_MAX, "clstm_ctc_beam: beam must lie in [1, 32]");
+  REQUIRE(nbest >= 1 && nbest <= beam, "clstm_ctc_beam: nbest must lie in [1, beam]");
+  REQUIRE(line_off_h[0] >= 0, "bad offsets");
+  pl.K = beam_classes(nc, beam);
+  const BeamLds L = beam_lds_layout(beam, pl.K);
+  const long long room = BEAM_LDS_WORDS - L.sections;
+  for (int b = 0; b < bs; b++) {
+    const long long T = (long long)line_off_h[b + 1] - line_off_h[b];
+    REQUIRE(T >= 0, "bad offsets");
+    REQUIRE(T * nc < (1ll << 29) && T * beam < (1ll << 28), "clstm_ctc_beam: a line's posteriors or its prefix trie exceed 2 GB");
+    if (T == 0) continue;
+    const long long nn = 1 + T * beam;
+    long long H = 64;
+    while (H < 2 * nn) H *= 2;
+    const long long need[BS_COUNT] = {H, 3 * nn, 2 * T * pl.K, T * nc};
+    BeamLine ln{};
+    ln.row = line_off_h[b]; ln.T = (int)T; ln.line = b; ln.hmask = (int)(H - 1); ln.nnmax = (int)nn;
+    long long used = 0;
+    for (int s = 0; s < BS_COUNT; s++) {
+      if (used + need[s] <= room) { ln.in_lds |= 1 << s; ln.off[s] = used; used += need[s]; }
+      else { ln.off[s] = pl.ws_words; pl.ws_words += need[s]; }
+    }
+    pl.lds_words = std::max(pl.lds_words, (int)used);
+    pl.all_lds = pl.all_lds && ln.in_lds == (1 << BS_COUNT) - 1;
+    pl.lines.push_back(ln);
+  }
+  REQUIRE(pl.ws_words < (1ll << 40), "clstm_ctc_beam: workspace too large");
+  std::stable_sort(pl.lines.begin(), pl.lines.end(), [](const BeamLine& x, const BeamLine& y) { return x.T > y.T; });   // longest first
+  pl.lds_words += L.sections;
+}
+static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest,
+                         int* nhyp_h, int* len_h, float* score_h, int* labels_h, hipStream_t s) {
+  BeamPlan pl;
+  plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest);
+  REQUIRE(probs && nhyp_h && score_h, "clstm_ctc_beam: probs, nhyp_h and score_h are required");
+  const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest;
+  const size_t nout = (size_t)bs + 2 * nslot + (labels_h ? (size_t)nbest * N : 0);
+  for (int b = 0; b < bs; b++) nhyp_h[b] = 0;
+  for (size_t i = 0; i < nslot; i++) { score_h[i] = -INFINITY; if (len_h) len_h[i] = 0; }
+  if (pl.lines.empty()) return;
+  const size_t nln = pl.lines.size() * sizeof(BeamLine);
+  w.meta.reserve(nln);
+  w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
+  w.out.reserve(nout);
+  w.host.reserve(nout);
+  char* stage = (char*)w.ring.acquire(nln);
+  memcpy(stage, pl.lines.data(), nln);
+  HIPCHECK(hipMemcpyAsync(w.meta.p, stage, nln, hipMemcpyHostToDevice, s));
+  w.ring.commit(s);
+  HIPCHECK(hipMemsetAsync(w.out.p, 0, nout * sizeof(int), s));   // lines without frames, label slots beyond a hypothesis
+  BeamArgs a{};
+  a.lines = (const BeamLine*)w.meta.p;
+  a.P = probs; a.ws = w.ws.p;
+  a.nhyp = w.out.p; a.len = w.out.p + bs; a.score = reinterpret_cast<float*>(w.out.p + bs + nslot);
+  a.labels = labels_h ? w.out.p + bs + 2 * nslot : nullptr;
+  a.nc = nc; a.beam = beam; a.nbest = nbest; a.K = pl.K; a.bs = bs; a.N = (int)N;
+  const size_t smem = (size_t)pl.lds_words * sizeof(float);
+  const dim3 grid((unsigned)pl.lines.size());
+  if (pl.all_lds) {
+#ifndef CLSTM_HIP_EMU
+    score_allow_smem((const void*)ctc_beam_kernel<true>, 2, smem);
+#endif
+    CLSTM_LAUNCH(ctc_beam_kernel<true>, grid, dim3(BEAM_THREADS), smem, s, a);
+  } else {
+#ifndef CLSTM_HIP_EMU
+    score_allow_smem((const void*)ctc_beam_kernel<false>, 3, smem);
+#endif
+    CLSTM_LAUNCH(ctc_beam_kernel<false>, grid, dim3(BEAM_THREADS), smem, s, a);
+  }
+  check_launch();
+  g_path_count[PC_BEAM]++;
+  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  for (const BeamLine& ln : pl.lines) {   // (lines without frames keep nhyp = 0, len = 0, score = -inf)
+    const int b = ln.line;
+    nhyp_h[b] = w.host.p[b];
+    for (int k = 0; k < nbest; k++) {
+      const size_t i = (size_t)b * nbest + k;
+      if (len_h) len_h[i] = w.host.p[bs + i];
+      memcpy(&score_h[i], &w.host.p[bs + nslot + i], sizeof(float));
+    }
+  }
+  if (labels_h) memcpy(labels_h, w.host.p + bs + 2 * nslot, (size_t)nbest * N * sizeof(int));
+}
+
 static thread_local CtcWorkspace* g_ctc_ws = nullptr;
 static thread_local DecodeWorkspace* g_dec_ws = nullptr;
 static thread_local ScoreWorkspace* g_score_ws = nullptr;
+static thread_local BeamWorkspace* g_beam_ws = nullptr;
 

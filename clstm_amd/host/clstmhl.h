@@ -83,6 +83,8 @@ inline void trivial_decode_host(Classes& cs, const float* out, int T, int nc) {
 }
 
 struct CharPrediction { int i, x; char32_t c; float p; };
+// one of a line's n best transcripts (CLSTMOCR::predict_nbest)
+struct Hypothesis { ustring text; float score; };
 // forced alignment: the frame columns x0 .. x1 a transcript's i-th character occupies on a best path (-1, -1: the path never visits it)
 struct CharSpan { int i, x0, x1; char32_t c; };
 
@@ -442,6 +444,35 @@ struct CLSTMOCR {
     vector<ustring> texts;
     predict_frames(lines, texts);
     score_current(batch_T, transcripts, nullptr, &spans);
+  }
+  // ---- n-best transcripts (clstm_net_beam: CTC prefix beam search on the device, include/clstm_abi.h).  nbest_current works on the
+  // net's CURRENT minibatch as score_current does; per line up to nbest hypotheses, best first.  A score is the log-probability the
+  // beam gathered for the text -- not on the scale of score().
+  void nbest_current(const vector<int>& Ts, int beam, int nbest, vector<vector<Hypothesis>>& out) {
+    const int bs = (int)Ts.size();
+    out.assign(bs, vector<Hypothesis>());
+    if (bs == 0) return;
+    size_t N = 0;
+    for (int t : Ts) N += t;
+    vector<int> nhyp(bs), len((size_t)bs * nbest), labels(std::max<size_t>(N * nbest, 1));
+    vector<float> sc((size_t)bs * nbest);
+    chk(clstm_net_beam(net, beam, nbest, nhyp.data(), len.data(), sc.data(), labels.data()), "clstm_net_beam");
+    size_t off = 0;
+    for (int b = 0; b < bs; b++) {
+      for (int k = 0; k < nhyp[b]; k++) {
+        const int* l = labels.data() + (size_t)nbest * off + (size_t)k * Ts[b];
+        out[b].push_back(Hypothesis{codec.decode(Classes(l, l + len[(size_t)b * nbest + k])), sc[(size_t)b * nbest + k]});
+      }
+      off += Ts[b];
+    }
+  }
+  // predict_frames (normalised lines) or, with gpu_prep, predict_batch_gpu (raw lines), then the n best of every line
+  void predict_nbest(const vector<const Image*>& lines, int beam, int nbest, vector<ustring>& out, vector<vector<Hypothesis>>& hyps,
+                     vector<vector<CharPrediction>>* preds = nullptr, bool gpu_prep = false) {
+    hyps.clear();
+    if (gpu_prep) predict_batch_gpu(lines, out, preds);
+    else predict_frames(lines, out, preds);
+    if (!lines.empty()) nbest_current(batch_T, beam, nbest, hyps);
   }
   void get_outputs_batch(vector<Image>& outs) {   // [T_b][nclasses] of every line of the last predict_frames() minibatch
     int N = 0;

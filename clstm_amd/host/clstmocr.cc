@@ -15,6 +15,7 @@ static int main1(int argc, char** argv) {
   if (argc != 2 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) {
     std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " IMAGEFILE-LIST\n  Variables: load (required) conf output save_text\n"
               << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)\n"
+              << "             beam nbest (beam=W: the nbest <= W best transcripts of every line follow its output; default off)   (not in the reference)\n"
               << "             gpu_prep (1: lines are normalised on the device, helper threads only read PNGs; default 0)   (not in the reference)\n";
     return EXIT_FAILURE;
   }
@@ -39,6 +40,22 @@ static int main1(int argc, char** argv) {
   // the first and last frame column it occupies on the best path (-1 -1: never visited) --, then "end <score>" with the ground
   // truth's CTC score on the line (CLSTMOCR::score)
   const bool do_align = getienv("align", 0) != 0;
+  // beam=W nbest=K (default beam=0: nothing changes): every line's ordinary output is followed by "nbest <file>", one line
+  // "<k>\t<score>\t<text>" per hypothesis of the device's CTC prefix beam search (CLSTMOCR::predict_nbest; width W, the K best,
+  // K defaults to W; the score is the log-probability the beam gathered for the text), then "end".  With align=1 a line that has no
+  // ground truth beside it gets the alignment of its top hypothesis.
+  const int beam = getienv("beam", 0);
+  const int nbest = beam > 0 ? getienv("nbest", beam) : 0;
+  if (beam != 0 && (beam < 1 || beam > 32 || nbest < 1 || nbest > beam)) fail("beam / nbest: 1 <= nbest <= beam <= 32");
+  auto print_nbest = [&](const string& name, const vector<Hypothesis>& hyps) {
+    std::cout << "nbest " << name << std::endl;
+    for (size_t k = 0; k < hyps.size(); k++) {
+      char buf[64];
+      snprintf(buf, sizeof buf, "%.9g", (double)hyps[k].score);
+      std::cout << k << "\t" << buf << "\t" << utf32_to_utf8(hyps[k].text) << std::endl;
+    }
+    std::cout << "end" << std::endl;
+  };
   auto print_alignment = [&](const string& name, const vector<CharSpan>& spans, float score) {
     std::cout << "align " << name << std::endl;
     for (const CharSpan& c : spans) std::cout << utf32_to_utf8(ustring(1, c.c)) << "\t" << c.x0 << "\t" << c.x1 << std::endl;
@@ -94,7 +111,9 @@ static int main1(int argc, char** argv) {
       for (auto& f : cur.frames) ptrs.push_back(&f);
       vector<ustring> outs;
       vector<vector<CharPrediction>> preds;
-      if (gpu_prep) clstm.predict_batch_gpu(ptrs, outs, conf ? &preds : nullptr);
+      vector<vector<Hypothesis>> hyps;
+      if (beam > 0) clstm.predict_nbest(ptrs, beam, nbest, outs, hyps, conf ? &preds : nullptr, gpu_prep);
+      else if (gpu_prep) clstm.predict_batch_gpu(ptrs, outs, conf ? &preds : nullptr);
       else clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
       vector<Image> posteriors;
       if (output != "text") clstm.get_outputs_batch(posteriors);
@@ -106,7 +125,10 @@ static int main1(int argc, char** argv) {
         noalign.assign(cur.names.size(), "");
         for (size_t k = 0; k < cur.names.size(); k++) {
           ustring gt;
-          if (!ground_truth(cur.names[k], gt, &noalign[k])) continue;
+          if (!ground_truth(cur.names[k], gt, &noalign[k])) {
+            if (beam == 0 || !noalign[k].empty() || hyps[k].empty()) continue;
+            gt = hyps[k][0].text;   // no ground truth: the top hypothesis
+          }
           gt_line.push_back((int)k);
           gts.push_back(gt);
         }
@@ -132,6 +154,7 @@ static int main1(int argc, char** argv) {
             for (float& v : posteriors[k].d) v = scaled_log(v);
           write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), posteriors[k]);
         }
+        if (beam > 0) print_nbest(name, hyps[k]);
         if (next_gt < gt_line.size() && gt_line[next_gt] == (int)k) { print_alignment(name, spans[next_gt], gt_score[next_gt]); next_gt++; }
         else if (do_align && !noalign[k].empty()) std::cout << noalign[k] << std::endl;
       }
@@ -167,9 +190,16 @@ static int main1(int argc, char** argv) {
         for (float& v : outputs.d) v = scaled_log(v);
       write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), outputs);
     } else fail("unknown output format");
+    vector<vector<Hypothesis>> hyps;
+    if (beam > 0) {
+      clstm.nbest_current(vector<int>(1, clstm.T), beam, nbest, hyps);
+      print_nbest(line, hyps[0]);
+    }
     ustring gt;
     string note;
-    if (do_align && !ground_truth(line, gt, &note)) {
+    bool have_gt = do_align && ground_truth(line, gt, &note);
+    if (do_align && !have_gt && note.empty() && beam > 0 && !hyps[0].empty()) { gt = hyps[0][0].text; have_gt = true; }
+    if (do_align && !have_gt) {
       if (!note.empty()) std::cout << note << std::endl;
     } else if (do_align) {
       vector<vector<CharSpan>> spans;

@@ -190,6 +190,19 @@ class Network:
         state 2k + 1, blanks the even states; -1 on frames before a late start).  See spans()."""
         return self._score(transcripts, lines, False, False, True)[2]
 
+    def beam(self, beam=8, nbest=None):
+        """The n best transcripts of every line of the current minibatch by CTC prefix beam search (clstm_net_beam; the algorithm
+        in clstm_amd/csrc/ctc_beam.h).  Per line a list of (labels array, score), best first; score is the log-probability the
+        beam gathered for that labelling -- not on the scale of score().  nbest defaults to beam."""
+        nbest = beam if nbest is None else nbest
+        bs = len(self.T)
+        nhyp = np.zeros(bs, np.int32)
+        ln = np.zeros(max(1, bs * nbest), np.int32)
+        sc = np.zeros(max(1, bs * nbest), np.float32)
+        lab = np.zeros(max(1, nbest * self.N), np.int32)
+        self.lib.call("clstm_net_beam", self.h, int(beam), int(nbest), ptr(nhyp), ptr(ln), ptr(sc), ptr(lab))
+        return unpack_beam(self.T, nbest, nhyp, ln, sc, lab)
+
     def backward(self):
         self.lib.call("clstm_net_backward", self.h)
 
@@ -482,6 +495,19 @@ def make_net(kind, ninput, noutput, nhidden, nhidden2=None, lib=None, **bufs):
 
 def sgd_update(net):
     net.update()
+
+
+def unpack_beam(T, nbest, nhyp, ln, sc, lab):
+    """the arrays of clstm_ctc_beam_batch / clstm_net_beam (include/clstm_abi.h) as a list per line of (labels, score)"""
+    out, off = [], 0
+    for b, t in enumerate(T):
+        hyps = []
+        for k in range(int(nhyp[b])):
+            s = nbest * off + k * t
+            hyps.append((lab[s:s + ln[b * nbest + k]].copy(), float(sc[b * nbest + k])))
+        out.append(hyps)
+        off += t
+    return out
 
 
 def spans(path, L):

@@ -118,6 +118,18 @@ int clstm_ctc_align_batch(const float* probs, float* deltas, float* aligned, int
 int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int bs, const int* states_h,
                           const int* state_off_h, const int* cand_line_h, int ncand,
                           float* score_h, float* vscore_h, int* path_h);
+/* The n best labellings of every line by CTC prefix beam search in the log domain on the plain posteriors (class 0 = blank,
+ * lp = log(max(p, 1e-30f)), f32) -- clstm_amd/csrc/ctc_beam.h states the algorithm.  1 <= nbest <= beam <= 32, nc >= 2, any T.
+ * A score is the log-probability the beam gathered for the labelling (a sum over a subset of its paths, so <= its CTC
+ * log-likelihood): a true log-probability, NOT comparable with clstm_ctc_score_batch's unnormalised score.
+ *   nhyp_h  [bs]         min(nbest, entries alive after the last frame); 0 for a line without frames
+ *   score_h [bs*nbest]   hypothesis (b, k) in slot b*nbest + k, best first; unused slots -INFINITY
+ *   len_h   [bs*nbest]   labels per hypothesis (<= T_b), unused slots 0; may be NULL
+ *   labels_h[nbest*N]    the labels of (b, k): len ints from nbest*line_off[b] + k*T_b, each in [1, nc); may be NULL
+ * Ties between candidates are broken by a fixed total order: a line's result does not depend on bs or on the other lines.  A
+ * non-finite posterior can make that line's scores non-finite; lengths and labels stay in range, other lines are unaffected. */
+int clstm_ctc_beam_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
+                         int* nhyp_h, int* len_h, float* score_h, int* labels_h);
 /* mktargets  ctc.cc:148-157: 2L+1 state classes, blank (0) on even positions.  HOST arrays. */
 int clstm_mktargets(int* states_h, const int* transcript_h, int L);
 /* trivial_decode  ctc.cc:159-190 (+ argmax tensor.h:357-366), batched.  probs DEVICE [N][nc];
@@ -208,6 +220,11 @@ int clstm_net_ctc(clstm_net* net, const int* labels_h, const int* L_h, float* al
  * next minibatch are untouched.  Kernel time under "ctc_score" (clstm_net_kernel_time_ms). */
 int clstm_net_score(clstm_net* net, const int* labels_h, const int* L_h, const int* cand_line_h, int ncand,
                     float* score_h, float* vscore_h, int* path_h);
+/* clstm_ctc_beam_batch on the outputs of the net's current minibatch.  Exactly the preconditions and guarantees of clstm_net_score:
+ * needs a current minibatch; works after clstm_net_forward, after a training step and after clstm_net_predict; rank-local;
+ * parameters, derivs, grads, deltas, the step count, the device error words and a declared next minibatch are untouched.  Kernel
+ * time under "ctc_beam". */
+int clstm_net_beam(clstm_net* net, int beam, int nbest, int* nhyp_h, int* len_h, float* score_h, int* labels_h);
 /* net->backward(): accumulates this minibatch's gradient sum into grads (zeroed first). */
 int clstm_net_backward(clstm_net* net);
 /* input deltas of the first layer are only computed if enabled (nothing on the OCR path reads
@@ -439,6 +456,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *     computed only the 32 frames it visits first, helper workgroups of the launch the rest (26 does not move for them);
  *  28  score launches (clstm_ctc_score_batch / clstm_net_score): one per form a call launched -- the sum form for score_h, the
  *     max-plus form for vscore_h / path_h;
+ *  29  beam-search launches (clstm_ctc_beam_batch / clstm_net_beam): one per call that had a line with frames;
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
