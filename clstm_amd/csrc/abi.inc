@@ -776,6 +776,17 @@ int clstm_debug_wide_plan(const int* shape, int* plan) {   // host arithmetic on
   memcpy(plan, &p, sizeof(p));
   ABI_END
 }
+int clstm_debug_narrow_plan(const int* shape, int* plan) {   // host arithmetic only: no net, no device (runtime.inc:narrow_plan)
+  ABI_BEGIN
+  REQUIRE(shape && plan, "null argument");
+  static_assert(sizeof(NarrowShape) == 30 * sizeof(int) && sizeof(NarrowPlan) == 11 * sizeof(int), "include/clstm_abi.h documents the int layout");
+  NarrowShape h;
+  memcpy(&h, shape, sizeof(h));
+  REQUIRE(h.pass >= NP_FWD_SAVE && h.pass <= NP_BWD && h.no > 0 && h.ndir >= 1 && h.bs > 0 && h.ncu >= 0, "bad shape");
+  const NarrowPlan p = narrow_plan(h);
+  memcpy(plan, &p, sizeof(p));
+  ABI_END
+}
 int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
                          int* line_plan_h) {   // host arithmetic only: no net, no device (ctc.h: ctc_batch_plan / ctc_line_plan)
   ABI_BEGIN

@@ -26,7 +26,7 @@ inline constexpr DbgOptDef DBG_OPTS[] = {
     {"gemm_x3", 1},          // 0: ... / for the softmax layer's backward pair (what clstm_net_set_strict_f32 selects per net)
     {"split_terms", 3},      // 2: two-term split of the backward products
     {"xd_prologue", 2},      // the softmax layer's x.d: 2 the recurrence workgroups of the top layer's fused backward launch compute
-                             //   only the 32 frames they visit first, helper items of the launch the rest (where Net::xd_mode
+                             //   only the 32 frames they visit first, helper items of the launch the rest (where narrow_plan
                              //   admits it, else as 1); 1 every recurrence workgroup computes its whole slice in front of its
                              //   first step; 0 a launch of its own in front of the backward launch
     {"fwd_mfma", 1},         // the batched-MFMA narrow forward recurrence: 0 never, 1 from 640 lines, 2 always

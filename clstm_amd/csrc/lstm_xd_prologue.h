@@ -29,7 +29,7 @@ constexpr int XD_MAX_K = 32 * XD_KB;
 constexpr int XD_ROWS = 32;              // frames per round (two 16-row MFMA tiles)
 constexpr int XD_UNITS = XD_ROWS * XD_KB * 4;   // staging units of a round: 8 consecutive k of one row
 constexpr int XD_RING = 3;               // rounds of z.d in flight in registers
-// staging units per thread: the smallest workgroup of an NK4 instantiation (pick_nk4: 1 -> one wave, 2 -> two, 4 -> three,
+// staging units per thread: the smallest workgroup of an NK4 instantiation (narrow_class: 1 -> one wave, 2 -> two, 4 -> three,
 // 7 -> five, 8 -> eight) still covers a round; the host checks nthreads * xd_maxu >= XD_UNITS
 constexpr int xd_maxu(int nk4) { return nk4 <= 1 ? 6 : nk4 == 2 ? 3 : nk4 <= 7 ? 2 : 1; }
 constexpr int xd_smem_floats(int nt) { return 2 * nt * XD_KB * XD_ROWS * 32 / 2; }   // 24 KB (NT = 2) / 36 KB (NT = 3)

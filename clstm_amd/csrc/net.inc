@@ -1,10 +1,11 @@
 // net.inc -- part of clstm_hip.hip (namespace clstm): Layer and Net = the step scheduler of the fused path -- arenas per layer,
 // batch geometry, forward / CTC hand-off / backward / update with every launch decision (which recurrence kernel, fused or separate
 // launches, which GEMM form), the chunk tables of the in-launch weight-gradient items, reductions, the gradient exchange.
-// The forward recurrence family of a layer is chosen in ONE place, Net::forward_family: forward() and predict() are the same
-// layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by the same answer.
-// Likewise the backward pass: Net::backward_family names a layer's family; backward() is backward_softmax, then per layer the
-// recurrence, the layer's BwdPlan (decided ONCE, behind the recurrence launch), the weight gradient, the input deltas.
+// Which kernels a layer's pass runs is decided in ONE place per layer kind, both in runtime.inc: narrow_plan for the register-resident
+// layers (Net::narrow_shape reads the device, the options and the build into its shape), wide_plan for the lock-step ones (Net::wide_shape).
+// forward() and predict() are the same layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by
+// the same plan.  backward() asks for every layer's backward plan once, then is backward_softmax and per layer the recurrence, the
+// layer's BwdPlan (decided ONCE, behind the recurrence launch), the weight gradient, the input deltas.
 // And the step: Net::step_plan decides a StepPlan ONCE per training step; backward(plan) returns what the pass left (PassLeft) and
 // update(left) consumes it -- nothing of a step's plan is a member of Net.  The step sequence itself is step.inc.
 // Not a stand-alone header: included once by clstm_hip.hip behind runtime.inc.
@@ -63,11 +64,9 @@ struct Layer {
   float* srow() const { return H.p + hofs - 1; }        // [1 | h] = the next layer's / softmax's source row
 };
 
-// the forward recurrence of one layer of the current minibatch (Net::forward_family): the whole forward half as one launch
-// (lstm_fwd_fused.h), batched over 16 lines on the MFMA (lstm_mfma.h), one workgroup per line (lstm_seq.h), lock-step (lstm_wide.h)
-enum class FwdFamily { Fused, Mfma, PerLine, Wide };
-// ... and its backward recurrence (Net::backward_family): with the chunked weight-gradient items of gemm_dw.h in or behind its launch
-// (backward_layer_overlapped), lock-step (lstm_wide.h), or the narrow layer's alone with the weight gradient as a product behind it
+// the backward recurrence of one layer of the current minibatch (Net::backward): with the chunked weight-gradient items of gemm_dw.h in
+// or behind its launch (backward_layer_overlapped; NarrowPlan::overlapped), lock-step (lstm_wide.h), or the narrow layer's alone with the
+// weight gradient as a product behind it
 enum class BwdFamily { Overlapped, Wide, Narrow };
 // what the weight-gradient and input-delta steps of a layer need to know: Net::backward_plan, once the recurrence has been launched
 struct BwdPlan {
@@ -152,7 +151,6 @@ struct Net {
   XcdSync coop_sync;          // sync words of the persistent lock-step kernels + the stamp base of their next launch
   Timing timing;
   // --- weight-gradient GEMM beside the backward recurrence (gemm_dw.h) ---
-  static const int PROG_LINES = 2048;                          // overlap only for minibatches up to this many lines
   static const int PROG_WORDS = 2 * PROG_LINES * PROG_STRIDE;   // progress words at the tail of a narrow layer's D allocation: [ndir][bs], one per 128 B
   // CLSTM_OVERLAP / clstm_net_set_overlap: 0 off (GEMM after the recurrence); 1 (default): recurrence and GEMM as two
   // roles of ONE launch (lstm_bwd_dw.h) for batches large enough -- 0.369 -> 0.356 ms per step at the bench shape;
@@ -161,14 +159,13 @@ struct Net {
   int overlap = getenv("CLSTM_OVERLAP") ? atoi(getenv("CLSTM_OVERLAP")) : 1;
   unsigned dw_done_total = 0;     // recurrence workgroups launched so far through the fused launch (GemmDwArgs::done)
   DevBuf<long long> dw_trace;
-  DevBuf<int> xd_ready;           // producer form of the top layer's x.d (xd_mode 2): rounds-complete words of the dH items
+  DevBuf<int> xd_ready;           // producer form of the top layer's x.d (NarrowPlan::xd = 2): rounds-complete words of the dH items
   DevBuf<int> dw_ktab, dw_slabs, dw_queue;   // dw_queue: the monitor's published minima and the `done` counter, each on its own 128-byte line
   std::vector<int> dw_key;        // line offsets the tables were built for
-  // the softmax layer's W.d as independent items of the top layer's fused backward launch (gemm_dw.h, GemmDwArgs::x*)
+  // the softmax layer's W.d as independent items of the top layer's fused backward launch (gemm_dw.h, GemmDwArgs::x*; NarrowPlan::dwx)
   DevBuf<int> dwx_tab;            // [entries][2] contiguous 16-frame entries | slabs
   long long dwx_N = -1;
   int dwx_nslabs = 0, dwx_entries = 0;
-  bool dwx_active = false;        // this backward pass: the top layer's launch carries them
   int dw_nslabs = 0, dw_slabs_per_dir = 0, dw_ntiles_max = 0;
   int prog_base = 1024;           // grows with every backward launch: stale progress words never look complete
   long long dw_launches = 0;      // overlapped backward passes so far (tests check the path was taken)
@@ -312,18 +309,20 @@ struct Net {
       y.ni = ni;
       y.no = ds.nhidden[l];
       REQUIRE(y.no > 0, "nhidden must be positive");
-      y.nk4 = pick_nk4(y.no);
+      const NarrowClass k = narrow_class(y.no);
       const bool force_wide = getenv("CLSTM_FORCE_WIDE") && atoi(getenv("CLSTM_FORCE_WIDE")) != 0;
-      y.wide = y.nk4 < 0 || force_wide;
-      if (y.wide) y.nk4 = 1;
-      y.nthreads = y.wide ? 64 : 64 * ((y.no + 15) / 16);
+      y.wide = !k.nk4 || force_wide;
+      y.nk4 = y.wide ? 1 : k.nk4;
+      y.nthreads = y.wide ? 64 : 64 * k.waves;
+      // (what the x.d prologue asks of a class, not of a minibatch: its smallest workgroup covers a staging round -- lstm_xd_prologue.h)
+      REQUIRE(y.wide || y.nthreads * xd_maxu(y.nk4) >= XD_UNITS, "internal: a workgroup of this class does not cover a staging round of the x.d prologue");
       y.kp16f = wide_kp16_fwd(y.no); y.kp16b = wide_kp16_bwd(y.no);
       y.rowsf = (y.no + 3) / 4 * 16; y.rowsb = (y.no + 15) / 16 * 16;
       y.bwd_exact = y.kp16b == 4 * y.no;
       y.lds = ((1 + y.ni + y.no + 15) / 16) * 16;   // source rows [1 | x | h_prev], padded to 64-byte rows
       y.ldh = ((y.hofs + ndir * y.no + 15) / 16) * 16;   // 64-byte aligned rows
       const long long blk = (long long)y.no * (1 + y.ni + y.no);
-      y.pd.ni = y.ni; y.pd.no = y.no; y.pd.ndir = ndir; y.pd.nk4 = y.nk4; y.pd.nthreads = y.wide ? 0 : y.nthreads; y.pd.ku = pick_ku(y.no, y.nk4);
+      y.pd.ni = y.ni; y.pd.no = y.no; y.pd.ndir = ndir; y.pd.nk4 = y.nk4; y.pd.nthreads = y.wide ? 0 : y.nthreads; y.pd.ku = y.wide ? 4 : k.ku;
       for (int dir = 0; dir < ndir; dir++) {
         for (int s = 0; s < 4; s++) y.pd.p_off[dir][s] = off + blockidx[s] * blk;
         off += 4 * blk;
@@ -478,16 +477,16 @@ struct Net {
   // predict: only what a forward-only pass writes -- the input block, H, Z and, for the families that stage pre-activations in
   // it (every one but the batched-MFMA recurrence of an upper layer; layer 0's routed twins stage theirs there when the device
   // finds |x| > 255), G.  No C, S, D, dH, Dz.  A net that has no no-save kernels (predict_nosave_ok) reserves everything.
-  // (By forward_family, as forward_pass launches: the fused launch's rule looks at H, which grows here, but it stages like the per-line kernels.)
+  // (By the layer's forward plan, as forward_pass launches: the fused launch's rule looks at H, which grows here, but it stages like the per-line kernels.)
   void reserve_batch(bool predict) {
     if (predict && !predict_nosave_ok()) predict = false;
     geom_predict = predict;
     hipStream_t s = stream();
     X.reserve((size_t)N * desc.ninput);
     for (auto& y : L) {
-      const FwdFamily fam = forward_family(y);
-      const bool mf_full = predict && forward_saves(y, fam, false);   // (the training-form kernel under predict: it writes G, C, S)
-      const bool mf_upper = predict && &y != &L[0] && fam == FwdFamily::Mfma && !mf_full;
+      const NarrowPlan np = forward_plan((int)(&y - L.data()), false);
+      const bool mf_full = predict && np.saves;   // (the training-form kernel under predict: it writes G, C, S)
+      const bool mf_upper = predict && &y != &L[0] && np.fwd == NF_MFMA && !mf_full;
       if (!mf_upper) y.G.reserve((size_t)N * ndir * 4 * y.no);
       if (!predict || mf_full) y.C.reserve((size_t)N * ndir * y.no);
       {
@@ -638,40 +637,34 @@ struct Net {
     y.sx_valid = true;
   }
 
-  // ---- narrow layers, chip-filling minibatches: the recurrence batched over 16 lines per workgroup on the MFMA (lstm_mfma.h) ----
-  // fwd_mfma: 0 never, 1 (default) from 640 lines per GPU on (measured crossover, profiles/r06_mfma_v3_vs_perline.txt: below
-  // that the launch has fewer 16-line workgroups than the chip has CUs and the per-line kernel wins), 2 always (tests).
-  // clstm_net_set_strict_f32: never by the rule (its products are f16 split products, not the f32 MFMA's); the forced option wins.
-  bool mfma_eligible(const Layer& y) const {
+  // ---- narrow layers: what narrow_plan (runtime.inc) decides from, read HERE and nowhere else -- the device, the net's settings, the
+  // experiment options (each per pass: tests switch them inside one process; a forward pass reads fwd_mfma, a backward pass the other
+  // three) and whether this is the host emulator build
+  NarrowShape narrow_shape(int l, int pass) const {
+    const Layer& y = L[l];
+    NarrowShape h{};
+    h.pass = pass; h.no = y.no; h.ni = y.ni; h.ndir = ndir;
+    h.nlayers = (int)L.size(); h.first = l == 0; h.top = l + 1 == (int)L.size();
+    h.bs = bs; h.tmax = tmax; h.N = (int)N; h.nc = desc.nclasses;
+    h.ldh = y.ldh; h.lds = y.lds; h.ldx = layer_input_ld(l);
+    h.h_cap = (int)std::min<size_t>(y.H.cap, 2147483647); h.d_cap = (int)std::min<size_t>(y.D.cap, 2147483647);
+    h.wk = y.Wk != nullptr; h.wk_njp = y.wk_njp; h.w1k_kps = w1k_kps;
+    h.overlap = overlap; h.bf16_gemm = bf16_gemm; h.strict_f32 = strict_f32;
+    h.dw_x3 = dw_x3; h.split_terms = split_terms;
+    if (pass != NP_BWD) h.fwd_mfma = dbg_opt("fwd_mfma");
+    else { h.bwd_mfma = dbg_opt("bwd_mfma"); h.bwd_mfma_fused = dbg_opt("bwd_mfma_fused"); h.xd_prologue = dbg_opt("xd_prologue"); }
+    h.ncu = device_cu_count();
 #ifdef CLSTM_HIP_EMU
-    return false;
-#else
-    const int mode = dbg_opt("fwd_mfma");
-    if (!mode || y.wide || bf16_gemm) return false;
-    if (strict_f32 && mode < 2) return false;
-    if (!((y.no == 64 || y.no == 100 || y.no == 128) && y.ni == 48)) return false;   // the instantiated (cells, inputs) geometries
-    const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
-    if ((double)N * ndir * 4 * y.no * 4 >= lim || (double)N * y.ldh * 4 >= lim || (double)N * y.lds * 4 >= lim) return false;
-    if ((double)N * layer_input_ld((int)(&y - L.data())) * 4 >= lim) return false;
-    return mode >= 2 || bs >= 640;
+    h.emu = 1;
 #endif
+    return h;
   }
-  // geometries whose batched forward recurrence has a no-save instantiation (lstm_mfma.h: not the 128-cell one, which spills)
-  static bool mfma_nosave_ok(const Layer& y) { return y.no == 64 || y.no == 100; }
-  // THE launch rule of the forward pass: forward_pass (training and recognition) launches by it and reserve_batch sizes the
-  // predict geometry by it -- nothing else decides.  The batched recurrence goes before the fused launch (which only a net of
-  // one narrow layer can take); the strict and forced options act through the two predicates.
-  FwdFamily forward_family(const Layer& y) {
-    if (y.wide) return FwdFamily::Wide;
-    if (mfma_eligible(y)) return FwdFamily::Mfma;
-    return forward_fused_eligible() ? FwdFamily::Fused : FwdFamily::PerLine;
-  }
-  // ... and whether that family runs its training form -- G, C and S written -- in a pass that asked for save or not: always when
-  // asked to, and where the family has no no-save instantiation for the layer
-  static bool forward_saves(const Layer& y, FwdFamily fam, bool save) { return save || (fam == FwdFamily::Mfma && !mfma_nosave_ok(y)); }
+  // the plan of layer l's forward / backward pass; of a wide layer: none (fwd NF_NONE, bwd NB_NONE, nothing rides its launch)
+  NarrowPlan forward_plan(int l, bool save) const { return L[l].wide ? NarrowPlan{} : narrow_plan(narrow_shape(l, save ? NP_FWD_SAVE : NP_FWD_NOSAVE)); }
+  NarrowPlan backward_plan_narrow(int l) const { return L[l].wide ? NarrowPlan{} : narrow_plan(narrow_shape(l, NP_BWD)); }
 #ifndef CLSTM_HIP_EMU
   template <int NO, int NI, bool SAVE = true>
-  void launch_mfma_no(Layer& y, bool fwd, hipStream_t s) {
+  void launch_mfma_no(Layer& y, hipStream_t s) {
     using Gm = MfmaGeom<NO, NI, SAVE>;
     const int l = (int)(&y - L.data());
     if (y.mf_epoch != params_epoch) {
@@ -698,9 +691,8 @@ struct Net {
     lstm_prof.reserve(128); a.prof = lstm_prof.p;
 #endif
     static const bool smem_set = (coop_set_smem(lstm_fwd_mfma_kernel<NO, NI, SAVE>, (size_t)Gm::SMEM), true);
-    (void)smem_set; (void)fwd;
+    (void)smem_set;
     CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI, SAVE>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
-    g_path_count[SAVE ? PC_MFMA_FWD : PC_MFMA_NOSAVE]++;
     if (l == 0) launch_routed_per_line(y, s, SAVE);
   }
   // the per-line forward pass of layer 0 (hoisted f32 W_x.x product + lstm_seq.h recurrence, as forward() launches them for
@@ -719,10 +711,7 @@ struct Net {
                  gemm_kc(layer_input(0), layer_input_ld(0), N), gemm_mc(y.Wt, M, y.ni, 0), StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni, ksplit,
                  gx, gy, (const unsigned*)y.mf_xmax.p);
     const LstmSeqArgs a = seq_args(y, true, save);
-#define CASE_(N, K) if (y.nk4 == N && y.pd.ku == K) { launch_routed_lstm<N, K>(y, a, s, save); return; }
-    CASE_(4, 16) CASE_(7, 25) CASE_(8, 32)    // (the cell counts mfma_eligible admits: 64, 100, 128)
-#undef CASE_
-    REQUIRE(false, "internal: per-line geometry of a batched layer");
+    narrow_dispatch<NCAP_ROUTED>(y.nk4, y.pd.ku, [&](auto c) { launch_routed_lstm<decltype(c)::NK4, decltype(c)::KU>(y, a, s, save); });
   }
 #endif
   // the argument block of the per-line recurrence kernels (lstm_seq.h) for one layer and pass; save = false: C and S stay null
@@ -735,23 +724,6 @@ struct Net {
     a.S = save ? y.S.p : nullptr; a.lds = y.lds; a.sofs = 1 + y.ni; a.sdir = (long long)N * y.lds;
     a.prog_off = -1; a.prog_base = 0;
     return a;
-  }
-  // bwd_mfma: the backward twin (lstm_mfma_bwd.h): 0 never, 1 (default) from 640 lines per GPU on, 2 always (tests).  It gives up
-  // the fused launch (the weight-gradient items then run behind it as a launch of their own).  Crossover with the per-line fused
-  // launch, whole step (profiles/r06_mfma_bwd_leaveout.txt): 512 lines 311.9k vs 327.3k lines/s, 640: 343.6k vs 330.4k,
-  // 768: 373.7k vs 355.8k, 896: 403.7k vs 358.4k
-  bool mfma_bwd_eligible(const Layer& y) const {
-#ifdef CLSTM_HIP_EMU
-    return false;
-#else
-    const int mode = dbg_opt("bwd_mfma");
-    if (!mode || y.wide || bf16_gemm) return false;
-    if (strict_f32 && mode < 2) return false;   // (R^T.delta from two bf16 terms: not what strict promises; forced: the option wins)
-    if (!(y.no == 64 || y.no == 100)) return false;   // (128 cells: image + operand staging would need 176 KB of LDS)
-    const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
-    if ((double)N * ndir * 4 * y.no * 4 >= lim) return false;
-    return mode >= 2 || bs >= 640;
-#endif
   }
 #ifndef CLSTM_HIP_EMU
   // argument block of the batched backward kernels from the per-line one; the R^T fragments repacked when the parameters have moved
@@ -779,11 +751,10 @@ struct Net {
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
     (void)smem_set;
     CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
-    g_path_count[PC_MFMA_BWD]++;
   }
-  // ... and as ONE launch with the weight-gradient items (lstm_mfma_bwd_dw.h); false: not instantiated for this layer / arithmetic
+  // ... and as ONE launch with the weight-gradient items (lstm_mfma_bwd_dw.h), whose items are instantiated for three split terms
   template <int NO>
-  bool launch_mfma_bwd_dw_no(Layer& y, const LstmSeqArgs& sa, const GemmDwArgs& g, unsigned ngemm, hipStream_t s) {
+  void launch_mfma_bwd_dw_no(Layer& y, const LstmSeqArgs& sa, const GemmDwArgs& g, unsigned ngemm, hipStream_t s) {
     constexpr int NT = 2;
     using Gr = MfmaBwdRowsGeom<NO, NT>;
     const LstmMfmaBwdArgs a = mfma_bwd_args<NO, NT>(y, sa, s);
@@ -791,49 +762,33 @@ struct Net {
     static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM), true);
     (void)smem_set;
     CLSTM_LAUNCH((lstm_bwd_mfma_dw_kernel<NO, NT, 3>), dim3((unsigned)nrec + ngemm), dim3(512), (size_t)Gr::SMEM, s, a, g, nrec, ngroups);
-    g_path_count[PC_MFMA_BWD]++; g_path_count[PC_MFMA_BWD_DW]++;
-    return true;
-  }
-  // (pays while the recurrence leaves most CUs idle -- same box, lines/s fused vs separate: 640 lines 368.1k vs 340.0k, 768: 395.7k
-  //  vs 374.8k, 896: 398.0k vs 395.1k, 960: 406.6k vs 407.9k, 1024: 414.6k vs 419.0k, 1536: 430.2k vs 471.2k; option bwd_mfma_fused:
-  //  0 never, 1 that rule, 2 always (tests))
-  bool mfma_bwd_fused_ok(const Layer& y, const GemmDwArgs& g) const {
-    const int mode = dbg_opt("bwd_mfma_fused");
-    return mfma_bwd_eligible(y) && mode && g.x3 && g.terms >= 3 && (mode >= 2 || bs < 900);
   }
 #endif
-  // the narrow layer's backward recurrence: batched over lines on the MFMA where that pays, else one workgroup per line
-  // xd: the softmax layer's x.d as the prologue of every workgroup (top layer, xd_in_launch)
-  void launch_bwd_narrow(Layer& y, const LstmSeqArgs& a, hipStream_t s, const XdArgs* xd = nullptr) {
-    if (xd) {
-      REQUIRE(launch_lstm_bwd_xd(y.nk4, y.pd.ku, a, *xd, split_terms, bs, y.nthreads, s), "internal: no per-line backward instantiation");
-      return;
-    }
+  // the batched forward recurrence of the plan (lstm_mfma.h), in its saving or its no-save form
+  void launch_mfma(Layer& y, hipStream_t s, bool save) {
 #ifndef CLSTM_HIP_EMU
-    if (mfma_bwd_eligible(y)) {
-      if (y.no == 64) launch_mfma_bwd_no<64>(y, a, s);
-      else launch_mfma_bwd_no<100>(y, a, s);
-      check_launch();
-      return;
-    }
-#endif
-    launch_lstm(false, y.nk4, y.pd.ku, a, bs, y.nthreads, s);
-  }
-  void launch_mfma(Layer& y, bool fwd, hipStream_t s, bool save = true) {
-#ifndef CLSTM_HIP_EMU
-    if (save) {
-      if (y.no == 64) launch_mfma_no<64, 48>(y, fwd, s);
-      else if (y.no == 100) launch_mfma_no<100, 48>(y, fwd, s);
-      else launch_mfma_no<128, 48>(y, fwd, s);
-    } else {
-      REQUIRE(mfma_nosave_ok(y), "internal: no no-save instantiation of the batched recurrence for this layer");
-      if (y.no == 64) launch_mfma_no<64, 48, false>(y, fwd, s);
-      else launch_mfma_no<100, 48, false>(y, fwd, s);
-    }
-    check_launch();
+    if (save) mfma_dispatch<MCAP_FWD>(y.no, [&](auto no) { launch_mfma_no<decltype(no)::value, 48>(y, s); });
+    else mfma_dispatch<MCAP_NOSAVE>(y.no, [&](auto no) { launch_mfma_no<decltype(no)::value, 48, false>(y, s); });
 #else
-    (void)y; (void)fwd; (void)s; (void)save;
+    (void)y; (void)s; (void)save; no_instantiation();
 #endif
+  }
+  // ... and the batched backward recurrence (lstm_mfma_bwd.h): alone, or (g) as one launch with the weight-gradient items
+  void launch_mfma_bwd(Layer& y, const LstmSeqArgs& a, hipStream_t s, const GemmDwArgs* g = nullptr, unsigned ngemm = 0) {
+#ifndef CLSTM_HIP_EMU
+    mfma_dispatch<MCAP_BWD>(y.no, [&](auto no) {
+      if (g) launch_mfma_bwd_dw_no<decltype(no)::value>(y, a, *g, ngemm, s); else launch_mfma_bwd_no<decltype(no)::value>(y, a, s);
+    });
+#else
+    (void)y; (void)a; (void)s; (void)g; (void)ngemm; no_instantiation();
+#endif
+  }
+  // the narrow layer's backward recurrence alone, in the plan's form: batched over lines on the MFMA, one workgroup per line, or that with
+  // the softmax layer's x.d as the prologue of every workgroup (xd: the top layer where NarrowPlan::xd = 1 meets the two-launch form)
+  void launch_bwd_narrow(Layer& y, const NarrowPlan& np, const LstmSeqArgs& a, hipStream_t s, const XdArgs* xd = nullptr) {
+    if (np.bwd == NB_LINE_XD_DW) launch_lstm_bwd_xd(y.nk4, y.pd.ku, a, *xd, np.terms, bs, y.nthreads, s);
+    else if (np.bwd == NB_MFMA || np.bwd == NB_MFMA_THEN_DW) launch_mfma_bwd(y, a, s);
+    else launch_lstm(false, y.nk4, y.pd.ku, a, bs, y.nthreads, s);
   }
 
   void forward() {
@@ -844,18 +799,18 @@ struct Net {
     forward_pass(true);
   }
   // The forward pass of training (save) and of recognition (!save: predict, on its own geometry).  Every layer runs the family
-  // forward_family names, in the form forward_saves names; without save nothing is kept for a backward pass -- no C, no source
+  // its plan names (narrow_plan / wide_plan), in the form NarrowPlan::saves names; without save nothing is kept for a backward pass -- no C, no source
   // rows S (ensure_source_x is never called), G only as staging -- and the per-layer validity flags are left as predict set them.
   // Wide layers and the bf16 modes exist with save only (predict_nosave_ok).
   void forward_pass(bool save) {
     flush_line_off();
     repack();
     hipStream_t s = stream();
-    if (forward_family(L[0]) == FwdFamily::Fused) { forward_fused(save); return; }
     for (int l = 0; l < (int)L.size(); l++) {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
-      const FwdFamily fam = forward_family(y);
+      const NarrowPlan np = forward_plan(l, save);
+      if (np.fwd == NF_FUSED) { forward_fused(np, save); return; }   // (a net of one layer: the launch is the whole forward half)
       const bool x_from_hbf = hbf_feeds(l) && L[l - 1].fwd_persistent;   // (a fact: the layer below has run)
       // the lock-step recurrence of a wide layer as planned + what follows it (bf16 source rows for the weight gradient); false: the
       // plan was the kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) and it did not run
@@ -915,14 +870,15 @@ struct Net {
       }
       if (fx_done) { if (!y.sbf_ready) ensure_source_x(l); continue; }
       if (l > 0 && !x_from_hbf) ensure_h_f32(l - 1);   // the products below read the f32 outputs of the layer underneath
-      if (fam == FwdFamily::Mfma) {
+      if (np.fwd == NF_MFMA) {
         // chip-filling minibatch of a narrow layer: the input product is part of the batched recurrence (lstm_mfma.h) -- no
         // hoisted W_x GEMM, no pre-activation array; the [1 | x] columns of the source rows are still the weight gradient's
         // (so not built without save, not even for the 128-cell layer whose training form runs then -- it has no no-save
         //  instantiation, reserve_batch kept its arrays: the kernel reads the frames themselves)
         if (save) { y.sx_valid = l == 0 && src0_ready; ensure_source_x(l); }
         timing.begin("lstm_fwd", s);
-        launch_mfma(y, true, s, forward_saves(y, fam, save));
+        launch_mfma(y, s, np.saves);
+        count_moves(np.moves);
         if (save) y.h_f32_valid = y.sh_valid = true;
         timing.end(s);
         continue;
@@ -956,7 +912,7 @@ struct Net {
       // only if something still asks for them: a fallback path or the state API)
       if (save) y.sx_valid = l == 0 && src0_ready;
       if (save && (l == 0 || !y.wide)) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
-      if (fam == FwdFamily::Wide) run_wide(wide_plan(wide_shape(y, true)), wide_args(y, true));
+      if (y.wide) run_wide(wide_plan(wide_shape(y, true)), wide_args(y, true));
       else {
         LstmSeqArgs a = seq_args(y, true, save);
 #ifdef CLSTM_LSTM_PROF
@@ -964,8 +920,8 @@ struct Net {
 #endif
         timing.begin("lstm_fwd", s);
         launch_lstm(true, y.nk4, y.pd.ku, a, bs, y.nthreads, s, save);
+        count_moves(np.moves);
         if (save) y.h_f32_valid = y.sh_valid = true;
-        else g_path_count[PC_LINE_NOSAVE]++;
         timing.end(s);
       }
       if (save && !y.sbf_ready) ensure_source_x(l);
@@ -1001,7 +957,7 @@ struct Net {
   }
 
   // ---- recognition: the forward pass of a minibatch nobody will run backward on (clstm_net_predict) ----
-  // forward_pass without save: the family of every layer is chosen by forward_family, the one function forward() and
+  // forward_pass without save: the family of every layer is chosen by its forward plan, the one rule forward() and
   // reserve_batch ask too (fused launch / batched MFMA / per line, strict and forced options included), and runs in its no-save
   // form: identical arithmetic, so identical outputs.  The training NaN flag is not passed (what clstm_net_set_training(net, 0)
   // does, without changing that setting), nbackward and the training state are untouched.
@@ -1019,17 +975,7 @@ struct Net {
     forward_pass(false);
   }
 
-  // ---- the forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h) ----
-  bool forward_fused_eligible() {
-    if (!overlap || L.size() != 1 || bf16_gemm) return false;
-    const Layer& y = L[0];
-    if (!y.Wk || y.wide || y.nthreads < 64 * FWD_CW || y.no % 16 == 0 || y.wk_njp > FWD_JW * FWD_CW || w1k_kps > 16 * FWD_CG) return false;     // >= 5 waves, the last lane owns no cell
-    if (desc.nclasses > SMX_COLS || bs > PROG_LINES || bs >= (1 << 18) || tmax >= (1 << 16)) return false;
-    if ((overlap == 1) && (tmax < 64 || N < 2048)) return false;                 // too small to profit
-    if ((double)y.H.cap * 4.0 >= 2147483000.0) return false;                     // 32-bit byte offsets inside one descriptor
-    // the recurrence workgroups (one per CU, dispatched first) wait for producers: CUs must be left for those
-    return bs * ndir <= device_cu_count() - std::max(8, device_cu_count() / 8);
-  }
+  // ---- the forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h; the rule: narrow_plan) ----
   void build_fwd_items() {
     if (fw_key == line_off_h && fw_ncitems > 0) return;
     fw_chunks = (tmax + 15) / 16;
@@ -1061,7 +1007,7 @@ struct Net {
     ring.commit(s);
     fw_key = line_off_h;
   }
-  void forward_fused(bool save = true) {   // save = false: the recurrence role in its no-save form (predict)
+  void forward_fused(const NarrowPlan& np, bool save) {   // save = false: the recurrence role in its no-save form (predict)
     hipStream_t s = stream();
     Layer& y = L[0];
     build_fwd_items();
@@ -1069,7 +1015,7 @@ struct Net {
     fw_prog_base += tmax + 64;
     if (fw_prog_base > (1 << 30)) fw_prog_base = 1024;
     fw_launches++;
-    g_path_count[save ? PC_FWD_FUSED : PC_FUSED_NOSAVE]++;
+    count_moves(np.moves);
     FwdFusedKernelArgs k{};
     LstmSeqArgs& a = k.a;
     a = seq_args(y, true, save);
@@ -1092,7 +1038,7 @@ struct Net {
     const size_t trace_rows = (size_t)h.nrec + fw_npitems + fw_ncitems;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); HIPCHECK(hipMemsetAsync(dw_trace.p, 0, trace_rows * 4 * sizeof(long long), s)); h.trace = dw_trace.p; }
     timing.begin("lstm_fwd", s);
-    REQUIRE(launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s, save), "internal: no fused forward instantiation");
+    launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s, save);
     timing.end(s);
     if (trace_path)
       dump_trace(trace_path, dw_trace.p, trace_rows, s,
@@ -1111,7 +1057,7 @@ struct Net {
   // ~0 (a tanh gate at -0.0021 came out 5.6e-6 off where the parity bar allows 2.2e-6), and with K = 49 the split costs
   // more staging than it saves MFMA time (28.5 vs 20.9 us).
   bool gemm_x3_on = dbg_opt("gemm_x3") != 0;
-  bool strict_f32 = false;   // clstm_net_set_strict_f32: no split-product recurrences by the library's own rule either (mfma_eligible)
+  bool strict_f32 = false;   // clstm_net_set_strict_f32: no split-product recurrences by the library's own rule either (narrow_plan)
   // exact-f32 mode, wide layers: the persistent BACKWARD recurrence as an f32-grade x3 product on the bf16 MFMA (lstm_wide.h:
   // lstm_xcd_bwd_x3) like the backward GEMMs of this mode; off with them (gemm_x3=0 / strict f32) or alone (rec_x3=0, CLSTM_DEBUG options;
   // read per pass: tests compare both kernels in one process)
@@ -1136,51 +1082,7 @@ struct Net {
   }
 
   // ---- overlap machinery ---------------------------------------------------------------------------------------
-  bool overlap_eligible(const Layer& y) const {
-    if (!overlap || y.wide || y.no % 16 == 0) return false;          // the reporting lane must own no cell
-    if (bs > PROG_LINES) return false;
-    if ((overlap == 1) && (tmax < 64 || N < 2048)) return false;     // too small to profit
-    if ((double)y.D.cap * 4.0 >= 2147483000.0) return false;         // 32-bit byte offsets inside one descriptor
-    return overlap == 2 || y.nthreads >= 256;                        // one launch, two workgroup roles (lstm_bwd_dw.h)
-  }
-  // THE launch rule of the backward pass: the layer loop, the slab count, the weight-gradient step and dwx_active all ask here.
-  // Overlapped: through backward_layer_overlapped, whatever launch form it picks (mfma_bwd_eligible / mfma_bwd_fused_ok choose a
-  // form INSIDE a family, as mfma_eligible does on the forward side).
-  BwdFamily backward_family(const Layer& y) const {
-    if (!bf16_gemm && overlap_eligible(y)) return BwdFamily::Overlapped;
-    return y.wide ? BwdFamily::Wide : BwdFamily::Narrow;
-  }
-  // Does the top layer's backward launch compute the softmax layer's x.d itself (lstm_xd_prologue.h)?  backward_softmax (which
-  // then launches nothing) and backward_layer_overlapped (which hands the prologue its operands) both ask here.  All of:
-  //  * dwx_active -- this pass's condition for the lone x.d launch: top layer Overlapped, dw_x3, bs * ndir * 4 <= 3 * CUs;
-  //  * the per-line recurrence kernel runs it (fused launch or, below four waves / on the host emulator, the two-launch form):
-  //    the batched-MFMA backward recurrence keeps the separate launch;
-  //  * the split is two or three bf16 terms (dw_x3 says so: the launch rounds split_terms to one of the two, as gemm_x3 does);
-  //  * nc <= XD_MAX_K = 96: three k-blocks of W fragments (3 x NT x 4 VGPRs) stay in registers for the whole prologue, and three
-  //    blocks are what the launch it replaces runs for such nc, zero blocks included (bit-identity);
-  //  * experiment option xd_prologue (default 2: the producer form where xd_mode admits it, else as 1; 1 the whole prologue; 0 the separate launch).
-  // Lines: inherits dwx_active's bound (bs * ndir <= 192 on 256 CUs); measured 64 / 96 bidirectional lines, EXPERIMENTS 15.
-  // xd_mode is THE decision: 0 the separate launch, 1 the whole prologue in every recurrence workgroup, 2 (experiment option
-  // xd_prologue=2, the default) the producer form -- the recurrence workgroup computes only the 32 frames it visits first, helper items of the
-  // same launch the rest (lstm_xd_prologue.h).  Form 2 needs the one-launch form of the overlapped pass (four or more waves, not the
-  // host emulator: backward_layer_overlapped's rule) and recurrence workgroups on at most half of the CUs -- the items are workgroups of its helper role, one wave per column tile like
-  // the recurrence role -- and whatever is eligible for 1 but not for 2 runs 1 unchanged.
-  int xd_mode() const {
-    const Layer& top = L.back();
-    const int opt = dbg_opt("xd_prologue");
-    const bool ok = dwx_active && !mfma_bwd_eligible(top) && desc.nclasses <= XD_MAX_K && top.nthreads >= 64 * ((top.no + 15) / 16) &&
-                    top.nthreads * xd_maxu(top.nk4) >= XD_UNITS &&   // (always: the smallest workgroup of an instantiation covers a staging round)
-                    opt != 0;
-    if (!ok) return 0;
-#ifndef CLSTM_HIP_EMU
-    // ... and a CU of its own for every item: an item that shares a CU with a recurrence workgroup takes issue slots from the
-    // latency-bound time loop (96 bidirectional lines, 192 + 192 workgroups on 256 CUs: form 2 measured 5.5 us per step SLOWER than
-    // form 1; 64 lines, 128 + 128: 4.1 us faster -- profiles/ab_xd_producers.txt)
-    if (opt >= 2 && top.nthreads >= 256 && (long long)bs * ndir * 2 <= device_cu_count()) return 2;
-#endif
-    return 1;
-  }
-  bool xd_in_launch() const { return xd_mode() != 0; }
+  // the operands of the softmax layer's x.d for the top layer's backward launch (NarrowPlan::xd: the prologue forms of lstm_xd_prologue.h)
   XdArgs xd_args() const {
     const Layer& top = L.back();
     const int nc = desc.nclasses;
@@ -1266,8 +1168,8 @@ struct Net {
     ring.commit(s);
     dw_key = line_off_h;
   }
-  // backward recurrence + the chunked weight-gradient GEMM as two workgroup roles of one launch
-  void backward_layer_overlapped(Layer& y, LstmSeqArgs a, int R, int Cn) {
+  // backward recurrence + the chunked weight-gradient GEMM, as one launch or as two: the launch form the layer's plan names (NarrowPlan::bwd)
+  void backward_layer_overlapped(Layer& y, const NarrowPlan& np, LstmSeqArgs a, int R, int Cn) {
     hipStream_t s = stream();
     build_dw_tables();
     const int M = ndir * 4 * y.no;
@@ -1297,10 +1199,8 @@ struct Net {
     g.x3 = dw_x3;
     g.terms = split_terms;
     unsigned nextra = 0;
-    const bool xd = &y == &L.back() && xd_in_launch();   // (only the top layer's dH comes from the softmax layer)
-    const int xdm = &y == &L.back() ? xd_mode() : 0;
-    if (xd) { g.xd = xd_args(); g_path_count[xdm == 2 ? PC_XD_PRODUCERS : PC_XD_PROLOGUE]++; }
-    if (xdm == 2) {   // the items' rounds-complete words: [ndir][bs], one per 128 bytes; zero is below every prog_base
+    if (np.xd) g.xd = xd_args();   // (only the top layer's plan has it: only its dH comes from the softmax layer)
+    if (np.xd == 2) {   // the items' rounds-complete words: [ndir][bs], one per 128 bytes; zero is below every prog_base
       const size_t nw = (size_t)ndir * bs * PROG_STRIDE;
       if (nw > xd_ready.cap || prog_base_wrapped) {
         xd_ready.reserve(nw);
@@ -1309,7 +1209,7 @@ struct Net {
       g.xd.ready = xd_ready.p; g.xd.ready0 = prog_base;
       a.timeouts = g.timeouts;   // (the recurrence role's bounded wait for a round)
     }
-    if (dwx_active && &y == &L.back()) {
+    if (np.dwx) {
       const int xR = 1 + sm_ni, xCn = desc.nclasses;
       g.xS = y.srow(); g.xlds = y.ldh; g.xs_elems = (long long)N * y.ldh + 3;
       g.xD = Dz.p; g.xM = xCn; g.xd_elems = (long long)N * xCn + 3;
@@ -1322,45 +1222,26 @@ struct Net {
     const size_t trace_rows = (size_t)bs * ndir + (size_t)((dw_nslabs + 7) / 8) * 8 * g.gx * g.gy + 8;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); g.trace = dw_trace.p; g.trace_base = bs * ndir; }
     // the monitor + (producer form) one dH item per recurrence workgroup + the independent items + one per item
-    const unsigned nblk = 1u + (xdm == 2 ? (unsigned)(bs * ndir) : 0u) + nextra + (unsigned)((dw_nslabs + 7) / 8) * 8u * g.gx * g.gy;
-#ifndef CLSTM_HIP_EMU
-    if (mfma_bwd_fused_ok(y, g)) {   // chip-filling minibatch: the batched-MFMA recurrence and the items as one launch
-      timing.begin("lstm_bwd", s);
-      g.done = nullptr; g.done_target = 0;   // (every chunk through the monitor)
-      const bool ok = y.no == 64 ? launch_mfma_bwd_dw_no<64>(y, a, g, nblk, s) : launch_mfma_bwd_dw_no<100>(y, a, g, nblk, s);
-      timing.end(s);
-      check_launch();
-      if (ok) return;
-    }
-    if (y.nthreads >= 256 && !mfma_bwd_eligible(y)) {   // ONE launch: the recurrence's workgroups first, the GEMM's (one (slab, tile) item each) behind them
-      timing.begin("lstm_bwd", s);
+    const unsigned nblk = 1u + (np.xd == 2 ? (unsigned)(bs * ndir) : 0u) + nextra + (unsigned)((dw_nslabs + 7) / 8) * 8u * g.gx * g.gy;
+    timing.begin("lstm_bwd", s);
+    if (np.bwd == NB_MFMA_DW) launch_mfma_bwd(y, a, s, &g, nblk);   // chip-filling minibatch: the batched-MFMA recurrence and the items as one launch (every chunk through the monitor)
+    else if (np.bwd == NB_BWD_DW) {   // ONE launch: the recurrence's workgroups first, the GEMM's (one (slab, tile) item each) behind them
       g.done = g.minprog + 2 * PROG_STRIDE;   // own 128-byte line behind the monitor's words; zero-filled once, then only added to
       dw_done_total += (unsigned)(bs * ndir);
       g.done_target = (int)dw_done_total;
-      REQUIRE(launch_lstm_bwd_dw(y.nk4, y.pd.ku, a, g, bs * ndir, nblk, y.nthreads, s), "internal: no fused instantiation");
-      timing.end(s);
-      if (trace_path)
-        dump_trace(trace_path, dw_trace.p, trace_rows, s,
-                   "# rows 0..%d: recurrence workgroups (start, x.d prologue returned, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
-      return;
-    }
-#endif
-    // two launches one after the other (host emulator; layers too narrow for the GEMM role's 256 threads when the
-    // tests force the path): the items find every progress word complete
-    // (... and minibatches whose backward recurrence runs batched on the MFMA, lstm_mfma_bwd.h: it marks its lines complete)
-    REQUIRE(xdm != 2, "internal: the producer form of x.d outside the one-launch form");
-    timing.begin("lstm_bwd", s);
-    launch_bwd_narrow(y, a, s, xd ? &g.xd : nullptr);
+      launch_lstm_bwd_dw(y.nk4, y.pd.ku, a, g, np.terms, bs * ndir, nblk, y.nthreads, s);
+    } else launch_bwd_narrow(y, np, a, s, &g.xd);   // two launches one after the other: the items find every progress word complete
     timing.end(s);
+    if (np.bwd == NB_BWD_DW && trace_path)
+      dump_trace(trace_path, dw_trace.p, trace_rows, s,
+                 "# rows 0..%d: recurrence workgroups (start, x.d prologue returned, end); then one row per (slab, tile) item: start ready done need_it; 100 MHz ticks\n", bs * ndir - 1);
+    if (np.bwd == NB_MFMA_DW || np.bwd == NB_BWD_DW) return;
     timing.begin("gemm_gates_dw", s);
-    if (g.x3 && g.terms >= 3) CLSTM_LAUNCH(gemm_dw_kernel<3>, dim3(nblk), dim3(256), 0, s, g);
-    else if (g.x3) CLSTM_LAUNCH(gemm_dw_kernel<2>, dim3(nblk), dim3(256), 0, s, g);
-    else CLSTM_LAUNCH(gemm_dw_kernel<0>, dim3(nblk), dim3(256), 0, s, g);
+    launch_gemm_dw(g, np.terms, nblk, s);
     timing.end(s);
-    check_launch();
   }
 
-  // ... and of the softmax layer's W.d items in the top layer's launch (dwx_active): contiguous frames, entries of 16, slabs of
+  // ... and of the softmax layer's W.d items in the top layer's launch (NarrowPlan::dwx): contiguous frames, entries of 16, slabs of
   // 32 entries (512 frames: one short item each)
   void build_dwx_table() {
     if (dwx_N == N) return;
@@ -1393,11 +1274,14 @@ struct Net {
     flush_line_off();
     repack();
     hipStream_t s = stream();
+    // every layer's backward plan, asked for ONCE, in front of backward_softmax (which reads the top layer's)
+    NarrowPlan np[CLSTM_MAX_LAYERS];
+    for (int l = 0; l < (int)L.size(); l++) np[l] = backward_plan_narrow(l);
     // every entry of g is assigned by exactly one reduce below: no clearing pass
-    backward_softmax();
+    backward_softmax(np[L.size() - 1]);
     for (int l = (int)L.size() - 1; l >= 0; l--) {
-      const BwdFamily fam = backward_family(L[l]);
-      const bool bwd_persistent = backward_recurrence(l, fam);
+      const BwdFamily fam = L[l].wide ? BwdFamily::Wide : np[l].overlapped ? BwdFamily::Overlapped : BwdFamily::Narrow;
+      const bool bwd_persistent = backward_recurrence(l, fam, np[l]);
       const BwdPlan p = backward_plan(L[l], fam, bwd_persistent);
       if (!p.dw_from_bf16) { ensure_source(l); ensure_delta_f32(l); }   // the f32-source products below read S and D
       if (!backward_weight_gradient(l, p, rt)) backward_input_deltas(l, p);   // (true: the input deltas rode the weight-gradient launch)
@@ -1413,7 +1297,7 @@ struct Net {
   }
   // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T.  (A side stream for these products was measured
   // on MI355X: no gain -- the recurrence workgroups it would overlap with slow down by as much -- so everything stays on one stream.)
-  void backward_softmax() {
+  void backward_softmax(const NarrowPlan& top_plan) {
     hipStream_t s = stream();
     Layer& top = L.back();
     const int nc = desc.nclasses, R = 1 + sm_ni, Cn = nc;
@@ -1424,18 +1308,17 @@ struct Net {
     // W.d depends on nothing the backward recurrence produces: when the top layer's backward runs as the fused launch
     // (lstm_bwd_dw.h) its slabs are items of THAT launch -- they execute on the idle half of the chip during the ~14 us
     // before the recurrence's first chunk is released -- and only x.d stays in front of the recurrence.
-    // (only while the recurrence leaves CUs idle: with 256 lines the same items cost the fused launch +42 us for 19 saved)
-    dwx_active = dw_x3 && backward_family(top) == BwdFamily::Overlapped && (long long)bs * ndir * 4 <= 3LL * device_cu_count();
-    if (dwx_active) { build_dwx_table(); ns = dwx_nslabs; }
+    // (NarrowPlan::dwx: the rule)
+    if (top_plan.dwx) { build_dwx_table(); ns = dwx_nslabs; }
     partial_sm.reserve((size_t)ns * R * Cn);
     // W.d (split-K slabs) and x.d in ONE launch: two small independent products, each mostly prologue and
     // epilogue latency on its own (13.9 + 12.4 us back to back)
     const GemmOperand Wk = gemm_kc(W1 + nc, nc, sm_ni, 0);
     const StorePartial wd_store{partial_sm.p, R, Cn};
     const StorePlain xd_store{top.dH.p, sm_ni};
-    const bool launches = !xd_in_launch();   // (else nothing is launched here: the top layer's backward launch computes x.d)
+    const bool launches = !top_plan.xd;   // (else nothing is launched here: the top layer's backward launch computes x.d)
     if (launches) timing.begin("gemm_softmax_dw_dx", s);
-    if (dwx_active) {
+    if (top_plan.dwx) {
       if (launches) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, split_terms);
     } else if (sm_big) {
       gemm_x3_big<GEMM_MC, GEMM_MC>(s, gemm_mc(top.srow(), top.ldh, N, 32), gemm_mc(Dz.p, nc, N, 32), wd_store, R, Cn, (int)N, ns);
@@ -1451,13 +1334,14 @@ struct Net {
     sm_red = ReduceDesc{partial_sm.p, nullptr, (long long)sm_off, ns, 1, R, Cn, nc};
     check_launch();
   }
-  // the backward recurrence of layer l in the family backward_family named; returns whether it ran as a persistent lock-step kernel
-  bool backward_recurrence(int l, BwdFamily fam) {
+  // the backward recurrence of layer l in the family and form its plan named; returns whether it ran as a persistent lock-step kernel
+  bool backward_recurrence(int l, BwdFamily fam, const NarrowPlan& np) {
     Layer& y = L[l];
     hipStream_t s = stream();
     const LstmSeqArgs a = seq_args(y, false);   // (no progress words: backward_layer_overlapped sets them in its copy)
     if (fam == BwdFamily::Overlapped) {   // the recurrence and the weight-gradient GEMM run side by side (gemm_dw.h)
-      backward_layer_overlapped(y, a, 1 + y.ni + y.no, 4 * y.no);
+      backward_layer_overlapped(y, np, a, 1 + y.ni + y.no, 4 * y.no);
+      count_moves(np.moves);
       return false;
     }
     timing.begin("lstm_bwd", s);
@@ -1467,7 +1351,7 @@ struct Net {
       const LstmWideArgs w = wide_args(y, false);
       ran = launch_lstm_wide(wide_plan(wide_shape(y, false)), w, coop_sync, step_graphs, s);
       skipped_d = w.skip_d;
-    } else launch_bwd_narrow(y, a, s);
+    } else { launch_bwd_narrow(y, np, a, s); count_moves(np.moves); }
     timing.end(s);
     const bool persistent = ran == WideRan::Persistent;
     y.d_f32_valid = !(persistent && bf16_rec && skipped_d);   // (launch_lstm_wide moved the plan's path counters)

@@ -1,5 +1,5 @@
 // runtime.inc -- part of clstm_hip.hip (namespace clstm): errors, device buffers and the pinned staging ring, GEMM store functors,
-// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), the lock-step layer's kernel choice (wide_plan),
+// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), the layers' kernel choices (narrow_plan, wide_plan),
 // device error words, per-kernel timing, roctx.
 // Not a stand-alone header: included once, inside the namespace, by clstm_hip.hip.
 
@@ -194,12 +194,60 @@ struct StorePartialRot {  // split-K slabs whose operand rows were ordered [x | 
 #ifndef GEMM_BK_DW
 #define GEMM_BK_DW 16   // frames staged per barrier pair in the weight-gradient GEMM (32 measured slower: 61.1 vs 58.3 us)
 #endif
-static const int kNK4Table[] = {1, 2, 4, 7, 8};
-static int pick_nk4(int no) {
-  int need = ((no + 3) / 4 + 3) / 4;
-  for (int v : kNK4Table)
-    if (v >= need) return v;
-  return -1;
+// ---- the register-resident (narrow, nhidden <= 128) recurrence: every instantiation of its kernels is named HERE, once ----
+// The six (NK4, KU) classes of lstm_seq.h: NK4 k-quads per lane, KU the k values per lane actually used -- the padded 4 * NK4 in general,
+// exact for the 97..100-cell case (uw3 BiLSTM(100)).  Every class has the per-line kernels (forward, no-save forward, backward, backward
+// with the x.d prologue); the columns say what a class has beyond them:
+//   FUSED   lstm_fwd_fused_kernel (the fused form needs >= 6 waves, 64 * FWD_CW threads: a polling wave among the first four, consumer
+//           waves behind them, so the classes that reach six waves);
+//   DW      lstm_bwd_dw_kernel (the thread count must cover the GEMM role's 256: the classes that reach four waves);
+//   ROUTED  lstm_fwd_routed_kernel, the per-line twins of the batched-MFMA forward (the classes of its cell counts: 64, 100, 128).
+#define NARROW_CLASSES(X) X(1, 4, 0, 0, 0) X(2, 8, 0, 0, 0) X(4, 16, 0, 1, 1) X(7, 25, 1, 1, 1) X(7, 28, 1, 1, 0) X(8, 32, 1, 1, 1)
+// ... and the geometries (cells; 48 inputs) of the recurrence batched over 16 lines on the MFMA: NOSAVE lstm_fwd_mfma_kernel<.., false>
+// (not the 128-cell one, which spills), BWD lstm_bwd_mfma_rows_kernel / lstm_bwd_mfma_dw_kernel (128 cells: image + operand staging would
+// need 176 KB of LDS); every geometry has the saving forward kernel
+#define MFMA_GEOMS(X) X(64, 1, 1) X(100, 1, 1) X(128, 0, 0)
+struct NarrowClass { int nk4, ku, waves; bool fused, dw, routed; };   // nk4 = 0: no instantiation (the layer is wide); waves = ceil(no / 16)
+static NarrowClass narrow_class(int no) {
+  const int k4 = (no + 3) / 4, waves = (no + 15) / 16;   // the first class whose 4 NK4 k-quads hold the cells' k4, KU exact or padded
+#define ROW_(N, K, F, D, R) if (4 * N >= k4 && (K == 4 * N || K == k4)) return NarrowClass{N, K, waves, F != 0, D != 0, R != 0};
+  NARROW_CLASSES(ROW_)
+#undef ROW_
+  return NarrowClass{0, 0, 1, false, false, false};
+}
+struct MfmaGeomCaps { int no; bool nosave, bwd; };
+static const MfmaGeomCaps* mfma_geom(int no) {
+#define ROW_(NO, NOSAVE, BWD) {NO, NOSAVE != 0, BWD != 0},
+  static const MfmaGeomCaps table[] = {MFMA_GEOMS(ROW_)};
+#undef ROW_
+  for (const auto& g : table)
+    if (g.no == no) return &g;
+  return nullptr;
+}
+// the lookup: f(NarrowNK<NK4, KU>) for the class if it has capability CAP -- a plan (narrow_plan answers from the same lists) cannot
+// name a kernel that is not instantiated, and no kernel is instantiated for a class that has none
+[[noreturn]] static void no_instantiation() { throw Error("internal: the plan names a recurrence kernel that is not instantiated"); }
+template <int N, int K> struct NarrowNK { static constexpr int NK4 = N, KU = K; };
+enum NarrowCap { NCAP_LINE, NCAP_FUSED, NCAP_DW, NCAP_ROUTED };
+template <int CAP, class F>
+static void narrow_dispatch(int nk4, int ku, F&& f) {
+#define CASE_(N, K, FUSED, DW, ROUTED) \
+  if constexpr (CAP == NCAP_LINE || (CAP == NCAP_FUSED && FUSED) || (CAP == NCAP_DW && DW) || (CAP == NCAP_ROUTED && ROUTED)) \
+    if (nk4 == N && ku == K) { f(NarrowNK<N, K>{}); check_launch(); return; }
+  NARROW_CLASSES(CASE_)
+#undef CASE_
+  no_instantiation();
+}
+// ... and of the MFMA geometries: f(integral_constant<int, cells>) where the geometry has the kernel asked for
+enum MfmaCap { MCAP_FWD, MCAP_NOSAVE, MCAP_BWD };
+template <int CAP, class F>
+static void mfma_dispatch(int no, F&& f) {
+#define CASE_(NO, NOSAVE, BWD) \
+  if constexpr (CAP == MCAP_FWD || (CAP == MCAP_NOSAVE && NOSAVE) || (CAP == MCAP_BWD && BWD)) \
+    if (no == NO) { f(std::integral_constant<int, NO>{}); check_launch(); return; }
+  MFMA_GEOMS(CASE_)
+#undef CASE_
+  no_instantiation();
 }
 template <int NK4, int KU, bool SAVE = true>
 static void launch_fwd(const LstmSeqArgs& a, int bs, int nthreads, hipStream_t s) {
@@ -221,48 +269,44 @@ static void launch_fwd_fused(const FwdFusedKernelArgs& k, unsigned nblk, int nth
 #endif
 }
 // save = false: the recurrence role in its no-save form (recognition; lstm_seq.h)
-static bool launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, unsigned nblk, int nthreads, hipStream_t s, bool save = true) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { if (save) launch_fwd_fused<N, K>(k, nblk, nthreads, s); else launch_fwd_fused<N, K, false>(k, nblk, nthreads, s); check_launch(); return true; }
-  CASE_(7, 25) CASE_(7, 28) CASE_(8, 32)    // (the fused form needs >= 5 waves: a polling wave among the first four, a reporting wave behind them)
-#undef CASE_
-  return false;
+static void launch_lstm_fwd_fused(int nk4, int ku, const FwdFusedKernelArgs& k, unsigned nblk, int nthreads, hipStream_t s, bool save = true) {
+  narrow_dispatch<NCAP_FUSED>(nk4, ku, [&](auto c) {
+    constexpr int N = decltype(c)::NK4, K = decltype(c)::KU;
+    if (save) launch_fwd_fused<N, K>(k, nblk, nthreads, s); else launch_fwd_fused<N, K, false>(k, nblk, nthreads, s);
+  });
 }
-// k values per lane actually used: the padded 4*nk4 in general, exact for the 97..100-cell case (uw3 BiLSTM(100))
-static int pick_ku(int no, int nk4) { return (nk4 == 7 && (no + 3) / 4 == 25) ? 25 : 4 * nk4; }
 // save = false (forward only): the recurrence in its no-save form (recognition: only h leaves; lstm_seq.h)
-static void launch_lstm(bool fwd, int nk4, int ku, LstmSeqArgs a, int bs, int nthreads, hipStream_t s, bool save = true) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { \
-    if (!fwd) launch_bwd<N, K>(a, bs, nthreads, s); else if (save) launch_fwd<N, K>(a, bs, nthreads, s); else launch_fwd<N, K, false>(a, bs, nthreads, s); \
-    check_launch(); return; }
-  CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
-#undef CASE_
-  throw Error("unsupported nhidden for the register-resident recurrence");
+static void launch_lstm(bool fwd, int nk4, int ku, const LstmSeqArgs& a, int bs, int nthreads, hipStream_t s, bool save = true) {
+  narrow_dispatch<NCAP_LINE>(nk4, ku, [&](auto c) {
+    constexpr int N = decltype(c)::NK4, K = decltype(c)::KU;
+    if (!fwd) launch_bwd<N, K>(a, bs, nthreads, s); else if (save) launch_fwd<N, K>(a, bs, nthreads, s); else launch_fwd<N, K, false>(a, bs, nthreads, s);
+  });
 }
-
-// the per-line backward recurrence with the softmax layer's x.d as its prologue (lstm_xd_prologue.h); terms as gemm_x3
-static bool launch_lstm_bwd_xd(int nk4, int ku, const LstmSeqArgs& a, const XdArgs& x, int terms, int bs, int nthreads, hipStream_t s) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { \
-    const size_t smem = (2 * 16 * (size_t)lstm_qstride(N) + 4) * sizeof(float); \
-    if (terms >= 3) CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 3>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x); \
-    else CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 2>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x); \
-    check_launch(); return true; }
-  CASE_(1, 4) CASE_(2, 8) CASE_(4, 16) CASE_(7, 28) CASE_(7, 25) CASE_(8, 32)
-#undef CASE_
-  return false;
+// the per-line backward recurrence with the softmax layer's x.d as its prologue (lstm_xd_prologue.h); terms: 3 or 2 (NarrowPlan::terms)
+static void launch_lstm_bwd_xd(int nk4, int ku, const LstmSeqArgs& a, const XdArgs& x, int terms, int bs, int nthreads, hipStream_t s) {
+  narrow_dispatch<NCAP_LINE>(nk4, ku, [&](auto c) {
+    constexpr int N = decltype(c)::NK4, K = decltype(c)::KU;
+    const size_t smem = (2 * 16 * (size_t)lstm_qstride(N) + 4) * sizeof(float);
+    if (terms >= 3) CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 3>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x);
+    else CLSTM_LAUNCH((lstm_bwd_xd_kernel<N, K, 2>), dim3(bs, a.ndir), dim3(nthreads), smem, s, a, x);
+  });
 }
-
-template <int NK4, int KU>
-static void launch_bwd_dw(const LstmSeqArgs& a, const GemmDwArgs& g, int nrec, unsigned ngemm, int nthreads, hipStream_t s) {
-  const size_t smem = (2 * 16 * (size_t)lstm_qstride(NK4) + 4) * sizeof(float);
-  if (g.x3 && g.terms >= 3) CLSTM_LAUNCH((lstm_bwd_dw_kernel<NK4, KU, 3>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
-  else if (g.x3) CLSTM_LAUNCH((lstm_bwd_dw_kernel<NK4, KU, 2>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
-  else CLSTM_LAUNCH((lstm_bwd_dw_kernel<NK4, KU, 0>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
+// recurrence + weight-gradient items as two workgroup roles of one launch (lstm_bwd_dw.h); terms: 3, 2 or 0 = f32 MFMA (NarrowPlan::terms)
+static void launch_lstm_bwd_dw(int nk4, int ku, const LstmSeqArgs& a, const GemmDwArgs& g, int terms, int nrec, unsigned ngemm, int nthreads, hipStream_t s) {
+  narrow_dispatch<NCAP_DW>(nk4, ku, [&](auto c) {
+    constexpr int N = decltype(c)::NK4, K = decltype(c)::KU;
+    const size_t smem = (2 * 16 * (size_t)lstm_qstride(N) + 4) * sizeof(float);
+    if (terms >= 3) CLSTM_LAUNCH((lstm_bwd_dw_kernel<N, K, 3>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
+    else if (terms) CLSTM_LAUNCH((lstm_bwd_dw_kernel<N, K, 2>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
+    else CLSTM_LAUNCH((lstm_bwd_dw_kernel<N, K, 0>), dim3(nrec + ngemm), dim3(nthreads), smem, s, a, g, nrec);
+  });
 }
-static bool launch_lstm_bwd_dw(int nk4, int ku, const LstmSeqArgs& a, const GemmDwArgs& g, int nrec, unsigned ngemm, int nthreads, hipStream_t s) {
-#define CASE_(N, K) if (nk4 == N && ku == K) { launch_bwd_dw<N, K>(a, g, nrec, ngemm, nthreads, s); check_launch(); return true; }
-  CASE_(7, 25) CASE_(7, 28) CASE_(4, 16) CASE_(8, 32)    // (thread count must cover the GEMM role's 256)
-#undef CASE_
-  return false;
+// the chunked weight-gradient items as a launch of their own, behind a recurrence that has marked every line complete (gemm_dw.h)
+static void launch_gemm_dw(const GemmDwArgs& g, int terms, unsigned nblk, hipStream_t s) {
+  if (terms >= 3) CLSTM_LAUNCH(gemm_dw_kernel<3>, dim3(nblk), dim3(256), 0, s, g);
+  else if (terms) CLSTM_LAUNCH(gemm_dw_kernel<2>, dim3(nblk), dim3(256), 0, s, g);
+  else CLSTM_LAUNCH(gemm_dw_kernel<0>, dim3(nblk), dim3(256), 0, s, g);
+  check_launch();
 }
 
 // lock-step recurrence (lstm_wide.h): one persistent launch for the whole sequence when every workgroup
@@ -468,6 +512,121 @@ static void copy_d2h(float* dst, const float* src, size_t n) {
 static int g_debug_fail_claims = 0;      // tests: this many upcoming persistent launches fail their placement check ...
 static int g_debug_fail_skip = 0;        // ... after this many that do not
 
+// ---- the narrow layer (register-resident, nhidden <= 128): WHICH kernels a pass runs, in how many launches, is decided once per layer
+// and pass by narrow_plan, a pure function of a NarrowShape (no device, no global, no environment, no option: Net::narrow_shape reads those
+// into the shape); the passes of net.inc only execute the plan.  clstm_debug_narrow_plan asks narrow_plan without a net: both structs are
+// plain ints in the order documented in include/clstm_abi.h.
+enum NarrowPass { NP_FWD_SAVE = 0, NP_FWD_NOSAVE, NP_BWD };
+enum NarrowFwd { NF_NONE = 0, NF_LINE, NF_FUSED, NF_MFMA };   // one workgroup per line (lstm_seq.h) | the whole forward half as one launch (lstm_fwd_fused.h) | 16 lines per workgroup on the MFMA (lstm_mfma.h)
+enum NarrowBwd {
+  NB_NONE = 0,
+  NB_LINE,           // lstm_bwd_kernel; the weight gradient is a product behind it (family Narrow)
+  NB_LINE_DW,        // (Overlapped) lstm_bwd_kernel, then gemm_dw_kernel: the items find every progress word complete
+  NB_LINE_XD_DW,     // (Overlapped) lstm_bwd_xd_kernel -- the x.d prologue in every workgroup -- then gemm_dw_kernel
+  NB_BWD_DW,         // (Overlapped) ONE launch, lstm_bwd_dw_kernel: the recurrence's workgroups first, the items behind them
+  NB_MFMA,           // lstm_bwd_mfma_rows_kernel alone (family Narrow)
+  NB_MFMA_THEN_DW,   // (Overlapped) lstm_bwd_mfma_rows_kernel (it marks its lines complete), then gemm_dw_kernel
+  NB_MFMA_DW         // (Overlapped) ONE launch, lstm_bwd_mfma_dw_kernel: the batched recurrence and the items
+};
+struct NarrowShape {
+  int pass, no, ni, ndir;                  // NarrowPass; the layer: cells, inputs, directions
+  int nlayers, first, top;                 // layers of the net; this one is the first / the top one
+  int bs, tmax, N, nc;                     // the minibatch: lines, longest line, frames; classes of the softmax layer
+  int ldh, lds, ldx, h_cap, d_cap;         // what the 32-bit offsets must cover: row strides of H, S and the input rows, capacities of H and D (floats)
+  int wk, wk_njp, w1k_kps;                 // the fused forward's operands: Wk packed, its column tiles, the softmax rows' padded k
+  int overlap, bf16_gemm, strict_f32;      // clstm_net_set_overlap / CLSTM_OVERLAP, clstm_net_set_gemm_precision, clstm_net_set_strict_f32
+  int dw_x3, split_terms;                  // options read when the net was created (strict_f32 clears dw_x3)
+  int fwd_mfma, bwd_mfma, bwd_mfma_fused, xd_prologue;   // options read per pass (forward passes: fwd_mfma; backward: the other three)
+  int ncu, emu;                            // CUs of the device; this is the host emulator build
+};
+struct NarrowPlan {
+  int nk4, ku, waves;                      // the class (narrow_class)
+  int fwd, saves;                          // forward passes: NarrowFwd, and whether it runs its saving form (G, C, S written)
+  int overlapped, bwd;                     // backward: the family is Overlapped (the chunked weight-gradient items in or behind the launch), NarrowBwd
+  int terms;                               // ... split-term instantiation of the items and of the x.d prologue: 3, 2, or 0 = f32 MFMA
+  int dwx, xd;                             // top layer: the softmax layer's W.d slabs ride its launch; x.d form 0 a launch of its own, 1 the whole prologue, 2 producers
+  int moves;                               // bit c: the pass moves path counter c
+};
+static const int PROG_LINES = 2048;        // progress words exist for minibatches up to this many lines (Net::PROG_WORDS)
+static NarrowPlan narrow_plan(const NarrowShape& h) {
+  NarrowPlan p{};
+  const NarrowClass k = narrow_class(h.no);
+  p.nk4 = k.nk4; p.ku = k.ku; p.waves = k.waves;
+  const int nthreads = 64 * k.waves, ncu = h.ncu;
+  const MfmaGeomCaps* const mg = mfma_geom(h.no);
+  const double lim = 2147483000.0;   // 32-bit byte offsets inside one descriptor
+  const bool gates32 = (double)h.N * h.ndir * 4 * h.no * 4 < lim;
+  const bool big_enough = h.overlap != 1 || (h.tmax >= 64 && h.N >= 2048);   // overlap = 1: smaller minibatches are too small to profit
+  if (h.pass != NP_BWD) {
+    // ---- THE launch rule of the forward pass: forward_pass (training and recognition) launches by it and reserve_batch sizes the predict
+    // geometry by it -- nothing else decides.  The batched recurrence goes before the fused launch (which only a net of one narrow layer
+    // can take); the strict and forced options act through the two rules.
+    // Chip-filling minibatches: the recurrence batched over 16 lines per workgroup on the MFMA (lstm_mfma.h).  fwd_mfma: 0 never, 1 (default)
+    // from 640 lines per GPU on (measured crossover, profiles/r06_mfma_v3_vs_perline.txt: below that the launch has fewer 16-line workgroups
+    // than the chip has CUs and the per-line kernel wins), 2 always (tests).  clstm_net_set_strict_f32: never by the rule (its products are
+    // f16 split products, not the f32 MFMA's); the forced option wins.  The instantiated (cells, inputs) geometries: MFMA_GEOMS x 48.
+    const bool mfma = !h.emu && h.fwd_mfma && !h.bf16_gemm && !(h.strict_f32 && h.fwd_mfma < 2) && mg && h.ni == 48 && (!h.first || k.routed) &&
+                      gates32 && (double)h.N * h.ldh * 4 < lim && (double)h.N * h.lds * 4 < lim && (double)h.N * h.ldx * 4 < lim &&
+                      (h.fwd_mfma >= 2 || h.bs >= 640);
+    // The forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h).  Six waves (FWD_CW) of which the
+    // last lane owns no cell, at most FWD_JW column tiles per wave, the softmax operand in FWD_CG 16-k groups of registers; H addressed by 32-bit
+    // byte offsets.  The recurrence workgroups (one per CU, dispatched first) wait for producers: CUs must be left for those.
+    const bool fused = !mfma && h.overlap && h.nlayers == 1 && !h.bf16_gemm && h.wk && k.fused && nthreads >= 64 * FWD_CW && h.no % 16 != 0 &&
+                       h.wk_njp <= FWD_JW * FWD_CW && h.w1k_kps <= 16 * FWD_CG && h.nc <= SMX_COLS && h.bs <= PROG_LINES && h.bs < (1 << 18) &&
+                       h.tmax < (1 << 16) && big_enough && (double)h.h_cap * 4.0 < lim && h.bs * h.ndir <= ncu - std::max(8, ncu / 8);
+    p.fwd = mfma ? NF_MFMA : fused ? NF_FUSED : NF_LINE;
+    // ... and whether that family runs its training form -- G, C and S written -- in a pass that asked for save or not: always when asked
+    // to, and where the family has no no-save instantiation for the layer
+    p.saves = h.pass == NP_FWD_SAVE || (mfma && !mg->nosave);
+    p.moves = mfma ? 1 << (p.saves ? PC_MFMA_FWD : PC_MFMA_NOSAVE) : fused ? 1 << (p.saves ? PC_FWD_FUSED : PC_FUSED_NOSAVE) : p.saves ? 0 : 1 << PC_LINE_NOSAVE;
+    return p;
+  }
+  // ---- THE launch rule of the backward pass: the layer loop, the slab count, the weight-gradient step and backward_softmax all read this plan.
+  // Overlapped: recurrence and the chunked weight-gradient GEMM (gemm_dw.h) side by side.  The reporting lane must own no cell; progress words
+  // for up to PROG_LINES lines at the tail of D, addressed by 32-bit byte offsets; by the rule (overlap = 1) only where the one-launch form
+  // with its two workgroup roles exists (lstm_bwd_dw.h: four waves), forced (overlap = 2: tests) everywhere.
+  p.overlapped = !h.bf16_gemm && h.overlap && h.no % 16 != 0 && h.bs <= PROG_LINES && big_enough && (double)h.d_cap * 4.0 < lim &&
+                 (h.overlap == 2 || nthreads >= 256);
+  // bwd_mfma: the batched backward twin (lstm_mfma_bwd.h): 0 never, 1 (default) from 640 lines per GPU on, 2 always (tests).  It gives up the
+  // fused launch (the weight-gradient items then run behind it as a launch of their own).  Crossover with the per-line fused launch, whole
+  // step (profiles/r06_mfma_bwd_leaveout.txt): 512 lines 311.9k vs 327.3k lines/s, 640: 343.6k vs 330.4k, 768: 373.7k vs 355.8k, 896: 403.7k
+  // vs 358.4k.  (strict: R^T.delta from two bf16 terms is not what strict promises; forced: the option wins)
+  const bool mfma = !h.emu && h.bwd_mfma && !h.bf16_gemm && !(h.strict_f32 && h.bwd_mfma < 2) && mg && mg->bwd && gates32 && (h.bwd_mfma >= 2 || h.bs >= 640);
+  p.terms = !h.dw_x3 ? 0 : h.split_terms >= 3 ? 3 : 2;   // (the launch rounds split_terms to one of the two, as gemm_x3 does)
+  // The softmax layer's W.d depends on nothing the backward recurrence produces: when the top layer's backward runs overlapped its slabs are
+  // items of THAT launch (only while the recurrence leaves CUs idle: with 256 lines the same items cost the fused launch +42 us for 19 saved)
+  p.dwx = h.top && h.dw_x3 && p.overlapped && (long long)h.bs * h.ndir * 4 <= 3LL * ncu;
+  // Does the top layer's backward launch compute the softmax layer's x.d itself (lstm_xd_prologue.h)?  All of:
+  //  * dwx -- this pass's condition for the lone x.d launch: top layer Overlapped, dw_x3, bs * ndir * 4 <= 3 * CUs;
+  //  * the per-line recurrence kernel runs it (one launch or, below four waves / on the host emulator, the two-launch form): the batched-MFMA
+  //    backward recurrence keeps the separate launch;
+  //  * the split is two or three bf16 terms (dw_x3 says so);
+  //  * nc <= XD_MAX_K = 96: three k-blocks of W fragments (3 x NT x 4 VGPRs) stay in registers for the whole prologue, and three blocks are
+  //    what the launch it replaces runs for such nc, zero blocks included (bit-identity);
+  //  * experiment option xd_prologue (default 2: the producer form where admitted, else as 1; 1 the whole prologue; 0 the separate launch).
+  // (Every class's smallest workgroup covers a staging round, nthreads * xd_maxu(nk4) >= XD_UNITS: checked once, in Net::build.)
+  // Lines: inherits dwx's bound (bs * ndir <= 192 on 256 CUs); measured 64 / 96 bidirectional lines, EXPERIMENTS 15.
+  // Form 2, the producer form: the recurrence workgroup computes only the 32 frames it visits first, helper items of the same launch the rest.
+  // It needs the one-launch form (below) and recurrence workgroups on at most half of the CUs -- the items are workgroups of its helper role, one
+  // wave per column tile like the recurrence role -- i.e. a CU of its own for every item: an item that shares a CU with a recurrence workgroup takes issue
+  // slots from the latency-bound time loop (96 bidirectional lines, 192 + 192 workgroups on 256 CUs: form 2 measured 5.5 us per step SLOWER
+  // than form 1; 64 lines, 128 + 128: 4.1 us faster -- profiles/ab_xd_producers.txt).  Whatever is eligible for 1 but not for 2 runs 1 unchanged.
+  const bool one_launch = !h.emu && k.dw && nthreads >= 256 && !mfma;   // (the emulator, and layers too narrow for the GEMM role's 256 threads when the tests force the path: two launches)
+  p.xd = !(p.dwx && !mfma && h.nc <= XD_MAX_K && h.xd_prologue != 0) ? 0 : h.xd_prologue >= 2 && one_launch && (long long)h.bs * h.ndir * 2 <= ncu ? 2 : 1;
+  if (!p.overlapped) p.bwd = mfma ? NB_MFMA : NB_LINE;
+  // the batched recurrence and the items as ONE launch pays while the recurrence leaves most CUs idle -- same box, lines/s fused vs separate:
+  // 640 lines 368.1k vs 340.0k, 768: 395.7k vs 374.8k, 896: 398.0k vs 395.1k, 960: 406.6k vs 407.9k, 1024: 414.6k vs 419.0k, 1536: 430.2k vs
+  // 471.2k; option bwd_mfma_fused: 0 never, 1 that rule, 2 always (tests); instantiated for three split terms only
+  else if (mfma) p.bwd = h.bwd_mfma_fused && p.terms == 3 && (h.bwd_mfma_fused >= 2 || h.bs < 900) ? NB_MFMA_DW : NB_MFMA_THEN_DW;
+  else p.bwd = one_launch ? NB_BWD_DW : p.xd ? NB_LINE_XD_DW : NB_LINE_DW;
+  p.moves = (mfma ? 1 << PC_MFMA_BWD : 0) | (p.bwd == NB_MFMA_DW ? 1 << PC_MFMA_BWD_DW : 0) | (p.xd == 2 ? 1 << PC_XD_PRODUCERS : p.xd ? 1 << PC_XD_PROLOGUE : 0);
+  return p;
+}
+static void count_moves(int moves) {
+  for (int c = 0; c < PC_COUNT; c++)
+    if (moves >> c & 1) g_path_count[c]++;
+}
+
 // ---- the lock-step layer (lstm_wide.h): WHICH of its eleven kernels runs is decided once per pass by wide_plan, a pure function of a
 // WideShape (no device, no global, no environment: the caller reads those into the shape -- Net::wide_shape); launch_lstm_wide only
 // executes the plan.  clstm_debug_wide_plan asks wide_plan without a net: both structs are plain ints in the order documented there.
@@ -639,8 +798,7 @@ static void launch_wide_steps(const WidePlan& p, const LstmWideArgs& a, StepGrap
 enum class WideRan { Nothing, Steps, Persistent };
 static WideRan launch_lstm_wide(const WidePlan& p, LstmWideArgs a, XcdSync& sync, StepGraphCache& graphs, hipStream_t s) {
   if (p.kernel != WK_NONE && launch_wide_persistent(p, a, sync, s)) {
-    for (int c = 0; c < PC_COUNT; c++)
-      if (p.moves >> c & 1) g_path_count[c]++;
+    count_moves(p.moves);
     return WideRan::Persistent;
   }
   if (p.step_kernel == WK_NONE) return WideRan::Nothing;

@@ -452,7 +452,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *  25  lines normalised on the device (clstm_normalizer_run_*);
  *  26  backward passes whose top layer's recurrence workgroups computed the softmax layer's input deltas themselves, in front of
  *     their first step (lstm_xd_prologue.h), instead of a product launch of its own (experiment option xd_prologue=0);
- *  27  backward passes that took the producer form of the same instead (the default where Net::xd_mode admits it; xd_prologue=1: never): every recurrence workgroup
+ *  27  backward passes that took the producer form of the same instead (the default where narrow_plan admits it; xd_prologue=1: never): every recurrence workgroup
  *     computed only the 32 frames it visits first, helper workgroups of the launch the rest (26 does not move for them);
  *  28  score launches (clstm_ctc_score_batch / clstm_net_score): one per form a call launched -- the sum form for score_h, the
  *     max-plus form for vscore_h / path_h;
@@ -482,6 +482,21 @@ int clstm_debug_set_device_error(int which, int value);
  *   11 wide_bwd_step16_bf16, 0 none (behind kernel 3 the caller runs the hoisted product and asks again with fx_mode 0); step_grid[3];
  *   moves (bit c: a successful persistent pass moves clstm_debug_path_count(c)); fx_ngx (the folded projection was asked for). */
 int clstm_debug_wide_plan(const int* shape, int* plan);
+/* Which kernels a narrow (register-resident, nhidden <= 128) layer's pass runs, and in which launches (csrc/runtime.inc: narrow_plan, the one
+ * place that decides): host arithmetic, no net, no device.
+ * shape (30 ints, HOST in): pass (0 forward with save, 1 forward without save, 2 backward), no, ni, ndir; nlayers, first, top (this layer is
+ *   the first / the top layer of the net); bs, tmax, N (frames), nc (classes); ldh, lds, ldx (row strides of the output, source and input
+ *   rows), h_cap, d_cap (capacities of the output and delta buffers in floats: the 32-bit offset checks); wk (the fused forward's weights
+ *   are packed), wk_njp, w1k_kps; overlap, bf16_gemm, strict_f32; dw_x3, split_terms (options, read at net creation); fwd_mfma (read by
+ *   forward passes), bwd_mfma, bwd_mfma_fused, xd_prologue (by backward passes); ncu, emu (the host emulator build).
+ * plan (11 ints, HOST out): nk4, ku, waves -- the class (nk4 0: none, the layer is wide); fwd -- forward family: 1 one workgroup per line,
+ *   2 the fused forward launch, 3 batched over 16 lines on the MFMA; saves -- it runs its saving form; overlapped -- the backward family
+ *   has the chunked weight-gradient items in or behind its launch; bwd -- launch form: 1 lstm_bwd_kernel, 2 that followed by
+ *   gemm_dw_kernel, 3 lstm_bwd_xd_kernel (the x.d prologue) followed by gemm_dw_kernel, 4 one lstm_bwd_dw_kernel launch, 5 MFMA rows alone,
+ *   6 MFMA rows followed by gemm_dw_kernel, 7 MFMA rows and items as one launch; terms -- split-term instantiation 3 / 2 / 0 (f32 MFMA);
+ *   dwx -- the softmax layer's W.d slabs ride the launch; xd -- x.d form 0 (a launch of its own) / 1 (whole prologue) / 2 (producers);
+ *   moves (bit c: the pass moves clstm_debug_path_count(c)).  Forward passes leave overlapped .. xd zero, backward passes fwd and saves. */
+int clstm_debug_narrow_plan(const int* shape, int* plan);
 /* Which path of the alignment kernel every line of a minibatch takes (csrc/ctc.h: ctc_batch_plan, ctc_line_plan, ctc_scores_in_lds -- the
  * functions clstm_ctc_align_batch and the kernel's workgroups themselves decide with): host arithmetic, no net, no device.  Arguments as
  * clstm_ctc_align_batch's.  A line's path depends on the other lines of its minibatch through tile and smax.

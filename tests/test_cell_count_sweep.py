@@ -1,10 +1,11 @@
 """Parity sweep over hidden sizes at every edge of the per-line recurrence's instantiations (lstm_seq.h and the launches built on it).
 
-The recurrence is specialised by cell count ((NK4, KU) from runtime.inc:pick_nk4 / pick_ku), by workgroup size (net.inc:Net::build,
+The recurrence is specialised by cell count ((NK4, KU) from runtime.inc:narrow_class), by workgroup size (net.inc:Net::build,
 nthreads = 64 * ceil(no / 16): 1 to 8 waves, workgroups of more than four waves staggered into group A = waves 0..3 and group B = the
 rest, devintrin.h:stag_on) and by launch form (plain, fused forward, overlapped backward as one or two launches, the x.d prologue forms,
-no-save).  geometry() restates the first two ONCE in Python; the predicates below restate the eligibility rules of net.inc, and every
-case asserts the path counters the rule predicts -- which form ran follows from the rule, never from the result.
+no-save).  tests/narrow_rule.py restates the rule (runtime.inc:narrow_plan) ONCE in Python, and every case asserts the path counters the
+rule predicts -- which form ran follows from the rule, never from the result -- and that the library's own plan for its shape
+(clstm_debug_narrow_plan) is the restated one.
 
 Every oracle comparison is test_net_parity.run_case at its default bars (1e-4 / 2e-6 on saved activations, bit-exact decodes, 1e-4 on
 CTC posteriors, deltas, the minibatch gradient and the momentum buffer, the derived bar on the update), weights init x 12, lr 1e-3.
@@ -18,7 +19,6 @@ forms and recognition, with 6 inputs, 9 classes and the first four lengths; the 
 Each test prints `SWEEP <case> class=(NK4, KU, waves) moved=<counters> worst=<largest error / bar> <per quantity>`.
 `python tests/test_cell_count_sweep.py [pytest output of a GPU run]` prints the table of DESIGN.md from geometry() and the rules."""
 import contextlib
-import os
 import re
 import sys
 
@@ -32,9 +32,10 @@ import test_net_parity
 from test_net_parity import run_case, set_opt, _forget_debug_options, _path_count  # noqa: F401  (autouse fixture)
 from test_predict import NOSAVE_FUSED, NOSAVE_LINE, TRAIN_FUSED, check_identity, count, make_net, varied_params
 from test_xd_producers import check_case
+from narrow_rule import assert_net_plans_agree, cus, fused_forward, geometry, klass, narrow, overlapped, xd_form  # noqa: F401
 
 SIZES = [1, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 50, 63, 64, 65, 79, 80, 81, 95, 96, 97, 100, 101, 111, 112, 113, 120, 127, 128]
-WIDE = 129                                  # the smallest size that takes lstm_wide.h by itself (pick_nk4 finds no instantiation)
+WIDE = 129                                  # the smallest size that takes lstm_wide.h by itself (narrow_class finds no instantiation)
 T_ORACLE = [37, 16, 1, 20, 6, 2, 17]
 T_BYTES = [65, 1, 33, 0, 16, 6]
 SCALE, LR = 12.0, 1e-3
@@ -42,59 +43,7 @@ PC_FWD_FUSED, PC_LINE_NOSAVE, PC_FUSED_NOSAVE, PC_XD_PROLOGUE, PC_XD_PRODUCERS =
 COUNTERS = (PC_FWD_FUSED, PC_LINE_NOSAVE, PC_FUSED_NOSAVE, PC_XD_PROLOGUE, PC_XD_PRODUCERS)
 
 
-# ---- 1. the rule, restated once ---------------------------------------------------------------------------------------------------
-def geometry(no):
-    """(nk4, ku, waves, waves in group B, last lane owns a cell) of a layer of `no` cells; nk4 = ku = None where no register-resident
-    instantiation exists (the layer is wide)"""
-    need = ((no + 3) // 4 + 3) // 4                                               # runtime.inc:pick_nk4
-    nk4 = next((v for v in (1, 2, 4, 7, 8) if v >= need), None)                   # runtime.inc:kNK4Table
-    if nk4 is None:
-        return None, None, 1, 0, False                                            # net.inc:Net::build: wide layers launch one wave per workgroup role
-    ku = 25 if nk4 == 7 and (no + 3) // 4 == 25 else 4 * nk4                      # runtime.inc:pick_ku
-    waves = (no + 15) // 16                                                       # net.inc:Net::build, y.nthreads = 64 * ((y.no + 15) / 16)
-    group_b = waves - 4 if nk4 >= 5 else 0                                        # devintrin.h:stag_on, group A = waves 0..3
-    return nk4, ku, waves, group_b, no % 16 == 0
-
-
-def klass(no):
-    return geometry(no)[:3]
-
-
-def cus(kind):
-    """runtime.inc:device_cu_count"""
-    return 256 if kind == "hip" else int(os.environ.get("CLSTM_EMU_CUS", 16))
-
-
-def narrow(no):
-    return geometry(no)[0] is not None
-
-
-def overlapped(no, overlap):
-    """net.inc:overlap_eligible for the small minibatches of this file: only when forced (mode 1 wants tmax >= 64 and 2048 frames)"""
-    return overlap == 2 and narrow(no) and not geometry(no)[4]
-
-
-def fused_forward(nh, uni, nc, nlines, overlap, kind):
-    """net.inc:forward_fused_eligible"""
-    if overlap != 2 or len(nh) != 1 or not narrow(nh[0]):
-        return False
-    no, ndir = nh[0], 1 if uni else 2
-    waves, owns = geometry(no)[2], geometry(no)[4]
-    if waves < 6 or owns or (4 * no + 15) // 16 > 5 * 6 or (ndir * no + 15) // 16 * 16 > 16 * 14 or nc > 96:     # FWD_CW, FWD_JW, FWD_CG, SMX_COLS
-        return False
-    return nlines * ndir <= cus(kind) - max(8, cus(kind) // 8)
-
-
-def xd_form(nh, uni, nc, nlines, overlap, kind, strict=False):
-    """net.inc:xd_mode with the default option (2): 0 the separate launch, 1 the whole prologue (counter 26), 2 the producer form
-    (counter 27).  dwx_active wants the split products (not strict f32) and lines x directions x 4 <= 3 CUs;
-    backward_layer_overlapped launches one kernel -- what form 2 needs -- for four or more waves on a real GPU."""
-    ndir = 1 if uni else 2
-    if strict or not overlapped(nh[-1], overlap) or nlines * ndir * 4 > 3 * cus(kind) or nc > 96:
-        return 0
-    return 2 if kind == "hip" and geometry(nh[-1])[2] >= 4 and nlines * ndir * 2 <= cus(kind) else 1
-
-
+# ---- 1. the rule: tests/narrow_rule.py ---------------------------------------------------------------------------------------------
 def expected_training(nh, uni, nc, nlines, overlap, kind, strict=False):
     """({counter: moves} of one forward + backward, overlapped backward passes)"""
     moves = {}
@@ -176,6 +125,8 @@ def oracle_case(backend, ora32, name, nh, uni=False, overlap=None, strict=False,
     if split_terms is not None:
         set_opt(backend, "split_terms", split_terms)          # (read when the net is created)
     want_moves, want_passes = expected_training(nh, uni, nc, len(T), overlap, backend.kind, strict)
+    assert_net_plans_agree(backend.lib, nh, ni=ni, uni=uni, nc=nc, nlines=len(T), tmax=max(T), frames=sum(T), overlap=overlap, strict=strict,
+                           kind=backend.kind, split_terms=3 if split_terms is None else split_terms)
     before = {c: _path_count(backend, c) for c in COUNTERS}
     net, moved, passes, timeouts = None, None, -1, -1
     with recording() as worst:
@@ -214,7 +165,7 @@ def test_default_rule_bidirectional(backend, ora32, no):
 @pytest.mark.parametrize("backend,no", both(SIZES + [WIDE], LOWEST), indirect=["backend"], ids=ids)
 def test_overlap_forced_bidirectional(backend, ora32, no):
     """overlap = 2: the fused forward (81..111 cells) and the overlapped backward -- one launch from four waves on, two below, none
-    where the last lane owns a cell -- with the x.d prologue in the form xd_mode picks; no wait ran into its watchdog"""
+    where the last lane owns a cell -- with the x.d prologue in the form narrow_plan picks; no wait ran into its watchdog"""
     oracle_case(backend, ora32, "overlap2 bidi %d" % no, [no], overlap=2)
 
 

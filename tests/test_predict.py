@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from common import ATOL, RTOL, assert_close, synth_lines
+from narrow_rule import fused_forward
 
 NOSAVE_LINE, NOSAVE_FUSED, NOSAVE_MFMA = 22, 23, 15      # clstm_debug_path_count (include/clstm_abi.h)
 TRAIN_FUSED, TRAIN_MFMA, ROUTED = 5, 16, 21
@@ -177,6 +178,7 @@ def test_predict_fused_forced_small(backend):
     ni, nh, nc = 48, [100], 83
     rng = np.random.default_rng(12)
     lines = synth_lines(rng, [21, 3, 37, 16], ni)
+    assert fused_forward(nh, False, nc, len(lines), 2, backend.kind)      # (the rule admits it: tests/narrow_rule.py)
     net = make_net(backend, ni, nh, nc, varied_params(backend, ni, nh, nc, lines), overlap=2)
     c0 = count(backend, TRAIN_FUSED)
     check_identity(backend, net, lines, NOSAVE_FUSED)
@@ -191,6 +193,7 @@ def test_predict_fused_64x200_gpu():
     ni, nh, nc = 48, [100], 83
     rng = np.random.default_rng(13)
     lines = synth_lines(rng, [200] * 64, ni)
+    assert fused_forward(nh, False, nc, 64, None, "hip", tmax=200)        # (by the default rule, overlap = 1: tests/narrow_rule.py)
     net = make_net(backend, ni, nh, nc, varied_params(backend, ni, nh, nc, lines))
     c0 = count(backend, TRAIN_FUSED)
     check_identity(backend, net, lines, NOSAVE_FUSED)

@@ -7,7 +7,7 @@ compared AS BYTES across xd_prologue = 0 (the product launch), 1 (the whole prol
 direction, the fresh gradient, parameters and momentum buffer after each of two consecutive steps of the SAME net with a fresh
 minibatch per step -- ready words left by the first pass must not satisfy the second.
 
-Which form runs follows from the launch rule (Net::xd_mode, net.inc), not from the result:
+Which form runs follows from the launch rule (runtime.inc:narrow_plan, restated in tests/narrow_rule.py), not from the result:
   * form 2 needs form 1's eligibility (test_xd_prologue.py) AND the one-launch form of the overlapped pass -- a real GPU and a layer
     of four or more waves -- AND a CU for every item: lines x directions x 2 <= CUs.  There counter 27 moves by one per step and
     counter 26 stays put;
@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from common import bits, synth_lines
+from narrow_rule import xd_form
 from test_net_parity import set_opt, _forget_debug_options, _path_count  # noqa: F401  (autouse fixture)
 
 DELTAS = ("d_gi", "d_gf", "d_go", "d_ci")
@@ -40,7 +41,7 @@ CASES = {
     # below four waves: the two-launch form of the overlapped pass, which keeps the whole prologue
     "bilstm9_nc5_two_launch_form": (6, [9], 5, [70, 13, 40], False, True, False),
 }
-# (far above what the emulator's 16 CUs admit: GPU only)  192 recurrence workgroups: the bound of dwx_active on 256 CUs -- eligible for
+# (far above what the emulator's 16 CUs admit: GPU only)  192 recurrence workgroups: the bound of NarrowPlan::dwx on 256 CUs -- eligible for
 # form 1, but form 2 wants a CU of its own for every dH item, i.e. recurrence workgroups on at most half of the MI355X's 256 CUs;
 # 128 recurrence workgroups: that bound
 CUS = 256
@@ -103,6 +104,8 @@ def expected_moves(backend, case):
     eligible, four_waves = case[5], case[6]
     nrec = len(case[3]) * (1 if case[4] else 2)
     producers = eligible and four_waves and backend.kind == "hip" and 2 * nrec <= CUS
+    form = xd_form(case[1], case[4], case[2], len(case[3]), 2, backend.kind, ni=case[0], tmax=max(case[3]), frames=sum(case[3]))
+    assert (form != 0, form == 2) == (eligible, producers), (form, eligible, producers)      # (the case table agrees with the restated rule)
     one = (1, 0) if eligible else (0, 0)
     return (0, 0), one, ((0, 1) if producers else one)
 

@@ -3,7 +3,7 @@ their first step (clstm_amd/csrc/lstm_xd_prologue.h, experiment option xd_prolog
 it replaces (xd_prologue=0): the prologue restates that launch's arithmetic expression for expression, so everything downstream
 of dH is compared AS BYTES -- the gate deltas of every layer and direction, the fresh gradient, the parameters and the momentum
 buffer after each of two consecutive steps (a fresh minibatch per step: the first step's dH cannot satisfy the second), the input
-deltas where enabled.  Counter 26 moves by one per step exactly where Net::xd_in_launch (net.inc) says the case is eligible.
+deltas where enabled.  Counter 26 moves by one per step exactly where NarrowPlan::xd (runtime.inc:narrow_plan) says the case is eligible.
 
 Every net runs with overlap mode 2: these line counts are far below what mode 1 overlaps, and the prologue belongs to the
 overlapped backward launch.  Which cases are eligible follows from the launch rule, not from the result:
