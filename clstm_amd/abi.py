@@ -63,6 +63,9 @@ _SIGS = {
     "clstm_ctc_align_batch": [_P, _P, _P, _I, _P, _P, _P, _I],
     "clstm_ctc_score_batch": [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P],
     "clstm_ctc_beam_batch": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    "clstm_charlm_create": [_P, _I, _I, _P, _P],
+    "clstm_charlm_destroy": [_P],
+    "clstm_ctc_beam_lm_batch": [_P, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
     "clstm_mktargets": [_P, _P, _I],
     "clstm_trivial_decode_batch": [_P, _I, _P, _I, _P, _P, _P],
     "clstm_net_nparams_for": [_P],
@@ -89,6 +92,7 @@ _SIGS = {
     "clstm_net_ctc": [_P, _P, _P, _P],
     "clstm_net_score": [_P, _P, _P, _P, _I, _P, _P, _P],
     "clstm_net_beam": [_P, _I, _I, _P, _P, _P, _P],
+    "clstm_net_beam_lm": [_P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
     "clstm_net_backward": [_P],
     "clstm_net_enable_input_deltas": [_P, _I],
     "clstm_net_get_input_deltas_h": [_P, _P],

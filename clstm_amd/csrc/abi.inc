@@ -23,6 +23,7 @@ struct clstm_net {
   REQUIRE(h, "null argument"); \
   REQUIRE_CURRENT(h); \
   REQUIRE((h)->net.N > 0, "set_batch first")
+struct clstm_charlm { CharLm lm; };
 struct clstm_normalizer {
   std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
   Normalizer nz;
@@ -161,6 +162,37 @@ int clstm_ctc_beam_batch(const float* probs, int nc, const int* line_off_h, int 
   run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
   ABI_END
 }
+int clstm_charlm_create(clstm_charlm** out, int order, int nc, const float* table_h, const float* end_h) {
+  ABI_BEGIN
+  REQUIRE(out && table_h, "null argument");
+  REQUIRE(order == 2 || order == 3, "clstm_charlm_create: order must be 2 or 3");
+  REQUIRE(nc >= 2, "clstm_charlm_create: the class count must be at least 2");
+  long long nctx = 1;
+  for (int k = 1; k < order; k++) nctx *= nc;   // (nc < 2^31: no overflow for order <= 3)
+  REQUIRE(nctx * nc <= (1ll << 26), "clstm_charlm_create: the table exceeds 2^26 floats");
+  for (long long i = 0; i < nctx * nc; i++) REQUIRE(std::isfinite(table_h[i]), "clstm_charlm_create: a table entry is not finite");
+  for (long long i = 0; end_h && i < nctx; i++) REQUIRE(std::isfinite(end_h[i]), "clstm_charlm_create: an end table entry is not finite");
+  std::unique_ptr<clstm_charlm> h(new clstm_charlm());
+  h->lm.order = order; h->lm.nc = nc; h->lm.nctx = nctx; h->lm.has_end = end_h != nullptr;
+  h->lm.table.reserve((size_t)(nctx * nc));
+  copy_h2d(h->lm.table.p, table_h, (size_t)(nctx * nc));
+  if (end_h) {
+    h->lm.end.reserve((size_t)nctx);
+    copy_h2d(h->lm.end.p, end_h, (size_t)nctx);
+  }
+  *out = h.release();
+  ABI_END
+}
+int clstm_charlm_destroy(clstm_charlm* lm) { ABI_BEGIN delete lm; ABI_END }
+int clstm_ctc_beam_lm_batch(const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest, const clstm_charlm* lm,
+                            float weight, float bonus, int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h) {
+  ABI_BEGIN
+  REQUIRE(lm, "clstm_ctc_beam_lm: the language model is required");
+  if (!g_beam_ws) g_beam_ws = new BeamWorkspace();
+  const BeamLm with{&lm->lm, weight, bonus, am_score_h};
+  run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
+  ABI_END
+}
 int clstm_trivial_decode_batch(const float* probs, int nc, const int* line_off_h, int bs, int* classes_h,
                                int* locs_h, int* counts_h) {
   ABI_BEGIN
@@ -274,6 +306,21 @@ int clstm_net_beam(clstm_net* h, int beam, int nbest, int* nhyp_h, int* len_h, f
   n.timing.begin("ctc_beam", g_stream);
   struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
+  ABI_END
+}
+int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm, float weight, float bonus, int* nhyp_h, int* len_h,
+                      float* score_h, float* am_score_h, int* labels_h) {
+  ABI_BEGIN
+  REQUIRE_OUTPUTS(h);
+  Net& n = h->net;
+  REQUIRE(lm, "clstm_net_beam_lm: the language model is required");
+  REQUIRE(nhyp_h && score_h, "clstm_net_beam_lm: nhyp_h and score_h are required");
+  REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam_lm: 1 <= nbest <= beam <= 32");
+  RoctxRange range_("clstm:beam_lm");
+  n.timing.begin("ctc_beam_lm", g_stream);
+  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  const BeamLm with{&lm->lm, weight, bonus, am_score_h};
+  run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
 }
 int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.backward(); ABI_END }

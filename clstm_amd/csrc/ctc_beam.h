@@ -31,6 +31,30 @@
 // node ids within the beam.  Table, nodes, the per-frame class lists and the line's lp each lie in LDS when the line's fit (the host
 // decides per line, BeamLine::in_lds) and in the workspace otherwise; the code is the same, only slower.  The trie is touched by
 // wave 0 alone: look-ups one entry per lane, the few insertions one lane at a time.
+//
+// ---- with a character n-gram language model (ctc_beam_kernel<.., true>: clstm_ctc_beam_lm_batch / clstm_net_beam_lm) ----
+// The model is a dense f32 table lm[ctx][c] of order 2 or 3: nc^(order-1) rows of nc columns, labels 1 .. nc-1, 0 = "no label yet".
+// Order 2: ctx = the last label (0 for the empty prefix); order 3: ctx = nc (the label before last, or 0) + the last label.
+// Column 0 (blank) is never read.  An end table end[ctx] is optional.  Entries are finite (checked at creation), not necessarily
+// normalised.  The LM value of a prefix: lm(()) = 0, lm(l + c) = lm(l) + (weight lm[ctx(l)][c] + bonus), f32 in exactly that
+// association (beam_lm_term: the product rounded, then the sum), weight >= 0.  It depends on the prefix alone, so it is stored once per
+// trie node when the node is made (nlm, nctx beside parent / label / depth); a prefix that leaves the beam and is extended again
+// finds its node and with it the same value.  A stay adds nothing; the second a of "a a" (through a blank) is an extension and adds
+// its term.
+//   (lb, lnb), stay, merge, extend and tot are the expressions above, unchanged.  Only selection changes: the key of a candidate is
+// (logadd(lb', lnb') + lm(its prefix), ~index) -- -inf stays -inf and is never kept --, index and total order as above.  The key no
+// longer carries a candidate's acoustic value: a kept stay takes tot from stay_tot, a kept extension recomputes lp[c] + (c == e ?
+// lb_i : tot_i), the same expression on the same operands.  After the last frame the live entries are ranked by
+// (tot + lm(l)) + weight end[ctx(l)] (the last term with an end table only), key (that total, ~entry position), and the first nbest
+// leave with two scores: that total, and the acoustic tot -- the log-probability the beam gathered, what the search without a model
+// reports.
+//   The class list is lossless by being complete: with a model every entry has its own order of extensions, so K = nc - 1 and every
+// class is a candidate of every entry, beam (nc - 1) <= BEAM_LM_CANDS extension keys per frame (the host refuses more).  The
+// prologue still sorts a frame's classes by lp: the order decides nothing, it only puts the acoustically likely candidates in front
+// of the key list, where the first counting pass finds them.  That list (2 T (nc - 1) words) always lies in the workspace -- it is
+// read one frame ahead into the small LDS tile --, so ALL_LDS here means the other three sections.  Each entry gets ctx and lm from
+// its node when phase C names the node, so phase A reads them from LDS; the table itself lies in global memory (one read per
+// candidate, rows of one context contiguous).
 #pragma once
 #include "devintrin.h"
 #include <math.h>
@@ -39,6 +63,7 @@ namespace clstm {
 
 constexpr int BEAM_THREADS = 256;
 constexpr int BEAM_MAX = 32;
+constexpr int BEAM_LM_CANDS = 4096;         // with a language model: beam (nc - 1), the extension keys of a frame, at most
 constexpr int BEAM_LDS_WORDS = 36 * 1024;   // of the 40 K words (160 KB) of a CU: fixed part + the sections of a line that fit
 enum BeamSection { BS_HASH = 0, BS_NODES, BS_CLS, BS_LP, BS_COUNT };
 
@@ -53,11 +78,18 @@ struct BeamArgs {
   float* score;        // [bs nbest]
   int* labels;         // [nbest N], or null
   int nc, beam, nbest, K, bs, N;
+  // language model form only
+  const float* table;  // [nc^(order-1)][nc]
+  const float* end;    // [nc^(order-1)], or null
+  float* am_score;     // [bs nbest], or null
+  float weight, bonus;
+  int order;
 };
 // fixed LDS words in front of the sections
-struct BeamLds { int ent, stay, misc, ft, keys, surv, sections; };
+struct BeamLds { int ent, stay, misc, ft, keys, surv, lm, sections; };
 constexpr int BEAM_ENT_FIELDS = 7;   // node, last, lb, lnb, tot, ppos, pnode / written flag
-inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K) {
+constexpr int BEAM_LM_WORDS = 5 * BEAM_MAX;   // language model form: ctx and lm of the entries, double-buffered, and the stays' tot
+inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K, bool lm = false) {
   BeamLds l;
   int o = 0;
   l.keys = o; o += 2 * (beam + beam * K);       // 64-bit keys first: 8-byte aligned
@@ -66,6 +98,7 @@ inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K) {
   l.stay = o; o += 2 * BEAM_MAX;
   l.ft = o;   o += 2 * (2 * K + 2);             // the next frame's class list, their lp and lp[0], double-buffered
   l.misc = o; o += 4;
+  l.lm = o;   o += lm ? BEAM_LM_WORDS : 0;
   o += o & 1;
   l.sections = o;
   return l;
@@ -87,6 +120,14 @@ DEVFN unsigned long long beam_key(float s, unsigned index) {
   const unsigned o = beam_ord(s);
   return o <= 0x007FFFFFu ? 0ull : (((unsigned long long)o << 32) | (unsigned)~index);   // -inf (and below): never kept
 }
+// weight x + bonus with the product rounded before the sum (no fused multiply-add: the referee's two roundings)
+DEVFN float beam_lm_term(float weight, float x, float bonus) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const float p = weight * x;
+  return p + bonus;
+}
 DEVFN unsigned beam_hash(int parent, int label) {
   unsigned h = (unsigned)parent * 0x9E3779B1u ^ ((unsigned)label * 0x85EBCA6Bu + 0x7F4A7C15u);
   h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 13;
@@ -106,14 +147,16 @@ DEVFN BeamEnt beam_ent(float* base, int side) {
 
 // ALL_LDS: every section of every line of the launch lies in LDS (the OCR shapes): the section pointers are LDS addresses the
 // compiler can see, not a choice between two address spaces that only flat instructions can follow.  The arithmetic is the same.
-template <bool ALL_LDS>
+// LM: the language model form (the header's second part); without it the kernel is the plain search, instruction for instruction.
+template <bool ALL_LDS, bool LM = false>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   float* lds = dyn_smem<float>();
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const BeamLine ln = a.lines[blockIdx.x];
   const int T = ln.T, nc = a.nc, beam = a.beam, K = a.K;
-  const BeamLds L = beam_lds_layout(beam, K);
+  const BeamLds L = beam_lds_layout(beam, K, LM);
   auto section = [&](int s) -> int* {
+    if (LM && s == BS_CLS) return a.ws + ln.off[s];   // (the complete class list: always in the workspace)
     if constexpr (ALL_LDS) return reinterpret_cast<int*>(lds + L.sections) + (int)ln.off[s];
     else return (ln.in_lds >> s & 1) ? reinterpret_cast<int*>(lds + L.sections) + ln.off[s] : a.ws + ln.off[s];
   };
@@ -121,6 +164,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   int* const npar = section(BS_NODES);
   int* const nlab = npar + ln.nnmax;
   int* const ndep = nlab + ln.nnmax;
+  int* const nlm = ndep + ln.nnmax;                          // (LM: the prefix's LM value as float bits, then its context)
+  int* const nctx = nlm + ln.nnmax;
+  int* const ent_ctx = reinterpret_cast<int*>(lds + L.lm);   // (LM) [side][BEAM_MAX]
+  float* const ent_lm = lds + L.lm + 2 * BEAM_MAX;           // (LM) [side][BEAM_MAX]
+  float* const stay_tot = lds + L.lm + 4 * BEAM_MAX;         // (LM)
   int* const ccls = section(BS_CLS);                         // [T][K] classes, then [T][K] their lp
   float* const clp = reinterpret_cast<float*>(ccls) + (size_t)T * K;
   float* const lp = reinterpret_cast<float*>(section(BS_LP));   // [T][nc]
@@ -142,6 +190,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     misc[0] = 1; misc[1] = 1; misc[2] = 0;
     const BeamEnt e = beam_ent(lds + L.ent, 0);
     e.node[0] = 0; e.last[0] = 0; e.lb[0] = 0.0f; e.lnb[0] = beam_neg_inf(); e.tot[0] = 0.0f; e.ppos[0] = -1;
+    if constexpr (LM) { nlm[0] = 0; nctx[0] = 0; ent_ctx[0] = 0; ent_lm[0] = 0.0f; }
   }
   drain_vmem();   // (sections in the workspace: written here, read by other waves -- the trie with system-scope loads)
   __syncthreads();
@@ -172,7 +221,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     if (j < K) { ft[j] = __builtin_bit_cast(float, ccls[(size_t)t * K + j]); ft[K + j] = clp[(size_t)t * K + j]; }
     else if (j == K) ft[2 * K] = lp[(size_t)t * nc];
   };
-  if (tid <= K) stage_frame(0, tid);
+  if constexpr (LM) { for (int j = tid; j <= K; j += BEAM_THREADS) stage_frame(0, j); }   // (K = nc - 1: more than one round)
+  else if (tid <= K) stage_frame(0, tid);
   __syncthreads();
 
   int n = 1;   // live entries (workgroup-uniform)
@@ -181,6 +231,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     const float* ft = lds + L.ft + (t & 1) * ftw;
     const float* row = lp + (size_t)t * nc;
     const int next = n * K, ncand = beam + next;
+    const int* const cctx = ent_ctx + (t & 1) * BEAM_MAX;   // (LM) the current entries' context and LM value
+    const float* const clm = ent_lm + (t & 1) * BEAM_MAX;
     // ---- A: the candidates' keys; stay i -> keys[i], extension (i, class of rank r) -> keys[beam + r n + i] ----
     if (tid < beam) {
       unsigned long long key = 0ull;
@@ -194,7 +246,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
           if (j >= 0) lnbn = beam_logadd(lnbn, le + (cur.last[j] == e ? cur.lb[j] : cur.tot[j]));
         }
         stay_lb[i] = lbn; stay_lnb[i] = lnbn;
-        key = beam_key(beam_logadd(lbn, lnbn), (unsigned)i);
+        const float totn = beam_logadd(lbn, lnbn);
+        if constexpr (LM) { stay_tot[i] = totn; key = beam_key(totn + clm[i], (unsigned)i); }
+        else key = beam_key(totn, (unsigned)i);
       }
       keys[tid] = key;
       nxt.aux[tid] = 0;
@@ -206,7 +260,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
       bool skip = false;
 #pragma unroll 8
       for (int k = 0; k < n; k++) skip |= (cur.ppos[k] == i) & (cur.last[k] == c);   // (no short circuit: independent reads)
-      keys[beam + m] = skip ? 0ull : beam_key(v, (unsigned)(beam + i * nc + c));
+      float s = v;
+      if constexpr (LM) s = v + (clm[i] + beam_lm_term(a.weight, a.table[(size_t)cctx[i] * nc + c], a.bonus));
+      keys[beam + m] = skip ? 0ull : beam_key(s, (unsigned)(beam + i * nc + c));
     }
     __syncthreads();
     // ---- B: rank by counting.  First against the front of the list; who may still be in goes to the survivors ----
@@ -244,18 +300,22 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
         const int i = index;
         nxt.node[rank] = cur.node[i]; nxt.last[rank] = cur.last[i];
         nxt.lb[rank] = stay_lb[i]; nxt.lnb[rank] = stay_lnb[i];
-        nxt.tot[rank] = v;
+        if constexpr (LM) nxt.tot[rank] = stay_tot[i];
+        else nxt.tot[rank] = v;
         nxt.aux[rank] = 1;
       } else {
         const int i = (index - beam) / nc, c = (index - beam) - i * nc;
         nxt.node[rank] = -1; nxt.last[rank] = c;
-        nxt.lb[rank] = beam_neg_inf(); nxt.lnb[rank] = v; nxt.tot[rank] = v;
+        float va = v;
+        if constexpr (LM) va = row[c] + (c == cur.last[i] ? cur.lb[i] : cur.tot[i]);   // (the key holds va + lm: the acoustic value again)
+        nxt.lb[rank] = beam_neg_inf(); nxt.lnb[rank] = va; nxt.tot[rank] = va;
         nxt.aux[rank] = 2 + cur.node[i];   // the parent's node
       }
     }
     __syncthreads();
     // ---- C: wave 0 names the new entries' nodes; the other waves stage the next frame's class list ----
-    if (tid >= 64 && t + 1 < T && tid - 64 <= K) stage_frame(t + 1, tid - 64);
+    if constexpr (LM) { if (tid >= 64 && t + 1 < T) for (int j = tid - 64; j <= K; j += BEAM_THREADS - 64) stage_frame(t + 1, j); }
+    else if (tid >= 64 && t + 1 < T && tid - 64 <= K) stage_frame(t + 1, tid - 64);
     if (wave == 0) {
       const int w = lane < beam ? lane : 0;
       const int aux = lane < beam ? nxt.aux[w] : 0;
@@ -282,12 +342,25 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
           nd = misc[0];
           misc[0] = nd + 1;
           store_i32_wt(npar + nd, pn); store_i32_wt(nlab + nd, c); store_i32_wt(ndep + nd, load_i32_wt(ndep + pn) + 1);
+          if constexpr (LM) {   // the prefix's LM value and context, once
+            const int pctx = load_i32_wt(nctx + pn);
+            const float plm = __builtin_bit_cast(float, load_i32_wt(nlm + pn));
+            const float lmv = plm + beam_lm_term(a.weight, a.table[(size_t)pctx * nc + c], a.bonus);
+            store_i32_wt(nlm + nd, __builtin_bit_cast(int, lmv));
+            store_i32_wt(nctx + nd, a.order == 3 ? nc * load_i32_wt(nlab + pn) + c : c);
+          }
           store_i32_wt(tab + slot, nd);
         }
         drain_vmem();
         wave_lds_fence();
       }
       if (lane < nn) nxt.node[lane] = nd;
+      if constexpr (LM) {
+        if (lane < nn) {
+          ent_ctx[((t + 1) & 1) * BEAM_MAX + lane] = load_i32_wt(nctx + nd);
+          ent_lm[((t + 1) & 1) * BEAM_MAX + lane] = __builtin_bit_cast(float, load_i32_wt(nlm + nd));
+        }
+      }
       wave_lds_fence();
       if (lane < nn) {
         const int par = nd == 0 ? -1 : load_i32_wt(npar + nd);
@@ -305,15 +378,43 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   const BeamEnt fin = beam_ent(lds + L.ent, T & 1);
   const int nh = n < a.nbest ? n : a.nbest;
   if (tid == 0) a.nhyp[ln.line] = nh;
+  if constexpr (LM) {   // the live entries ranked by their total; entry ent_ctx[r] of the beam leaves as hypothesis r
+    const float* const flm = ent_lm + (T & 1) * BEAM_MAX;
+    int* const fctx = ent_ctx + (T & 1) * BEAM_MAX;
+    unsigned long long key = 0ull;
+    if (tid < n) {
+      float total = fin.tot[tid] + flm[tid];
+      if (a.end) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+        const float e = a.weight * a.end[fctx[tid]];
+        total = total + e;
+      }
+      stay_tot[tid] = total;
+      key = ((unsigned long long)beam_ord(total) << 32) | (unsigned)~(unsigned)tid;
+      keys[tid] = key;
+    }
+    __syncthreads();
+    if (tid < n) {
+      int rank = 0;
+      for (int q = 0; q < n; q++) rank += keys[q] > key ? 1 : 0;
+      fctx[rank] = tid;
+    }
+    __syncthreads();
+  }
   if (tid < a.nbest) {
     const int k = tid, slot = ln.line * a.nbest + k;
     int len = 0;
-    float sc = beam_neg_inf();
+    float sc = beam_neg_inf(), am = beam_neg_inf();
     if (k < nh) {
-      int nd = fin.node[k];
+      int src = k;
+      if constexpr (LM) src = ent_ctx[(T & 1) * BEAM_MAX + k];
+      int nd = fin.node[src];
       len = load_i32_wt(ndep + nd);
       len = len > T ? T : len;
-      sc = fin.tot[k];
+      sc = fin.tot[src];
+      if constexpr (LM) { am = sc; sc = stay_tot[src]; }
       if (a.labels) {
         int* out = a.labels + (size_t)a.nbest * ln.row + (size_t)k * T;
         for (int d = len - 1; d >= 0 && nd > 0; d--) {
@@ -324,6 +425,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     }
     if (a.len) a.len[slot] = len;
     a.score[slot] = sc;
+    if constexpr (LM) { if (a.am_score) a.am_score[slot] = am; }
   }
 }
 

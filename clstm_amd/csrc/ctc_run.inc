@@ -271,7 +271,7 @@ static void plan_ctc_score(ScorePlan& pl, int nc, const int* line_off_h, int bs,
 #ifndef CLSTM_HIP_EMU
 // the dynamic-LDS ceiling of a kernel is a property of the function ON A DEVICE: remembered per device, per calling thread
 static void score_allow_smem(const void* kernel, int which, size_t smem) {
-  static thread_local std::map<int, size_t> allowed[4];   // score sum, score max-plus, beam (all in LDS), beam
+  static thread_local std::map<int, size_t> allowed[6];   // score sum, score max-plus, beam (all in LDS), beam, the two with a language model
   int dev = 0;
   HIPCHECK(hipGetDevice(&dev));
   size_t& have = allowed[which][dev];
@@ -350,6 +350,7 @@ struct BeamWorkspace {
   DevBuf<char> meta;
   DevBuf<int> ws;
   DevBuf<int> out;            // [nhyp bs | len bs nbest | score bs nbest (float bits) | labels nbest N]: ONE copy brings the results back
+                              // (with a language model: [nhyp | len | score | am_score bs nbest | labels])
   PinnedBuf<int> host;
 };
 // what the launch will be, from the arguments alone; every section of a line goes to LDS while the line's sections still fit
@@ -359,14 +360,24 @@ struct BeamPlan {
   int K = 1, lds_words = 0;
   bool all_lds = true;        // every section of every line in LDS: ctc_beam_kernel<true>
 };
-static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, int beam, int nbest) {
+// a character n-gram model on the device (ctc_beam.h, second part): the table is checked and uploaded once, at creation
+struct CharLm {
+  int order = 0, nc = 0;
+  long long nctx = 0;
+  bool has_end = false;
+  DevBuf<float> table, end;
+};
+// what a language model call brings beside the plain search's arguments
+struct BeamLm { const CharLm* lm; float weight, bonus; float* am_score_h; };
+static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, int beam, int nbest, bool lm = false) {
   REQUIRE(bs > 0 && line_off_h, "empty batch / null argument");
   REQUIRE(nc >= 2 && nc < (1 << 26), "clstm_ctc_beam: the class count must lie in [2, 2^26)");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX, "clstm_ctc_beam: beam must lie in [1, 32]");
   REQUIRE(nbest >= 1 && nbest <= beam, "clstm_ctc_beam: nbest must lie in [1, beam]");
   REQUIRE(line_off_h[0] >= 0, "bad offsets");
-  pl.K = beam_classes(nc, beam);
-  const BeamLds L = beam_lds_layout(beam, pl.K);
+  if (lm) REQUIRE((long long)beam * (nc - 1) <= BEAM_LM_CANDS, "clstm_ctc_beam_lm: beam * (nc - 1) exceeds 4096 (every class is a candidate of every entry)");
+  pl.K = lm ? nc - 1 : beam_classes(nc, beam);
+  const BeamLds L = beam_lds_layout(beam, pl.K, lm);
   const long long room = BEAM_LDS_WORDS - L.sections;
   for (int b = 0; b < bs; b++) {
     const long long T = (long long)line_off_h[b + 1] - line_off_h[b];
@@ -376,16 +387,16 @@ static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, i
     const long long nn = 1 + T * beam;
     long long H = 64;
     while (H < 2 * nn) H *= 2;
-    const long long need[BS_COUNT] = {H, 3 * nn, 2 * T * pl.K, T * nc};
+    const long long need[BS_COUNT] = {H, (lm ? 5 : 3) * nn, 2 * T * pl.K, T * nc};
     BeamLine ln{};
     ln.row = line_off_h[b]; ln.T = (int)T; ln.line = b; ln.hmask = (int)(H - 1); ln.nnmax = (int)nn;
     long long used = 0;
     for (int s = 0; s < BS_COUNT; s++) {
-      if (used + need[s] <= room) { ln.in_lds |= 1 << s; ln.off[s] = used; used += need[s]; }
+      if (used + need[s] <= room && !(lm && s == BS_CLS)) { ln.in_lds |= 1 << s; ln.off[s] = used; used += need[s]; }
       else { ln.off[s] = pl.ws_words; pl.ws_words += need[s]; }
     }
     pl.lds_words = std::max(pl.lds_words, (int)used);
-    pl.all_lds = pl.all_lds && ln.in_lds == (1 << BS_COUNT) - 1;
+    pl.all_lds = pl.all_lds && (ln.in_lds | (lm ? 1 << BS_CLS : 0)) == (1 << BS_COUNT) - 1;
     pl.lines.push_back(ln);
   }
   REQUIRE(pl.ws_words < (1ll << 40), "clstm_ctc_beam: workspace too large");
@@ -393,14 +404,24 @@ static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, i
   pl.lds_words += L.sections;
 }
 static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest,
-                         int* nhyp_h, int* len_h, float* score_h, int* labels_h, hipStream_t s) {
+                         int* nhyp_h, int* len_h, float* score_h, int* labels_h, hipStream_t s, const BeamLm* lm = nullptr) {
+  if (lm) {   // (everything is refused before anything is enqueued or written)
+    REQUIRE(lm->lm, "clstm_ctc_beam_lm: the language model is required");
+    REQUIRE(lm->lm->nc == nc, "clstm_ctc_beam_lm: the language model was made for another class count");
+    REQUIRE(std::isfinite(lm->weight) && lm->weight >= 0.0f, "clstm_ctc_beam_lm: weight must be finite and not negative");
+    REQUIRE(std::isfinite(lm->bonus), "clstm_ctc_beam_lm: bonus must be finite");
+  }
   BeamPlan pl;
-  plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest);
+  plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest, lm != nullptr);
   REQUIRE(probs && nhyp_h && score_h, "clstm_ctc_beam: probs, nhyp_h and score_h are required");
-  const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest;
-  const size_t nout = (size_t)bs + 2 * nslot + (labels_h ? (size_t)nbest * N : 0);
+  const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest, nsc = lm ? 2 : 1;
+  const size_t nout = (size_t)bs + (1 + nsc) * nslot + (labels_h ? (size_t)nbest * N : 0);
   for (int b = 0; b < bs; b++) nhyp_h[b] = 0;
-  for (size_t i = 0; i < nslot; i++) { score_h[i] = -INFINITY; if (len_h) len_h[i] = 0; }
+  for (size_t i = 0; i < nslot; i++) {
+    score_h[i] = -INFINITY;
+    if (len_h) len_h[i] = 0;
+    if (lm && lm->am_score_h) lm->am_score_h[i] = -INFINITY;
+  }
   if (pl.lines.empty()) return;
   const size_t nln = pl.lines.size() * sizeof(BeamLine);
   w.meta.reserve(nln);
@@ -416,11 +437,26 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
   a.lines = (const BeamLine*)w.meta.p;
   a.P = probs; a.ws = w.ws.p;
   a.nhyp = w.out.p; a.len = w.out.p + bs; a.score = reinterpret_cast<float*>(w.out.p + bs + nslot);
-  a.labels = labels_h ? w.out.p + bs + 2 * nslot : nullptr;
+  a.labels = labels_h ? w.out.p + bs + (1 + nsc) * nslot : nullptr;
   a.nc = nc; a.beam = beam; a.nbest = nbest; a.K = pl.K; a.bs = bs; a.N = (int)N;
   const size_t smem = (size_t)pl.lds_words * sizeof(float);
   const dim3 grid((unsigned)pl.lines.size());
-  if (pl.all_lds) {
+  if (lm) {
+    a.table = lm->lm->table.p; a.end = lm->lm->has_end ? lm->lm->end.p : nullptr;
+    a.am_score = reinterpret_cast<float*>(w.out.p + bs + 2 * nslot);
+    a.weight = lm->weight; a.bonus = lm->bonus; a.order = lm->lm->order;
+    if (pl.all_lds) {
+#ifndef CLSTM_HIP_EMU
+      score_allow_smem((const void*)ctc_beam_kernel<true, true>, 4, smem);
+#endif
+      CLSTM_LAUNCH((ctc_beam_kernel<true, true>), grid, dim3(BEAM_THREADS), smem, s, a);
+    } else {
+#ifndef CLSTM_HIP_EMU
+      score_allow_smem((const void*)ctc_beam_kernel<false, true>, 5, smem);
+#endif
+      CLSTM_LAUNCH((ctc_beam_kernel<false, true>), grid, dim3(BEAM_THREADS), smem, s, a);
+    }
+  } else if (pl.all_lds) {
 #ifndef CLSTM_HIP_EMU
     score_allow_smem((const void*)ctc_beam_kernel<true>, 2, smem);
 #endif
@@ -432,7 +468,7 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
     CLSTM_LAUNCH(ctc_beam_kernel<false>, grid, dim3(BEAM_THREADS), smem, s, a);
   }
   check_launch();
-  g_path_count[PC_BEAM]++;
+  g_path_count[lm ? PC_BEAM_LM : PC_BEAM]++;
   HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   for (const BeamLine& ln : pl.lines) {   // (lines without frames keep nhyp = 0, len = 0, score = -inf)
@@ -442,9 +478,10 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
       const size_t i = (size_t)b * nbest + k;
       if (len_h) len_h[i] = w.host.p[bs + i];
       memcpy(&score_h[i], &w.host.p[bs + nslot + i], sizeof(float));
+      if (lm && lm->am_score_h) memcpy(&lm->am_score_h[i], &w.host.p[bs + 2 * nslot + i], sizeof(float));
     }
   }
-  if (labels_h) memcpy(labels_h, w.host.p + bs + 2 * nslot, (size_t)nbest * N * sizeof(int));
+  if (labels_h) memcpy(labels_h, w.host.p + bs + (1 + nsc) * nslot, (size_t)nbest * N * sizeof(int));
 }
 
 static thread_local CtcWorkspace* g_ctc_ws = nullptr;

@@ -7,6 +7,7 @@
 #include "model.h"
 #include <future>
 #include <thread>
+#include "charlm.h"
 #include "normalizer.h"
 #include "png_io.h"
 
@@ -84,7 +85,8 @@ inline void trivial_decode_host(Classes& cs, const float* out, int T, int nc) {
 
 struct CharPrediction { int i, x; char32_t c; float p; };
 // one of a line's n best transcripts (CLSTMOCR::predict_nbest)
-struct Hypothesis { ustring text; float score; };
+// (score: what the search ranked; am_score: the acoustic log-probability -- the same number unless a language model is set)
+struct Hypothesis { ustring text; float score; float am_score; };
 // forced alignment: the frame columns x0 .. x1 a transcript's i-th character occupies on a best path (-1, -1: the path never visits it)
 struct CharSpan { int i, x0, x1; char32_t c; };
 
@@ -107,8 +109,11 @@ struct CLSTMOCR {
   vector<float> aligned;  // [T][nclasses] of the last fwdbwd
   int T = 0;
 
+  clstm_charlm* lm = nullptr;                   // set_lm: the n-best calls search with it (clstm_net_beam_lm)
+  float lm_weight = 0.0f, lm_bonus = 0.0f;
   clstm_normalizer* gpu_normalizer = nullptr;   // the device twin of `normalizer` (created at first use: predict_batch_gpu, normalize_batch_gpu)
   ~CLSTMOCR() {
+    if (lm) clstm_charlm_destroy(lm);
     if (gpu_normalizer) clstm_normalizer_destroy(gpu_normalizer);
     if (net) clstm_net_destroy(net);
   }
@@ -448,6 +453,18 @@ struct CLSTMOCR {
   // ---- n-best transcripts (clstm_net_beam: CTC prefix beam search on the device, include/clstm_abi.h).  nbest_current works on the
   // net's CURRENT minibatch as score_current does; per line up to nbest hypotheses, best first.  A score is the log-probability the
   // beam gathered for the text -- not on the scale of score().
+  // set_lm: a character n-gram model (charlm.h; written by clstmlm or clstm_amd.lm.CharLM.save) for the model's classes; from then
+  // on predict_nbest / nbest_current search with it inside the beam (weight >= 0, bonus per character) and a Hypothesis carries both
+  // scores.  An empty path takes the model away again.
+  void set_lm(const string& path, float weight, float bonus) {
+    if (lm) chk(clstm_charlm_destroy(lm), "clstm_charlm_destroy");
+    lm = nullptr;
+    if (path.empty()) return;
+    const CharLMTables m = CharLMTables::load(path);
+    if (m.nc != nclasses) fail(path + ": the language model has " + std::to_string(m.nc) + " classes, the network " + std::to_string(nclasses));
+    chk(clstm_charlm_create(&lm, m.order, m.nc, m.table.data(), m.has_end ? m.end.data() : nullptr), "clstm_charlm_create");
+    lm_weight = weight; lm_bonus = bonus;
+  }
   void nbest_current(const vector<int>& Ts, int beam, int nbest, vector<vector<Hypothesis>>& out) {
     const int bs = (int)Ts.size();
     out.assign(bs, vector<Hypothesis>());
@@ -455,13 +472,17 @@ struct CLSTMOCR {
     size_t N = 0;
     for (int t : Ts) N += t;
     vector<int> nhyp(bs), len((size_t)bs * nbest), labels(std::max<size_t>(N * nbest, 1));
-    vector<float> sc((size_t)bs * nbest);
-    chk(clstm_net_beam(net, beam, nbest, nhyp.data(), len.data(), sc.data(), labels.data()), "clstm_net_beam");
+    vector<float> sc((size_t)bs * nbest), am((size_t)bs * nbest);
+    if (lm) chk(clstm_net_beam_lm(net, beam, nbest, lm, lm_weight, lm_bonus, nhyp.data(), len.data(), sc.data(), am.data(), labels.data()), "clstm_net_beam_lm");
+    else {
+      chk(clstm_net_beam(net, beam, nbest, nhyp.data(), len.data(), sc.data(), labels.data()), "clstm_net_beam");
+      am = sc;
+    }
     size_t off = 0;
     for (int b = 0; b < bs; b++) {
       for (int k = 0; k < nhyp[b]; k++) {
         const int* l = labels.data() + (size_t)nbest * off + (size_t)k * Ts[b];
-        out[b].push_back(Hypothesis{codec.decode(Classes(l, l + len[(size_t)b * nbest + k])), sc[(size_t)b * nbest + k]});
+        out[b].push_back(Hypothesis{codec.decode(Classes(l, l + len[(size_t)b * nbest + k])), sc[(size_t)b * nbest + k], am[(size_t)b * nbest + k]});
       }
       off += Ts[b];
     }

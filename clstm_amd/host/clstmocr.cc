@@ -16,6 +16,7 @@ static int main1(int argc, char** argv) {
     std::cerr << "Usage: [VAR=VAL...] " << argv[0] << " IMAGEFILE-LIST\n  Variables: load (required) conf output save_text\n"
               << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)\n"
               << "             beam nbest (beam=W: the nbest <= W best transcripts of every line follow its output; default off)   (not in the reference)\n"
+              << "             lm lm_weight lm_bonus (with beam=W: a character n-gram model file inside the search; hypotheses gain an am_score column)   (not in the reference)\n"
               << "             gpu_prep (1: lines are normalised on the device, helper threads only read PNGs; default 0)   (not in the reference)\n";
     return EXIT_FAILURE;
   }
@@ -47,12 +48,22 @@ static int main1(int argc, char** argv) {
   const int beam = getienv("beam", 0);
   const int nbest = beam > 0 ? getienv("nbest", beam) : 0;
   if (beam != 0 && (beam < 1 || beam > 32 || nbest < 1 || nbest > beam)) fail("beam / nbest: 1 <= nbest <= beam <= 32");
+  // lm=FILE lm_weight=A lm_bonus=B (with beam=W only; default none: nothing changes): the search runs with the character n-gram model
+  // of FILE (clstmlm writes one) inside the extension step (CLSTMOCR::set_lm), and a hypothesis line becomes
+  // "<k>\t<score>\t<am_score>\t<text>": the total that was ranked, then the acoustic log-probability beam=W alone prints.
+  const string lm_name = getsenv("lm", "");
+  const bool with_lm = !lm_name.empty();
+  if (with_lm && beam == 0) fail("lm= needs beam=W: the language model works inside the beam search");
+  if (with_lm) clstm.set_lm(lm_name, (float)getdenv("lm_weight", 1.0), (float)getdenv("lm_bonus", 0.0));
   auto print_nbest = [&](const string& name, const vector<Hypothesis>& hyps) {
     std::cout << "nbest " << name << std::endl;
     for (size_t k = 0; k < hyps.size(); k++) {
-      char buf[64];
+      char buf[64], am[64];
       snprintf(buf, sizeof buf, "%.9g", (double)hyps[k].score);
-      std::cout << k << "\t" << buf << "\t" << utf32_to_utf8(hyps[k].text) << std::endl;
+      snprintf(am, sizeof am, "%.9g", (double)hyps[k].am_score);
+      std::cout << k << "\t" << buf << "\t";
+      if (with_lm) std::cout << am << "\t";
+      std::cout << utf32_to_utf8(hyps[k].text) << std::endl;
     }
     std::cout << "end" << std::endl;
   };

@@ -203,6 +203,22 @@ class Network:
         self.lib.call("clstm_net_beam", self.h, int(beam), int(nbest), ptr(nhyp), ptr(ln), ptr(sc), ptr(lab))
         return unpack_beam(self.T, nbest, nhyp, ln, sc, lab)
 
+    def beam_lm(self, lm, weight, bonus=0.0, beam=8, nbest=None):
+        """beam() with a character n-gram language model (clstm_amd.lm.CharLM) inside the search (clstm_net_beam_lm; the algorithm
+        in clstm_amd/csrc/ctc_beam.h, second part).  Per line a list of (labels array, score, am_score), best first: score is
+        what was ranked -- am_score plus the labelling's weighted LM value, bonus and end term --, am_score the acoustic
+        log-probability beam() reports."""
+        nbest = beam if nbest is None else nbest
+        bs = len(self.T)
+        nhyp = np.zeros(bs, np.int32)
+        ln = np.zeros(max(1, bs * nbest), np.int32)
+        sc = np.zeros(max(1, bs * nbest), np.float32)
+        am = np.zeros(max(1, bs * nbest), np.float32)
+        lab = np.zeros(max(1, nbest * self.N), np.int32)
+        self.lib.call("clstm_net_beam_lm", self.h, int(beam), int(nbest), lm.handle(self.lib), float(weight), float(bonus),
+                      ptr(nhyp), ptr(ln), ptr(sc), ptr(am), ptr(lab))
+        return unpack_beam(self.T, nbest, nhyp, ln, sc, lab, am)
+
     def backward(self):
         self.lib.call("clstm_net_backward", self.h)
 
@@ -497,14 +513,16 @@ def sgd_update(net):
     net.update()
 
 
-def unpack_beam(T, nbest, nhyp, ln, sc, lab):
-    """the arrays of clstm_ctc_beam_batch / clstm_net_beam (include/clstm_abi.h) as a list per line of (labels, score)"""
+def unpack_beam(T, nbest, nhyp, ln, sc, lab, am=None):
+    """the arrays of clstm_ctc_beam_batch / clstm_net_beam (include/clstm_abi.h) as a list per line of (labels, score); with the
+    am_score array of the language model calls: of (labels, score, am_score)"""
     out, off = [], 0
     for b, t in enumerate(T):
         hyps = []
         for k in range(int(nhyp[b])):
             s = nbest * off + k * t
-            hyps.append((lab[s:s + ln[b * nbest + k]].copy(), float(sc[b * nbest + k])))
+            hyp = (lab[s:s + ln[b * nbest + k]].copy(), float(sc[b * nbest + k]))
+            hyps.append(hyp if am is None else hyp + (float(am[b * nbest + k]),))
         out.append(hyps)
         off += t
     return out

@@ -130,6 +130,26 @@ int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int
  * non-finite posterior can make that line's scores non-finite; lengths and labels stay in range, other lines are unaffected. */
 int clstm_ctc_beam_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
                          int* nhyp_h, int* len_h, float* score_h, int* labels_h);
+/* A character n-gram language model for the beam search: a dense table lm[ctx][c], HOST float32, nc^(order-1) rows of nc columns.
+ * Labels are 1 .. nc-1, 0 = "no label yet".  order 2: ctx = the last label (0 for the empty prefix); order 3: ctx = nc * (the
+ * label before last, or 0) + the last label.  Column 0 (blank) is never read.  end_h[nc^(order-1)] (or NULL) is added, weighted,
+ * when the hypotheses are ranked after the last frame.  Entries need not be normalised.  Refused: order outside {2, 3}, nc < 2, a
+ * table above 2^26 floats, a non-finite entry.  The tables are copied to the device here; the handle belongs to the creating
+ * thread's device. */
+typedef struct clstm_charlm clstm_charlm;
+int clstm_charlm_create(clstm_charlm** out, int order, int nc, const float* table_h, const float* end_h);
+int clstm_charlm_destroy(clstm_charlm* lm);
+/* clstm_ctc_beam_batch with the language model inside the extension step (clstm_amd/csrc/ctc_beam.h, second part): a prefix's LM
+ * value is lm(()) = 0, lm(l + c) = lm(l) + (weight * lm[ctx(l)][c] + bonus) in f32; candidates are selected by
+ * logadd(lb', lnb') + lm(prefix), and after the last frame the entries are ranked by tot + lm(l) (+ weight * end[ctx(l)]).  Every
+ * class is a candidate of every entry, so the result is that of the algorithm without any class cut.
+ *   score_h    [bs*nbest]  the total that was ranked;  am_score_h [bs*nbest] (may be NULL) the acoustic tot, the quantity
+ *                          clstm_ctc_beam_batch reports;  nhyp_h, len_h, labels_h as there.
+ * Refused before anything is enqueued: lm made for another nc, weight negative or non-finite, bonus non-finite, and
+ * beam * (nc - 1) > 4096.  weight = 0, bonus = 0 and no end table give clstm_ctc_beam_batch's bytes. */
+int clstm_ctc_beam_lm_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
+                            const clstm_charlm* lm, float weight, float bonus,
+                            int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
 /* mktargets  ctc.cc:148-157: 2L+1 state classes, blank (0) on even positions.  HOST arrays. */
 int clstm_mktargets(int* states_h, const int* transcript_h, int L);
 /* trivial_decode  ctc.cc:159-190 (+ argmax tensor.h:357-366), batched.  probs DEVICE [N][nc];
@@ -225,6 +245,10 @@ int clstm_net_score(clstm_net* net, const int* labels_h, const int* L_h, const i
  * parameters, derivs, grads, deltas, the step count, the device error words and a declared next minibatch are untouched.  Kernel
  * time under "ctc_beam". */
 int clstm_net_beam(clstm_net* net, int beam, int nbest, int* nhyp_h, int* len_h, float* score_h, int* labels_h);
+/* clstm_ctc_beam_lm_batch on the outputs of the net's current minibatch: the preconditions and guarantees of clstm_net_beam.  Kernel
+ * time under "ctc_beam_lm". */
+int clstm_net_beam_lm(clstm_net* net, int beam, int nbest, const clstm_charlm* lm, float weight, float bonus,
+                      int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
 /* net->backward(): accumulates this minibatch's gradient sum into grads (zeroed first). */
 int clstm_net_backward(clstm_net* net);
 /* input deltas of the first layer are only computed if enabled (nothing on the OCR path reads
@@ -457,6 +481,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *  28  score launches (clstm_ctc_score_batch / clstm_net_score): one per form a call launched -- the sum form for score_h, the
  *     max-plus form for vscore_h / path_h;
  *  29  beam-search launches (clstm_ctc_beam_batch / clstm_net_beam): one per call that had a line with frames;
+ *  30  the same with a language model (clstm_ctc_beam_lm_batch / clstm_net_beam_lm); 29 does not move for them;
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
