@@ -834,6 +834,17 @@ int clstm_debug_narrow_plan(const int* shape, int* plan) {   // host arithmetic 
   memcpy(plan, &p, sizeof(p));
   ABI_END
 }
+int clstm_debug_product_plan(const int* shape, int* plan) {   // host arithmetic only: no net, no device (runtime.inc:product_plan)
+  ABI_BEGIN
+  REQUIRE(shape && plan, "null argument");
+  static_assert(sizeof(ProductShape) == 35 * sizeof(int) && sizeof(ProductPlan) == 39 * sizeof(int), "include/clstm_abi.h documents the int layout");
+  ProductShape h;
+  memcpy(&h, shape, sizeof(h));
+  REQUIRE(h.pass >= PP_FWD && h.pass <= PP_BWD && h.no > 0 && h.ni > 0 && h.ndir >= 1 && h.N > 0 && h.nclasses >= 2 && h.ncu >= 0, "bad shape");
+  const ProductPlan p = product_plan(h);
+  memcpy(plan, &p, sizeof(p));
+  ABI_END
+}
 int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
                          int* line_plan_h) {   // host arithmetic only: no net, no device (ctc.h: ctc_batch_plan / ctc_line_plan)
   ABI_BEGIN
@@ -849,6 +860,8 @@ int clstm_debug_lane_ops(float* out) {
 int clstm_debug_gemm(int mode, const float* A, const float* B, float* Cm, int R, int Cn, int K, int nsplit) {
   ABI_BEGIN
   static thread_local DevBuf<float>* part = nullptr;
+  // (no net, no plan: the tile rule of runtime.inc asked directly, as product_plan asks it)
+  const int sq = gemm_bf16_big(R, Cn) ? GB2_BT : GEMM_BT, kk = gemm_tile256(R, Cn) ? 256 : GB2_BT;
   // user arrays are exact-size: no slack, the descriptor ends at the last element
   if (mode == 0) gemm_f32<GEMM_KC, GEMM_MC>(g_stream, gemm_kc(A, K, R, 0), gemm_mc(B, Cn, K, 0), StorePlain{Cm, Cn}, R, Cn, K);
   else if (mode == 1) gemm_f32<GEMM_KC, GEMM_KC>(g_stream, gemm_kc(A, K, R, 0), gemm_kc(B, K, Cn, 0), StorePlain{Cm, Cn}, R, Cn, K);
@@ -859,27 +872,27 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* Cm, int R,
     gemm_f32<GEMM_MC, GEMM_MC>(g_stream, gemm_mc(A, R, K, 0), gemm_mc(B, Cn, K, 0), StorePartial{part->p, R, Cn}, R, Cn, K, nsplit);
     CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks((size_t)R * Cn)), dim3(256), 0, g_stream,
                  (ReduceDesc{part->p, nullptr, 0LL, nsplit, 1, R, Cn, Cn}), (ReduceDesc{}), Cm, (int*)nullptr, 0, (UpdateFuse{}));
-  } else if (mode == 10) gemm_bf16<GEMM_KC, GEMM_MC>(g_stream, gemm_kc(A, K, R, 0), gemm_mc(B, Cn, K, 0), StorePlain{Cm, Cn}, R, Cn, K);
-  else if (mode == 11) gemm_bf16<GEMM_KC, GEMM_KC>(g_stream, gemm_kc(A, K, R, 0), gemm_kc(B, K, Cn, 0), StorePlain{Cm, Cn}, R, Cn, K);
+  } else if (mode == 10) gemm_bf16<GEMM_KC, GEMM_MC>(g_stream, gemm_kc(A, K, R, 0), gemm_mc(B, Cn, K, 0), StorePlain{Cm, Cn}, R, Cn, K, sq);
+  else if (mode == 11) gemm_bf16<GEMM_KC, GEMM_KC>(g_stream, gemm_kc(A, K, R, 0), gemm_kc(B, K, Cn, 0), StorePlain{Cm, Cn}, R, Cn, K, sq);
   else if (mode == 12) {
     if (!part) part = new DevBuf<float>();
     if (nsplit < 1) nsplit = 1;
     part->reserve((size_t)nsplit * R * Cn);
-    gemm_bf16<GEMM_MC, GEMM_MC>(g_stream, gemm_mc(A, R, K, 0), gemm_mc(B, Cn, K, 0), StorePartial{part->p, R, Cn}, R, Cn, K, nsplit);
+    gemm_bf16<GEMM_MC, GEMM_MC>(g_stream, gemm_mc(A, R, K, 0), gemm_mc(B, Cn, K, 0), StorePartial{part->p, R, Cn}, R, Cn, K, sq, nsplit);
     CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks((size_t)R * Cn)), dim3(256), 0, g_stream,
                  (ReduceDesc{part->p, nullptr, 0LL, nsplit, 1, R, Cn, Cn}), (ReduceDesc{}), Cm, (int*)nullptr, 0, (UpdateFuse{}));
   } else if (mode == 34) {   // the kk product with its tiles brought in by LDS-DMA (gemm_b16kk_dma_kernel)
     gemm_b16kk(g_stream, GemmOperand16{(const unsigned short*)A, K, (long long)R * K}, GemmOperand16{(const unsigned short*)B, K, (long long)Cn * K},
-               StorePlain{Cm, Cn}, R, Cn, K, 2);
+               StorePlain{Cm, Cn}, R, Cn, K, kk, 2);
   } else if (mode == 30 || mode == 31) {   // A: [R][K] bf16, B: [Cn][K] bf16 (the caller passes halfs in float-typed pointers); 31: the one-barrier loop
     gemm_b16kk(g_stream, GemmOperand16{(const unsigned short*)A, K, (long long)R * K}, GemmOperand16{(const unsigned short*)B, K, (long long)Cn * K},
-               StorePlain{Cm, Cn}, R, Cn, K, mode == 31 ? 0 : 1);
+               StorePlain{Cm, Cn}, R, Cn, K, kk, mode == 31 ? 0 : 1);
   } else if (mode == 32 || mode == 33 || mode == 35) {   // A: [K][R] bf16, B: [K][Cn] bf16 (R, Cn multiples of 8), split-K slabs reduced afterwards; 33: the one-barrier loop
     if (!part) part = new DevBuf<float>();
     if (nsplit < 1) nsplit = 1;
     part->reserve((size_t)nsplit * R * Cn);
     gemm_b16mc(g_stream, GemmOperand16B{(const unsigned short*)A, R, (long long)K * R, 0}, GemmOperand16B{(const unsigned short*)B, Cn, (long long)K * Cn, 0},
-               StorePartial{part->p, R, Cn}, R, Cn, K, nsplit, 1, GemmOperand16B{nullptr, 0, 0, 0}, 0, mode == 33 ? 0 : mode == 35 ? 3 : 1);   // 35: tiles by LDS-DMA
+               StorePartial{part->p, R, Cn}, R, Cn, K, gemm_mc_rows_per_tile(R, Cn), mode == 33 ? 0 : mode == 35 ? 3 : 1, nsplit);   // 35: tiles by LDS-DMA
     CLSTM_LAUNCH(k_reduce_scatter, dim3(nblocks((size_t)R * Cn)), dim3(256), 0, g_stream,
                  (ReduceDesc{part->p, nullptr, 0LL, nsplit, 1, R, Cn, Cn}), (ReduceDesc{}), Cm, (int*)nullptr, 0, (UpdateFuse{}));
   } else if (mode == 20) gemm_x3<GEMM_KC, GEMM_MC>(g_stream, gemm_kc(A, K, R, 0), gemm_mc(B, Cn, K, 0), StorePlain{Cm, Cn}, R, Cn, K);

@@ -791,15 +791,16 @@ __global__ __launch_bounds__(512, 2) void gemm_b16kk_dma_kernel(GemmOperand16 A,
   __shared__ __attribute__((aligned(1024))) unsigned short S[GKD_SMEM_HALFS];
   gemm_b16kk_dma_body<FE>(S, A, B, fe, R, Cn, K, blockIdx.x + gridDim.x * blockIdx.y, gridDim.x, gridDim.y);
 }
-inline bool gemm_tile256(int R, int Cn);
-inline int gemm_stag_default() {   // experiment switch (dbgopt.h): 2 LDS-DMA tiles + staggered wave groups, 1 register-staged + staggered, 0 the one-barrier loop
-  return dbg_opt("gemm_stag");
+// The launchers of this file take their tile from the caller (product_plan, runtime.inc: the one place that chooses) and only check it.
+inline void gemm_check_tile(bool ok) {
+  if (!ok) throw std::runtime_error("internal: the plan names a product tile its launcher does not have");
 }
+// tile: 256 or 128; stag (experiment option gemm_stag): 2 LDS-DMA tiles + staggered wave groups, 1 register-staged + staggered, 0 the one-barrier loop
 template <class FE>
-inline void gemm_b16kk(hipStream_t stream, GemmOperand16 A, GemmOperand16 B, FE fe, int R, int Cn, int K, int stag = -1) {
+inline void gemm_b16kk(hipStream_t stream, GemmOperand16 A, GemmOperand16 B, FE fe, int R, int Cn, int K, int tile, int stag) {
   if (R <= 0 || Cn <= 0 || K <= 0) return;
-  if (stag < 0) stag = gemm_stag_default();
-  if (gemm_tile256(R, Cn)) {
+  gemm_check_tile(tile == 256 || tile == GB2_BT);
+  if (tile == 256) {
     dim3 grid((Cn + 255) / 256, (R + 255) / 256, 1);
     if (stag == 2 && K % GB_BK == 0 && K >= 2 * GB_BK && (A.ld & 7) == 0 && (B.ld & 7) == 0) {   // operand tiles by LDS-DMA (16-byte aligned chunks)
       CLSTM_LAUNCH((gemm_b16kk_dma_kernel<FE>), grid, dim3(512), 0, stream, A, B, fe, R, Cn, K);
@@ -1136,41 +1137,25 @@ __global__ __launch_bounds__(512, 2) void gemm_dw_dx_kernel(GemmOperand16B A, Ge
 // s_waitcnt vmcnt(0) in front of the first ds_read_b64_tr_b16 of every block -- it cannot see which LDS bytes the BUILTIN reads
 // and takes every pending DMA for its producer -- so the request pipeline drained at every block.  With the reads as inline asm
 // (devintrin.h:lds_read_tr16_raw) the unit image runs 240 us.  profiles/r05_gemm_variants.txt.)
-// 256 x 256 tiles where the problem is large enough and their padding costs at most 25 % more work than 128 x 128 tiles do:
-// the big tile runs ~1.4x faster per flop (1537 rows: 7 x 256 vs 13 x 128, + 8 %; 561 rows: 3 x 256 vs 5 x 128, + 20 %:
-// 98 vs 116 us for one direction of the first layer's weight gradient)
-inline bool gemm_tile256(int R, int Cn) {
-  if (R < 192 || Cn < 192) return false;
-  const long long w256 = (long long)((R + 255) / 256) * ((Cn + 255) / 256) * 4, w128 = (long long)((R + 127) / 128) * ((Cn + 127) / 128);
-  return 4 * w256 <= 5 * w128;
-}
-// tile height of the big-tile contraction-major product: 256 rows, or 192 where that pads R less (576 = 3 x 192)
-inline int gemm_mc_tile_rows(int R) {
-  const int p256 = (R + 255) / 256 * 256, p192 = (R + 191) / 192 * 192;
-  return p192 < p256 ? 192 : 256;
-}
-// rows of one output tile of gemm_b16mc / gemm_dw_dx for an R x Cn product: an EXTERNAL x block (operand A2: rows that are not
-// copied into the source array but read from the layer below's bf16 outputs) must fill whole tiles.  The forward pass decides
-// "external" with this same function for every R the backward pass may launch with (R, and R - 1 when the bias row is left out),
-// and the launchers REFUSE an A2 that does not fit instead of dropping it (the x rows would then be read from columns nobody wrote).
-inline int gemm_mc_rows_per_tile(int R, int Cn) { return gemm_tile256(R, Cn) ? gemm_mc_tile_rows(R) : 128; }
+// An EXTERNAL x block (operand A2: output rows that are not copied into the source array but read from the layer below's bf16 outputs) must
+// fill whole row tiles: product_plan (runtime.inc) decides "external" and the tile height from the same shape for both passes, and the
+// launchers REFUSE an A2 that does not fit instead of dropping it (the x rows would then be read from columns nobody wrote).
 inline void gemm_mc_check_a2(const void* a2, int a2_rows, int th) {
   if (a2 && a2_rows % th != 0) throw std::runtime_error("internal: external x rows of the weight-gradient product do not fill whole row tiles");
 }
+// th: rows of an output tile, 256 / 192 (x 256 columns) or 128 (x 128) -- product_plan's; stag as gemm_b16kk's
 template <class FE>
-inline void gemm_b16mc(hipStream_t stream, GemmOperand16B A, GemmOperand16B B, FE fe, int R, int Cn, int K, int nsplit = 1, int nbatch = 1,
-                       GemmOperand16B A2 = GemmOperand16B{nullptr, 0, 0, 0}, int a2_rows = 0, int stag = -1) {
+inline void gemm_b16mc(hipStream_t stream, GemmOperand16B A, GemmOperand16B B, FE fe, int R, int Cn, int K, int th, int stag, int nsplit = 1, int nbatch = 1,
+                       GemmOperand16B A2 = GemmOperand16B{nullptr, 0, 0, 0}, int a2_rows = 0) {
   if (R <= 0 || Cn <= 0 || K <= 0) return;
+  gemm_check_tile(th == 256 || th == 192 || th == GB2_BT);
   if (nsplit < 1) nsplit = 1;
-  if (stag < 0) stag = gemm_stag_default();
   // (64 contraction rows per barrier on the 256 x 256 tile -- 231 VGPRs, 130 KB LDS -- measured equal to the 32-row
   // loop, 227 vs 226 us at 1544 x 2048 x 25600, and is gone)
-  const bool big = gemm_tile256(R, Cn);
   int ksplit = (K + nsplit - 1) / nsplit;
   const int kq = nsplit > 1 ? GT_PF * GB_BK : GB_BK;   // whole ring rounds per slab
   ksplit = ((ksplit + kq - 1) / kq) * kq;
-  if (big) {
-    const int th = gemm_mc_tile_rows(R);
+  if (th != GB2_BT) {
     dim3 grid((Cn + 255) / 256, (R + th - 1) / th, nsplit * nbatch);
     gemm_mc_check_a2(A2.p, a2_rows, th);
     const bool dma_ok = stag >= 2 && (A.ld & 7) == 0 && (B.ld & 7) == 0 && (A.bstride & 7) == 0 && (B.bstride & 7) == 0 && (!A2.p || (A2.ld & 7) == 0) &&
@@ -1192,18 +1177,18 @@ inline void gemm_b16mc(hipStream_t stream, GemmOperand16B A, GemmOperand16B B, F
   CLSTM_LAUNCH((gemm_b16mc_kernel<FE, 4, 1>), grid, dim3(256), 0, stream, A, B, fe, R, Cn, K, ksplit, nsplit, A2, a2_rows);
 }
 
-// weight gradient (contraction-major, big tiles) + input deltas (k-contiguous, LDS-DMA) as one launch; false: not eligible, nothing launched
+// weight gradient (contraction-major, big tiles of th = 256 / 192 rows) + input deltas (k-contiguous, 256 x 256 tiles by LDS-DMA) as one launch, where
+// product_plan has found both shapes eligible; false: an x.d operand is not 16-byte aligned (no buffer of the library: they come from hipMalloc),
+// nothing launched
 template <class FEW, class FEX>
-inline bool gemm_dw_dx(hipStream_t stream, GemmOperand16B A, GemmOperand16B B, FEW few, int R, int Cn, int K, int nsplit, int nbatch, GemmOperand16B A2, int a2_rows,
+inline bool gemm_dw_dx(hipStream_t stream, GemmOperand16B A, GemmOperand16B B, FEW few, int R, int Cn, int K, int th, int nsplit, int nbatch, GemmOperand16B A2, int a2_rows,
                        GemmOperand16 XA, GemmOperand16 XB, FEX fex, int XR, int XCn, int XK) {
-  if (gemm_stag_default() != 2 || !gemm_tile256(R, Cn) || !gemm_tile256(XR, XCn)) return false;
-  if (XK % GB_BK != 0 || XK < 2 * GB_BK || (XA.ld & 7) != 0 || (XB.ld & 7) != 0 || R <= 0 || Cn <= 0 || K <= 0) return false;
+  gemm_check_tile((th == 256 || th == 192) && XK % GB_BK == 0 && XK >= 2 * GB_BK && (XA.ld & 7) == 0 && (XB.ld & 7) == 0 && R > 0 && Cn > 0 && K > 0);
   if ((((size_t)XA.p | (size_t)XB.p) & 15) != 0) return false;   // the x.d role stages by LDS-DMA: 16-byte aligned operands only
   if (nsplit < 1) nsplit = 1;
   int ksplit = (K + nsplit - 1) / nsplit;
   const int kq = nsplit > 1 ? GT_PF * GB_BK : GB_BK;
   ksplit = ((ksplit + kq - 1) / kq) * kq;
-  const int th = gemm_mc_tile_rows(R);
   gemm_mc_check_a2(A2.p, a2_rows, th);
   const unsigned gxw = (Cn + 255) / 256, gyw = (R + th - 1) / th, gzw = nsplit * nbatch, gxx = (XCn + 255) / 256, gyx = (XR + 255) / 256;
   const dim3 grid(gxw * gyw * gzw + gxx * gyx);
@@ -1442,8 +1427,6 @@ inline void gemm_x3_pair(hipStream_t stream, GemmProblem p1, FE1 fe1, GemmProble
     CLSTM_LAUNCH((gemm_x3_pair_kernel<A1, B1, FE1, A2, B2, FE2, 2>), dim3(nb1 + nb2), dim3(256), 0, stream, p1, fe1, p2, fe2, nb1);
 }
 
-// shapes that fill 128 x 128 tiles reasonably
-inline bool gemm_bf16_big(int R, int Cn) { return R >= 96 && Cn >= 96; }
 // f32-grade product on 128 x 128 tiles (gemm_x3_128_kernel); same signature as gemm_f32 / gemm_bf16
 template <int AMODE, int BMODE, class FE>
 inline void gemm_x3_big(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe, int R, int Cn, int K, int nsplit = 1, int nbatch = 1) {
@@ -1467,15 +1450,16 @@ inline void gemm_x3_big(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe,
 // Operand slack: the second float4 of a KC row may run 7 floats past the row end (library buffers carry
 // >= 64 floats of slack; exact-size user arrays get a descriptor that ends at the last element).
 template <int AMODE, int BMODE, class FE>
-inline void gemm_bf16(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe, int R, int Cn, int K, int nsplit = 1,
-                      int nbatch = 1) {
+inline void gemm_bf16(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe, int R, int Cn, int K, int tile, int nsplit = 1,
+                      int nbatch = 1) {   // tile: 128 or 64 (product_plan, runtime.inc)
   if (R <= 0 || Cn <= 0) return;
+  gemm_check_tile(tile == GB2_BT || tile == GEMM_BT);
   if (nsplit < 1) nsplit = 1;
   int ksplit = (K + nsplit - 1) / nsplit;
   const int kq = nsplit > 1 ? GB_PF * GB_BK : GB_BK;
   ksplit = ((ksplit + kq - 1) / kq) * kq;
   if (ksplit < kq) ksplit = kq;
-  if (gemm_bf16_big(R, Cn)) {
+  if (tile == GB2_BT) {
     // (KC rows are read 16 floats at a time here: up to 15 floats past the row end, same slack rule)
     dim3 grid((Cn + GB2_BT - 1) / GB2_BT, (R + GB2_BT - 1) / GB2_BT, nsplit * nbatch);
     CLSTM_LAUNCH((gemm_bf16_128_kernel<AMODE, BMODE, FE>), grid, dim3(256), 0, stream, A, B, fe, R, Cn, K, ksplit, nsplit);

@@ -5,7 +5,9 @@
 // layers (Net::narrow_shape reads the device, the options and the build into its shape), wide_plan for the lock-step ones (Net::wide_shape).
 // forward() and predict() are the same layer loop (forward_pass, with and without save) and reserve_batch sizes the predict geometry by
 // the same plan.  backward() asks for every layer's backward plan once, then is backward_softmax and per layer the recurrence, the
-// layer's BwdPlan (decided ONCE, behind the recurrence launch), the weight gradient, the input deltas.
+// weight gradient, the input deltas.  The matrix products around the recurrences -- kernel, tile, rows, slabs, the bf16 arrays a pass writes for
+// them -- are decided by product_plan (runtime.inc; Net::product_shape reads the device, the options and the Layer into its shape): the passes
+// here ask for a layer's ProductPlan once and switch on it.
 // And the step: Net::step_plan decides a StepPlan ONCE per training step; backward(plan) returns what the pass left (PassLeft) and
 // update(left) consumes it -- nothing of a step's plan is a member of Net.  The step sequence itself is step.inc.
 // Not a stand-alone header: included once by clstm_hip.hip behind runtime.inc.
@@ -44,10 +46,10 @@ struct Layer {
   DevBuf<float> G, C, H, D, dH, S;
   DevBuf<unsigned short> Hbf;  // per-frame bf16 h of both directions written by the persistent forward kernel (A operand of the next layer's W_x product)
   DevBuf<unsigned short> WtbT; // bf16 W_x, k-contiguous ([M][ni]): B operand of that product
-  bool fwd_persistent = false; // this forward pass ran the persistent kernel (Hbf is valid)
+  bool hbf_valid = false;      // this forward pass ran the persistent kernel and it wrote Hbf
   DevBuf<unsigned short> Sbf;  // bf16 source rows [x | h_{t-1} | 1] per direction (x: k_source_x_bf16, h: the persistent forward kernel)
   bool sbf_ready = false;      // ... complete for this forward pass
-  bool sbf_x_external = false; // ... except their x columns: the weight-gradient GEMM reads those from the layer below's Hbf (gemm_b16mc A2)
+                               // (except their x columns where ProductPlan::a2_rows says the weight-gradient GEMM reads those from the layer below's Hbf)
   long long sbf_one_key = -1;  // batch geometry (N) the constant bias column of Sbf was written for
   bool d_f32_valid = true;     // D (f32 gate deltas) is current (a persistent bf16 backward pass may leave only Dbf)
   bool sx_valid = true;        // the [1 | x] columns of S (f32) are current (built lazily when the bf16 rows serve the weight gradient)
@@ -68,15 +70,6 @@ struct Layer {
 // or behind its launch (backward_layer_overlapped; NarrowPlan::overlapped), lock-step (lstm_wide.h), or the narrow layer's alone with the
 // weight gradient as a product behind it
 enum class BwdFamily { Overlapped, Wide, Narrow };
-// what the weight-gradient and input-delta steps of a layer need to know: Net::backward_plan, once the recurrence has been launched
-struct BwdPlan {
-  BwdFamily family;
-  bool bwd_persistent;   // the recurrence ran as a persistent lock-step kernel (in bf16 mode: Dbf and dbias are this pass's)
-  bool dw_from_bf16;     // the weight-gradient product takes the bf16 rows their producers left (Sbf, Dbf)
-  bool dw_bias_out;      // ... in dw_rows < R rows (Net::dw_bf16_rows): without the bias row, which k_bias_rows lays from dbias
-  bool x3_big;           // exact-f32 mode, wide layer: the product as f32-grade bf16 x 3 on 128 x 128 tiles
-  int dw_rows, ns;       // ns: split-K slabs per direction the reduction will find
-};
 
 // host-side view of one minibatch as the step entries take it: line lengths, frames, packed transcripts and their lengths
 struct Minibatch {
@@ -399,8 +392,7 @@ struct Net {
     for (auto& y : L) {
       const int M = ndir * 4 * y.no, KQP = 4 * y.nk4;
       const size_t nr = y.wide ? 0 : (size_t)ndir * 4 * KQP * y.nthreads;
-      if (y.wide && bf16_rec && y.no % 128 == 0 && y.ni % 32 == 0 && y.kp16f == y.no && y.bwd_exact &&
-          dbg_opt("pack_tiles") != 0) {
+      if (product_plan(product_shape((int)(&y - L.data()), PP_FWD)).tiled_pack) {
         // every bf16-mode copy of the layer in one tiled pass (ops.h:k_pack_wide_tiles)
         y.Wtb.reserve((size_t)y.ni * M + 64);
         y.WtbT.reserve((size_t)y.ni * M + 64);
@@ -527,29 +519,38 @@ struct Net {
   int layer_input_ld(int l) const { return l == 0 ? desc.ninput : L[l - 1].ldh; }
   int layer_input_slack(int l) const { return 32; }   // X and H are over-allocated by >= 64 floats
 
-  // Layer l can take the bf16 rows (Hbf) the layer below leaves as they are -- the A operand of its W_x product, the x columns of its
-  // bf16 source rows: the half of that question that the net's build and mode answer.  The other half is whether the layer below RAN
-  // its persistent forward kernel, which alone writes Hbf: a fact once it has run (forward_pass: x_from_hbf), a prediction while its
-  // own arguments are made (wide_args: next_takes_hbf -- only the persistent kernel reads skip_h, so a wrong prediction costs nothing)
-  bool hbf_feeds(int l) const {
-    return bf16_gemm && bf16_rec && l > 0 && l < (int)L.size() && L[l - 1].Hbf.p && L[l].WtbT.p && L[l].ni == ndir * L[l - 1].no && (L[l].ni & 1) == 0;
+  // ---- the products: what product_plan (runtime.inc) decides from, read HERE and nowhere else -- the device, the net's settings, the experiment
+  // options (per pass: tests switch them inside one process), the layer's recurrence plan and the facts earlier launches left in the Layer
+  ProductShape product_shape(int l, int pass, const NarrowPlan& np = NarrowPlan{}) const {
+    const Layer& y = L[l];
+    ProductShape h{};
+    h.pass = pass; h.ni = y.ni; h.no = y.no; h.ndir = ndir; h.wide = y.wide;
+    h.first = l == 0; h.top = l + 1 == (int)L.size(); h.nlayers = (int)L.size();
+    h.bwd_exact = y.bwd_exact; h.kp16f_is_no = y.kp16f == y.no;
+    h.N = (int)N; h.bs = bs; h.nclasses = desc.nclasses; h.sm_ni = sm_ni;
+    h.precision = bf16_rec ? 2 : bf16_gemm ? 1 : 0; h.gemm_x3_on = gemm_x3_on; h.split_terms = split_terms; h.strict = strict_f32;
+    h.gemm_b16mc = dbg_opt("gemm_b16mc") != 0; h.gemm_stag = dbg_opt("gemm_stag"); h.pack_tiles = dbg_opt("pack_tiles") != 0; h.fuse_wx = dbg_opt("fuse_wx");
+    h.ncu = device_cu_count(); h.want_dx0 = want_dx0;
+    h.fwd_family = np.fwd; h.overlapped = np.overlapped; h.dwx = np.dwx; h.xd = np.xd;
+    h.dw_slabs_per_dir = dw_slabs_per_dir; h.dwx_nslabs = dwx_nslabs;
+    h.below_hbf = l > 0 && L[l - 1].hbf_valid; h.fwd_sbf = y.sbf_ready;
+    h.packs = y.WtbT.p && y.Wtb.p; h.above_packs = !h.top && L[l + 1].WtbT.p;
+    return h;
   }
-  // the forward pass of a wide layer leaves bf16 source rows [x | h_{t-1} | 1] for the weight-gradient product (gemm_b16mc)
-  bool wants_sbf(const Layer& y) const { return bf16_rec && dbg_opt("gemm_b16mc") != 0 && bf16_gemm && (y.ni & 7) == 0 && (y.no & 7) == 0 && y.bwd_exact; }
   // what wide_plan decides from, read here: the device, the environment, the options (each per pass: tests switch them inside one process)
-  WideShape wide_shape(const Layer& y, bool fwd, int fx_mode = 0) const {
+  WideShape wide_shape(const Layer& y, bool fwd, const ProductPlan& pp, bool fx = false) const {
     WideShape h{};
     h.fwd = fwd; h.no = y.no; h.x_ni = y.ni; h.ndir = ndir; h.bs = bs; h.tmax = tmax; h.N = (int)N;
     h.kp = fwd ? y.kpf : y.kpb; h.kp16 = fwd ? y.kp16f : y.kp16b;
-    h.bf16 = bf16_rec; h.x3 = !fwd && rec_x3() && y.r2b_ready; h.fx_mode = fx_mode;
+    h.bf16 = bf16_rec; h.x3 = !fwd && rec_x3() && y.r2b_ready; h.fx_mode = fx ? pp.fx_mode : 0;
     h.ncu = device_cu_count();
     h.xcd_on = !(getenv("CLSTM_XCD_REC") && atoi(getenv("CLSTM_XCD_REC")) == 0);
     h.xcd_failed = g_xcd_failed;
     h.c32_on = dbg_opt("bwd_c32") != 0;
-    h.sbf = fwd && wants_sbf(y); h.sbf_ld = y.ni + y.no + 8; h.lds = y.lds; h.ldh = y.ldh;
+    h.sbf = (pp.writes & PW_SBF) != 0; h.sbf_ld = y.ni + y.no + 8; h.lds = y.lds; h.ldh = y.ldh;
     return h;
   }
-  LstmWideArgs wide_args(Layer& y, bool fwd) {
+  LstmWideArgs wide_args(Layer& y, bool fwd, const ProductPlan& pp) {   // (the bf16 arrays the pass writes and the f32 stores it skips: the plan's)
     REQUIRE((double)N * ndir * 4 * y.no * 4 < 2147483000.0,
             "minibatch too large for the lock-step recurrence (frames x 4 x nhidden x ndir x 4 B must stay below 2 GiB)");
     LstmWideArgs w{};
@@ -572,28 +573,17 @@ struct Net {
       w.kp16 = fwd ? y.kp16f : y.kp16b;
       w.rw_elems = (long long)ndir * (fwd ? y.rowsf : y.rowsb) * w.kp16;
       w.Hb = y.Hb.p; w.Db = y.Db.p;
-      if (!fwd && y.bwd_exact) {
+      if (pp.writes & PW_DBF) {
         y.Dbf.reserve((size_t)N * ndir * w.kp16 + 64); w.Dbf = y.Dbf.p;
-        // with bf16 GEMMs behind it, nobody reads the f32 deltas of a persistent pass (16 bytes per lane and step, 0.17 ms
-        // per configs[4] minibatch); ensure_delta_f32() expands Dbf for a fallback product
-        w.skip_d = bf16_gemm;
         y.dbias.reserve((size_t)bs * ndir * 4 * y.no + 64); w.dbias = y.dbias.p;   // per-line bias-gradient sums (lstm_wide.h: LstmWideArgs::dbias)
       }
-      if (fwd && wants_sbf(y)) {
+      if (pp.writes & PW_SBF) {
         const int ldsb = y.ni + y.no + 8;
         { const size_t cap0 = y.Sbf.cap; y.Sbf.reserve((size_t)N * ndir * ldsb + 64); if (y.Sbf.cap != cap0) y.sbf_one_key = -1; }
         w.Sbf = y.Sbf.p; w.sbf_ld = ldsb; w.sbf_ofs = y.ni; w.sbf_dir = (long long)N * ldsb;
       }
-      if (fwd && (y.no & 1) == 0 && &y != &L.back()) { y.Hbf.reserve((size_t)N * ndir * y.no + 64); w.Hbf = y.Hbf.p; w.hbf_ld = ndir * y.no; }
-      // Stores nobody reads in this mode (the per-frame stores of the persistent kernel cost per INSTRUCTION, seven per wave
-      // and step): the f32 outputs of a layer whose consumer takes Hbf (the next layer's W_x product and source rows), the
-      // f32 h_{t-1} source columns when the weight gradient takes Sbf.  ensure_h_f32 / ensure_source rebuild them exactly.
-      if (fwd) {   // (measured at configs[4]: forward passes 1.647 -> 1.580 ms per minibatch)
-        const int l = (int)(&y - L.data());
-        const bool next_takes_hbf = w.Hbf && hbf_feeds(l + 1);
-        w.skip_h = next_takes_hbf;
-        w.skip_s = w.Sbf != nullptr;
-      }
+      if (pp.writes & PW_HBF) { y.Hbf.reserve((size_t)N * ndir * y.no + 64); w.Hbf = y.Hbf.p; w.hbf_ld = ndir * y.no; }
+      w.skip_h = (pp.skips & PS_H) != 0; w.skip_s = (pp.skips & PS_S) != 0; w.skip_d = (pp.skips & PS_D) != 0;
     }
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); w.prof = lstm_prof.p;    // (the last pass launched before clstm_debug_lstm_cycles is what it reads)
@@ -806,12 +796,15 @@ struct Net {
     flush_line_off();
     repack();
     hipStream_t s = stream();
+    Product logits{};
     for (int l = 0; l < (int)L.size(); l++) {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
       const NarrowPlan np = forward_plan(l, save);
       if (np.fwd == NF_FUSED) { forward_fused(np, save); return; }   // (a net of one layer: the launch is the whole forward half)
-      const bool x_from_hbf = hbf_feeds(l) && L[l - 1].fwd_persistent;   // (a fact: the layer below has run)
+      const ProductPlan pp = product_plan(product_shape(l, PP_FWD, np));   // (the layer below has run: what it left is a fact)
+      const bool x_from_hbf = pp.wx.kernel == PK_B16KK && !pp.x_copy;
+      logits = pp.logits;   // (the top layer's plan names the softmax layer's product)
       // the lock-step recurrence of a wide layer as planned + what follows it (bf16 source rows for the weight gradient); false: the
       // plan was the kernel with the input projection folded in (lstm_wide.h:lstm_xcd_fwd_bf16_fx) and it did not run
       auto run_wide = [&](const WidePlan& plan, const LstmWideArgs& w) {
@@ -819,18 +812,14 @@ struct Net {
         const WideRan ran = launch_lstm_wide(plan, w, coop_sync, step_graphs, s);
         timing.end(s);
         if (ran == WideRan::Nothing) return false;
-        y.fwd_persistent = ran == WideRan::Persistent && bf16_rec;
-        y.h_f32_valid = !(y.fwd_persistent && w.skip_h);   // (the per-step kernels store everything)
-        y.sh_valid = !(y.fwd_persistent && w.skip_s);
-        y.sbf_ready = y.fwd_persistent && w.Sbf;
+        const bool persistent = ran == WideRan::Persistent && bf16_rec;
+        y.hbf_valid = persistent && w.Hbf;
+        y.h_f32_valid = !(persistent && w.skip_h);   // (the per-step kernels store everything)
+        y.sh_valid = !(persistent && w.skip_s);
+        y.sbf_ready = persistent && w.Sbf;
         if (y.sbf_ready) {   // the non-recurrent columns of the bf16 source rows (the recurrence stored the h columns)
-          // (x_from_hbf: with Sbf written -- bf16 GEMMs, ni % 8 == 0, the bf16 packs made -- it is no more than "the layer below left Hbf of this width")
-          if (l > 0 && !x_from_hbf) ensure_h_f32(l - 1);
-          // x columns that fill whole tiles of the weight-gradient GEMM are not copied: the GEMM reads them from Hbf itself
-          // (for the row count the backward pass WILL launch that GEMM with: dw_bf16_rows)
-          const int R_ = 1 + y.ni + y.no, Cn_ = 4 * y.no;
-          y.sbf_x_external = x_from_hbf && y.ni % gemm_mc_rows_per_tile(dw_bf16_rows(y, R_, Cn_), Cn_) == 0;
-          if (y.sbf_x_external) {
+          // x columns that fill whole tiles of the weight-gradient GEMM are not copied: the GEMM reads them from Hbf itself (ProductPlan::a2_rows)
+          if (pp.a2_rows) {
             if (y.sbf_one_key != (long long)N) {
               CLSTM_LAUNCH(k_source_one_bf16, dim3(nblocks((size_t)N)), dim3(256), 0, s, y.Sbf.p, (size_t)N, y.ni + y.no, w.sbf_ld, ndir, w.sbf_dir);
               y.sbf_one_key = (long long)N;
@@ -843,18 +832,16 @@ struct Net {
         }
         return true;
       };
-      // bf16 mode, wide layer: no hoisted product at all when the persistent recurrence can take the input projection with it
-      // (its operands are the bf16 rows the layer below left, or a bf16 copy of the input frames)
-      // (its gate is wide_plan's: here only whether its operands exist.)
-      bool fx_done = false;
-      // experiment option fuse_wx (CLSTM_DEBUG): 0 never, 1 (default) layers of up to 128 inputs, 2 every eligible layer.  Measured at configs[4]
+      // bf16 mode, wide layer: no hoisted product at all when the persistent recurrence can take the input projection with it (wide_plan's
+      // gate, asked where ProductPlan::fx_mode says its operands exist).  Experiment option fuse_wx: 0 never, 1 (default) layers of up to 128
+      // inputs, 2 every eligible layer.  Measured at configs[4]
       // (profiles/r04_xcd_phase_cycles_fused_wx.txt): there is no idle shadow to hide the x-part in -- a step's "group wait" is
       // one L2 round trip of the poll, not waiting for late tiles -- so the fused work lands on the chain: +400 cycles per step
       // for 64 inputs (67 us per pass against the 121 us of product + bf16 copy it replaces: kept), +2,950 for 1024 inputs
-      // (490 us against 321: not kept).  (read per pass: tests switch it inside one process)
-      const int fx_mode = dbg_opt("fuse_wx");
-      if (y.wide && bf16_gemm && bf16_rec && y.WtbT.p && (l == 0 || x_from_hbf)) {
-        const WidePlan plan = wide_plan(wide_shape(y, true, fx_mode));
+      // (490 us against 321: not kept).
+      bool fx_done = false;
+      if (pp.fx_mode) {
+        const WidePlan plan = wide_plan(wide_shape(y, true, pp, true));
         if (plan.fx_ngx) {   // asked for: the bf16 input frames are made before the rest of the gate is looked at (as ever; the hoisted product makes them again)
           const unsigned short* xb = l > 0 ? L[l - 1].Hbf.p : nullptr;
           if (l == 0) {
@@ -862,14 +849,14 @@ struct Net {
             CLSTM_LAUNCH(k_to_bf16, dim3(nblocks((size_t)N * y.ni)), dim3(256), 0, s, layer_input(0), xbf.p, (size_t)N * y.ni);
             xb = xbf.p;
           }
-          LstmWideArgs w = wide_args(y, true);
+          LstmWideArgs w = wide_args(y, true, pp);
           w.Xb = xb; w.x_ld = y.ni; w.x_ni = y.ni; w.Wxb = y.WtbT.p; w.bias = y.bias;
           y.sx_valid = l == 0 && src0_ready;
           fx_done = plan.kernel == WK_XCD_FWD_BF16_FX && run_wide(plan, w);
         }
       }
       if (fx_done) { if (!y.sbf_ready) ensure_source_x(l); continue; }
-      if (l > 0 && !x_from_hbf) ensure_h_f32(l - 1);   // the products below read the f32 outputs of the layer underneath
+      if (pp.needs & PN_H_BELOW) ensure_h_f32(l - 1);   // the products below read the f32 outputs of the layer underneath
       if (np.fwd == NF_MFMA) {
         // chip-filling minibatch of a narrow layer: the input product is part of the batched recurrence (lstm_mfma.h) -- no
         // hoisted W_x GEMM, no pre-activation array; the [1 | x] columns of the source rows are still the weight gradient's
@@ -885,26 +872,24 @@ struct Net {
       }
       if (!save) REQUIRE(y.G.p && y.G.cap >= (size_t)N * M, "internal: predict geometry without a pre-activation array");
       timing.begin("gemm_gates_x", s);
-      if (x_from_hbf)
-      {
-        // the layer below left its outputs as a k-contiguous bf16 array: both operands go to LDS as they are
-        g_path_count[PC_WX_FROM_BF16]++;
-        gemm_b16kk(s, GemmOperand16{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni}, GemmOperand16{y.WtbT.p, y.ni, (long long)M * y.ni},
-                   StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
-      } else if (bf16_gemm && bf16_rec && l == 0 && y.wide && y.WtbT.p && (y.ni & 7) == 0 && gemm_tile256((int)N, M)) {
-        // first layer: a bf16 copy of the input frames (N x ni, a few MB) buys the bf16-source kernel with its 256 x 256
-        // tiles and 16-byte stores for the product whose 4 M floats of pre-activations per frame-line are its whole cost
-        xbf.reserve((size_t)N * y.ni + 64);
-        CLSTM_LAUNCH(k_to_bf16, dim3(nblocks((size_t)N * y.ni)), dim3(256), 0, s, layer_input(0), xbf.p, (size_t)N * y.ni);
-        g_path_count[PC_WX_FROM_BF16]++;
-        gemm_b16kk(s, GemmOperand16{xbf.p, y.ni, (long long)N * y.ni}, GemmOperand16{y.WtbT.p, y.ni, (long long)M * y.ni},
-                   StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
-      } else if (bf16_gemm)
-        gemm_bf16<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), layer_input_ld(l), N, layer_input_slack(l)),
-                                    gemm_mc(y.Wt, M, y.ni, y.wt_slack), StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
-      else
-        gemm_f32<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), layer_input_ld(l), N), gemm_mc(y.Wt, M, y.ni, 0),
-                                   StoreBias{y.G.p, M, y.bias}, (int)N, M, y.ni);
+      const int ldx = layer_input_ld(l);
+      const StoreBias gates{y.G.p, M, y.bias};
+      count_moves(pp.moves);
+      switch (pp.wx.kernel) {
+        case PK_B16KK: {   // both operands k-contiguous bf16 arrays, to LDS as they are: the layer below's outputs, or a copy of the input frames
+          if (pp.x_copy) {
+            xbf.reserve((size_t)N * y.ni + 64);
+            CLSTM_LAUNCH(k_to_bf16, dim3(nblocks((size_t)N * y.ni)), dim3(256), 0, s, layer_input(0), xbf.p, (size_t)N * y.ni);
+          }
+          gemm_b16kk(s, GemmOperand16{pp.x_copy ? xbf.p : L[l - 1].Hbf.p, y.ni, (long long)N * y.ni}, GemmOperand16{y.WtbT.p, y.ni, (long long)M * y.ni}, gates,
+                     (int)N, M, y.ni, pp.wx.tile, pp.stag);
+          break;
+        }
+        case PK_BF16:
+          gemm_bf16<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), ldx, N, layer_input_slack(l)), gemm_mc(y.Wt, M, y.ni, y.wt_slack), gates, (int)N, M, y.ni, pp.wx.tile);
+          break;
+        default: gemm_f32<GEMM_KC, GEMM_MC>(s, gemm_kc(layer_input(l), ldx, N), gemm_mc(y.Wt, M, y.ni, 0), gates, (int)N, M, y.ni);
+      }
       timing.end(s);
       check_launch();
       // the [1 | x] columns of the f32 source rows: written now -- unless this is an upper layer whose weight-gradient
@@ -912,7 +897,7 @@ struct Net {
       // only if something still asks for them: a fallback path or the state API)
       if (save) y.sx_valid = l == 0 && src0_ready;
       if (save && (l == 0 || !y.wide)) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
-      if (y.wide) run_wide(wide_plan(wide_shape(y, true)), wide_args(y, true));
+      if (y.wide) run_wide(wide_plan(wide_shape(y, true, pp)), wide_args(y, true, pp));
       else {
         LstmSeqArgs a = seq_args(y, true, save);
 #ifdef CLSTM_LSTM_PROF
@@ -926,22 +911,22 @@ struct Net {
       }
       if (save && !y.sbf_ready) ensure_source_x(l);
     }
-    forward_softmax();
+    forward_softmax(logits);
   }
   // the softmax layer behind the top recurrence (every family but the fused launch, whose consumer items are that layer)
-  void forward_softmax() {
+  void forward_softmax(const Product& logits) {
     hipStream_t s = stream();
     const int nc = desc.nclasses;
     const float* W1 = v + sm_off;
     // the top layer's output rows are [1 | h]: they ARE the softmax layer's source rows
-    if (nc <= SMX_COLS) {   // logits, limexp and normalisation in one kernel (softmax_fused.h)
+    if (logits.kernel == PK_SOFTMAX_FUSED) {   // logits, limexp and normalisation in one kernel (softmax_fused.h)
       timing.begin("gemm_softmax", s);
       softmax_fwd(s, gemm_kc(L.back().hrow(), L.back().ldh, N), W1, (long long)nc * (1 + sm_ni), Z.p, (int)N, nc, sm_ni, fwd_nanflag(), step_no() + 1);
       timing.end(s);
       check_launch();
     } else {
       timing.begin("gemm_softmax", s);
-      if (bf16_gemm && gemm_x3_on && gemm_bf16_big((int)N, nc))   // bf16 modes: f32-grade bf16 x 3 on 128 x 128 tiles (88 -> ~30 us at configs[4])
+      if (logits.kernel == PK_X3_BIG)   // bf16 modes: f32-grade bf16 x 3 on 128 x 128 tiles
         gemm_x3_big<GEMM_KC, GEMM_MC>(s, gemm_kc(L.back().hrow(), L.back().ldh, N, 32), gemm_mc(W1 + nc, nc, sm_ni, 0),
                                       StoreBias{Z.p, nc, W1}, (int)N, nc, sm_ni);
       else
@@ -971,7 +956,7 @@ struct Net {
     if (!geom_predict) { forward(); return; }   // (no no-save kernels for this net: see reserve_batch)
     nosave = true;
     src0_ready = false;
-    for (auto& y : L) { y.sx_valid = y.sh_valid = false; y.h_f32_valid = true; y.sbf_ready = false; y.fwd_persistent = false; }
+    for (auto& y : L) { y.sx_valid = y.sh_valid = false; y.h_f32_valid = true; y.sbf_ready = false; y.hbf_valid = false; }
     forward_pass(false);
   }
 
@@ -1065,22 +1050,6 @@ struct Net {
     if (bf16_gemm || bf16_rec || !gemm_x3_on) return false;
     return dbg_opt("rec_x3") != 0;
   }
-  // split-K slabs for the weight-gradient GEMMs: enough workgroups to cover the 256 CUs, at least 64 frames per slab, 1..64 slabs
-  int clamp_split(long long want) const { return (int)std::max(1LL, std::min({want, (long long)(N + 63) / 64, 64LL})); }
-  // big tiles of the contraction-major bf16 product (gemm_b16mc: 256 or 192 rows x 256 columns): one workgroup per CU, never a second round
-  int pick_split_mc(int R, int Cn, int nbatch) const {
-    const int th = gemm_mc_tile_rows(R);
-    const long long tiles = (long long)((R + th - 1) / th) * ((Cn + 255) / 256) * nbatch;
-    return clamp_split(device_cu_count() / tiles);
-  }
-  int pick_split(int R, int Cn, int nbatch = 1, int tile = GEMM_BT) const {
-    const long long tiles = (long long)((R + tile - 1) / tile) * ((Cn + tile - 1) / tile) * nbatch;
-    const long long target = tile == GEMM_BT ? 640 : 480;   // 64 x 64 tiles: 640 measured best (272: slower); 128 x 128 tiles: two workgroups per CU
-    long long want = (target + tiles - 1) / tiles;
-    if (tile == 256) want = device_cu_count() / tiles;          // 256 x 256 tiles: one workgroup per CU, never a second round
-    return clamp_split(want);
-  }
-
   // ---- overlap machinery ---------------------------------------------------------------------------------------
   // the operands of the softmax layer's x.d for the top layer's backward launch (NarrowPlan::xd: the prologue forms of lstm_xd_prologue.h)
   XdArgs xd_args() const {
@@ -1088,12 +1057,6 @@ struct Net {
     const int nc = desc.nclasses;
     return XdArgs{gemm_kc(Dz.p, nc, N), gemm_kc(v + sm_off + nc, nc, sm_ni, 0), top.dH.p, sm_ni, nc, nullptr, 0};
   }
-  // Rows of the bf16-source weight-gradient product of an R x Cn gradient: R - 1 when the bias row is produced outside it
-  // (backward_dw_bf16), else R.  backward_plan launches with it and forward_pass PREDICTS it to decide sbf_x_external with the same
-  // tile-height function -- should the backward pass still come out with another tile height, gemm_mc_check_a2 refuses the launch
-  // loudly instead of reading x rows nobody wrote.  (Requiring BOTH R and R - 1 to fit, the first form of that fix, switched the
-  // path off at configs[4]: 1537 rows pick 192-row tiles.)  The first condition is wide_args' for reserving Dbf and dbias.
-  static int dw_bf16_rows(const Layer& y, int R, int Cn) { return y.bwd_exact && gemm_bf16_big(R - 1, Cn) ? R - 1 : R; }
   // Slab geometry of the chunked weight-gradient GEMM (measured at the bench shape unless said otherwise):
   // - chunks of DW_CHUNK iterations (8: 0.407 ms per step, 16: 0.356, 32: 0.359, 48: 0.360, a decreasing plan 64..16: 0.3615);
   // - ~16 slabs per direction, at most DW_STAB_MAX k-tiles (of 16 frames) each: a slab's table must fit the items' LDS copy.  At
@@ -1275,16 +1238,33 @@ struct Net {
     repack();
     hipStream_t s = stream();
     // every layer's backward plan, asked for ONCE, in front of backward_softmax (which reads the top layer's)
+    // ... and every layer's product plan (the slab tables of the Overlapped items first: the plans name their slab counts)
     NarrowPlan np[CLSTM_MAX_LAYERS];
-    for (int l = 0; l < (int)L.size(); l++) np[l] = backward_plan_narrow(l);
+    ProductShape ps[CLSTM_MAX_LAYERS];
+    ProductPlan pp[CLSTM_MAX_LAYERS];
+    const int top = (int)L.size() - 1;
+    for (int l = 0; l <= top; l++) {
+      np[l] = backward_plan_narrow(l);
+      if (np[l].overlapped) build_dw_tables();
+      if (np[l].dwx) build_dwx_table();
+      ps[l] = product_shape(l, PP_BWD, np[l]);
+      pp[l] = product_plan(ps[l]);
+    }
     // every entry of g is assigned by exactly one reduce below: no clearing pass
-    backward_softmax(np[L.size() - 1]);
-    for (int l = (int)L.size() - 1; l >= 0; l--) {
+    backward_softmax(np[top], pp[top]);
+    for (int l = top; l >= 0; l--) {
       const BwdFamily fam = L[l].wide ? BwdFamily::Wide : np[l].overlapped ? BwdFamily::Overlapped : BwdFamily::Narrow;
-      const bool bwd_persistent = backward_recurrence(l, fam, np[l]);
-      const BwdPlan p = backward_plan(L[l], fam, bwd_persistent);
-      if (!p.dw_from_bf16) { ensure_source(l); ensure_delta_f32(l); }   // the f32-source products below read S and D
-      if (!backward_weight_gradient(l, p, rt)) backward_input_deltas(l, p);   // (true: the input deltas rode the weight-gradient launch)
+      // the one fact only the launch can tell completes the layer's plan: the recurrence ran as a persistent lock-step kernel
+      ps[l].bwd_persistent = backward_recurrence(l, fam, np[l], pp[l]);
+      if (ps[l].bwd_persistent) pp[l] = product_plan(ps[l]);
+      if (pp[l].needs & PN_SOURCE) ensure_source(l);   // the f32-source products below read S and D
+      if (pp[l].needs & PN_DELTA_F32) ensure_delta_f32(l);
+      int moves = pp[l].moves;
+      if (!backward_weight_gradient(l, fam, pp[l], rt)) {   // (false: an unaligned x.d operand kept the input deltas out of the weight-gradient launch)
+        if (pp[l].merged) { moves &= ~(1 << PC_DW_DX_ONE_LAUNCH); pp[l].dx = Product{PK_B16KK, pp[l].dx.tile, pp[l].dx.rows, 1}; }
+        backward_input_deltas(l, pp[l]);
+      }
+      count_moves(moves);
     }
     if (!pending_red.empty()) {
       timing.begin("reduce_scatter", s);
@@ -1297,36 +1277,33 @@ struct Net {
   }
   // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T.  (A side stream for these products was measured
   // on MI355X: no gain -- the recurrence workgroups it would overlap with slow down by as much -- so everything stays on one stream.)
-  void backward_softmax(const NarrowPlan& top_plan) {
+  void backward_softmax(const NarrowPlan& top_plan, const ProductPlan& pp) {
     hipStream_t s = stream();
     Layer& top = L.back();
     const int nc = desc.nclasses, R = 1 + sm_ni, Cn = nc;
     const float* W1 = v + sm_off;
-    // (bf16 modes, shapes that fill 128 x 128 tiles: the two products as launches of the big-tile f32-grade kernel)
-    const bool sm_big = bf16_gemm && gemm_x3_on && gemm_bf16_big(R, Cn) && gemm_bf16_big((int)N, sm_ni);
-    int ns = sm_big ? pick_split(R, Cn, 1, GB2_BT) : pick_split(R, Cn);
     // W.d depends on nothing the backward recurrence produces: when the top layer's backward runs as the fused launch
     // (lstm_bwd_dw.h) its slabs are items of THAT launch -- they execute on the idle half of the chip during the ~14 us
     // before the recurrence's first chunk is released -- and only x.d stays in front of the recurrence.
-    // (NarrowPlan::dwx: the rule)
-    if (top_plan.dwx) { build_dwx_table(); ns = dwx_nslabs; }
+    // (NarrowPlan::dwx: the rule; ProductPlan::sm_wd, sm_xd: the kernels and the slab count)
+    const int ns = pp.sm_wd.slabs;
     partial_sm.reserve((size_t)ns * R * Cn);
     // W.d (split-K slabs) and x.d in ONE launch: two small independent products, each mostly prologue and
     // epilogue latency on its own (13.9 + 12.4 us back to back)
     const GemmOperand Wk = gemm_kc(W1 + nc, nc, sm_ni, 0);
     const StorePartial wd_store{partial_sm.p, R, Cn};
     const StorePlain xd_store{top.dH.p, sm_ni};
-    const bool launches = !top_plan.xd;   // (else nothing is launched here: the top layer's backward launch computes x.d)
+    const bool launches = pp.sm_wd.kernel != PK_NONE || pp.sm_xd.kernel != PK_NONE;   // (else the top layer's backward launch computes both)
     if (launches) timing.begin("gemm_softmax_dw_dx", s);
     if (top_plan.dwx) {
-      if (launches) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, split_terms);
-    } else if (sm_big) {
+      if (launches) gemm_x3<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N), Wk, xd_store, (int)N, sm_ni, nc, 1, 1, pp.terms);
+    } else if (pp.sm_wd.kernel == PK_X3_BIG) {
       gemm_x3_big<GEMM_MC, GEMM_MC>(s, gemm_mc(top.srow(), top.ldh, N, 32), gemm_mc(Dz.p, nc, N, 32), wd_store, R, Cn, (int)N, ns);
       gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(Dz.p, nc, N, 32), Wk, xd_store, (int)N, sm_ni, nc);
     } else {
       const GemmProblem wd = gemm_problem(gemm_mc(top.srow(), top.ldh, N), gemm_mc(Dz.p, nc, N), R, Cn, (int)N, ns);
       const GemmProblem xd = gemm_problem(gemm_kc(Dz.p, nc, N), Wk, (int)N, sm_ni, nc);
-      if (gemm_x3_on) gemm_x3_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store, split_terms);
+      if (pp.sm_wd.kernel == PK_X3_PAIR) gemm_x3_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store, pp.terms);
       else gemm_f32_pair<GEMM_MC, GEMM_MC, StorePartial, GEMM_KC, GEMM_KC, StorePlain>(s, wd, wd_store, xd, xd_store);
     }
     if (launches) timing.end(s);
@@ -1335,7 +1312,7 @@ struct Net {
     check_launch();
   }
   // the backward recurrence of layer l in the family and form its plan named; returns whether it ran as a persistent lock-step kernel
-  bool backward_recurrence(int l, BwdFamily fam, const NarrowPlan& np) {
+  bool backward_recurrence(int l, BwdFamily fam, const NarrowPlan& np, const ProductPlan& pp) {
     Layer& y = L[l];
     hipStream_t s = stream();
     const LstmSeqArgs a = seq_args(y, false);   // (no progress words: backward_layer_overlapped sets them in its copy)
@@ -1348,8 +1325,8 @@ struct Net {
     WideRan ran = WideRan::Nothing;
     int skipped_d = 0;
     if (fam == BwdFamily::Wide) {
-      const LstmWideArgs w = wide_args(y, false);
-      ran = launch_lstm_wide(wide_plan(wide_shape(y, false)), w, coop_sync, step_graphs, s);
+      const LstmWideArgs w = wide_args(y, false, pp);
+      ran = launch_lstm_wide(wide_plan(wide_shape(y, false, pp)), w, coop_sync, step_graphs, s);
       skipped_d = w.skip_d;
     } else { launch_bwd_narrow(y, np, a, s); count_moves(np.moves); }
     timing.end(s);
@@ -1357,31 +1334,15 @@ struct Net {
     y.d_f32_valid = !(persistent && bf16_rec && skipped_d);   // (launch_lstm_wide moved the plan's path counters)
     return persistent;
   }
-  BwdPlan backward_plan(const Layer& y, BwdFamily fam, bool bwd_persistent) const {
-    const int R = 1 + y.ni + y.no, Cn = 4 * y.no;
-    BwdPlan p{};
-    p.family = fam; p.bwd_persistent = bwd_persistent;
-    p.dw_from_bf16 = bf16_gemm && bf16_rec && bwd_persistent && y.sbf_ready && y.Dbf.p && gemm_bf16_big(R, Cn);
-    p.dw_rows = p.dw_from_bf16 ? dw_bf16_rows(y, R, Cn) : R;
-    p.dw_bias_out = p.dw_rows < R;
-    REQUIRE(!p.dw_bias_out || y.dbias.p, "internal: bias row left out of the weight-gradient product without the recurrence's per-line sums");
-    // exact-f32 mode, wide layer: the backward products as f32-grade bf16 x 3 on 128 x 128 tiles (gemm_x3_128_kernel) -- what
-    // narrow layers already do inside their fused backward launch; gemm_x3=0 (CLSTM_DEBUG) / clstm_net_set_strict_f32: the f32 MFMA
-    p.x3_big = !bf16_gemm && y.wide && gemm_x3_on && gemm_bf16_big(R, Cn);
-    p.ns = fam == BwdFamily::Overlapped ? dw_slabs_per_dir
-           : p.dw_bias_out && gemm_tile256(p.dw_rows, Cn) ? pick_split_mc(p.dw_rows, Cn, ndir)
-           : p.dw_from_bf16 && gemm_tile256(R, Cn) ? pick_split_mc(R, Cn, ndir)
-           : (bf16_gemm || p.x3_big) && gemm_bf16_big(R, Cn) ? pick_split(R, Cn, ndir, GB2_BT) : pick_split(R, Cn, ndir);
-    return p;
-  }
   // W.d += delta [1; x_t; h_{t-1}]^T for the four gates of each direction (both directions in one batched launch: half the slabs per
   // direction fill the chip) unless the recurrence launch's items have left the slabs already (Overlapped), and the slab reduction: queued
   // in a stacked net (see reduce_layer), launched here, in this step's bracket, for a single layer.  true: x.d rode the launch (gemm_dw_dx).
-  bool backward_weight_gradient(int l, const BwdPlan& p, const ReduceTarget& rt) {
+  bool backward_weight_gradient(int l, BwdFamily fam, const ProductPlan& pp, const ReduceTarget& rt) {
     Layer& y = L[l];
     hipStream_t s = stream();
     const int M = ndir * 4 * y.no, R = 1 + y.ni + y.no, Cn = 4 * y.no;
-    const bool product = p.family != BwdFamily::Overlapped, stacked = L.size() > 1;
+    const bool product = fam != BwdFamily::Overlapped, stacked = L.size() > 1;
+    const int ns = pp.dw.slabs;
     DevBuf<float>& pbuf = layer_partial(y);
     // the bracket of this step: a product family reports its GEMM -- and, in a single-layer net, the reduction behind it -- as
     // "gemm_gates_dw"; a single overlapped layer reports its reduction as "reduce_scatter"; a stacked overlapped layer launches
@@ -1390,16 +1351,18 @@ struct Net {
     if (bracket) timing.begin(bracket, s);
     bool dx_done = false;
     if (product) {
-      pbuf.reserve((size_t)ndir * p.ns * R * Cn);
+      pbuf.reserve((size_t)ndir * ns * R * Cn);
       const GemmOperand src = gemm_batched(gemm_mc(y.S.p, y.lds, N), (long long)N * y.lds, ndir);
       const GemmOperand dlt = gemm_batched(gemm_mc(y.D.p, M, N, 0), 4LL * y.no, 1);
       const StorePartial store{pbuf.p, R, Cn};
-      if (p.dw_from_bf16) dx_done = backward_dw_bf16(l, p, pbuf.p);
-      else if (bf16_gemm) gemm_bf16<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
-      else if (p.x3_big) gemm_x3_big<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
-      else gemm_f32<GEMM_MC, GEMM_MC, StorePartial, GEMM_BK_DW>(s, src, dlt, store, R, Cn, (int)N, p.ns, ndir);
+      switch (pp.dw.kernel) {
+        case PK_B16MC: case PK_DW_DX: dx_done = backward_dw_bf16(l, pp, pbuf.p); break;
+        case PK_BF16: gemm_bf16<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, pp.dw.tile, ns, ndir); break;
+        case PK_X3_BIG: gemm_x3_big<GEMM_MC, GEMM_MC>(s, src, dlt, store, R, Cn, (int)N, ns, ndir); break;
+        default: gemm_f32<GEMM_MC, GEMM_MC, StorePartial, GEMM_BK_DW>(s, src, dlt, store, R, Cn, (int)N, ns, ndir);
+      }
     }
-    const ReduceDesc gates{pbuf.p, y.moff, 0LL, p.ns, ndir, R, Cn, y.no};
+    const ReduceDesc gates{pbuf.p, y.moff, 0LL, ns, ndir, R, Cn, y.no};
     const ReduceDesc extra = l == (int)L.size() - 1 ? sm_red : ReduceDesc{};   // the softmax layer's slabs ride the top layer's
     if (stacked) pending_red.push_back(PendingReduce{gates, extra});
     else reduce_layer(gates, extra, true, rt);
@@ -1409,54 +1372,42 @@ struct Net {
   }
   // ... from both operands in bf16 as their producers left them (deltas: the persistent backward recurrence; sources: the forward
   // pass), transposed by the LDS on the way into the MFMA.  true: the layer's input deltas were computed by the same launch.
-  bool backward_dw_bf16(int l, const BwdPlan& p, float* slabs) {
+  bool backward_dw_bf16(int l, const ProductPlan& pp, float* slabs) {
     Layer& y = L[l];
     hipStream_t s = stream();
-    const int M = ndir * 4 * y.no, R = 1 + y.ni + y.no, Cn = 4 * y.no, ldsb = y.ni + y.no + 8;
-    g_path_count[PC_DW_FROM_BF16]++;
+    const int M = ndir * 4 * y.no, R = 1 + y.ni + y.no, Cn = 4 * y.no, ldsb = y.ni + y.no + 8, ns = pp.dw.slabs;
     const GemmOperand16B src{y.Sbf.p, ldsb, (long long)N * ndir * ldsb, (long long)N * ldsb}, dlt{y.Dbf.p, M, (long long)N * M, 4LL * y.no};
-    const GemmOperand16B a2 = y.sbf_x_external ? GemmOperand16B{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni, 0} : GemmOperand16B{nullptr, 0, 0, 0};
-    const int a2_rows = y.sbf_x_external ? y.ni : 0;
-    bool dx_done = false;
-    if (!p.dw_bias_out) gemm_b16mc(s, src, dlt, StorePartialRot{slabs, R, Cn}, R, Cn, (int)N, p.ns, ndir, a2, a2_rows);
-    else {
-      // The bias row W.d[:,0] += sum_b y.d (clstm_compute.cc:301) is not a row of this product: 1 + ni + no rows are one more than a
-      // whole number of row panels at both configs[4] layers (1537 = 6 x 256 + 1: a seventh panel, 14 % of the product, for one row;
-      // 577 = 3 x 192 + 1) -- the persistent backward recurrence sums the deltas of a line while it produces them (LstmWideArgs::
-      // dbias) and k_bias_rows lays the sum over lines into row 0 of the first slab.  Where the layer also owes input deltas from the
-      // same bf16 delta array, BOTH products as one launch (gemm_bf16.h:gemm_dw_dx_kernel: apart, each leaves a quarter of the chip idle)
-      const StorePartialShift store{slabs, R, Cn};
-      float* const dxp = l > 0 ? L[l - 1].dH.p : nullptr;
-      dx_done = dxp && y.bwd_exact && y.Wtb.p &&
-                gemm_dw_dx(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows, GemmOperand16{y.Dbf.p, M, (long long)N * M},
-                           GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dxp, y.ni}, (int)N, y.ni, M);
-      if (!dx_done) gemm_b16mc(s, src, dlt, store, p.dw_rows, Cn, (int)N, p.ns, ndir, a2, a2_rows);
-      CLSTM_LAUNCH(k_bias_rows, dim3((unsigned)(((size_t)ndir * Cn + 63) / 64)), dim3(64), 0, s, (const float*)y.dbias.p, slabs, bs, ndir, p.ns, R, Cn);
-      g_path_count[PC_DW_BIAS_OUT]++;
-      if (dx_done) { g_path_count[PC_DX_FROM_BF16]++; g_path_count[PC_DW_DX_ONE_LAUNCH]++; }
-    }
-    if (y.sbf_x_external) g_path_count[PC_DW_X_EXTERNAL]++;
+    const GemmOperand16B a2 = pp.a2_rows ? GemmOperand16B{L[l - 1].Hbf.p, y.ni, (long long)N * y.ni, 0} : GemmOperand16B{nullptr, 0, 0, 0};
+    if (!pp.bias_out) { gemm_b16mc(s, src, dlt, StorePartialRot{slabs, R, Cn}, R, Cn, (int)N, pp.dw.tile, pp.stag, ns, ndir, a2, pp.a2_rows); return false; }
+    // The bias row W.d[:,0] += sum_b y.d (clstm_compute.cc:301) is not a row of this product (product_plan: dw16_rows) -- the persistent backward
+    // recurrence sums the deltas of a line while it produces them (LstmWideArgs::dbias) and k_bias_rows lays the sum over lines into row 0 of the
+    // first slab.  Where the plan says so, the layer's input deltas ride the launch (gemm_bf16.h:gemm_dw_dx_kernel)
+    REQUIRE(y.dbias.p, "internal: bias row left out of the weight-gradient product without the recurrence's per-line sums");
+    const StorePartialShift store{slabs, R, Cn};
+    const bool dx_done = pp.merged && gemm_dw_dx(s, src, dlt, store, pp.dw.rows, Cn, (int)N, pp.dw.tile, ns, ndir, a2, pp.a2_rows, GemmOperand16{y.Dbf.p, M, (long long)N * M},
+                                                 GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{L[l - 1].dH.p, y.ni}, (int)N, y.ni, M);
+    if (!dx_done) gemm_b16mc(s, src, dlt, store, pp.dw.rows, Cn, (int)N, pp.dw.tile, pp.stag, ns, ndir, a2, pp.a2_rows);
+    CLSTM_LAUNCH(k_bias_rows, dim3((unsigned)(((size_t)ndir * Cn + 63) / 64)), dim3(64), 0, s, (const float*)y.dbias.p, slabs, bs, ndir, ns, R, Cn);
     return dx_done;
   }
   // input deltas: x.d = sum_dir W_x^T delta (Parallel::backward sums both subs, clstm.cc:538-541)
-  void backward_input_deltas(int l, const BwdPlan& p) {
+  void backward_input_deltas(int l, const ProductPlan& pp) {
     Layer& y = L[l];
     hipStream_t s = stream();
     const int M = ndir * 4 * y.no;
     if (l == 0 && want_dx0) dX0.reserve((size_t)N * y.ni);
     float* const dx = l > 0 ? L[l - 1].dH.p : want_dx0 ? dX0.p : nullptr;   // the layer below's output deltas, or what the caller asked for
-    if (!dx) return;
+    if (pp.dx.kernel == PK_NONE) return;
     timing.begin("gemm_gates_dx", s);
-    if (bf16_gemm && bf16_rec && p.bwd_persistent && y.bwd_exact && y.Wtb.p && y.Dbf.p) {
-      // the persistent recurrence left the deltas as a k-contiguous bf16 array: both operands go to LDS as they are
-      g_path_count[PC_DX_FROM_BF16]++;
-      gemm_b16kk(s, GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dx, y.ni}, (int)N, y.ni, M);
-    } else if (ensure_delta_f32(l), bf16_gemm)
-      gemm_bf16<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni}, (int)N, y.ni, M);
-    else if (y.wide && gemm_x3_on && gemm_bf16_big((int)N, y.ni))
-      gemm_x3_big<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N, 32), gemm_kc(y.Wt, M, y.ni, y.wt_slack), StorePlain{dx, y.ni}, (int)N, y.ni, M);
-    else
-      gemm_f32<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N), gemm_kc(y.Wt, M, y.ni, 0), StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    const GemmOperand D = gemm_kc(y.D.p, M, N, 32), W = gemm_kc(y.Wt, M, y.ni, y.wt_slack);
+    switch (pp.dx.kernel) {
+      case PK_B16KK:   // the persistent recurrence left the deltas as a k-contiguous bf16 array: both operands go to LDS as they are
+        gemm_b16kk(s, GemmOperand16{y.Dbf.p, M, (long long)N * M}, GemmOperand16{y.Wtb.p, M, (long long)y.ni * M}, StorePlain{dx, y.ni}, (int)N, y.ni, M, pp.dx.tile, pp.stag);
+        break;
+      case PK_BF16: gemm_bf16<GEMM_KC, GEMM_KC>(s, D, W, StorePlain{dx, y.ni}, (int)N, y.ni, M, pp.dx.tile); break;
+      case PK_X3_BIG: gemm_x3_big<GEMM_KC, GEMM_KC>(s, D, W, StorePlain{dx, y.ni}, (int)N, y.ni, M); break;
+      default: gemm_f32<GEMM_KC, GEMM_KC>(s, gemm_kc(y.D.p, M, N), gemm_kc(y.Wt, M, y.ni, 0), StorePlain{dx, y.ni}, (int)N, y.ni, M);
+    }
     timing.end(s);
     check_launch();
   }

@@ -1,5 +1,5 @@
 // runtime.inc -- part of clstm_hip.hip (namespace clstm): errors, device buffers and the pinned staging ring, GEMM store functors,
-// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), the layers' kernel choices (narrow_plan, wide_plan),
+// kernel launch helpers (per-line / fused / lock-step recurrences, hipGraph cache), the layers' kernel choices (narrow_plan, wide_plan, product_plan),
 // device error words, per-kernel timing, roctx.
 // Not a stand-alone header: included once, inside the namespace, by clstm_hip.hip.
 
@@ -625,6 +625,184 @@ static NarrowPlan narrow_plan(const NarrowShape& h) {
 static void count_moves(int moves) {
   for (int c = 0; c < PC_COUNT; c++)
     if (moves >> c & 1) g_path_count[c]++;
+}
+
+// ---- the matrix products around the recurrences -- the input projection W_x.x, the softmax layer's logits, its W.d and x.d, a layer's weight
+// gradient and its input deltas: WHICH kernel, tile, row count and slab count each is launched with, which bf16 arrays a pass writes for them and
+// which f32 stores it skips, is decided once per layer and pass by product_plan, a pure function of a ProductShape (no device, no global, no
+// environment, no option, no pointer: Net::product_shape reads those into the shape); the passes of net.inc and the launchers of gemm_bf16.h only
+// execute the plan.  clstm_debug_product_plan asks product_plan without a net: both structs are plain ints in the order documented in
+// include/clstm_abi.h.
+enum ProductPass { PP_FWD = 0, PP_BWD };
+enum ProductKernel {
+  PK_NONE = 0,        // nothing launched for it: part of a recurrence launch (fused forward, batched MFMA, the Overlapped items, the x.d prologue)
+  PK_F32,             // gemm_f32, 64 x 64 tiles
+  PK_BF16,            // gemm_bf16: f32 operands rounded on the way in, 64- or 128-tiles
+  PK_B16KK,           // gemm_b16kk: both operands bf16 and k-contiguous as their producers left them, 128- or 256-tiles
+  PK_B16MC,           // gemm_b16mc: both operands bf16 and contraction-major, 128 x 128, 192 x 256 or 256 x 256 tiles
+  PK_DW_DX,           // gemm_dw_dx: the weight gradient (as PK_B16MC) and the input deltas (as PK_B16KK, 256-tiles) as ONE launch
+  PK_X3,              // gemm_x3: f32-grade bf16 split product, 64-tiles
+  PK_X3_BIG,          // gemm_x3_big: the same on 128 x 128 tiles
+  PK_X3_PAIR,         // gemm_x3_pair: the softmax layer's W.d and x.d as one launch
+  PK_F32_PAIR,        // gemm_f32_pair: the same on the f32 MFMA
+  PK_SOFTMAX_FUSED    // softmax_fwd: logits, limexp and normalisation in one kernel (tile 0: the kernel's own)
+};
+enum ProductWrites { PW_SBF = 1, PW_HBF = 2, PW_DBF = 4 };               // bf16 arrays the recurrence of the pass writes: Sbf | Hbf | Dbf and dbias
+enum ProductSkips { PS_H = 1, PS_S = 2, PS_D = 4 };                      // f32 stores its persistent kernel may skip: H | the h columns of S | D
+enum ProductNeeds { PN_SOURCE = 1, PN_DELTA_F32 = 2, PN_H_BELOW = 4 };   // built first: ensure_source | ensure_delta_f32 | ensure_h_f32 of the layer below
+struct ProductShape {
+  int pass;                                    // ProductPass
+  int ni, no, ndir, wide;                      // the layer: inputs, cells, directions, lock-step
+  int first, top, nlayers;                     // it is the first / the top layer; layers of the net
+  int bwd_exact, kp16f_is_no;                  // Layer::bwd_exact, kp16f == no (the rule reads no row stride: those it needs follow from ni, no, ndir)
+  int N, bs;                                   // the minibatch: frames, lines (bs: carried, read by no rule today)
+  int nclasses, sm_ni;                         // the softmax layer
+  int precision, gemm_x3_on, split_terms, strict;   // clstm_net_set_gemm_precision 0 / 1 / 2; options read at net creation; clstm_net_set_strict_f32
+  int gemm_b16mc, gemm_stag, pack_tiles, fuse_wx;   // options read per pass
+  int ncu, want_dx0;                           // CUs of the device; clstm_net_enable_input_deltas
+  int fwd_family, overlapped, dwx, xd;         // the layer's recurrence plan: NarrowPlan::fwd (a wide layer: NF_NONE) / overlapped / dwx / xd
+  int dw_slabs_per_dir, dwx_nslabs;            // slab counts of the Overlapped items' tables (Net::build_dw_tables, build_dwx_table)
+  // facts of earlier launches:
+  int below_hbf;                               // the layer below ran its persistent bf16 forward kernel and left Hbf
+  int fwd_sbf;                                 // this layer's forward pass ran persistent and wrote Sbf
+  int bwd_persistent;                          // its backward recurrence ran persistent (known once launched: Net::backward completes the shape)
+  int packs, above_packs;                      // the bf16 packs of W_x (Wtb, WtbT) exist for this layer / for the layer above
+};
+struct Product { int kernel, tile, rows, slabs; };   // ProductKernel; rows of a tile (64 / 128 / 192 / 256); rows it is launched with; split-K slabs per direction
+struct ProductPlan {
+  Product wx, logits;                          // forward: the input projection (behind the folded one where that does not run: fx_mode) | the softmax layer's logits (top layer)
+  Product sm_wd, sm_xd, dw, dx;                // backward: the softmax layer's W.d and x.d (top layer) | the layer's weight gradient | its input deltas
+  int merged;                                  // dw and dx are one launch (PK_DW_DX)
+  int bias_out;                                // the bias row is produced outside dw (k_bias_rows from dbias)
+  int dw16_rows, dw16_tile, x_external;        // FROM THE SHAPE AND MODE ALONE, equal in both passes whatever the facts: rows and tile height of the
+                                               // bf16-source weight gradient, and whether the x block fills whole tiles of it (may stay external, A2)
+  int a2_rows;                                 // ... and does: rows the product reads from the layer below's Hbf instead of copies in Sbf (0: copied)
+  int x_copy;                                  // wx reads a bf16 copy of the input frames (k_to_bf16 first)
+  int fx_mode;                                 // WideShape::fx_mode: option fuse_wx where the folded input projection has its operands, else 0
+  int tiled_pack;                              // Net::repack: every bf16 copy of the layer by k_pack_wide_tiles
+  int stag, terms;                             // option gemm_stag for PK_B16KK / PK_B16MC; split terms (3 / 2) for PK_X3 / PK_X3_PAIR
+  int writes, skips, needs;                    // ProductWrites, ProductSkips, ProductNeeds
+  int moves;                                   // bit c: the pass moves path counter c (2, 3, 4, 8, 13, 14)
+};
+// shapes that fill 128 x 128 tiles reasonably
+static bool gemm_bf16_big(int R, int Cn) { return R >= 96 && Cn >= 96; }
+// 256 x 256 tiles where the problem is large enough and their padding costs at most 25 % more work than 128 x 128 tiles do:
+// the big tile runs ~1.4x faster per flop (1537 rows: 7 x 256 vs 13 x 128, + 8 %; 561 rows: 3 x 256 vs 5 x 128, + 20 %:
+// 98 vs 116 us for one direction of the first layer's weight gradient)
+static bool gemm_tile256(int R, int Cn) {
+  if (R < 192 || Cn < 192) return false;
+  const long long w256 = (long long)((R + 255) / 256) * ((Cn + 255) / 256) * 4, w128 = (long long)((R + 127) / 128) * ((Cn + 127) / 128);
+  return 4 * w256 <= 5 * w128;
+}
+// tile height of the big-tile contraction-major product: 256 rows, or 192 where that pads R less (576 = 3 x 192)
+static int gemm_mc_tile_rows(int R) {
+  const int p256 = (R + 255) / 256 * 256, p192 = (R + 191) / 192 * 192;
+  return p192 < p256 ? 192 : 256;
+}
+// rows of one output tile of gemm_b16mc / gemm_dw_dx for an R x Cn product
+static int gemm_mc_rows_per_tile(int R, int Cn) { return gemm_tile256(R, Cn) ? gemm_mc_tile_rows(R) : GB2_BT; }
+static ProductPlan product_plan(const ProductShape& h) {
+  ProductPlan p{};
+  const bool bf16_gemm = h.precision >= 1, bf16_rec = h.precision == 2, x3 = h.gemm_x3_on && !h.strict;
+  const int N = h.N, M = h.ndir * 4 * h.no, R = 1 + h.ni + h.no, Cn = 4 * h.no, nc = h.nclasses;
+  const auto sq = [](int R_, int Cn_) { return gemm_bf16_big(R_, Cn_) ? GB2_BT : GEMM_BT; };   // 128- or 64-tiles of gemm_bf16
+  const auto kk = [](int R_, int Cn_) { return gemm_tile256(R_, Cn_) ? 256 : GB2_BT; };        // 256- or 128-tiles of gemm_b16kk
+  // split-K slabs for the weight-gradient GEMMs: enough workgroups to cover the CUs, at least 64 frames per slab, 1..64 slabs
+  const auto clamp_split = [&](long long want) { return (int)std::max(1LL, std::min({want, ((long long)N + 63) / 64, 64LL})); };
+  const auto split = [&](int R_, int Cn_, int nbatch, int tile) {
+    const long long tiles = (long long)((R_ + tile - 1) / tile) * ((Cn_ + tile - 1) / tile) * nbatch;
+    const long long target = tile == GEMM_BT ? 640 : 480;   // 64 x 64 tiles: 640 workgroups measured best (272: slower); 128 x 128 tiles: two workgroups per CU
+    return clamp_split((target + tiles - 1) / tiles);
+  };
+  // big tiles of the contraction-major bf16 product (256 or 192 rows x 256 columns): one workgroup per CU, never a second round
+  const auto split_mc = [&](int R_, int Cn_, int nbatch) {
+    const int th = gemm_mc_tile_rows(R_);
+    return clamp_split(h.ncu / ((long long)((R_ + th - 1) / th) * ((Cn_ + 255) / 256) * nbatch));
+  };
+  p.stag = h.gemm_stag; p.terms = h.split_terms >= 3 ? 3 : 2;
+  // ---- ONE answer for both passes.  Rows of the bf16-source weight gradient: R - 1 when the bias row is produced outside it (1 + ni + no rows
+  // are one more than a whole number of row panels at both configs[4] layers -- 1537 = 6 x 256 + 1: a seventh panel, 14 % of the product, for
+  // one row; 577 = 3 x 192 + 1), else R.  The forward pass leaves the x block of Sbf external (a2_rows) only where it fills whole tiles of THAT
+  // height, and the backward pass launches with these same fields: nothing here reads a fact that is unknown during the forward pass.
+  // (Requiring BOTH R and R - 1 to fit, the first form of this rule, switched the path off at configs[4]: 1537 rows pick 192-row tiles.)
+  p.dw16_rows = h.bwd_exact && gemm_bf16_big(R - 1, Cn) ? R - 1 : R;
+  p.dw16_tile = gemm_mc_rows_per_tile(p.dw16_rows, Cn);
+  p.x_external = bf16_rec && !h.first && h.ni % p.dw16_tile == 0;
+  // this layer takes the bf16 rows the layer below left as they are (its ni is ndir x the cells below: Net::build)
+  const bool x_from_hbf = bf16_rec && !h.first && h.below_hbf && h.packs && (h.ni & 1) == 0;
+  if (h.pass == PP_FWD) {
+    p.tiled_pack = h.wide && bf16_rec && h.no % 128 == 0 && h.ni % 32 == 0 && h.kp16f_is_no && h.bwd_exact && h.pack_tiles;
+    if (h.wide && bf16_rec) {
+      // bf16 source rows [x | h_{t-1} | 1] for the weight-gradient product; bf16 outputs for the layer above.  Stores nobody reads in this mode
+      // (the per-frame stores of the persistent kernel cost per INSTRUCTION, seven per wave and step; measured at configs[4]: forward passes
+      // 1.647 -> 1.580 ms per minibatch): the f32 outputs of a layer whose consumer takes Hbf, the f32 h_{t-1} source columns when the weight
+      // gradient takes Sbf.  ensure_h_f32 / ensure_source rebuild them exactly.  (Only the persistent kernel reads the skips.)
+      if (h.gemm_b16mc && (h.ni & 7) == 0 && (h.no & 7) == 0 && h.bwd_exact) { p.writes |= PW_SBF; p.skips |= PS_S; }
+      if ((h.no & 1) == 0 && !h.top) { p.writes |= PW_HBF; if (h.above_packs) p.skips |= PS_H; }
+    }
+    // the input projection folded into the persistent forward kernel (wide_plan's gate; here only whether its operands exist: the bf16 rows the
+    // layer below left, or a bf16 copy of the input frames)
+    p.fx_mode = h.wide && bf16_rec && h.packs && (h.first || x_from_hbf) ? h.fuse_wx : 0;
+    if (!h.first && !x_from_hbf) p.needs |= PN_H_BELOW;   // the products read the f32 outputs of the layer underneath
+    if (h.fwd_family == NF_FUSED) return p;               // the launch is the whole forward half, logits included
+    if (h.fwd_family == NF_MFMA) p.wx = Product{};        // the input product is part of the batched recurrence
+    else if (x_from_hbf) p.wx = Product{PK_B16KK, kk(N, M), N, 1};
+    // first layer: a bf16 copy of the input frames (N x ni, a few MB) buys the bf16-source kernel with its 256 x 256 tiles and 16-byte stores
+    // for the product whose 4 M floats of pre-activations per frame-line are its whole cost
+    else if (bf16_rec && h.first && h.wide && h.packs && (h.ni & 7) == 0 && gemm_tile256(N, M)) { p.wx = Product{PK_B16KK, 256, N, 1}; p.x_copy = 1; }
+    else if (bf16_gemm) p.wx = Product{PK_BF16, sq(N, M), N, 1};
+    else p.wx = Product{PK_F32, GEMM_BT, N, 1};
+    if (p.wx.kernel == PK_B16KK) p.moves |= 1 << PC_WX_FROM_BF16;
+    p.a2_rows = x_from_hbf && p.x_external ? h.ni : 0;    // (where Sbf is written: else nobody reads it)
+    // the fused softmax up to SMX_COLS classes; beyond, in the bf16 modes: f32-grade bf16 x 3 on 128 x 128 tiles (88 -> ~30 us at configs[4])
+    if (h.top) p.logits = nc <= SMX_COLS ? Product{PK_SOFTMAX_FUSED, 0, N, 1} : bf16_gemm && x3 && gemm_bf16_big(N, nc) ? Product{PK_X3_BIG, GB2_BT, N, 1} : Product{PK_F32, GEMM_BT, N, 1};
+    return p;
+  }
+  if (h.wide && bf16_rec && h.bwd_exact) {
+    // per-frame bf16 deltas and per-line bias sums; with bf16 GEMMs behind it nobody reads the f32 deltas of a persistent pass (16 bytes per
+    // lane and step, 0.17 ms per configs[4] minibatch): ensure_delta_f32 expands Dbf for a fallback product
+    p.writes |= PW_DBF;
+    if (bf16_gemm) p.skips |= PS_D;
+  }
+  if (h.top) {
+    // the softmax layer's W.d (split-K slabs) and x.d.  W.d depends on nothing the backward recurrence produces: where the top layer's plan says
+    // so (dwx) its slabs are items of THAT launch and only x.d stays in front of it -- or rides it too (xd).  Else in ONE launch: two small
+    // independent products, each mostly prologue and epilogue latency on its own (13.9 + 12.4 us back to back); bf16 modes, shapes that fill
+    // 128 x 128 tiles: two launches of the big-tile f32-grade kernel
+    const int sR = 1 + h.sm_ni;
+    const bool sm_big = bf16_gemm && x3 && gemm_bf16_big(sR, nc) && gemm_bf16_big(N, h.sm_ni);
+    const int ns = h.dwx ? h.dwx_nslabs : split(sR, nc, 1, sm_big ? GB2_BT : GEMM_BT);
+    const int pair = x3 ? PK_X3_PAIR : PK_F32_PAIR;
+    p.sm_wd = h.dwx ? Product{PK_NONE, GEMM_BT, sR, ns} : sm_big ? Product{PK_X3_BIG, GB2_BT, sR, ns} : Product{pair, GEMM_BT, sR, ns};
+    p.sm_xd = h.dwx ? Product{h.xd ? PK_NONE : PK_X3, GEMM_BT, N, 1} : sm_big ? Product{PK_X3_BIG, GB2_BT, N, 1} : Product{pair, GEMM_BT, N, 1};
+  }
+  // the weight gradient from both operands in bf16 as their producers left them (Sbf: the forward pass, Dbf: the persistent backward recurrence)
+  const bool dw16 = bf16_rec && h.bwd_persistent && h.fwd_sbf && h.bwd_exact && gemm_bf16_big(R, Cn);
+  const int rows = dw16 ? p.dw16_rows : R;
+  p.bias_out = rows < R;
+  // exact-f32 mode, wide layer: the backward products as f32-grade bf16 x 3 on 128 x 128 tiles -- what narrow layers already do inside their
+  // fused backward launch; gemm_x3 = 0 / clstm_net_set_strict_f32: the f32 MFMA
+  const bool x3_big = !bf16_gemm && h.wide && x3 && gemm_bf16_big(R, Cn);
+  const int ns = h.overlapped ? h.dw_slabs_per_dir
+                 : p.bias_out && gemm_tile256(rows, Cn) ? split_mc(rows, Cn, h.ndir)
+                 : dw16 && gemm_tile256(R, Cn) ? split_mc(R, Cn, h.ndir)
+                 : (bf16_gemm || x3_big) && gemm_bf16_big(R, Cn) ? split(R, Cn, h.ndir, GB2_BT) : split(R, Cn, h.ndir, GEMM_BT);
+  // the input deltas from the bf16 deltas and the bf16 pack of W_x^T
+  const bool has_dx = !h.first || h.want_dx0, dx16 = bf16_rec && h.bwd_persistent && h.bwd_exact && h.packs;
+  // ... and where the layer owes both from the same bf16 delta array: BOTH products as one launch (apart, each leaves a quarter of the chip
+  // idle).  Both on their big tiles, the x.d role's operands (contraction length M) by LDS-DMA
+  p.merged = dw16 && p.bias_out && !h.first && dx16 && h.gemm_stag == 2 && gemm_tile256(rows, Cn) && gemm_tile256(N, h.ni) && M % GB_BK == 0 && M >= 2 * GB_BK;
+  p.dw = h.overlapped ? Product{PK_NONE, GEMM_BT, R, ns} : dw16 ? Product{p.merged ? PK_DW_DX : PK_B16MC, p.dw16_tile, rows, ns}
+         : bf16_gemm ? Product{PK_BF16, sq(R, Cn), R, ns} : x3_big ? Product{PK_X3_BIG, GB2_BT, R, ns} : Product{PK_F32, GEMM_BT, R, ns};
+  if (has_dx)
+    p.dx = p.merged ? Product{PK_DW_DX, 256, N, 1} : dx16 ? Product{PK_B16KK, kk(N, h.ni), N, 1} : bf16_gemm ? Product{PK_BF16, sq(N, h.ni), N, 1}
+           : h.wide && x3 && gemm_bf16_big(N, h.ni) ? Product{PK_X3_BIG, GB2_BT, N, 1} : Product{PK_F32, GEMM_BT, N, 1};
+  p.a2_rows = dw16 && x_from_hbf && p.x_external ? h.ni : 0;
+  if (!dw16) p.needs |= PN_SOURCE | PN_DELTA_F32;   // the f32-source products read S and D
+  if (has_dx && p.dx.kernel != PK_DW_DX && p.dx.kernel != PK_B16KK) p.needs |= PN_DELTA_F32;
+  p.moves = (dw16 ? 1 << PC_DW_FROM_BF16 : 0) | (p.bias_out ? 1 << PC_DW_BIAS_OUT : 0) | (p.a2_rows ? 1 << PC_DW_X_EXTERNAL : 0) |
+            (p.merged ? 1 << PC_DW_DX_ONE_LAUNCH : 0) | (p.dx.kernel == PK_DW_DX || p.dx.kernel == PK_B16KK ? 1 << PC_DX_FROM_BF16 : 0);
+  return p;
 }
 
 // ---- the lock-step layer (lstm_wide.h): WHICH of its eleven kernels runs is decided once per pass by wide_plan, a pure function of a

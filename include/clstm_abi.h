@@ -522,6 +522,29 @@ int clstm_debug_wide_plan(const int* shape, int* plan);
  *   dwx -- the softmax layer's W.d slabs ride the launch; xd -- x.d form 0 (a launch of its own) / 1 (whole prologue) / 2 (producers);
  *   moves (bit c: the pass moves clstm_debug_path_count(c)).  Forward passes leave overlapped .. xd zero, backward passes fwd and saves. */
 int clstm_debug_narrow_plan(const int* shape, int* plan);
+/* Which kernels the matrix products around a layer's recurrence run -- the input projection W_x.x, the softmax layer's logits, its W.d and x.d,
+ * the layer's weight gradient and its input deltas -- with which tile, rows and split-K slabs, and what the pass writes for them
+ * (csrc/runtime.inc: product_plan, the one place that decides): host arithmetic, no net, no device.
+ * shape (35 ints, HOST in): pass (0 forward, 1 backward); ni, no, ndir, wide (lock-step layer); first, top, nlayers; bwd_exact (the padded bf16
+ *   backward rows are exactly 4 no: no % 32 == 0), kp16f_is_no (no % 128 == 0); N (frames), bs (lines); nclasses, sm_ni (inputs of the softmax
+ *   layer); precision (clstm_net_set_gemm_precision), gemm_x3_on, split_terms (options, read at net creation), strict
+ *   (clstm_net_set_strict_f32); gemm_b16mc, gemm_stag, pack_tiles, fuse_wx (options, read per pass); ncu, want_dx0
+ *   (clstm_net_enable_input_deltas); fwd_family, overlapped, dwx, xd (the layer's narrow plan: fwd / overlapped / dwx / xd; a wide layer: 0),
+ *   dw_slabs_per_dir, dwx_nslabs (slab counts of the Overlapped items' tables); the facts of earlier launches: below_hbf (the layer below ran
+ *   its persistent bf16 forward kernel and left bf16 outputs), fwd_sbf (this layer's forward pass ran persistent and wrote bf16 source rows),
+ *   bwd_persistent (its backward recurrence ran persistent), packs, above_packs (the bf16 packs of W_x exist for this layer / the layer above).
+ * plan (39 ints, HOST out): six products of four ints each -- kernel, tile (rows of an output tile: 64 / 128 / 192 / 256, 0 the fused
+ *   softmax's own), rows (it is launched with), slabs (split-K slabs per direction) -- in the order wx, logits (forward), sm_wd, sm_xd, dw, dx
+ *   (backward); kernel: 0 none (part of a recurrence launch), 1 gemm_f32, 2 gemm_bf16, 3 gemm_b16kk, 4 gemm_b16mc, 5 gemm_dw_dx, 6 gemm_x3,
+ *   7 gemm_x3_big, 8 gemm_x3_pair, 9 gemm_f32_pair, 10 softmax_fwd.  Then merged (dw and dx are one launch), bias_out (the bias row is laid
+ *   outside dw); dw16_rows, dw16_tile, x_external (rows and tile height of the bf16-source weight gradient and whether the x block fills whole
+ *   tiles of it: functions of the shape and the mode alone, equal in both passes whatever the facts say); a2_rows (rows the weight gradient
+ *   reads from the layer below's bf16 outputs, 0: copied into the source rows); x_copy (wx reads a bf16 copy of the input frames); fx_mode
+ *   (fuse_wx where the folded input projection has its operands, else 0: clstm_debug_wide_plan's fx_mode); tiled_pack (the repack is
+ *   k_pack_wide_tiles); stag, terms; writes (bit 0 Sbf, 1 Hbf, 2 Dbf and dbias), skips (f32 stores the persistent kernel may skip: bit 0 H,
+ *   1 the h columns of S, 2 D), needs (built first: bit 0 the f32 source rows, 1 the f32 deltas, 2 the f32 outputs of the layer below);
+ *   moves (bit c: the pass moves clstm_debug_path_count(c); 2 where wx is launched, 3, 4, 8, 13, 14 by the backward pass). */
+int clstm_debug_product_plan(const int* shape, int* plan);
 /* Which path of the alignment kernel every line of a minibatch takes (csrc/ctc.h: ctc_batch_plan, ctc_line_plan, ctc_scores_in_lds -- the
  * functions clstm_ctc_align_batch and the kernel's workgroups themselves decide with): host arithmetic, no net, no device.  Arguments as
  * clstm_ctc_align_batch's.  A line's path depends on the other lines of its minibatch through tile and smax.

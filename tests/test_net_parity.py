@@ -350,7 +350,7 @@ def test_bf16_lockstep_recurrence_tracks_the_f32_path(backend, ora32, monkeypatc
     monkeypatch.setenv("CLSTM_FORCE_WIDE", "1")      # the lock-step path on sizes the emulator can run
     rng = np.random.default_rng(23)
     ni, nc = 12, 6
-    before = [_path_count(backend, k) for k in range(7)]
+    before, before_products = [_path_count(backend, k) for k in range(7)], _product_counts(backend)
     params = OracleNet(ora32, ni, nh, nc, seed=0.222).get_params() * 20.0
     lines = synth_lines(rng, T, ni)
     trs = [rng.integers(1, nc, max(1, t // 3)).astype(np.int32) for t in T]
@@ -382,6 +382,7 @@ def test_bf16_lockstep_recurrence_tracks_the_f32_path(backend, ora32, monkeypatc
     dl = net.state(len(nh) - 1, 0, "d_gi")
     assert np.isfinite(dl).all() and np.abs(dl).max() > 0
     took = [_path_count(backend, k) - before[k] for k in range(7)]
+    _assert_product_moves(backend, before_products, nh, ni, nc, T, steps=2, force_wide=True)
     if took[1] > 0 and took[3] + took[4] > 0 and 4 * nh[-1] % 128 == 0:
         assert np.array_equal((dl.view(np.uint32) & 0xFFFF), np.zeros(dl.shape, np.uint32))
     if nh == [32, 32]:
@@ -525,6 +526,22 @@ def test_unidirectional_wide_layer_takes_the_round4_backward_kernels(backend, mo
         assert np.array_equal(got["1"], got["0"])
     else:
         assert_close(got["1"], got["0"], rtol=1e-3, atol=1e-9, scale_atol=2e-5, what="gradient, x3 vs f32 MFMA backward recurrence")
+
+
+def _product_counts(backend):
+    """the path counters of the products around the recurrences (product_rule.PRODUCT_COUNTERS: 2, 3, 4, 8, 13, 14)"""
+    import product_rule
+    return {c: _path_count(backend, c) for c in product_rule.PRODUCT_COUNTERS}
+
+
+def _assert_product_moves(backend, before, nh, ni, nc, T, steps=1, **kw):
+    """what moved since `before` is what runtime.inc:product_plan, restated in product_rule.py, says for `steps` forward + backward passes of
+    the net in precision 2 -- every plan on the way compared with the library's own"""
+    import narrow_rule
+    import product_rule
+    want = product_rule.net_moves(backend.lib, nh, ni, T, 2, narrow_rule.cus(backend.kind), nc=nc, **kw)
+    got = {c: n - before[c] for c, n in _product_counts(backend).items() if n != before[c]}
+    assert got == {c: steps * n for c, n in want.items()}, (got, want, steps)
 
 
 def _path_count(backend, which):
@@ -760,9 +777,10 @@ def test_bias_gradient_outside_the_bf16_weight_gradient_product(backend, ora32, 
     net = Network(ni, nh, nc, lib=backend.lib)
     net.set_params(params)
     net.set_gemm_precision(2)
-    before = _path_count(backend, 13)
+    before, before_products = _path_count(backend, 13), _product_counts(backend)
     net.set_inputs(lines); net.forward(); net.ctc(trs); net.backward()
     assert _path_count(backend, 13) - before == len(nh)
+    _assert_product_moves(backend, before_products, nh, ni, nc, T, force_wide=True)
     g = net.get_grads().astype(np.float64)
     o = 0
     for l, no in enumerate(nh):
@@ -805,7 +823,9 @@ def test_external_x_rows_agree_with_the_weight_gradient_tiles(ora32, nh):
         if step == 0:
             net.set_params(params)
             net.set_gemm_precision(2)
+        before_products = _product_counts(backend)
         net.set_inputs(lines); net.forward(); net.ctc(trs); net.backward()
+        _assert_product_moves(backend, before_products, nh, ni, nc, T)
         g = net.get_grads()
         assert np.isfinite(g).all()
         # the upper layer's parameter blocks: after layer 1's 2 x 4 blocks of nh0 x (1 + ni + nh0)
@@ -832,8 +852,9 @@ def _merged_launch_case(backend, ora32):
         net = Network(ni, nh, nc, lib=backend.lib)
         net.set_params(params)
         net.set_gemm_precision(2)
-        before = _path_count(backend, 14)
+        before, before_products = _path_count(backend, 14), _product_counts(backend)
         net.set_inputs(lines); net.forward(); net.ctc(trs); net.backward()
+        _assert_product_moves(backend, before_products, nh, ni, nc, T, force_wide=True, gemm_stag=int(stag))
         res.append((net.get_grads(), net.state(0, 0, "d_gi"), _path_count(backend, 14) - before))
     backend.lib.call("clstm_debug_set_option", None, 0)
     assert res[0][2] == 1 and res[1][2] == 0, (res[0][2], res[1][2])       # the upper layer took the merged launch / did not

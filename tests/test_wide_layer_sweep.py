@@ -7,7 +7,8 @@ net.inc:Net::wide_shape; the weight packs: Net::repack) from the cell count -- t
 lstm_xcd_bwd_bf16_c32), no % 32, no % 128, no % 4, ntile <= 32 -- and from the line count: 16-line blocks, mt = 1 / 2 / 4 and ept =
 1 / 2 / 4 at 8 / 16 line-block x direction groups, chunks of 8 / ndir blocks per launch, mts of the per-step forward at 16 / 32 lines.
 wide_geometry() restates that rule ONCE in Python; every case asserts the path counters 0, 1, 6, 9, 11 it predicts -- which kernel
-ran follows from the rule, never from the result.
+ran follows from the rule, never from the result -- and the counters 2, 3, 4, 8, 13, 14 of the products around the recurrence as
+product_rule.py predicts them for the same shape (runtime.inc:product_plan), every plan compared with the library's.
 
 f32 modes (default: persistent forward + x3 backward; strict_f32: the f32 MFMA backward; CLSTM_XCD_REC=0: the per-step kernels) are
 test_net_parity.run_case at its default bars, weights init x scale_for(no), lr lr_for(no); test_the_inputs_are_adequate proves from
@@ -43,12 +44,13 @@ import pytest
 from common import ATOL, ROOT, RTOL, oracle_minibatch, synth_lines
 if ROOT not in sys.path:          # (run as a script for the table: no conftest.py has put the package on the path)
     sys.path.insert(0, ROOT)
+import product_rule
 import test_net_parity
 from test_net_parity import DELTAS, STATES, run_case, _forget_debug_options, _path_count  # noqa: F401  (autouse fixture)
 from test_cell_count_sweep import QUANTITIES, T_ORACLE, both, cus, ids, only_gpu, recording
 
 PC_FWD_PERSISTENT, PC_BWD_PERSISTENT, PC_FWD_FUSED_WX, PC_BWD_C32, PC_BWD_X3 = 0, 1, 6, 9, 11
-COUNTERS = (PC_FWD_PERSISTENT, PC_BWD_PERSISTENT, PC_FWD_FUSED_WX, PC_BWD_C32, PC_BWD_X3)
+COUNTERS = (PC_FWD_PERSISTENT, PC_BWD_PERSISTENT, PC_FWD_FUSED_WX, PC_BWD_C32, PC_BWD_X3) + product_rule.PRODUCT_COUNTERS
 SIZES = [129, 130, 143, 144, 145, 148, 159, 160, 161, 191, 192, 193, 255, 256, 257, 320, 321, 384, 385, 448, 449, 511, 512, 513, 528, 576]
 LINE_COUNTS = [1, 16, 17, 32, 33, 64, 65, 128, 129, 257]
 EMU_CHILD_CUS = 104               # 8 x 13 cell tiles: the persistent kernels up to 208 cells
@@ -153,7 +155,7 @@ PLAN_KERNELS = {1: "xcd_fwd_f32", 2: "xcd_fwd_bf16<%d>", 3: "xcd_fwd_bf16_fx<%d>
 def library_plan(lib, no, ni, ndir, nlines, tmax, precision, strict, ncu, xcd_rec=True, frames=None):
     """{fwd, fwd_launches, bwd, bwd_launches, moves} as wide_geometry names them, from the library's plans of the two passes"""
     bf16, out, moves = precision == 2, {}, 0
-    sbf = bf16 and ni % 8 == 0 and no % 8 == 0 and kp16_bwd(no) == 4 * no                     # net.inc:Net::wants_sbf
+    sbf = bf16 and ni % 8 == 0 and no % 8 == 0 and kp16_bwd(no) == 4 * no                     # runtime.inc:product_plan, PW_SBF
     for fwd in (1, 0):
         shape = (ctypes.c_int * 20)(fwd, no, ni, ndir, nlines, tmax, nlines * tmax if frames is None else frames,
                                     kp_fwd(no) if fwd else kp_bwd(no), kp16_fwd(no) if fwd else kp16_bwd(no), bf16,
@@ -367,6 +369,14 @@ def moved_since(backend, before):
     return {c: _path_count(backend, c) - before[c] for c in COUNTERS if _path_count(backend, c) != before[c]}
 
 
+def product_moves(backend, geo, no, ni, uni, T, precision, strict, check_dx=False):
+    """what the products of one forward + backward of the one-layer net move (product_rule.step_moves), given the recurrence kernels the
+    wide rule names; with every plan the library's own"""
+    return product_rule.step_moves(backend.lib, [no], ni, len(T), sum(T), precision, ["xcd" in geo["fwd"]], ["xcd" in geo["bwd"]],
+                                   fx=(0,) if geo["moves"].get(PC_FWD_FUSED_WX) else (), uni=uni, nc=shape(backend, no)[1], strict=strict,
+                                   ncu=cus(backend.kind), want_dx0=check_dx)
+
+
 def head(name, no, geo, moved):
     return "SWEEP %s class=%r fwd=%sx%d bwd=%sx%d moved=%r" % (name, klass(no), geo["fwd"], geo["fwd_launches"], geo["bwd"], geo["bwd_launches"], moved)
 
@@ -391,7 +401,7 @@ def f32_case(backend, ora32, name, no, mode, uni=False, check_dx=False, **shape_
             moved = moved_since(backend, before)
             print("%s worst=%.3f %s" % (head(name, no, geo, moved), max(worst.values()) if worst else 0.0,
                                         " ".join("%s=%.3f" % (q.replace(" ", "_"), f) for q, f in worst.items())))
-    assert moved == geo["moves"], (moved, geo["moves"])
+    assert moved == {**geo["moves"], **product_moves(backend, geo, no, ni, uni, T, 0, m.get("strict", False), check_dx)}, (moved, geo["moves"])
     assert set(worst) == set(QUANTITIES) | ({"input deltas"} if check_dx else set())
     assert worst.get("input deltas", 0.0) <= 1.0, worst
 
@@ -454,7 +464,7 @@ def bf16_case(backend, ora32, name, no, mode, uni=False, **shape_kw):
                 head(name, no, geo, moved), max(ratio.values(), default=0.0), ratio.get("outputs", 0.0), max((ratio[k] for k in states), default=0.0),
                 ratio.get("gradient", 0.0), dq["outputs"], max(dq[k] for k in dq if isinstance(k, tuple)), dq["gradient"],
                 err.get("outputs", 0.0), max((err[k] for k in states), default=0.0), err.get("gradient", 0.0)))
-    assert moved == geo["moves"], (moved, geo["moves"])
+    assert moved == {**geo["moves"], **product_moves(backend, geo, no, ni, uni, T, 2, False)}, (moved, geo["moves"])
     assert set(err) == set(dq) and np.isfinite(list(err.values())).all()
     over = {k: (err[k], bar[k]) for k in err if not err[k] <= bar[k]}
     assert not over, "kernel error beyond min(4 D_q, cap) (error, bar): %r" % over
