@@ -141,6 +141,7 @@ _SIGS = {
     "clstm_debug_set_option": [C.c_char_p, _I],
     "clstm_debug_set_device_error": [_I, _I],
     "clstm_debug_wide_plan": [_P, _P],
+    "clstm_debug_net_holds": [_P, _P],
     "clstm_debug_narrow_plan": [_P, _P],
     "clstm_debug_product_plan": [_P, _P],
     "clstm_debug_ctc_plan": [_I, _P, _P, _P, _I, _P, _P],
@@ -151,7 +152,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGS) + ["clstm_last_error", "clstm_abi_version"
 # host-arithmetic debug entries (no net, no device) added since ABI version 1: a library built before one of them existed still loads --
 # the emulator's build directory can outlive the sources it was made from when their time stamps move backwards -- and a CALL of the
 # entry there raises AttributeError.  (libclstm_hip.so must export them all: tests/test_abi_exports.py)
-_LATE = {"clstm_debug_wide_plan", "clstm_debug_narrow_plan", "clstm_debug_product_plan", "clstm_debug_ctc_plan"}
+_LATE = {"clstm_debug_net_holds", "clstm_debug_wide_plan", "clstm_debug_narrow_plan", "clstm_debug_product_plan", "clstm_debug_ctc_plan"}
 
 
 class Lib:

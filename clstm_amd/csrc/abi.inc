@@ -16,13 +16,7 @@ struct clstm_net {
 #define EW(kernel, len, ...) \
   CLSTM_LAUNCH(kernel, dim3(nblocks(len)), dim3(256), 0, g_stream, __VA_ARGS__); check_launch();
 
-#define REQUIRE_CURRENT(h) REQUIRE(!(h)->net.next.valid, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)")
-#define REFUSE_NOSAVE(h, what) REQUIRE(!(h)->net.nosave, what ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)")
-// what clstm_net_score and clstm_net_beam ask of the net: a current minibatch whose outputs stand (they read Z and nothing else)
-#define REQUIRE_OUTPUTS(h) \
-  REQUIRE(h, "null argument"); \
-  REQUIRE_CURRENT(h); \
-  REQUIRE((h)->net.N > 0, "set_batch first")
+// What a per-minibatch entry point needs of the net is ONE line at its top: Net::require(needs, name) (net.inc; the table: include/clstm_abi.h).
 struct clstm_charlm { CharLm lm; };
 struct clstm_normalizer {
   std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
@@ -247,33 +241,33 @@ int clstm_net_set_gradient_clip(clstm_net* h, float c) {
 int clstm_net_set_batch(clstm_net* h, const int* T_h, int bs) { ABI_BEGIN h->net.set_batch(T_h, bs); ABI_END }
 int clstm_net_set_inputs_h(clstm_net* h, const float* x) {
   ABI_BEGIN
-  REQUIRE(h->net.N > 0, "set_batch first");
-  h->net.next.valid = false;   // (a declared next minibatch whose frames the caller replaces is not that minibatch any more)
+  h->net.require(Net::NEED_BATCH, "clstm_net_set_inputs_h");
+  h->net.next_adopted();   // (a declared next minibatch whose frames the caller replaces is not that minibatch any more)
   h->net.ensure_training_buffers();
   copy_h2d(h->net.X.p, x, (size_t)h->net.N * h->net.desc.ninput);
-  h->net.src0_ready = false;
+  h->net.frames_ingested(false);
   ABI_END
 }
 int clstm_net_set_inputs_d(clstm_net* h, const float* x) {
   ABI_BEGIN
-  h->net.next.valid = false;
+  h->net.require(Net::NEED_BATCH, "clstm_net_set_inputs_d");
+  h->net.next_adopted();
   net_ingest(h->net, h->ctc, x);
   ABI_END
 }
 // (after clstm_net_train_step_next: the declared minibatch becomes the current one -- its outputs are addressable, and a later step
 //  call declares and ingests it again)
-int clstm_net_forward(clstm_net* h) { ABI_BEGIN h->net.next.valid = false; h->net.forward(); ABI_END }
+int clstm_net_forward(clstm_net* h) { ABI_BEGIN h->net.require(Net::NEED_BATCH, "clstm_net_forward"); h->net.next_adopted(); h->net.forward(); ABI_END }
 int clstm_net_outputs(clstm_net* h, float** p, float** d) {
   if (p) *p = h->net.Z.p;
   if (d) *d = h->net.Dz.p;
   return 0;
 }
-int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN REQUIRE_CURRENT(h); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
-int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN REFUSE_NOSAVE(h, "clstm_net_set_output_deltas_h"); copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
+int clstm_net_get_outputs_h(clstm_net* h, float* p) { ABI_BEGIN h->net.require(Net::NEED_OUTPUTS, "clstm_net_get_outputs_h"); copy_d2h(p, h->net.Z.p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
+int clstm_net_set_output_deltas_h(clstm_net* h, const float* p) { ABI_BEGIN h->net.require(Net::NEED_PASS, "clstm_net_set_output_deltas_h"); copy_h2d(h->net.Dz.p, p, (size_t)h->net.N * h->net.desc.nclasses); ABI_END }
 int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* aligned_h) {
   ABI_BEGIN
-  REQUIRE_CURRENT(h);
-  REFUSE_NOSAVE(h, "clstm_net_ctc");
+  h->net.require(Net::NEED_PASS, "clstm_net_ctc");
   net_ctc(h->net, h->ctc, Minibatch{nullptr, h->net.bs, nullptr, labels_h, L_h}, aligned_h);
   ABI_END
 }
@@ -282,8 +276,9 @@ int clstm_net_ctc(clstm_net* h, const int* labels_h, const int* L_h, float* alig
 int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int* cand_line_h, int ncand, float* score_h,
                     float* vscore_h, int* path_h) {
   ABI_BEGIN
-  REQUIRE_OUTPUTS(h);
+  REQUIRE(h, "null argument");
   Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_score");
   REQUIRE(score_h || vscore_h || path_h, "clstm_net_score: score_h, vscore_h and path_h are all NULL");
   REQUIRE(labels_h && L_h && ncand > 0, "null argument / no candidates");
   std::vector<int> soff, states;
@@ -298,8 +293,9 @@ int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int
 // n-best transcripts of the current minibatch's lines: the guards and guarantees of clstm_net_score (reads Z only, BeamWorkspace)
 int clstm_net_beam(clstm_net* h, int beam, int nbest, int* nhyp_h, int* len_h, float* score_h, int* labels_h) {
   ABI_BEGIN
-  REQUIRE_OUTPUTS(h);
+  REQUIRE(h, "null argument");
   Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_beam");
   REQUIRE(nhyp_h && score_h, "clstm_net_beam: nhyp_h and score_h are required");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam: 1 <= nbest <= beam <= 32");
   RoctxRange range_("clstm:beam");
@@ -311,8 +307,9 @@ int clstm_net_beam(clstm_net* h, int beam, int nbest, int* nhyp_h, int* len_h, f
 int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm, float weight, float bonus, int* nhyp_h, int* len_h,
                       float* score_h, float* am_score_h, int* labels_h) {
   ABI_BEGIN
-  REQUIRE_OUTPUTS(h);
+  REQUIRE(h, "null argument");
   Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_beam_lm");
   REQUIRE(lm, "clstm_net_beam_lm: the language model is required");
   REQUIRE(nhyp_h && score_h, "clstm_net_beam_lm: nhyp_h and score_h are required");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam_lm: 1 <= nbest <= beam <= 32");
@@ -323,12 +320,11 @@ int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm,
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
 }
-int clstm_net_backward(clstm_net* h) { ABI_BEGIN REQUIRE_CURRENT(h); REFUSE_NOSAVE(h, "clstm_net_backward"); h->net.backward(); ABI_END }
+int clstm_net_backward(clstm_net* h) { ABI_BEGIN h->net.require(Net::NEED_PASS, "clstm_net_backward"); h->net.backward(); ABI_END }
 int clstm_net_enable_input_deltas(clstm_net* h, int on) { h->net.want_dx0 = on != 0; return 0; }
 int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
   ABI_BEGIN
-  REFUSE_NOSAVE(h, "clstm_net_get_input_deltas_h");
-  REQUIRE(h->net.want_dx0 && h->net.dX0.p, "input deltas not enabled / no backward yet");
+  h->net.require(Net::NEED_DX0, "clstm_net_get_input_deltas_h");
   copy_d2h(dx, h->net.dX0.p, (size_t)h->net.N * h->net.desc.ninput);
   ABI_END
 }
@@ -336,9 +332,8 @@ int clstm_net_get_input_deltas_h(clstm_net* h, float* dx) {
 int clstm_net_update(clstm_net* h) { ABI_BEGIN PassLeft nothing; h->net.update(nothing); ABI_END }
 int clstm_net_decode(clstm_net* h, int* cls, int* locs, int* cnt) {
   ABI_BEGIN
-  REQUIRE_CURRENT(h);
   Net& n = h->net;
-  REQUIRE(n.N > 0, "set_batch first");
+  n.require(Net::NEED_OUTPUTS, "clstm_net_decode");
   run_decode(h->dec, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, cls, locs, cnt, g_stream);
   ABI_END
 }
@@ -352,11 +347,12 @@ static void net_predict(clstm_net* h, const int* T_h, int bs, const float* x, bo
   if (x_host) HIPCHECK(hipMemcpyAsync(n.X.p, x, nx * sizeof(float), hipMemcpyHostToDevice, g_stream));
   else {   // device frames: one launch, the line offsets riding it (ops.h: k_ingest_predict)
     const int nbx = nblocks(nx);
-    CLSTM_LAUNCH(k_ingest_predict, dim3(nbx + (n.lo_pending ? 1 : 0)), dim3(256), 0, g_stream, x, n.X.p, nx, nbx,
-                 n.lo_pending ? n.lo_stage : (const int*)nullptr, n.line_off.p, 2 * n.bs + 1);
+    const int* const lo = n.unsent_offsets();
+    CLSTM_LAUNCH(k_ingest_predict, dim3(nbx + (lo ? 1 : 0)), dim3(256), 0, g_stream, x, n.X.p, nx, nbx, lo, n.line_off.p, 2 * n.bs + 1);
     check_launch();
-    if (n.lo_pending) { n.ring.commit(g_stream); n.lo_pending = false; }
+    if (lo) n.offsets_sent(g_stream);
   }
+  n.frames_ingested(false);
   n.predict();
   run_decode(h->dec, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, cls, locs, cnt, g_stream, conf);
   // (as clstm_net_decode: the device error words are left to the next synchronisation point of the training loop)
@@ -412,10 +408,10 @@ int clstm_net_device_bytes(clstm_net* h, long long* bytes) {
 }
 int clstm_net_get_state_h(clstm_net* h, int layer, int dir, int which, float* out) {
   ABI_BEGIN
-  REQUIRE_CURRENT(h);
   Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_get_state_h");
   REQUIRE(layer >= 0 && layer < (int)n.L.size() && dir >= 0 && dir < n.ndir && which >= 0 && which <= 9, "bad state selector");
-  if (which != 5) REFUSE_NOSAVE(h, "clstm_net_get_state_h (which != 5)");
+  if (which != 5) n.require(Net::NEED_PASS, "clstm_net_get_state_h (which != 5)");
   Layer& y = n.L[layer];
   n.tmp.reserve((size_t)n.N * y.no);
   if (which >= 6) n.ensure_delta_f32(layer);   // (a persistent bf16 backward pass leaves the deltas as bf16 only)
@@ -439,7 +435,7 @@ int clstm_net_set_gemm_precision(clstm_net* h, int mode) {
   if (rec != n.bf16_rec) n.packed_dirty = true;   // the other weight packing is needed
   n.bf16_gemm = mode >= 1;
   n.bf16_rec = rec;
-  if (n.N > 0 && rec)   // a batch is already declared: make room for the bf16 operand copies
+  if (n.holds.batch != Net::Holds::NONE && rec)   // a batch is already declared: make room for the bf16 operand copies
     for (auto& y : n.L)
       if (y.wide) n.reserve_wide_rings(y);
   ABI_END
@@ -528,7 +524,6 @@ static std::vector<StateEntry> state_walk(const Net& n) {
 }
 // a reference Sequence is rectangular (size x rows x cols): every line of the batch must have the same length
 static int states_T(const Net& n) {
-  REQUIRE(n.N > 0, "no batch: run forward() (or set_states) first");
   const int T = n.line_off_h[1] - n.line_off_h[0];
   for (int b = 0; b < n.bs; b++)
     REQUIRE(n.line_off_h[b + 1] - n.line_off_h[b] == T, "state externalisation needs equal-length lines (a Sequence is size x rows x cols)");
@@ -565,7 +560,7 @@ static long long states_total(const Net& n, int T) {
 int clstm_net_n_states(clstm_net* h, long long* out) {
   ABI_BEGIN
   REQUIRE(out, "null argument");
-  REFUSE_NOSAVE(h, "clstm_net_n_states");
+  h->net.require(Net::NEED_PASS, "clstm_net_n_states");
   *out = states_total(h->net, states_T(h->net));
   ABI_END
 }
@@ -617,17 +612,14 @@ static void states_transfer(clstm_net* h, float* data, long long total, bool get
       }
       copy_h2d(y.G.p, a.G[l].data(), a.G[l].size()); copy_h2d(y.C.p, a.C[l].data(), a.C[l].size());
       copy_h2d(y.H.p, a.H[l].data(), a.H[l].size()); copy_h2d(y.S.p, a.S[l].data(), a.S[l].size());
-      y.sbf_ready = false;   // the bf16 copies made by the forward pass no longer match these states
-      y.h_f32_valid = y.sh_valid = y.sx_valid = true;   // (the f32 arrays were just written whole)
-      y.sx_valid = true;
     }
-    n.src0_ready = true;
+    n.states_set();   // (the f32 arrays were just written whole; the bf16 copies made by the forward pass no longer match them)
   }
 }
 int clstm_net_get_states_h(clstm_net* h, float* data, long long total) {
   ABI_BEGIN
   REQUIRE(data, "null argument");
-  REFUSE_NOSAVE(h, "clstm_net_get_states_h");
+  h->net.require(Net::NEED_PASS, "clstm_net_get_states_h");
   states_transfer(h, data, total, true);
   ABI_END
 }
@@ -810,6 +802,15 @@ int clstm_debug_path_count(int which, long long* out_h) {
     return 0;
   }
   *out_h = g_path_count[which];
+  ABI_END
+}
+int clstm_debug_net_holds(clstm_net* h, int* out) {   // host only: what the net holds (net.inc: Net::Holds), nothing enqueued, no device memory touched
+  ABI_BEGIN
+  REQUIRE(h && out, "null argument");
+  const Net& n = h->net;
+  const int rec[8] = {n.bs, (int)std::min<long long>(n.N, 2147483647LL), n.holds.batch, n.holds.training_buffers, n.holds.forward, n.holds.frames,
+                      n.holds.offsets_sent, n.holds.dx0};
+  memcpy(out, rec, sizeof(rec));
   ABI_END
 }
 int clstm_debug_wide_plan(const int* shape, int* plan) {   // host arithmetic only: no net, no device (runtime.inc:wide_plan)

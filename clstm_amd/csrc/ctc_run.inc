@@ -45,6 +45,10 @@ static void expand_transcripts(const int* labels_h, const int* L_h, int n, std::
     soff[b + 1] = soff[b] + 2 * L + 1;
   }
 }
+// target states are classes: the one statement of this refusal (the alignment, the plan's description, the score, check_minibatch)
+static void check_target_classes(int nc, const int* states_h, int ns) {
+  for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+}
 // the batch arithmetic of a minibatch (ctc.h: ctc_batch_plan) from its offsets, with the refusals run_ctc has always made
 static CtcBatchPlan ctc_minibatch_plan(int nc, const int* line_off_h, const int* state_off_h, int bs) {
   int smax = 1, tmax = 1;
@@ -72,7 +76,7 @@ static void describe_ctc_plan(int nc, const int* line_off_h, const int* states_h
   REQUIRE(bs > 0 && nc >= 1 && line_off_h && states_h && state_off_h && batch_plan_h && line_plan_h, "empty batch / null argument");
   for (int b = 0; b < bs; b++)
     REQUIRE(line_off_h[b + 1] >= line_off_h[b] && state_off_h[b + 1] >= state_off_h[b], "bad offsets");
-  for (int i = 0; i < state_off_h[bs]; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+  check_target_classes(nc, states_h, state_off_h[bs]);
   const CtcBatchPlan bp = ctc_minibatch_plan(nc, line_off_h, state_off_h, bs);
   batch_plan_h[0] = bp.tile; batch_plan_h[1] = bp.smax; batch_plan_h[2] = bp.ncp; batch_plan_h[3] = bp.smem;
   const int cap = ctc_region_words(ctc_lds_layout(bp.tile, bp.ncp, bp.smax), bp.tile);
@@ -104,7 +108,7 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
     lo[b + 1] += lo[b + 1] & 1;   // (8-byte alignment of those doubles)
   }
   const int ns = state_off_h[bs];
-  for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+  check_target_classes(nc, states_h, ns);
   w.lat.reserve((size_t)(lo[bs] > 0 ? lo[bs] : 1));
   ctc_distinct_classes(nc, states_h, state_off_h, bs, w.nu, w.seen);
   const std::vector<int>& nus = w.nu;
@@ -218,8 +222,7 @@ static void plan_ctc_score(ScorePlan& pl, int nc, const int* line_off_h, int bs,
     REQUIRE(state_off_h[c] >= 0 && state_off_h[c + 1] - state_off_h[c] >= 1, "bad offsets (a candidate has at least one state)");
     if (cand_line_h) REQUIRE(cand_line_h[c] >= 0 && cand_line_h[c] < bs, "cand_line out of range");
   }
-  const int ns = state_off_h[ncand];
-  for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
+  check_target_classes(nc, states_h, state_off_h[ncand]);
   // items in candidate order first; T = 0 lines have no lattice (the caller fills -inf)
   pl.path_off.assign(ncand + 1, 0);
   struct Cand { int c, b, T, S, form; };

@@ -46,15 +46,35 @@ struct Layer {
   DevBuf<float> G, C, H, D, dH, S;
   DevBuf<unsigned short> Hbf;  // per-frame bf16 h of both directions written by the persistent forward kernel (A operand of the next layer's W_x product)
   DevBuf<unsigned short> WtbT; // bf16 W_x, k-contiguous ([M][ni]): B operand of that product
-  bool hbf_valid = false;      // this forward pass ran the persistent kernel and it wrote Hbf
   DevBuf<unsigned short> Sbf;  // bf16 source rows [x | h_{t-1} | 1] per direction (x: k_source_x_bf16, h: the persistent forward kernel)
-  bool sbf_ready = false;      // ... complete for this forward pass
-                               // (except their x columns where ProductPlan::a2_rows says the weight-gradient GEMM reads those from the layer below's Hbf)
-  long long sbf_one_key = -1;  // batch geometry (N) the constant bias column of Sbf was written for
-  bool d_f32_valid = true;     // D (f32 gate deltas) is current (a persistent bf16 backward pass may leave only Dbf)
-  bool sx_valid = true;        // the [1 | x] columns of S (f32) are current (built lazily when the bf16 rows serve the weight gradient)
-  bool h_f32_valid = true;     // the f32 outputs H are current (a persistent bf16 forward pass of a lower layer leaves only Hbf)
-  bool sh_valid = true;        // the h_{t-1} columns of S (f32) are current (... only Sbf)
+  long long sbf_one_key = -1;  // batch geometry (N) the constant bias column of Sbf was written for: a cache key of that column, not a fact of a pass
+  // ---- the layer record: which copies of this layer's arrays are current.  Written by the five transitions below and by Net::ensure_* (each its
+  // own member) and by nothing else; read by Net::product_shape, the ensure_* functions and the forward scheduler.
+  struct Current {
+    bool h_f32 = true;         // the f32 outputs H (a persistent bf16 forward pass of a lower layer leaves only Hbf)
+    bool sx = true;            // the [1 | x] columns of S (f32) (built lazily when the bf16 rows serve the weight gradient)
+    bool sh = true;            // the h_{t-1} columns of S (f32) (a persistent bf16 forward pass may leave only Sbf)
+    bool d_f32 = true;         // D, the f32 gate deltas (a persistent bf16 backward pass may leave only Dbf)
+    bool hbf = false;          // Hbf: this forward pass ran the persistent kernel and it wrote Hbf
+    bool sbf = false;          // Sbf: complete for this forward pass (except the x columns where ProductPlan::a2_rows says the weight-gradient
+                               // GEMM reads those from the layer below's Hbf)
+  } cur;
+  // a saving forward pass begins; rows0: this is layer 0 and the ingest has written its [1 | x] columns already (Net::Holds::frames)
+  void forward_begins(bool rows0) { cur.sx = rows0; }
+  // the forward recurrence left ...: every family says so -- the per-line, batched-MFMA and fused launches store everything (all false)
+  void recurrence_left(bool persistent, bool skip_h, bool skip_s, bool wrote_hbf, bool wrote_sbf) {
+    cur.hbf = persistent && wrote_hbf; cur.sbf = persistent && wrote_sbf;
+    cur.h_f32 = !(persistent && skip_h); cur.sh = !(persistent && skip_s);
+  }
+  void backward_left(bool skipped_d) { cur.d_f32 = !skipped_d; }   // the backward recurrence left the f32 deltas, or only Dbf
+  // predict begins (no-save kernels: narrow layers in f32 mode): S is not written, H is; no bf16 copy is made.  Sbf is not touched, so
+  // sbf_one_key stands; D is not touched, so d_f32 stands
+  void predict_begins() { cur.sx = cur.sh = false; cur.h_f32 = true; cur.sbf = cur.hbf = false; }
+  // clstm_net_set_states_h wrote G, C, H and S whole: the f32 arrays are current and the bf16 copies the forward pass made (Sbf, Hbf) no longer
+  // match them.  Sbf's constant column is still what sbf_one_key says.  (hbf used to stay set here.  It could not feed a stale Hbf to a
+  // product: the only backward reader of the layer below's Hbf is the bf16-source weight gradient -- ProductPlan::a2_rows, which asks for
+  // THIS layer's sbf, cleared here on every layer -- and a forward pass runs the layer below first.  Cleared all the same: it is not true.)
+  void states_set() { cur.h_f32 = cur.sx = cur.sh = true; cur.sbf = cur.hbf = false; }
   DevBuf<unsigned short> Dbf;  // per-frame bf16 gate deltas written by the persistent backward kernel (A operand of the x.d GEMM)
   DevBuf<float> dbias;         // [bs][ndir][no][4] per-line sums of those deltas (the bias row of the weight gradient), same kernel
   DevBuf<float> partial;       // stacked nets: this layer's own split-K slabs of the weight gradient (reduced behind the LAST recurrence of the pass)
@@ -76,11 +96,13 @@ struct Minibatch {
   const int* T; int bs; const float* x; const int* labels; const int* L;
   bool given() const { return T && x && labels && L && bs > 0; }
 };
-// frames of a minibatch whose line lengths are acceptable
+// frames of a minibatch whose line lengths are acceptable: every refusal line lengths can earn, made here and nowhere else
 static long long batch_frames(const int* T_h, int nb) {
+  REQUIRE(T_h && nb > 0, "empty batch");
   long long n = 0;
   for (int b = 0; b < nb; b++) { REQUIRE(T_h[b] >= 0, "negative line length"); n += T_h[b]; }
   REQUIRE(n > 0, "batch has no frames");
+  REQUIRE(n < 2147483000LL, "batch has too many frames");   // (the line offsets are ints)
   return n;
 }
 // (host-fed steps) the pinned word the step's last kernel writes `id` into, and that number: Net::HostFeed::stage
@@ -121,20 +143,51 @@ struct Net {
   bool want_dx0 = false;
   // batch
   int bs = 0, tmax = 0;
-  bool src0_ready = false;    // layer 0's source rows [1 | x] already written by set_inputs_d
   long long N = 0;
   std::vector<int> line_off_h;
   DevBuf<int> line_off;            // [bs + 1] first frame of each line | [bs] dispatch order (set_batch)
   std::vector<int> order_h;
   PinnedRing ring;
-  const int* lo_stage = nullptr;   // pinned copy of the line offsets not yet on the device
-  bool lo_pending = false;
+  const int* lo_stage = nullptr;   // pinned copy of the line offsets (unsent_offsets: while they are not on the device)
+  // ---- the minibatch record: which minibatch this net holds and which of its results stand.  Plain data, reported as it is by
+  // clstm_debug_net_holds.  It changes through the transitions below and declare_batch / reserve_batch, all methods of Net; step.inc and
+  // abi.inc call those and ask require(), and assign nothing.  (Parameters are not the minibatch's: packed_dirty, the epochs, training.)
+  struct Holds {
+    enum Batch { NONE, CURRENT, NEXT };       // whose geometry bs / N / tmax / line_off_h are: nobody's; the current minibatch's; a declared NEXT one's, which a
+                                              // step's tail declared and ingested behind its last launch -- outputs of that minibatch do not exist
+    enum Forward { NO_PASS, SAVED, NOSAVE };  // no forward pass of this minibatch yet; one that saved what a backward pass needs; predict's, which saved nothing
+    enum Frames { NO_FRAMES, BLOCK, ROWS };   // its frames: nowhere; in the input block X; in X and in layer 0's source rows [1 | x]
+    int batch = NONE;
+    int training_buffers = 0;                 // the buffers are those of a training pass (0: the forward-only geometry of predict; reserve_batch)
+    int forward = NO_PASS;
+    int frames = NO_FRAMES;
+    int offsets_sent = 0;                     // the line offsets and the dispatch order are on the device (or ride a launch already enqueued)
+    int dx0 = 0;                              // a backward pass of this minibatch has written dX0
+  } holds;
+  // declared: declare_batch (resets the record; a declared next minibatch is dropped by it).  The other transitions:
+  void offsets_sent(hipStream_t s) { ring.commit(s); holds.offsets_sent = 1; }   // s: the stream of the copy / the launch that reads the pinned slot
+  const int* unsent_offsets() const { return holds.offsets_sent ? nullptr : lo_stage; }
+  void frames_ingested(bool rows) { holds.frames = rows ? Holds::ROWS : Holds::BLOCK; }
+  void forward_ran(bool saved) { holds.forward = saved ? Holds::SAVED : Holds::NOSAVE; }
+  void backward_ran() { holds.dx0 = want_dx0; }
+  void next_declared(const Minibatch& m) { next.remember(m); holds.batch = Holds::NEXT; }   // (by a step's tail: declared, ingested, its alignment prepared)
+  bool next_is(const Minibatch& m) const { return holds.batch == Holds::NEXT && holds.frames == Holds::ROWS && holds.offsets_sent && next.matches(m); }
+  void next_adopted() { if (holds.batch == Holds::NEXT) holds.batch = Holds::CURRENT; }   // the step that brings it; clstm_net_forward and clstm_net_set_inputs_*
+  void states_set() { frames_ingested(true); forward_ran(true); for (auto& y : L) y.states_set(); }   // clstm_net_set_states_h wrote every array of a forward pass
+  // The one guard of the per-minibatch entry points (abi.inc; the table is in include/clstm_abi.h): what the caller `who` needs of the record.
+  enum Need { NEED_BATCH = 1, NEED_CURRENT = 2, NEED_SAVED = 4, NEED_BACKWARD = 8,
+              NEED_OUTPUTS = NEED_BATCH | NEED_CURRENT, NEED_PASS = NEED_OUTPUTS | NEED_SAVED, NEED_DX0 = NEED_PASS | NEED_BACKWARD };
+  void require(int needs, const char* who) const {
+    REQUIRE(!(needs & NEED_BATCH) || holds.batch != Holds::NONE, "set_batch first");
+    REQUIRE(!(needs & NEED_CURRENT) || holds.batch != Holds::NEXT, "no current minibatch: the last clstm_net_train_step_next replaced it with the declared next one (its outputs are not addressable any more)");
+    REQUIRE(!(needs & NEED_SAVED) || holds.forward != Holds::NOSAVE, std::string(who) + ": the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass (run clstm_net_forward or a training step first)");
+    REQUIRE(!(needs & NEED_BACKWARD) || (want_dx0 && holds.dx0), "input deltas not enabled / no backward yet");
+  }
   void flush_line_off() {
-    if (!lo_pending) return;
+    if (holds.offsets_sent) return;
     hipStream_t s = stream();
     HIPCHECK(hipMemcpyAsync(line_off.p, lo_stage, (2 * bs + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    ring.commit(s);
-    lo_pending = false;
+    offsets_sent(s);
   }
   DevBuf<float> X, Z, Dz, dX0, partial, partial_sm, aligned, tmp;
   DevBuf<unsigned short> xbf;   // bf16 copy of the input frames (first wide layer's W_x product in precision mode 2)
@@ -237,9 +290,7 @@ struct Net {
   long long fw_launches = 0;
 
   hipStream_t stream() const { return g_stream; }
-  // recognition (predict): the current minibatch was declared with the buffers of a forward-only pass (geom_predict) and
-  // computed by kernels that saved nothing for a backward pass (nosave); in_predict: no training NaN flag (fwd_nanflag)
-  bool geom_predict = false, nosave = false, in_predict = false;
+  bool in_predict = false;      // a predict call is running: no training NaN flag (fwd_nanflag)
   size_t fixed_bytes = 0;       // device allocations of build() (clstm_net_device_bytes; the grow-only buffers count themselves: DevBuf)
   void dev_malloc(void** q, size_t bytes) { HIPCHECK(hipMalloc(q, bytes)); fixed_bytes += bytes; }
 
@@ -373,7 +424,7 @@ struct Net {
     for (auto& y : L) {
       (void)hipFree(y.Wt); (void)hipFree(y.bias); (void)hipFree(y.Rf); (void)hipFree(y.Rb); (void)hipFree(y.moff); (void)hipFree(y.Wk);
       (void)hipFree(y.Rwf); (void)hipFree(y.Rwb); (void)hipFree(y.Rbf); (void)hipFree(y.Rbb); y.dCc.release(); y.Hb.release(); y.Db.release(); y.Rf32.release(); y.R2b.release(); y.D2.release();
-      y.G.release(); y.C.release(); y.H.release(); y.D.release(); y.dH.release(); y.S.release(); y.Sbf.release(); y.sbf_ready = false; y.pack_tab.release(); y.pack_inv.release(); y.Wmf.release(); y.mf_scale.release(); y.mf_xmax.release(); y.Wmfb.release(); y.pack_inv_state = 0; y.partial.release(); y.dbias.release();
+      y.G.release(); y.C.release(); y.H.release(); y.D.release(); y.dH.release(); y.S.release(); y.Sbf.release(); y.pack_tab.release(); y.pack_inv.release(); y.Wmf.release(); y.mf_scale.release(); y.mf_xmax.release(); y.Wmfb.release(); y.pack_inv_state = 0; y.partial.release(); y.dbias.release();
     }
     (void)hipFree(W1k); fw_items.release(); fw_flags.release();
     for (int i = 0; i < 2; i++) { hf.xin[i].release(); if (hf.copied[i]) (void)hipEventDestroy(hf.copied[i]); }
@@ -431,7 +482,7 @@ struct Net {
   void set_batch(const int* T_h, int nb) { declare_batch(T_h, nb); reserve_batch(false); }
   void set_batch_predict(const int* T_h, int nb) { declare_batch(T_h, nb); reserve_batch(true); }   // forward-only geometry (clstm_net_predict)
   // a minibatch declared by predict that something else now wants to train on / write into: the buffers of a training pass
-  void ensure_training_buffers() { if (geom_predict) reserve_batch(false); }
+  void ensure_training_buffers() { if (holds.batch != Holds::NONE && !holds.training_buffers) reserve_batch(false); }
   // no-save kernels exist for narrow layers in f32 mode (lstm_seq.h, lstm_fwd_fused.h, lstm_mfma.h); a net with a wide layer
   // (lstm_wide.h) or in a bf16 mode runs the unchanged forward pass under predict
   bool predict_nosave_ok() const {
@@ -441,18 +492,15 @@ struct Net {
   }
   // T_h / nb are validated BEFORE the net is touched: a refused declaration leaves the previous minibatch the current one
   void declare_batch(const int* T_h, int nb) {
-    REQUIRE(T_h && nb > 0, "empty batch");
     const long long n = batch_frames(T_h, nb);
-    REQUIRE(n < 2147483000LL, "batch has too many frames");   // (the line offsets are ints)
-    next.valid = false;   // (whatever a step's tail had prepared is replaced by this declaration)
-    nosave = false;
+    holds = Holds{};   // (whatever a step's tail had prepared is replaced by this declaration)
+    holds.batch = Holds::CURRENT;
     bs = nb;
     line_off_h.assign(nb + 1, 0);
     for (int b = 0; b < nb; b++) line_off_h[b + 1] = line_off_h[b] + T_h[b];
     N = n;
     tmax = 0;
     for (int b = 0; b < nb; b++) tmax = std::max(tmax, T_h[b]);
-    src0_ready = false;
     // behind the offsets: the order in which the per-line workgroups take the lines -- longest first, so that when
     // there are more lines than CUs the long ones are not the last to start (stable: equal lengths keep their order)
     order_h.resize(nb);
@@ -464,7 +512,7 @@ struct Net {
     memcpy(stage + nb + 1, order_h.data(), nb * sizeof(int));
     // The device copy is made by the next input-ingest launch (which reads the pinned slot directly: one DMA
     // launch of ~4 us less per step) or, if something else needs it first, by flush_line_off().
-    lo_stage = stage; lo_pending = true;
+    lo_stage = stage;
   }
   // predict: only what a forward-only pass writes -- the input block, H, Z and, for the families that stage pre-activations in
   // it (every one but the batched-MFMA recurrence of an upper layer; layer 0's routed twins stage theirs there when the device
@@ -472,7 +520,7 @@ struct Net {
   // (By the layer's forward plan, as forward_pass launches: the fused launch's rule looks at H, which grows here, but it stages like the per-line kernels.)
   void reserve_batch(bool predict) {
     if (predict && !predict_nosave_ok()) predict = false;
-    geom_predict = predict;
+    holds.training_buffers = !predict;
     hipStream_t s = stream();
     X.reserve((size_t)N * desc.ninput);
     for (auto& y : L) {
@@ -533,7 +581,7 @@ struct Net {
     h.ncu = device_cu_count(); h.want_dx0 = want_dx0;
     h.fwd_family = np.fwd; h.overlapped = np.overlapped; h.dwx = np.dwx; h.xd = np.xd;
     h.dw_slabs_per_dir = dw_slabs_per_dir; h.dwx_nslabs = dwx_nslabs;
-    h.below_hbf = l > 0 && L[l - 1].hbf_valid; h.fwd_sbf = y.sbf_ready;
+    h.below_hbf = l > 0 && L[l - 1].cur.hbf; h.fwd_sbf = y.cur.sbf;
     h.packs = y.WtbT.p && y.Wtb.p; h.above_packs = !h.top && L[l + 1].WtbT.p;
     return h;
   }
@@ -594,37 +642,37 @@ struct Net {
 
   void ensure_delta_f32(int l) {
     Layer& y = L[l];
-    if (y.d_f32_valid) return;
+    if (y.cur.d_f32) return;
     CLSTM_LAUNCH(k_bf16_to_f32, dim3(nblocks((size_t)N * ndir * 4 * y.no)), dim3(256), 0, stream(), y.Dbf.p, y.D.p, (size_t)N * ndir * 4 * y.no);
-    y.d_f32_valid = true;
+    y.cur.d_f32 = true;
   }
   void ensure_h_f32(int l) {   // exact: the kernel's own h = tanh(c) * go (ops.h:k_h_from_state)
     Layer& y = L[l];
-    if (y.h_f32_valid) return;
+    if (y.cur.h_f32) return;
     CLSTM_LAUNCH(k_h_from_state, dim3(nblocks((size_t)N * ndir * y.no)), dim3(256), 0, stream(), y.H.p, (const float*)y.G.p, (const float*)y.C.p,
                  (size_t)N, y.no, ndir, y.ldh, y.hofs);
-    y.h_f32_valid = true;
+    y.cur.h_f32 = true;
   }
   void ensure_source_h(int l) {
     Layer& y = L[l];
-    if (y.sh_valid) return;
+    if (y.cur.sh) return;
     ensure_h_f32(l);
     flush_line_off();
     CLSTM_LAUNCH(k_source_h, dim3(nblocks((size_t)N * ndir * y.no)), dim3(256), 0, stream(), y.S.p, (const float*)y.H.p, (const int*)line_off.p, bs,
                  (size_t)N, y.no, ndir, y.ldh, y.hofs, y.lds, 1 + y.ni, (long long)N * y.lds);
-    y.sh_valid = true;
+    y.cur.sh = true;
   }
   void ensure_source(int l) { ensure_source_x(l); ensure_source_h(l); }   // whole f32 source rows [1 | x | h_prev]
   void ensure_source_x(int l) {
     Layer& y = L[l];
-    if (y.sx_valid) return;
+    if (y.cur.sx) return;
     if (l > 0) ensure_h_f32(l - 1);   // (reads the layer below's f32 outputs)
     hipStream_t s = stream();
     timing.begin("build_source", s);
     CLSTM_LAUNCH(k_build_source, dim3(nblocks((size_t)N * (1 + y.ni))), dim3(256), 0, s, y.S.p, layer_input(l),
                  (size_t)N, y.ni, layer_input_ld(l), y.lds, ndir, (long long)N * y.lds);
     timing.end(s);
-    y.sx_valid = true;
+    y.cur.sx = true;
   }
 
   // ---- narrow layers: what narrow_plan (runtime.inc) decides from, read HERE and nowhere else -- the device, the net's settings, the
@@ -782,11 +830,10 @@ struct Net {
   }
 
   void forward() {
-    REQUIRE(N > 0, "set_batch first");
     RoctxRange range_("clstm:forward");
     ensure_training_buffers();   // (a minibatch that clstm_net_predict declared)
-    nosave = false;
     forward_pass(true);
+    forward_ran(true);
   }
   // The forward pass of training (save) and of recognition (!save: predict, on its own geometry).  Every layer runs the family
   // its plan names (narrow_plan / wide_plan), in the form NarrowPlan::saves names; without save nothing is kept for a backward pass -- no C, no source
@@ -801,6 +848,7 @@ struct Net {
       Layer& y = L[l];
       const int M = ndir * 4 * y.no;
       const NarrowPlan np = forward_plan(l, save);
+      if (save) y.forward_begins(l == 0 && holds.frames == Holds::ROWS);   // (without save the record stays as predict_begins left it)
       if (np.fwd == NF_FUSED) { forward_fused(np, save); return; }   // (a net of one layer: the launch is the whole forward half)
       const ProductPlan pp = product_plan(product_shape(l, PP_FWD, np));   // (the layer below has run: what it left is a fact)
       const bool x_from_hbf = pp.wx.kernel == PK_B16KK && !pp.x_copy;
@@ -812,12 +860,8 @@ struct Net {
         const WideRan ran = launch_lstm_wide(plan, w, coop_sync, step_graphs, s);
         timing.end(s);
         if (ran == WideRan::Nothing) return false;
-        const bool persistent = ran == WideRan::Persistent && bf16_rec;
-        y.hbf_valid = persistent && w.Hbf;
-        y.h_f32_valid = !(persistent && w.skip_h);   // (the per-step kernels store everything)
-        y.sh_valid = !(persistent && w.skip_s);
-        y.sbf_ready = persistent && w.Sbf;
-        if (y.sbf_ready) {   // the non-recurrent columns of the bf16 source rows (the recurrence stored the h columns)
+        y.recurrence_left(ran == WideRan::Persistent && bf16_rec, w.skip_h, w.skip_s, w.Hbf != nullptr, w.Sbf != nullptr);   // (the per-step kernels store everything)
+        if (y.cur.sbf) {   // the non-recurrent columns of the bf16 source rows (the recurrence stored the h columns)
           // x columns that fill whole tiles of the weight-gradient GEMM are not copied: the GEMM reads them from Hbf itself (ProductPlan::a2_rows)
           if (pp.a2_rows) {
             if (y.sbf_one_key != (long long)N) {
@@ -851,22 +895,21 @@ struct Net {
           }
           LstmWideArgs w = wide_args(y, true, pp);
           w.Xb = xb; w.x_ld = y.ni; w.x_ni = y.ni; w.Wxb = y.WtbT.p; w.bias = y.bias;
-          y.sx_valid = l == 0 && src0_ready;
           fx_done = plan.kernel == WK_XCD_FWD_BF16_FX && run_wide(plan, w);
         }
       }
-      if (fx_done) { if (!y.sbf_ready) ensure_source_x(l); continue; }
+      if (fx_done) { if (!y.cur.sbf) ensure_source_x(l); continue; }
       if (pp.needs & PN_H_BELOW) ensure_h_f32(l - 1);   // the products below read the f32 outputs of the layer underneath
       if (np.fwd == NF_MFMA) {
         // chip-filling minibatch of a narrow layer: the input product is part of the batched recurrence (lstm_mfma.h) -- no
         // hoisted W_x GEMM, no pre-activation array; the [1 | x] columns of the source rows are still the weight gradient's
         // (so not built without save, not even for the 128-cell layer whose training form runs then -- it has no no-save
         //  instantiation, reserve_batch kept its arrays: the kernel reads the frames themselves)
-        if (save) { y.sx_valid = l == 0 && src0_ready; ensure_source_x(l); }
+        if (save) ensure_source_x(l);
         timing.begin("lstm_fwd", s);
         launch_mfma(y, s, np.saves);
         count_moves(np.moves);
-        if (save) y.h_f32_valid = y.sh_valid = true;
+        if (save) y.recurrence_left(false, false, false, false, false);
         timing.end(s);
         continue;
       }
@@ -895,7 +938,6 @@ struct Net {
       // the [1 | x] columns of the f32 source rows: written now -- unless this is an upper layer whose weight-gradient
       // product will read the bf16 rows instead (decided after the recurrence below; ensure_source_x() then builds them
       // only if something still asks for them: a fallback path or the state API)
-      if (save) y.sx_valid = l == 0 && src0_ready;
       if (save && (l == 0 || !y.wide)) ensure_source_x(l);   // (the register-resident recurrence of narrow layers reads whole source rows)
       if (y.wide) run_wide(wide_plan(wide_shape(y, true, pp)), wide_args(y, true, pp));
       else {
@@ -906,10 +948,10 @@ struct Net {
         timing.begin("lstm_fwd", s);
         launch_lstm(true, y.nk4, y.pd.ku, a, bs, y.nthreads, s, save);
         count_moves(np.moves);
-        if (save) y.h_f32_valid = y.sh_valid = true;
+        if (save) y.recurrence_left(false, false, false, false, false);
         timing.end(s);
       }
-      if (save && !y.sbf_ready) ensure_source_x(l);
+      if (save && !y.cur.sbf) ensure_source_x(l);
     }
     forward_softmax(logits);
   }
@@ -950,14 +992,12 @@ struct Net {
   // clstm_debug_path_count: 22 per-line no-save recurrences, 23 fused no-save launches, 15 batched-MFMA no-save launches.
   // The batched recurrence of a 128-cell layer has no no-save instantiation (lstm_mfma.h): its training form runs (counter 16).
   void predict() {
-    REQUIRE(N > 0, "set_batch first");
     RoctxRange range_("clstm:predict");
     struct Guard { bool& f; Guard(bool& x) : f(x) { f = true; } ~Guard() { f = false; } } guard_(in_predict);
-    if (!geom_predict) { forward(); return; }   // (no no-save kernels for this net: see reserve_batch)
-    nosave = true;
-    src0_ready = false;
-    for (auto& y : L) { y.sx_valid = y.sh_valid = false; y.h_f32_valid = true; y.sbf_ready = false; y.hbf_valid = false; }
+    if (holds.training_buffers) { forward(); return; }   // (no no-save kernels for this net: see reserve_batch)
+    for (auto& y : L) y.predict_begins();
     forward_pass(false);
+    forward_ran(false);
   }
 
   // ---- the forward half as one launch: W_x GEMM producers + recurrence + softmax consumers (lstm_fwd_fused.h; the rule: narrow_plan) ----
@@ -1018,13 +1058,14 @@ struct Net {
     h.prog = (const int*)(y.H.p + a.prog_off);
     h.nrec = bs * ndir; h.npb = fw_npitems;
     const unsigned nblk = (unsigned)(h.nrec + h.npb + fw_ncitems);   // one item per helper workgroup
-    if (save) { y.sx_valid = src0_ready; ensure_source_x(0); }
+    if (save) ensure_source_x(0);
     static const char* trace_path = getenv("CLSTM_FW_TRACE");   // diagnostics: wall-clock stamps of every workgroup / item of the launch
     const size_t trace_rows = (size_t)h.nrec + fw_npitems + fw_ncitems;
     if (trace_path) { dw_trace.reserve(trace_rows * 4); HIPCHECK(hipMemsetAsync(dw_trace.p, 0, trace_rows * 4 * sizeof(long long), s)); h.trace = dw_trace.p; }
     timing.begin("lstm_fwd", s);
     launch_lstm_fwd_fused(y.nk4, y.pd.ku, k, nblk, y.nthreads, s, save);
     timing.end(s);
+    if (save) y.recurrence_left(false, false, false, false, false);
     if (trace_path)
       dump_trace(trace_path, dw_trace.p, trace_rows, s,
                  "# %d recurrence rows (start - end -), %d producer items (start - done chunk), %d consumer items (start ready done ready_iteration); 100 MHz ticks\n",
@@ -1227,7 +1268,6 @@ struct Net {
   // the gradient goes, and what they leave for update()
   struct ReduceTarget { const StepPlan& plan; float* gdst; PassLeft& left; };
   PassLeft backward(const StepPlan& plan = StepPlan{}) {
-    REQUIRE(N > 0, "set_batch first");
     PassLeft left;
     left.ticket = plan.ticket;
     const ReduceTarget rt{plan, plan.peer ? comm->peer.slot_ptr(comm->peer.seq + 1) : g, left};
@@ -1273,6 +1313,7 @@ struct Net {
       timing.end(s);
       check_launch();
     }
+    backward_ran();
     return left;
   }
   // SoftmaxLayer::backward (clstm.cc:411-417): x.d = W^T z.d ; W.d += z.d [1;x]^T.  (A side stream for these products was measured
@@ -1331,7 +1372,7 @@ struct Net {
     } else { launch_bwd_narrow(y, np, a, s); count_moves(np.moves); }
     timing.end(s);
     const bool persistent = ran == WideRan::Persistent;
-    y.d_f32_valid = !(persistent && bf16_rec && skipped_d);   // (launch_lstm_wide moved the plan's path counters)
+    y.backward_left(persistent && bf16_rec && skipped_d);   // (launch_lstm_wide moved the plan's path counters)
     return persistent;
   }
   // W.d += delta [1; x_t; h_{t-1}]^T for the four gates of each direction (both directions in one batched launch: half the slabs per
@@ -1425,7 +1466,6 @@ struct Net {
   // launch reads) and enqueues it with the ingest blocks behind its own.
   void launch_deferred_reduce(DeferredReduce& deferred, const IngestTail* tail) {
     if (!deferred.armed) return;
-    deferred.armed = false;
     const int nb = nblocks(deferred.work);
     timing.begin("reduce_scatter", deferred.q);
     if (tail) {
@@ -1439,10 +1479,10 @@ struct Net {
     }
     timing.end(deferred.q);
     check_launch();
+    deferred.armed = false;   // only now: a launch that threw leaves it armed, and the caller's plain launch_deferred_reduce(.., nullptr) still enqueues it
   }
   // the minibatch whose front half (batch geometry, alignment metadata, ingest) the last step's tail has already done
-  struct NextBatch {
-    bool valid = false;
+  struct NextBatch {   // (its content; WHETHER the net holds it is Holds::batch)
     const float* x = nullptr;
     std::vector<int> T, labels, L;
     static size_t nlabels(const Minibatch& m) {
@@ -1451,7 +1491,7 @@ struct Net {
       return nl;
     }
     bool matches(const Minibatch& m) const {
-      if (!valid || x != m.x || (int)T.size() != m.bs) return false;
+      if (x != m.x || (int)T.size() != m.bs) return false;
       if (memcmp(T.data(), m.T, (size_t)m.bs * sizeof(int)) || memcmp(L.data(), m.L, (size_t)m.bs * sizeof(int))) return false;
       const size_t nl = nlabels(m);
       return nl == labels.size() && (nl == 0 || !memcmp(labels.data(), m.labels, nl * sizeof(int)));
@@ -1459,7 +1499,6 @@ struct Net {
     void remember(const Minibatch& m) {
       x = m.x; T.assign(m.T, m.T + m.bs); L.assign(m.L, m.L + m.bs);
       labels.assign(m.labels, m.labels + nlabels(m));
-      valid = true;
     }
   } next;
   DevBuf<float>& layer_partial(Layer& y) { return L.size() > 1 ? y.partial : partial; }

@@ -45,6 +45,7 @@ class Network:
         h = C.c_void_p()
         self.lib.call("clstm_net_create", C.byref(h), C.byref(d), ptr(params), ptr(derivs), ptr(grads))
         self.h = h
+        self._holds = (C.c_int * 8)()
         self.T = []
         self.N = 0
 
@@ -97,8 +98,19 @@ class Network:
         self.lib.call("clstm_net_set_gradient_clip", self.h, float(clip))
 
     # -- data ------------------------------------------------------------------------------
+    def holds(self):
+        """What the library says the net holds (clstm_debug_net_holds): [bs, N, batch, training_buffers, forward, frames,
+        offsets_sent, dx0] -- the record is the library's; this class keeps no copy of it."""
+        self.lib.call("clstm_debug_net_holds", self.h, self._holds)
+        return list(self._holds)
+
+    def _held(self, T, holds=None):
+        """T / N of the minibatch the library holds; T, the caller's line lengths of that minibatch, only splits N by lines."""
+        bs, N = (holds or self.holds())[:2]
+        assert len(T) == bs and sum(T) == N, "the library holds another minibatch"
+        self.T, self.N = list(T), N
+
     def set_batch(self, T):
-        self._declared = None
         self.T = [int(t) for t in T]
         self.N = int(sum(self.T))
         t = i32(self.T)
@@ -112,17 +124,15 @@ class Network:
             x = f32(np.concatenate([f32(x).reshape(-1, self.ninput) for x in lines], 0))
         else:
             x = f32(lines)
-        assert x.shape == (self.N, self.ninput)
+        assert x.shape == (self.holds()[1], self.ninput)    # (the library's N: a declared next minibatch is adopted by this call)
         self.lib.call("clstm_net_set_inputs_h", self.h, ptr(x))
 
     def set_inputs_device(self, x_dev):
         self.lib.call("clstm_net_set_inputs_d", self.h, ptr(x_dev))
 
     def forward(self):
-        if getattr(self, "_declared", None):      # a minibatch declared by the last train step becomes the current one
-            self.T, self.N = self._declared
-            self._declared = None
         self.lib.call("clstm_net_forward", self.h)
+        self._held(self.T)                        # (a minibatch declared by the last train step has become the current one)
 
     def outputs(self):
         p = np.empty((self.N, self.nclasses), np.float32)
@@ -253,14 +263,15 @@ class Network:
         step's last launch and the next call -- which must pass that very minibatch -- starts with its forward launch."""
         Tl, t, labels, L = prep
         self.T, self.N = Tl, int(sum(Tl))
-        self._declared = None
         if next_prep is None:
             self.lib.call("clstm_net_train_step", self.h, ptr(t), len(Tl), ptr(x_dev), ptr(labels), ptr(L))
         else:
             nTl, nt, nlabels, nL = next_prep
-            self._declared = (nTl, int(sum(nTl)))
             self.lib.call("clstm_net_train_step_next", self.h, ptr(t), len(Tl), ptr(x_dev), ptr(labels), ptr(L),
                           ptr(nt), len(nTl), ptr(next_x_dev), ptr(nlabels), ptr(nL))
+            # the geometry is the declared next minibatch's now -- unless the library refused it, or had no tail to declare it with
+            holds = self.holds()
+            self._held(nTl if holds[2] == 2 else Tl, holds)
 
     def train_step_host(self, prep, x_host):
         """The same step fed from host memory (numpy array or pinned torch tensor [sum T, ninput]): the frames travel on a
@@ -319,7 +330,6 @@ class Network:
         its no-save form + trivial_decode.  lines: list of [T_b, ninput] arrays.  Returns (decodes, locs, confs), one array per
         line each: the classes, their frames, and the softmax output at (frame, class).  The minibatch is the current one
         afterwards (outputs(), decode(), state(.., 'outputs')); nothing was saved for a backward pass."""
-        self._declared = None
         self.T = [len(x) for x in lines]
         self.N = int(sum(self.T))
         x = f32(np.concatenate([f32(x).reshape(-1, self.ninput) for x in lines], 0))
@@ -339,7 +349,6 @@ class Network:
         """predict() for RAW line images (ink = 1, [w, h] arrays): normalised on the device by `normalizer` (Normalizer.run_device),
         the frames handed to clstm_net_predict where they lie.  Returns what predict() returns."""
         T, _, frames_d = normalizer.run_device(images)
-        self._declared = None
         self.T = [int(t) for t in T]
         self.N = int(sum(self.T))
         cls, loc = np.zeros(self.N, np.int32), np.zeros(self.N, np.int32)

@@ -211,6 +211,27 @@ int clstm_net_set_learning_rate(clstm_net* net, float lr, float momentum);
  * and NaN are refused and the previous clip stays in force). */
 int clstm_net_set_gradient_clip(clstm_net* net, float clip);
 
+/* What the per-minibatch entry points need of the net.  The net keeps one record of the minibatch it holds (clstm_debug_net_holds) and every
+ * entry below states its needs against it in one line (csrc/net.inc: Net::require); a need that is not met is refused by its text:
+ *   batch declared            else "set_batch first"
+ *   current (no declared next) else "no current minibatch: ..." -- between a clstm_net_train_step_next that declared its next minibatch and
+ *                             the call that brings, adopts or drops it, the geometry is that NEXT minibatch's and no outputs of it exist
+ *   saved (not predict's)     else "<entry>: the current minibatch was computed by clstm_net_predict, which saves nothing for a backward pass ..."
+ *   backward ran              else "input deltas not enabled / no backward yet" (clstm_net_enable_input_deltas, then a backward pass of THIS minibatch)
+ *
+ *   entry                                              | batch declared | current (no declared next) | saved (not predict's) | backward ran
+ *   get_outputs_h, decode, score, beam, beam_lm        | yes            | yes                        |                       |
+ *   get_state_h which = 5                              | yes            | yes                        |                       |
+ *   get_state_h other, ctc, backward                   | yes            | yes                        | yes                   |
+ *   set_output_deltas_h                                | yes            | yes                        | yes                   |
+ *   n_states, get_states_h                             | yes            | yes                        | yes                   |
+ *   get_input_deltas_h (+ enabled)                     | yes            | yes                        | yes                   | yes
+ *   set_inputs_h, set_inputs_d, forward                | yes            | adopt / drop               |                       |
+ *
+ * adopt / drop: clstm_net_forward and clstm_net_set_inputs_* ADOPT a declared next minibatch -- it becomes the current one (forward computes
+ * its outputs from the frames the declaring step ingested; set_inputs_* replaces those frames), and a later step call that brings it declares
+ * and ingests it again, with identical results.  clstm_net_set_batch, clstm_net_predict, clstm_net_set_states_h and a step call that brings
+ * another minibatch DROP it. */
 /* Declare the next minibatch: bs lines of T_h[b] frames each (HOST).  N = sum T.  T_h / bs are validated before the net is touched
  * (no negative length, at least one frame, fewer than 2147483000): a refused call leaves the previous minibatch the current one. */
 int clstm_net_set_batch(clstm_net* net, const int* T_h, int bs);
@@ -367,8 +388,11 @@ int clstm_net_train_step(clstm_net* net, const int* T_h, int bs, const float* x_
  * call starts with its forward launch (one launch less per step: 5.7 us of a 64 x 200 step).  The next call must pass the same
  * x pointer and the same T / transcripts (compared by content) to profit; anything else -- another minibatch after all, a
  * communicator of several ranks, clstm_net_set_batch in between -- silently takes the ordinary path.  xn_d must stay unchanged
- * from this call on.  Until the next step the net has no current minibatch: clstm_net_get_outputs_h / decode / ctc / backward /
- * get_state_h refuse.  Results are bit-identical to clstm_net_train_step's. */
+ * from this call on.  Until the next step the net has no current minibatch: every entry of the table above clstm_net_set_batch that needs
+ * a current one refuses; clstm_net_forward and clstm_net_set_inputs_* adopt the declared minibatch.  A next minibatch that would be
+ * refused (a negative line length, no frames, a blank or out-of-range label, an alignment that does not fit) is found on the host before
+ * anything is touched: this step completes as clstm_net_train_step, its minibatch stays the current one with its outputs addressable,
+ * and the call that brings the bad minibatch reports the error.  Results are bit-identical to clstm_net_train_step's. */
 int clstm_net_train_step_next(clstm_net* net, const int* T_h, int bs, const float* x_d, const int* labels_h, const int* L_h,
                               const int* Tn_h, int bsn, const float* xn_d, const int* labels_n_h, const int* Ln_h);
 /* The same step fed from HOST memory (what clstmocrtrain has after read_png + CenterNormalizer, clstmocrtrain.cc:167-172,
@@ -507,6 +531,12 @@ int clstm_debug_set_device_error(int which, int value);
  *   11 wide_bwd_step16_bf16, 0 none (behind kernel 3 the caller runs the hoisted product and asks again with fx_mode 0); step_grid[3];
  *   moves (bit c: a successful persistent pass moves clstm_debug_path_count(c)); fx_ngx (the folded projection was asked for). */
 int clstm_debug_wide_plan(const int* shape, int* plan);
+/* What the net holds, as 8 ints; host only: enqueues nothing, touches no device memory.
+ *   out: bs, N (frames), then the record (csrc/net.inc: Net::Holds): batch (0 none, 1 the current minibatch, 2 a declared next one whose outputs
+ *   do not exist), training_buffers (1 the buffers of a training pass, 0 predict's forward-only geometry), forward (0 no pass of this minibatch
+ *   yet, 1 one that saved what a backward pass needs, 2 predict's no-save pass), frames (0 nowhere, 1 in the input block, 2 also in layer 0's
+ *   source rows), offsets_sent (the line offsets are on the device), dx0 (a backward pass of this minibatch has written the input deltas). */
+int clstm_debug_net_holds(clstm_net* net, int* out);
 /* Which kernels a narrow (register-resident, nhidden <= 128) layer's pass runs, and in which launches (csrc/runtime.inc: narrow_plan, the one
  * place that decides): host arithmetic, no net, no device.
  * shape (30 ints, HOST in): pass (0 forward with save, 1 forward without save, 2 backward), no, ni, ndir; nlayers, first, top (this layer is

@@ -486,7 +486,7 @@ def test_beam_leaves_the_training_state_alone(backend):
 
 def test_beam_between_training_steps_and_without_a_current_minibatch(backend):
     """a training trajectory with beam calls between the steps is bit-identical to one without; after
-    clstm_net_train_step_next there is no current minibatch and the call refuses by the REQUIRE_CURRENT text"""
+    clstm_net_train_step_next there is no current minibatch and the call refuses by the text of the one guard (Net::require)"""
     from clstm_amd.abi import ClstmError
     from clstm_amd.net import Network
     rng = np.random.default_rng(47)

@@ -443,7 +443,7 @@ def test_score_leaves_the_training_state_alone(backend):
 
 
 def test_score_refuses_without_a_current_minibatch_and_training_goes_on(backend):
-    """clstm_net_train_step_next leaves no current minibatch: score refuses by the REQUIRE_CURRENT text; a bad call after a forward is
+    """clstm_net_train_step_next leaves no current minibatch: score refuses by the text of the one guard (Net::require); a bad call after a forward is
     refused too, a good one accepted; the training step that follows gives the parameters of an undisturbed run"""
     from clstm_amd.abi import ClstmError
     from clstm_amd.net import Network

@@ -25,13 +25,16 @@ def _twins(backend, nh):
 
 
 def _batch(backend, rng, nlines, bad=False):
-    """(prep, frames on the device, frames on the host, T, transcripts); bad: one label past the last class"""
+    """(prep, frames on the device, frames on the host, T, transcripts); bad: one label past the last class, or ("size") a negative
+    line length"""
     from clstm_amd.net import Network
     T = [int(t) for t in rng.integers(3, 12, nlines)]
     trs = [rng.integers(1, NC, max(1, t // 3)).astype(np.int32) for t in T]
-    if bad:
-        trs[-1][0] = NC + 3
     x = np.ascontiguousarray(np.concatenate(synth_lines(rng, T, NI), 0), np.float32)
+    if bad == "size":
+        T[-1] = -T[-1]
+    elif bad:
+        trs[-1][0] = NC + 3
     return Network.prepare_step(T, trs), backend.up(x), x, T, trs
 
 
@@ -64,23 +67,36 @@ def _separate_calls(net, batch):
     net.update()
 
 
-def test_bad_next_minibatch_does_not_fail_the_step_that_declared_it(backend, nh):
-    """A step declares a next minibatch with a label out of range: the step itself completes (no ingest tail is launched for
-    it: counter 19 stays), the call that brings the bad minibatch as its current one reports the error, and a good step afterwards
-    equals the twin again."""
+def _bad_next_minibatch(backend, nh, how, text):
     rng = np.random.default_rng(31)
     a, b = _twins(backend, nh)
-    g0, bad, g1 = _batch(backend, rng, 3), _batch(backend, rng, 2, bad=True), _batch(backend, rng, 4)
+    g0, bad, g1 = _batch(backend, rng, 3), _batch(backend, rng, 2, bad=how), _batch(backend, rng, 4)
     a.train_step_prepared(g0[0], g0[1])
     tails = _count(backend, 19)
     b.train_step_prepared(g0[0], g0[1], bad[0], bad[1])
     assert _count(backend, 19) == tails
     _same(a, b, "the step that declared a bad next minibatch")
-    with pytest.raises(Exception, match="out of range"):
+    # the refused minibatch touched nothing: step k's minibatch is the current one and its outputs are addressable
+    assert b.holds() == [3, sum(g0[3]), 1, 1, 1, 2, 1, 0]
+    assert b.outputs().tobytes() == a.outputs().tobytes()
+    assert [d.tolist() for d in b.decode()] == [d.tolist() for d in a.decode()]
+    with pytest.raises(Exception, match=text):
         b.train_step_prepared(bad[0], bad[1])
     a.train_step_prepared(g1[0], g1[1])
     b.train_step_prepared(g1[0], g1[1])
     _same(a, b, "a good step after the refused one")
+
+
+def test_bad_next_minibatch_does_not_fail_the_step_that_declared_it(backend, nh):
+    """A step declares a next minibatch with a label out of range: the step itself completes (no ingest tail is launched for
+    it: counter 19 stays) and still holds its own minibatch -- outputs and decode equal the twin's --, the call that brings the bad
+    minibatch as its current one reports the error, and a good step afterwards equals the twin again."""
+    _bad_next_minibatch(backend, nh, True, "out of range")
+
+
+def test_next_minibatch_bad_by_size_does_not_fail_the_step_that_declared_it(backend, nh):
+    """The same with a next minibatch that is bad by size: a negative line length."""
+    _bad_next_minibatch(backend, nh, "size", "negative line length")
 
 
 def test_failed_step_after_a_good_declaration_leaves_no_plan_behind(backend, nh):
