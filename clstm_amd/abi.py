@@ -145,6 +145,9 @@ _SIGS = {
     "clstm_debug_narrow_plan": [_P, _P],
     "clstm_debug_product_plan": [_P, _P],
     "clstm_debug_ctc_plan": [_I, _P, _P, _P, _I, _P, _P],
+    "clstm_debug_ctc_split": [_I, _I, _P],
+    "clstm_debug_ctc_part_frames": [_I, _I, _I, _P],
+    "clstm_debug_ctc_cycles_part": [_I, _P],
 }
 # functions whose int return value is a result, not a status
 _VALUE_RETURN = {"clstm_net_nparams_for", "clstm_net_nparams", "clstm_abi_version", "clstm_comm_rank", "clstm_comm_size", "clstm_comm_peer_active"}
@@ -152,7 +155,8 @@ EXPORTED_SYMBOLS = sorted(list(_SIGS) + ["clstm_last_error", "clstm_abi_version"
 # host-arithmetic debug entries (no net, no device) added since ABI version 1: a library built before one of them existed still loads --
 # the emulator's build directory can outlive the sources it was made from when their time stamps move backwards -- and a CALL of the
 # entry there raises AttributeError.  (libclstm_hip.so must export them all: tests/test_abi_exports.py)
-_LATE = {"clstm_debug_net_holds", "clstm_debug_wide_plan", "clstm_debug_narrow_plan", "clstm_debug_product_plan", "clstm_debug_ctc_plan"}
+_LATE = {"clstm_debug_net_holds", "clstm_debug_wide_plan", "clstm_debug_narrow_plan", "clstm_debug_product_plan", "clstm_debug_ctc_plan",
+         "clstm_debug_ctc_split", "clstm_debug_ctc_part_frames", "clstm_debug_ctc_cycles_part"}
 
 
 class Lib:

@@ -852,6 +852,29 @@ int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, con
   describe_ctc_plan(nc, line_off_h, states_h, state_off_h, bs, batch_plan_h, line_plan_h);
   ABI_END
 }
+int clstm_debug_ctc_split(int bs, int ncu, int* nsplit_h) {   // host arithmetic only (ctc.h: ctc_nsplit under the option ctc_split as it stands)
+  ABI_BEGIN
+  REQUIRE(bs > 0 && ncu >= 0 && nsplit_h, "bad argument");
+  const int opt = dbg_opt("ctc_split");
+  REQUIRE(opt == 0 || opt == 1 || opt == 2 || opt == 4, "option ctc_split must be 0, 1, 2 or 4");
+  *nsplit_h = ctc_nsplit(bs, ncu > 0 ? ncu : device_cu_count(), opt);
+  ABI_END
+}
+int clstm_debug_ctc_part_frames(int T, int n, int k, int* range_h) {   // host arithmetic only (ctc.h: ctc_part_frames, the kernel's own)
+  ABI_BEGIN
+  REQUIRE(T >= 0 && n >= 1 && k >= 0 && k < n && range_h, "bad argument");
+  const CtcFrames f = ctc_part_frames(T, n, k);
+  range_h[0] = f.lo; range_h[1] = f.hi;
+  ABI_END
+}
+int clstm_debug_ctc_cycles_part(int part, long long* out_h) {
+  ABI_BEGIN
+  REQUIRE(g_last_ctc_prof, "no CTC launch yet");
+  REQUIRE(part >= 0 && part < 4 && out_h, "bad argument");
+  HIPCHECK(hipStreamSynchronize(g_stream));
+  HIPCHECK(hipMemcpy(out_h, g_last_ctc_prof + 16 * part, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+  ABI_END
+}
 int clstm_debug_lane_ops(float* out) {
   ABI_BEGIN
   CLSTM_LAUNCH(k_debug_lane_ops, dim3(1), dim3(64), 0, g_stream, out);

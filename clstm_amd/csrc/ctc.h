@@ -1,6 +1,7 @@
 // ctc.h -- clstm's CTC alignment (ctc.cc:24-134) and trivial_decode (ctc.cc:159-190) on device.
 //
-// One workgroup per text line.  clstm's variant is NOT the textbook CTC: transitions are
+// One workgroup per text line -- or, where CUs are idle and the line's lattices stay in LDS, several that each compute the line in full and
+// emit their own frames (ctc_nsplit, ctc_line_splits, ctc_part_frames).  clstm's variant is NOT the textbook CTC: transitions are
 // stay / advance-by-one only, every state and frame carries a skip = -5 boundary term,
 // log_add cuts off at |x-y| > 10 (tensor.h:86-89), posteriors are normalised per STATE over
 // time and then per frame.  All of that is replicated here:
@@ -49,7 +50,8 @@ constexpr int CTC_MAX_TILE = 256;  // frames per LDS tile (phases A and E)
 constexpr int CTC_PD = CLSTM_CTC_PD;   // frames the one-wave lattice recursions request their match scores ahead
 constexpr int CTC_PREG = 34;    // posteriors per thread held in registers across the state classification
 constexpr int CTC_NB = 12;      // items a thread of the short-line path takes per round in the match-score and write-out loops
-constexpr int CTC_CLANE = 32;   // frames per wave of the lane = state form of phases C / D (lines of up to 64 states and 256 frames)
+constexpr int CTC_NBS = 4;      // ... per round of the write-out of up to 4 x 512 items (a quarter of a bench line: 50 frames x 26 classes)
+constexpr int CTC_CLANE = 32;  // frames per wave of the lane = state form of phases C / D (lines of up to 64 states and 256 frames)
 constexpr int CTC_CCACHE = 26;  // lattice cells per thread kept in registers between the two passes of phase C (26 x 512 = 13312
                                 // cells: lines of up to 261 frames x 51 states -- a ragged OCR minibatch, T ~ U{150..250} -- stay on the short-line path;
                                 // at 24 the 10 % of such lines beyond 240 frames took the tiled path and the launch 107 us instead of 75)
@@ -61,7 +63,7 @@ constexpr int CTC_CCACHE = 26;  // lattice cells per thread kept in registers be
 // its states; the classification arrives at the same number)
 struct CtcLine { long long lat_off; int b, off, T, soff, S, nu; };
 struct CtcArgs {
-  const CtcLine* lines;  // [bs] per workgroup (largest lattice first)
+  const CtcLine* lines;  // [bs] line records, largest lattice first; workgroup i serves record i % bs as part i / bs (ctc_line_splits)
   const float* P;        // [N][nc] softmax outputs
   float* Dz;             // [N][nc] out: aligned - P
   float* aligned;        // [N][nc] out (optional, may be null): alignment posteriors
@@ -74,6 +76,8 @@ struct CtcArgs {
   int smax;              // max states of any line in the batch (sizes the LDS carve)
   long long* prof;       // optional [16] phase timestamps of block 0 (diagnostics)
   int float_logadd;      // experiment option ctc_float: log_add on the float transcendentals (ctc_align_kernel<true>; host side only)
+  int bs;                // line records; the launch has bs * nsplit workgroups
+  int nsplit;            // workgroups per line that splits (CtcBatchPlan::nsplit)
 };
 
 // LDS carve shared by host (size) and kernel (offsets); all offsets in 4-byte words
@@ -106,12 +110,36 @@ inline __host__ __device__ int ctc_region_words(const CtcLds& l, int tile) { ret
 
 // ---- WHICH path a line takes: the one statement of the rule.  ctc_batch_plan is the host's arithmetic, once per minibatch; ctc_line_plan
 // what a workgroup decides from it and from its own line; ctc_scores_in_lds the one decision that has to wait for the line's number of
-// distinct classes.  The kernel branches on these and nowhere re-derives them; clstm_debug_ctc_plan (include/clstm_abi.h) answers with
-// the same functions on the host, so a test can assert the path it means to cover (tests/test_ctc_path_sweep.py).
-struct CtcBatchPlan { int tile, smax, ncp, smem; };   // frames per LDS tile (< 1: the carve has no room for one), capped states, row stride, LDS bytes
-// smax_lines, tmax: the most states / frames of any line of the minibatch
-inline CtcBatchPlan ctc_batch_plan(int nc, int smax_lines, int tmax) {
+// distinct classes; ctc_nsplit / ctc_line_splits / ctc_part_frames how many workgroups serve a line and which frames each of them emits.
+// The kernel branches on these and nowhere re-derives them; clstm_debug_ctc_plan, _ctc_split and _ctc_part_frames (include/clstm_abi.h)
+// answer with the same functions on the host, so a test can assert the path it means to cover (tests/test_ctc_path_sweep.py,
+// tests/test_ctc_split.py).
+// frames per LDS tile (< 1: the carve has no room for one), capped states, row stride, LDS bytes, workgroups per line that splits
+struct CtcBatchPlan { int tile, smax, ncp, smem, nsplit; };
+// Workgroups per line.  One workgroup per line leaves every CU beyond the minibatch's lines idle for the whole launch; with n of them
+// per line every workgroup still computes phases A to D in full -- the same work on the same inputs, so the same bits, and nothing is
+// handed from one workgroup to another -- and emits only its own frames (ctc_part_frames): the per-frame phases behind the lattice
+// shorten to 1 / n on the line's critical path.  The rule: the largest n of 4, 2, 1 whose bs * n workgroups are resident at once, one
+// per CU (the carve is most of a CU's LDS).  opt: experiment option ctc_split -- 0 the rule, 1 never, 2 / 4 that many wherever
+// ctc_line_splits admits the line.
+inline int ctc_nsplit(int bs, int ncu, int opt) {
+  if (opt == 1 || opt == 2 || opt == 4) return opt;
+  for (int n = 4; n > 1; n >>= 1)
+    if ((long)bs * n <= ncu) return n;
+  return 1;
+}
+// frames [lo, hi) that part k of n emits of a line of T frames: contiguous, disjoint, together [0, T), at most ceil(T / n) each;
+// empty for the last parts where T < n
+struct CtcFrames { int lo, hi; };
+inline __host__ __device__ CtcFrames ctc_part_frames(int T, int n, int k) {
+  const int c = (T + n - 1) / n;
+  const int lo = k * c < T ? k * c : T, hi = (k + 1) * c < T ? (k + 1) * c : T;
+  return CtcFrames{lo, hi};
+}
+// smax_lines, tmax: the most states / frames of any line of the minibatch; bs, ncu, split_opt: ctc_nsplit's
+inline CtcBatchPlan ctc_batch_plan(int nc, int smax_lines, int tmax, int bs = 1, int ncu = 0, int split_opt = 1) {
   CtcBatchPlan p;
+  p.nsplit = ctc_nsplit(bs, ncu, split_opt);
   p.smax = smax_lines < 1 ? 1 : (smax_lines > CTC_SMAX_LDS ? CTC_SMAX_LDS : smax_lines);   // (longer lines do not use the per-state LDS arrays)
   if (tmax < 1) tmax = 1;
   p.ncp = nc | 1;                                   // odd row stride: conflict-free row-per-lane access
@@ -168,6 +196,13 @@ inline __host__ __device__ int ctc_scores_behind(int T, int S, int ncp) { return
 // ... and whether they do: the recursion then reads them where they are (ctc_lattice: LDS_SRC).  nu: distinct classes of the line
 inline __host__ __device__ bool ctc_scores_in_lds(const CtcLinePlan& p, int T, int S, int ncp, int nu, int cap) {
   return p.lds_lat && ctc_scores_behind(T, S, ncp) + T * (nu | 1) <= cap;
+}
+// Whether a line is served by the minibatch's nsplit workgroups: only where match scores and both lattices never leave LDS.  The
+// workgroups of such a line share no writable memory but their disjoint output rows, so none can see another's unfinished work; every
+// other short line keeps its lattices or scores in the line's one slice of the global workspace (CtcArgs::lat), as tiled and huge
+// lines do, and stays with one workgroup (the others return before their first load beyond the line record).
+inline __host__ __device__ bool ctc_line_splits(const CtcLinePlan& p, int T, int S, int ncp, int nu, int cap) {
+  return p.form == CTC_FORM_SHORT && ctc_scores_in_lds(p, T, S, ncp, nu, cap);
 }
 
 // Float-only form of log(exp(d) + 1) (experiment option ctc_float=1; NOT the default): exp as in ctc_limexp
@@ -433,7 +468,8 @@ DEVFN void ctc_lattice_huge(const float* lm, float* al, float* be, const CrTable
   }
 }
 
-#define CTC_STAMP(k) do { if (a.prof && b == 0 && threadIdx.x == 0) a.prof[k] = dev_clock(); } while (0)
+// (diagnostics: line 0's stamps, 16 slots per part of the line)
+#define CTC_STAMP(k) do { if (a.prof && b == 0 && threadIdx.x == 0) a.prof[16 * ipart + (k)] = dev_clock(); } while (0)
 constexpr int CTC_TREG = (CTC_TABLE_DOUBLES + CTC_THREADS - 1) / CTC_THREADS;
 
 // ---- lines whose lattice fits in LDS: phases A..E on one CU, see the header ------------------------------
@@ -443,9 +479,15 @@ constexpr int CTC_TREG = (CTC_TABLE_DOUBLES + CTC_THREADS - 1) / CTC_THREADS;
 template <bool FLA>
 DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const CrTables tb, const int b, float* lm,
                           const int off, const int T, const int S, const double (&treg)[CTC_TREG],
-                          const float (&preg)[CTC_PREG], const CtcLinePlan& pl) {
+                          const float (&preg)[CTC_PREG], const CtcLinePlan& pl, const int ipart, const int nparts) {
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int nc = a.nc, ncp = a.ncp;
+  // Part ipart of the line's nparts workgroups (ctc_line_splits; one workgroup: every frame).  Classification, A, B, C and the sums of
+  // D run over the whole line in every part; what is separable per frame -- the normalised store, the projection, the frame totals, the
+  // write-out, the absent-class rows under B -- covers the frames [t_lo, t_hi) only.  A cell is the same function of the same operands
+  // whichever workgroup, wave or lane forms it, so the parts' rows together are the rows one workgroup writes, bit for bit.
+  const CtcFrames fr = ctc_part_frames(T, nparts, ipart);
+  const int t_lo = fr.lo, t_hi = fr.hi;
   double* part = reinterpret_cast<double*>(lds + L.part);   // 512 doubles, reused phase by phase
   double* tot = reinterpret_cast<double*>(lds + L.tot);
   // One region (the carve's row buffer + lattice tile + row sums, `cap` words) is re-used phase by phase, so that a line
@@ -524,9 +566,10 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   // tid + 512, ..): requested HERE, a whole kernel ahead -- inside a training step such a load is a microsecond on the tail
   float pw[CTC_NB];
   {
-    const int n = T * nu;
+    const int n = (t_hi - t_lo) * nu;   // (the part's own items: its frames start at t_lo)
     const int dq = CTC_THREADS / nu, dr = CTC_THREADS - dq * nu;
     int tq = tid / nu, uq = tid - tq * nu;
+    tq += t_lo;
 #pragma unroll
     for (int u = 0; u < CTC_NB; u++) {
       const bool in = tid + u * CTC_THREADS < n;
@@ -655,13 +698,13 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
     for (int cb = 0; cb < nc; cb += 64) {   // one wave per frame, lanes over classes
       const int c = cb + lane;
       const bool absent = c < nc && ccol[c < nc ? c : 0] < 0;
-      for (int t0 = w0; t0 < T; t0 += 8 * nw) {
+      for (int t0 = t_lo + w0; t0 < t_hi; t0 += 8 * nw) {
         float x[8];
         unsigned ofs[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
           const int t = t0 + u * nw;
-          ofs[u] = (absent && t < T) ? (unsigned)(t * nc + c) * 4u : BUF_OOB;
+          ofs[u] = (absent && t < t_hi) ? (unsigned)(t * nc + c) * 4u : BUF_OOB;
           x[u] = buf_load(pb, ofs[u]);
         }
 #pragma unroll
@@ -748,13 +791,19 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
     __syncthreads();
     CTC_STAMP(9);
     const double it = tot[sl];
+    // The part's frames w + 8 k are the cells k_lo <= k < k_hi of this wave (one workgroup: 0 <= k < the line's cells).  The loop is
+    // issue-bound -- one wave per SIMD, an instruction every four cycles or so whatever its kind -- so the per-cell test is one bit
+    // of a wave-uniform mask: as comparisons of t against both ends of the range it cost the whole-line case 1.0k cycles more than the
+    // one comparison it had, and a wave-uniform branch per cell cost the parts more than the cells they skipped (EXPERIMENTS 24.3).
+    const int k_lo = (t_lo - wave + 7) >> 3, k_hi = (t_hi - wave + 7) >> 3;   // (t - wave + 7 >= 0: wave <= 7; k_hi <= 32: T <= 256)
+    const unsigned cells = (unsigned)(((1ull << k_hi) - 1ull) & ~((1ull << k_lo) - 1ull));
 #pragma unroll
     for (int g = 0; g < CTC_CLANE / 4; g++) {
-      if (wave + 32 * g < T) {
+      if ((cells >> (4 * g)) & 0xFu) {   // (wave-uniform: the group has a frame of this part)
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int k = 4 * g + u, t = wave + 8 * k;
-          float* w = (sok && t < T) ? &etile[t * sp + lane] : dump;
+          float* w = (sok && ((cells >> k) & 1u)) ? &etile[t * sp + lane] : dump;
           *w = (float)((double)bo[k] * it);
         }
       }
@@ -856,8 +905,8 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
         const int st = lists[nb + (fok ? f0 + lane : 0)];
         const int col = ucol[st];
         const double it = PRE ? 1.0 : tot[st];   // per-state normalisation (phase D), applied on the fly unless the tile holds it
-        int t0 = wave - 4;
-        for (; t0 + 28 < T; t0 += 4 * 8) {   // whole batches: only the lane guard
+        int t0 = t_lo + wave - 4;
+        for (; t0 + 28 < t_hi; t0 += 4 * 8) {   // whole batches: only the lane guard
           float x[8];
 #pragma unroll
           for (int u = 0; u < 8; u++) x[u] = etile[(t0 + 4 * u) * sp + st];
@@ -867,20 +916,20 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
             *w = PRE ? x[u] : (float)((double)x[u] * it);
           }
         }
-        if (t0 < T) {
+        if (t0 < t_hi) {
           float x[8];
 #pragma unroll
-          for (int u = 0; u < 8; u++) { const int t = t0 + 4 * u; x[u] = etile[(t < T ? t : T - 1) * sp + st]; }
+          for (int u = 0; u < 8; u++) { const int t = t0 + 4 * u; x[u] = etile[(t < t_hi ? t : t_hi - 1) * sp + st]; }
 #pragma unroll
           for (int u = 0; u < 8; u++) {
             const int t = t0 + 4 * u;
-            float* w = (fok && t < T) ? &rowc[t * nup + col] : dump;
+            float* w = (fok && t < t_hi) ? &rowc[t * nup + col] : dump;
             *w = PRE ? x[u] : (float)((double)x[u] * it);
           }
         }
       }
     } else {
-      for (int t = tid; t < T; t += 256) {
+      for (int t = t_lo + tid; t < t_hi; t += 256) {
         const float* e = etile + t * sp;
         double blank = 0.0;
         int i0 = 0;
@@ -915,7 +964,7 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   if (lanemap) project(std::true_type{}); else project(std::false_type{});
   __syncthreads();
   CTC_STAMP(10);
-  for (int t = tid; t < T; t += CTC_THREADS) {
+  for (int t = t_lo + tid; t < t_hi; t += CTC_THREADS) {
     float* row = rowc + t * nup;
     const float* e = etile + t * sp;
     for (int i = 0; i < nr; i++) {   // few; a class may repeat more than once: read-modify-write in state order
@@ -943,15 +992,20 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
   }
   __syncthreads();
   CTC_STAMP(11);
-  {  // per-frame normalisation and the fused delta  d = aligned - p  (clstmhl.h:211-212) for the present classes
-    const int n = T * nu;
+  // per-frame normalisation and the fused delta  d = aligned - p  (clstmhl.h:211-212) for the present classes of the part's frames.
+  // NB items per thread and round: CTC_NB, one round for a whole line of the bench shape; a quarter of such a line (and any line of
+  // up to CTC_NBS x 512 items) takes rounds of CTC_NBS, whose masked-off items would otherwise cost what live ones do
+  auto write_out = [&](auto nb_tag) {
+    constexpr int NB = decltype(nb_tag)::value;
+    const int n = (t_hi - t_lo) * nu;
     const int dq = CTC_THREADS / nu, dr = CTC_THREADS - dq * nu;   // (t, u) of item i, followed incrementally
     int tq = tid / nu, uq = tid - tq * nu;
-    for (int i0 = tid; i0 < n; i0 += CTC_NB * CTC_THREADS) {   // (every posterior of the thread requested before the first is used)
-      float p[CTC_NB], av[CTC_NB];
-      unsigned ofs[CTC_NB];
+    tq += t_lo;
+    for (int i0 = tid; i0 < n; i0 += NB * CTC_THREADS) {   // (every posterior of the thread requested before the first is used)
+      float p[NB], av[NB];
+      unsigned ofs[NB];
 #pragma unroll
-      for (int u = 0; u < CTC_NB; u++) {
+      for (int u = 0; u < NB; u++) {
         const bool in = i0 + u * CTC_THREADS < n;
         const int tc = in ? tq : 0, uc = in ? uq : 0;
         ofs[u] = in ? (unsigned)(tc * nc + ucls[uc]) * 4u : BUF_OOB;
@@ -959,20 +1013,22 @@ DEVFN void ctc_short_line(const CtcArgs& a, float* lds, const CtcLds& L, const C
         tq += dq; uq += dr;
         if (uq >= nu) { uq -= nu; tq++; }
       }
-      if (i0 == tid) {   // (uniform: every thread is in its first round together)
+      if (i0 == tid) {   // (uniform: every thread is in its first round together; item tid + u x 512 is the prefetch's whatever NB is)
 #pragma unroll
-        for (int u = 0; u < CTC_NB; u++) p[u] = pw[u];
+        for (int u = 0; u < NB; u++) p[u] = pw[u];
       } else {
 #pragma unroll
-        for (int u = 0; u < CTC_NB; u++) p[u] = buf_load(pb, ofs[u]);
+        for (int u = 0; u < NB; u++) p[u] = buf_load(pb, ofs[u]);
       }
 #pragma unroll
-      for (int u = 0; u < CTC_NB; u++) {
+      for (int u = 0; u < NB; u++) {
         buf_store(agb, ofs[u], av[u]);
         buf_store(dzb, ofs[u], av[u] - p[u]);
       }
     }
-  }
+  };
+  if ((t_hi - t_lo) * nu <= CTC_NBS * CTC_THREADS) write_out(std::integral_constant<int, CTC_NBS>{});
+  else write_out(std::integral_constant<int, CTC_NB>{});
   CTC_STAMP(5);
 }
 
@@ -992,13 +1048,18 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
   float* red = lds + L.red;
   const CrTables tb{tabs, tabs + 32, tabs + 96, tabs + 160};
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
-  const CtcLine ln = a.lines[blockIdx.x];
+  // workgroup i: part i / bs of line record i % bs (part-major: the parts 0 of all lines are dispatched first)
+  const int ipart = a.nsplit > 1 ? (int)blockIdx.x / a.bs : 0;
+  const CtcLine ln = a.lines[(int)blockIdx.x - ipart * a.bs];
   const int b = ln.b;
   const int nc = a.nc, ncp = a.ncp, TT = a.tile;
   const int off = ln.off, T = ln.T;
   const int soff = ln.soff, S = ln.S;
   const CtcLinePlan pl = ctc_line_plan(T, S, ln.nu, nc, ncp, TT, ctc_region_words(L, TT));   // uniform per workgroup
   if (pl.form == CTC_FORM_NONE) return;
+  // a line that does not split (ctc_line_splits) is part 0's alone: the other workgroups of it leave here
+  const int nparts = a.nsplit > 1 && ctc_line_splits(pl, T, S, ncp, ln.nu, ctc_region_words(L, TT)) ? a.nsplit : 1;
+  if (ipart >= nparts) return;
   const float* P = a.P + (size_t)off * nc;
   float* Dz = a.Dz + (size_t)off * nc;
   float* lm = a.lat + ln.lat_off;
@@ -1025,7 +1086,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(CtcArgs a) {
     if (tid < S) stl[tid] = st0;
     for (int s = tid + CTC_THREADS; s < S; s += CTC_THREADS) stl[s] = a.states[soff + s];
     __syncthreads();
-    ctc_short_line<FLA>(a, lds, L, tb, b, lm, off, T, S, treg, preg, pl);
+    ctc_short_line<FLA>(a, lds, L, tb, b, lm, off, T, S, treg, preg, pl, ipart, nparts);
     return;
   }
   // lines of more than CTC_SMAX_LDS states: the per-state arrays do not fit the LDS carve -- target states are read from

@@ -26,8 +26,9 @@ static void upload_ctc_tables(DevBuf<double>& tables) {
 }
 // the alignment run_ctc prepared (w.pending): at once, or -- in a training step -- behind the forward pass (step.inc)
 static void launch_ctc_align(const CtcWorkspace& w, hipStream_t s) {
-  if (!w.pending.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<false>, dim3(w.pending_bs), dim3(CTC_THREADS), w.pending_smem, s, w.pending);
-  else CLSTM_LAUNCH(ctc_align_kernel<true>, dim3(w.pending_bs), dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  const dim3 grid((unsigned)w.pending_bs * (unsigned)w.pending.nsplit);   // part-major: workgroup i is part i / bs of line record i % bs
+  if (!w.pending.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<false>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  else CLSTM_LAUNCH(ctc_align_kernel<true>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
   check_launch();
 }
 // n transcripts (packed labels, lengths) as blank-interleaved target states (clstm_mktargets) with their offsets: what the alignment
@@ -50,13 +51,15 @@ static void check_target_classes(int nc, const int* states_h, int ns) {
   for (int i = 0; i < ns; i++) REQUIRE(states_h[i] >= 0 && states_h[i] < nc, "target class out of range");
 }
 // the batch arithmetic of a minibatch (ctc.h: ctc_batch_plan) from its offsets, with the refusals run_ctc has always made
-static CtcBatchPlan ctc_minibatch_plan(int nc, const int* line_off_h, const int* state_off_h, int bs) {
+// ncu, split_opt: the device's CUs and the experiment option ctc_split (ctc.h: ctc_nsplit); the description of a plan asks for neither
+static CtcBatchPlan ctc_minibatch_plan(int nc, const int* line_off_h, const int* state_off_h, int bs, int ncu = 0, int split_opt = 1) {
   int smax = 1, tmax = 1;
   for (int b = 0; b < bs; b++) {
     smax = std::max(smax, state_off_h[b + 1] - state_off_h[b]);
     tmax = std::max(tmax, line_off_h[b + 1] - line_off_h[b]);
   }
-  const CtcBatchPlan bp = ctc_batch_plan(nc, smax, tmax);
+  REQUIRE(split_opt == 0 || split_opt == 1 || split_opt == 2 || split_opt == 4, "option ctc_split must be 0, 1, 2 or 4");
+  const CtcBatchPlan bp = ctc_batch_plan(nc, smax, tmax, bs, ncu, split_opt);
   REQUIRE(bp.tile >= 1, "too many classes / target states for the CTC row tile");
   REQUIRE(bp.smem <= 160 * 1024, "CTC LDS carve exceeds 160 KiB");
   return bp;
@@ -117,7 +120,7 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   w.meta.reserve(nln + nst);
   {
     char* stage = (char*)w.ring.acquire(nln + nst);
-    // workgroups take the lines largest lattice first (one workgroup per line; more lines than CUs run in rounds)
+    // workgroups take the lines largest lattice first (nsplit workgroups per line, part-major; more workgroups than CUs run in rounds)
     std::vector<int> order(bs);
     for (int b = 0; b < bs; b++) order[b] = b;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lo[x + 1] - lo[x] > lo[y + 1] - lo[y]; });
@@ -139,12 +142,28 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   a.P = probs; a.Dz = deltas; a.aligned = aligned;
   a.states = (const int*)(w.meta.p + nln);
   a.lat = w.lat.p; a.nc = nc;
-  w.prof.reserve(16); a.prof = w.prof.p; g_last_ctc_prof = w.prof.p;
+  w.prof.reserve(16 * 4); a.prof = w.prof.p; g_last_ctc_prof = w.prof.p;   // (16 stamps per part of line 0)
   a.float_logadd = dbg_opt("ctc_float") != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
   upload_ctc_tables(w.tables);
   a.tables = w.tables.p;
-  const CtcBatchPlan bp = ctc_minibatch_plan(nc, line_off_h, state_off_h, bs);   // (ctc.h: the one statement of the batch arithmetic)
+  // (ctc.h: the one statement of the batch arithmetic; the option is read per alignment)
+  const CtcBatchPlan bp = ctc_minibatch_plan(nc, line_off_h, state_off_h, bs, device_cu_count(), dbg_opt("ctc_split"));
   a.smax = bp.smax; a.ncp = bp.ncp; a.tile = bp.tile;
+  a.bs = bs; a.nsplit = bp.nsplit;
+  if (a.nsplit > 1) {
+    // One workgroup per line after all where no line splits (the other workgroups would only read their record and leave), and where
+    // an output overlaps the posteriors: one workgroup reads every posterior of an item before it writes there, several of a line would
+    // write rows that another still reads.
+    const int cap = ctc_region_words(ctc_lds_layout(bp.tile, bp.ncp, bp.smax), bp.tile);
+    bool any = false;
+    for (int b = 0; b < bs && !any; b++) {
+      const int T = line_off_h[b + 1] - line_off_h[b], S = state_off_h[b + 1] - state_off_h[b];
+      any = ctc_line_splits(ctc_line_plan(T, S, nus[b], nc, bp.ncp, bp.tile, cap), T, S, bp.ncp, nus[b], cap);
+    }
+    const uintptr_t p0 = (uintptr_t)probs, p1 = p0 + (size_t)line_off_h[bs] * nc * sizeof(float);
+    auto overlaps = [&](const float* o) { return o && (uintptr_t)o < p1 && (uintptr_t)o + (p1 - p0) > p0; };
+    if (!any || overlaps(deltas) || overlaps(aligned)) a.nsplit = 1;
+  }
   const size_t smem = (size_t)bp.smem;
 #ifndef CLSTM_HIP_EMU
   static size_t smem_set = 0;

@@ -34,6 +34,8 @@ inline constexpr DbgOptDef DBG_OPTS[] = {
     {"bwd_mfma_fused", 1},   // the batched backward recurrence and its weight-gradient items as one launch: 0 never,
                              //   1 below 900 lines, 2 always
     {"ctc_float", 0},        // 1: float-only log_add in the CTC alignment
+    {"ctc_split", 0},        // workgroups per line of the CTC alignment: 0 the rule (ctc.h: ctc_nsplit -- the largest of 4, 2, 1 that
+                             //   keeps lines x workgroups within the device's CUs), 1 one, 2 / 4 that many for every line that splits
     {"peer_two_phase", 1},   // form of the peer gradient exchange: 1 one-shot up to 4 MB and at two ranks, two-phase above 4 MB at
                              //   three or more (comm.h); 0 one-shot at every size; 2 two-phase at every size and rank count
 };

@@ -594,6 +594,17 @@ int clstm_debug_product_plan(const int* shape, int* plan);
  * Tests use it to make sure the path they mean to cover is the one that runs (tests/test_ctc_path_sweep.py). */
 int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
                          int* line_plan_h);
+/* How many workgroups the alignment launch gives every line that splits (csrc/ctc.h: ctc_nsplit): host arithmetic, no net, no device when
+ * ncu > 0.  bs: lines of the minibatch; ncu: CUs (0: the current device's; the emulator's stand-in).  *nsplit_h (HOST out): 4, 2 or 1 --
+ * the largest with bs * n <= ncu, or what the experiment option ctc_split (1, 2, 4) forces.  A line splits where clstm_debug_ctc_plan
+ * answers form 0 and lm_lds 1 (match scores and both lattices in LDS); every other line keeps one workgroup, and a minibatch without such
+ * a line, or whose outputs overlap its posteriors, is launched with one workgroup per line whatever this answers. */
+int clstm_debug_ctc_split(int bs, int ncu, int* nsplit_h);
+/* range_h[0 .. 1] (HOST out): the frames [lo, hi) that part k of the n workgroups of a line of T frames emits (csrc/ctc.h:
+ * ctc_part_frames, the function the kernel calls). */
+int clstm_debug_ctc_part_frames(int T, int n, int k, int* range_h);
+/* clstm_debug_ctc_cycles for part `part` (0 .. 3) of line 0's workgroups (part 0: the same stamps). */
+int clstm_debug_ctc_cycles_part(int part, long long* out_h);
 
 #ifdef __cplusplus
 }
