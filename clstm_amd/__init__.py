@@ -7,4 +7,4 @@ search).  See DESIGN.md and INTEGRATION.md.
 """
 from .abi import ClstmError, load  # noqa: F401
 from .lm import CharLM  # noqa: F401
-from .net import Network, Normalizer, make_net, sgd_update, mktargets  # noqa: F401
+from .net import Network, Normalizer, make_net, sgd_update, mktargets, edit_distance, cer  # noqa: F401

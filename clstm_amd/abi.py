@@ -66,6 +66,7 @@ _SIGS = {
     "clstm_charlm_create": [_P, _I, _I, _P, _P],
     "clstm_charlm_destroy": [_P],
     "clstm_ctc_beam_lm_batch": [_P, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
+    "clstm_edit_distance_batch": [_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     "clstm_mktargets": [_P, _P, _I],
     "clstm_trivial_decode_batch": [_P, _I, _P, _I, _P, _P, _P],
     "clstm_net_nparams_for": [_P],
@@ -93,6 +94,7 @@ _SIGS = {
     "clstm_net_score": [_P, _P, _P, _P, _I, _P, _P, _P],
     "clstm_net_beam": [_P, _I, _I, _P, _P, _P, _P],
     "clstm_net_beam_lm": [_P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
+    "clstm_net_errors": [_P, _P, _P, _P, _P, _P],
     "clstm_net_backward": [_P],
     "clstm_net_enable_input_deltas": [_P, _I],
     "clstm_net_get_input_deltas_h": [_P, _P],
@@ -145,6 +147,7 @@ _SIGS = {
     "clstm_debug_narrow_plan": [_P, _P],
     "clstm_debug_product_plan": [_P, _P],
     "clstm_debug_ctc_plan": [_I, _P, _P, _P, _I, _P, _P],
+    "clstm_debug_edit_plan": [_I, _I, _I, _P],
     "clstm_debug_ctc_split": [_I, _I, _P],
     "clstm_debug_ctc_part_frames": [_I, _I, _I, _P],
     "clstm_debug_ctc_cycles_part": [_I, _P],
@@ -156,7 +159,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGS) + ["clstm_last_error", "clstm_abi_version"
 # the emulator's build directory can outlive the sources it was made from when their time stamps move backwards -- and a CALL of the
 # entry there raises AttributeError.  (libclstm_hip.so must export them all: tests/test_abi_exports.py)
 _LATE = {"clstm_debug_net_holds", "clstm_debug_wide_plan", "clstm_debug_narrow_plan", "clstm_debug_product_plan", "clstm_debug_ctc_plan",
-         "clstm_debug_ctc_split", "clstm_debug_ctc_part_frames", "clstm_debug_ctc_cycles_part"}
+         "clstm_debug_ctc_split", "clstm_debug_ctc_part_frames", "clstm_debug_ctc_cycles_part", "clstm_debug_edit_plan"}
 
 
 class Lib:

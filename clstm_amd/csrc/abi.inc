@@ -11,6 +11,7 @@ struct clstm_net {
   DecodeWorkspace dec;
   ScoreWorkspace score;
   BeamWorkspace beam;
+  EditWorkspace edit;
 };
 
 #define EW(kernel, len, ...) \
@@ -187,6 +188,15 @@ int clstm_ctc_beam_lm_batch(const float* probs, int nc, const int* line_off_h, i
   run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
 }
+int clstm_edit_distance_batch(const int* hyp_h, const int* hyp_off_h, int npairs, const int* ref_h, const int* ref_off_h, int nref,
+                              const int* ref_of_h, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h, int* confusion_h) {
+  ABI_BEGIN
+  if (!g_edit_ws) g_edit_ws = new EditWorkspace();
+  edit_distance_batch(*g_edit_ws, hyp_h, hyp_off_h, npairs, ref_h, ref_off_h, nref, ref_of_h, nsym, dist_h, counts_h, nops_h, ops_h, confusion_h,
+                      g_stream);
+  ABI_END
+}
+int clstm_debug_edit_plan(int la, int lb, int want_script, int* plan) { ABI_BEGIN describe_edit_plan(la, lb, want_script, plan); ABI_END }
 int clstm_trivial_decode_batch(const float* probs, int nc, const int* line_off_h, int bs, int* classes_h,
                                int* locs_h, int* counts_h) {
   ABI_BEGIN
@@ -318,6 +328,38 @@ int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm,
   struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
   const BeamLm with{&lm->lm, weight, bonus, am_score_h};
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
+  ABI_END
+}
+// edit distance of every line's trivial_decode against its transcript: the guards and guarantees of clstm_net_score (reads Z only; the
+// decode and edit workspaces are its own).  The decoded classes are compared where decode_kernel leaves them: their lengths are known to
+// the device alone, so every line is planned for as many symbols as it has frames.
+int clstm_net_errors(clstm_net* h, const int* labels_h, const int* L_h, int* dist_h, int* counts_h, int* confusion_h) {
+  ABI_BEGIN
+  REQUIRE(h, "null argument");
+  Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_errors");
+  const char* const E = "clstm_net_errors";
+  const int nc = n.desc.nclasses, nsym = nc + 1;
+  check_edit_common(E, nsym, dist_h || counts_h || confusion_h, confusion_h != nullptr);
+  REQUIRE(labels_h && L_h, "clstm_net_errors: null argument");
+  std::vector<int> roff(n.bs + 1, 0);
+  for (int b = 0; b < n.bs; b++) {
+    REQUIRE(L_h[b] >= 0, std::string(E) + ": L_h[" + std::to_string(b) + "] is negative");
+    REQUIRE((long long)roff[b] + L_h[b] < 0x7FFFFFFFll, std::string(E) + ": the transcripts exceed 2^31 labels");
+    roff[b + 1] = roff[b] + L_h[b];
+  }
+  check_edit_labels(E, "reference", labels_h, roff[n.bs], nsym);   // (a hypothesis label would be checked against nc: decode emits none outside [1, nc))
+  EditJob job;
+  job.script = counts_h || confusion_h;
+  const int* lo = n.line_off_h.data();
+  for (int b = 0; b < n.bs; b++) edit_add_pair(job, E, b, lo[b], lo[b + 1] - lo[b], roff[b], L_h[b]);
+  RoctxRange range_("clstm:errors");
+  launch_decode(h->dec, n.Z.p, nc, lo, n.bs, g_stream, false);
+  n.timing.begin("edit_distance", g_stream);
+  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  static const int none = 0;
+  run_edit_distance(h->edit, job, roff[n.bs] ? labels_h : &none, roff[n.bs], nullptr, 0, h->dec.out.p + n.bs, h->dec.out.p, nsym, dist_h,
+                    counts_h, nullptr, nullptr, confusion_h, g_stream);
   ABI_END
 }
 int clstm_net_backward(clstm_net* h) { ABI_BEGIN h->net.require(Net::NEED_PASS, "clstm_net_backward"); h->net.backward(); ABI_END }

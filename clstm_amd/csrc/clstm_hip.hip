@@ -18,6 +18,7 @@
 #include "ctc.h"
 #include "ctc_score.h"
 #include "ctc_beam.h"
+#include "edit_distance.h"
 #include "devintrin.h"
 #include "gemm_mfma.h"
 #include "gemm_bf16.h"

@@ -182,20 +182,27 @@ struct DecodeWorkspace {
   DevBuf<int> out;            // [counts bs | classes N | locs N | peak values N (float bits)]: ONE copy brings the results back
   PinnedBuf<int> host;       // pinned landing buffer of that copy
 };
-// conf_h (may be null): the peak value of every emitted class (decode_kernel: out_val)
-static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs,
-                       int* classes_h, int* locs_h, int* counts_h, hipStream_t s, float* conf_h = nullptr) {
+// the two launches of a decode; the results stay in w.out on the device (run_decode brings them back, clstm_net_errors compares them
+// where they lie)
+static void launch_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, hipStream_t s, bool want_conf) {
   const int N = line_off_h[bs];
   REQUIRE(bs > 0 && N > 0, "empty batch");
   const size_t nout = (size_t)bs + 3 * (size_t)N;
   w.line_off.reserve(bs + 1); w.idx.reserve(N); w.val.reserve(N); w.out.reserve(nout);
-  w.host.reserve(nout);
   int* cnt_d = w.out.p; int* cls_d = cnt_d + bs; int* loc_d = cls_d + N; float* conf_d = reinterpret_cast<float*>(loc_d + N);
   HIPCHECK(hipMemcpyAsync(w.line_off.p, line_off_h, (bs + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   CLSTM_LAUNCH(argmax_kernel, dim3((N + 255) / 256), dim3(256), 0, s, probs, w.idx.p, w.val.p, N, nc);
   CLSTM_LAUNCH(decode_kernel, dim3(bs), dim3(64), 0, s, (const int*)w.idx.p, (const float*)w.val.p,
-               (const int*)w.line_off.p, cls_d, loc_d, cnt_d, conf_h ? conf_d : (float*)nullptr);
+               (const int*)w.line_off.p, cls_d, loc_d, cnt_d, want_conf ? conf_d : (float*)nullptr);
   check_launch();
+}
+// conf_h (may be null): the peak value of every emitted class (decode_kernel: out_val)
+static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs,
+                       int* classes_h, int* locs_h, int* counts_h, hipStream_t s, float* conf_h = nullptr) {
+  launch_decode(w, probs, nc, line_off_h, bs, s, conf_h != nullptr);
+  const int N = line_off_h[bs];
+  const size_t nout = (size_t)bs + 3 * (size_t)N;
+  w.host.reserve(nout);
   // (one transfer instead of one per array.  Measured on whole recognition calls of one line of 200 frames, before -> after this and
   //  predict's one-launch ingest: set_batch + set_inputs_d + forward + decode 199 -> 172 us per call, clstm_net_predict with conf 210 ->
   //  172 us; EXPERIMENTS 13.4)
@@ -506,6 +513,143 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
   if (labels_h) memcpy(labels_h, w.host.p + bs + (1 + nsc) * nslot, (size_t)nbest * N * sizeof(int));
 }
 
+// ---- edit distance, edit script, confusions (edit_distance.h) ----------------------------------------------------------------
+// A workspace of its own, as the score's and the beam's: an error count touches neither a prepared alignment nor anything of the net's.
+struct EditWorkspace {
+  PinnedRing ring;
+  DevBuf<char> meta;          // [pair records | references | hypotheses (where they come from the host)]
+  DevBuf<int> ws;             // direction words and edge columns beyond a wave's LDS carve
+  DevBuf<int> out;            // [dist np | counts 3 np | nops np | confusion nsym^2 | scripts]: ONE copy brings back what was asked for
+  PinnedBuf<int> host;
+};
+// what the launch will be, from the arguments alone (nothing is enqueued while this can still refuse)
+struct EditJob {
+  std::vector<EditPair> pairs;
+  long long ws_words = 0, ops_words = 0;
+  int lds_wave_words = 0;
+  bool script = false;
+};
+constexpr int EDIT_PLAN_INTS = 5;   // include/clstm_abi.h documents the record
+static void describe_edit_plan(int la, int lb, int want_script, int* plan) {
+  REQUIRE(la >= 0 && lb >= 0 && plan, "clstm_debug_edit_plan: negative length / null argument");
+  const EditPlan p = edit_plan(la, lb, want_script != 0);
+  plan[0] = p.nstrips; plan[1] = p.dirs; plan[2] = p.edge; plan[3] = p.nw; plan[4] = p.lds_words;
+}
+// the refusals every caller shares; each names the entry and the offending index
+static void check_edit_offsets(const char* entry, const char* what, const int* off, int n) {
+  REQUIRE(off[0] >= 0, std::string(entry) + ": " + what + "[0] is negative");
+  for (int i = 0; i < n; i++)
+    REQUIRE(off[i + 1] >= off[i], std::string(entry) + ": " + what + "[" + std::to_string(i + 1) + "] is smaller than the offset before it");
+}
+// labels lie in [1, bound): bound = nsym, except that a hypothesis of clstm_net_errors has no label nclasses = nsym - 1
+static void check_edit_labels(const char* entry, const char* what, const int* lab, long long n, int bound) {
+  for (long long i = 0; i < n; i++)
+    REQUIRE(lab[i] >= 1 && lab[i] < bound, std::string(entry) + ": " + what + " label " + std::to_string(lab[i]) + " at index " +
+                                               std::to_string(i) + " is outside [1, " + std::to_string(bound) + ")");
+}
+static void check_edit_common(const char* entry, int nsym, bool any_out, bool conf) {
+  REQUIRE(nsym >= 2, std::string(entry) + ": nsym must be at least 2");
+  REQUIRE(any_out, std::string(entry) + ": every output is NULL");
+  REQUIRE(!conf || (long long)nsym * nsym <= (1ll << 26), std::string(entry) + ": the confusion table exceeds 2^26 ints");
+}
+// one pair into the job: its slots, its workspace, the launch's LDS
+static void edit_add_pair(EditJob& job, const char* entry, int idx, int hyp_off, int la_cap, int ref_off, int lb) {
+  const EditPlan pl = edit_plan(la_cap, lb, job.script);
+  EditPair pr{};
+  pr.hyp_off = hyp_off; pr.la_cap = la_cap; pr.ref_off = ref_off; pr.lb = lb; pr.idx = idx;
+  pr.ops_off = (int)job.ops_words;
+  if (job.script) job.ops_words += (long long)la_cap + lb;
+  if (pl.dirs == EDIT_WS) { pr.ws_dirs = job.ws_words; job.ws_words += pl.dir_words; }
+  if (pl.edge == EDIT_WS) { pr.ws_edge = job.ws_words; job.ws_words += pl.edge_words; }
+  job.lds_wave_words = std::max(job.lds_wave_words, pl.lds_words);
+  REQUIRE(job.ops_words < 0x7FFFFFFFll, std::string(entry) + ": the scripts exceed 2^31 slots");
+  REQUIRE(job.ws_words < (1ll << 33), std::string(entry) + ": workspace too large");
+  job.pairs.push_back(pr);
+}
+// refs_h: nref_words packed reference labels; hyps_h (or NULL): nhyp_words packed hypothesis labels, copied behind them -- else the
+// hypotheses are hyp_d / hyp_len_d on the device (clstm_net_errors).  Everything has been validated.
+static void run_edit_distance(EditWorkspace& w, EditJob& job, const int* refs_h, long long nref_words, const int* hyps_h, long long nhyp_words,
+                              const int* hyp_d, const int* hyp_len_d, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h,
+                              int* conf_h, hipStream_t s) {
+  const size_t np = job.pairs.size(), nconf = conf_h ? (size_t)nsym * nsym : 0;
+  if (np == 0) {
+    if (conf_h) memset(conf_h, 0, nconf * sizeof(int));
+    return;
+  }
+  // waves take the pairs largest table first; a pair's results do not depend on where it runs
+  std::stable_sort(job.pairs.begin(), job.pairs.end(), [](const EditPair& x, const EditPair& y) {
+    return (long long)x.la_cap * x.lb > (long long)y.la_cap * y.lb;
+  });
+  const size_t npr = np * sizeof(EditPair), nrf = (size_t)nref_words * sizeof(int), nhy = (size_t)(hyps_h ? nhyp_words : 0) * sizeof(int);
+  const size_t nout = 5 * np + nconf + (size_t)job.ops_words;
+  w.meta.reserve(npr + nrf + nhy);
+  w.ws.reserve((size_t)(job.ws_words > 0 ? job.ws_words : 1));
+  w.out.reserve(nout);
+  w.host.reserve(nout);
+  char* stage = (char*)w.ring.acquire(npr + nrf + nhy);   // one pinned slot, one copy
+  memcpy(stage, job.pairs.data(), npr);
+  if (nrf) memcpy(stage + npr, refs_h, nrf);
+  if (nhy) memcpy(stage + npr + nrf, hyps_h, nhy);
+  HIPCHECK(hipMemcpyAsync(w.meta.p, stage, npr + nrf + nhy, hipMemcpyHostToDevice, s));
+  w.ring.commit(s);
+  if (nconf) HIPCHECK(hipMemsetAsync(w.out.p + 5 * np, 0, nconf * sizeof(int), s));
+  EditArgs a{};
+  a.pairs = (const EditPair*)w.meta.p;
+  a.ref = (const int*)(w.meta.p + npr);
+  a.hyp = hyps_h ? (const int*)(w.meta.p + npr + nrf) : hyp_d;
+  a.hyp_len = hyps_h ? nullptr : hyp_len_d;
+  a.ws = w.ws.p;
+  a.dist = w.out.p; a.counts = w.out.p + np; a.nops = w.out.p + 4 * np;
+  a.conf = nconf ? w.out.p + 5 * np : nullptr;
+  a.ops = w.out.p + 5 * np + nconf;
+  a.npairs = (int)np; a.nsym = nsym; a.lds_wave_words = job.lds_wave_words;
+  const size_t smem = (size_t)EDIT_WAVES * job.lds_wave_words * sizeof(int);   // (<= 64 KiB: EDIT_WAVE_WORDS)
+  const dim3 grid((unsigned)((np + EDIT_WAVES - 1) / EDIT_WAVES));
+  if (job.script) CLSTM_LAUNCH(edit_distance_kernel<true>, grid, dim3(EDIT_THREADS), smem, s, a);
+  else CLSTM_LAUNCH(edit_distance_kernel<false>, grid, dim3(EDIT_THREADS), smem, s, a);
+  check_launch();
+  g_path_count[PC_EDIT]++;
+  const size_t ncopy = !job.script ? np : 5 * np + nconf + (ops_h ? (size_t)job.ops_words : 0);
+  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (dist_h) memcpy(dist_h, w.host.p, np * sizeof(int));
+  if (counts_h) memcpy(counts_h, w.host.p + np, 3 * np * sizeof(int));
+  if (nops_h) memcpy(nops_h, w.host.p + 4 * np, np * sizeof(int));
+  if (conf_h) memcpy(conf_h, w.host.p + 5 * np, nconf * sizeof(int));
+  if (ops_h)   // (only the codes of each script: the rest of a pair's slots stays the caller's)
+    for (const EditPair& pr : job.pairs) {
+      const int n = w.host.p[4 * np + pr.idx];
+      memcpy(ops_h + pr.ops_off, w.host.p + 5 * np + nconf + pr.ops_off, (size_t)n * sizeof(int));
+    }
+}
+// clstm_edit_distance_batch: validation, the job, the call
+static void edit_distance_batch(EditWorkspace& w, const int* hyp_h, const int* hyp_off_h, int npairs, const int* ref_h, const int* ref_off_h,
+                                int nref, const int* ref_of_h, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h, int* conf_h,
+                                hipStream_t s) {
+  const char* const E = "clstm_edit_distance_batch";
+  check_edit_common(E, nsym, dist_h || counts_h || nops_h || ops_h || conf_h, conf_h != nullptr);
+  REQUIRE(npairs >= 0 && nref >= 0 && hyp_off_h && ref_off_h, std::string(E) + ": negative count / null offsets");
+  REQUIRE(ref_of_h || nref == npairs, std::string(E) + ": ref_of_h is NULL: one reference per pair expected (nref == npairs)");
+  check_edit_offsets(E, "hyp_off_h", hyp_off_h, npairs);
+  check_edit_offsets(E, "ref_off_h", ref_off_h, nref);
+  const int h0 = hyp_off_h[0], r0 = ref_off_h[0];
+  const long long nh = (long long)hyp_off_h[npairs] - h0, nr = (long long)ref_off_h[nref] - r0;
+  REQUIRE((nh == 0 || hyp_h) && (nr == 0 || ref_h), std::string(E) + ": null labels");
+  for (int p = 0; ref_of_h && p < npairs; p++)
+    REQUIRE(ref_of_h[p] >= 0 && ref_of_h[p] < nref, std::string(E) + ": ref_of_h[" + std::to_string(p) + "] is out of range");
+  if (nh) check_edit_labels(E, "hypothesis", hyp_h + h0, nh, nsym);
+  if (nr) check_edit_labels(E, "reference", ref_h + r0, nr, nsym);
+  EditJob job;
+  job.script = counts_h || nops_h || ops_h || conf_h;
+  for (int p = 0; p < npairs; p++) {
+    const int q = ref_of_h ? ref_of_h[p] : p;
+    edit_add_pair(job, E, p, hyp_off_h[p] - h0, hyp_off_h[p + 1] - hyp_off_h[p], ref_off_h[q] - r0, ref_off_h[q + 1] - ref_off_h[q]);
+  }
+  static const int none = 0;   // (no hypothesis symbol at all: still the host form)
+  run_edit_distance(w, job, nr ? ref_h + r0 : &none, nr, nh ? hyp_h + h0 : &none, nh, nullptr, nullptr, nsym, dist_h, counts_h, nops_h, ops_h, conf_h, s);
+}
+
+static thread_local EditWorkspace* g_edit_ws = nullptr;
 static thread_local CtcWorkspace* g_ctc_ws = nullptr;
 static thread_local DecodeWorkspace* g_dec_ws = nullptr;
 static thread_local ScoreWorkspace* g_score_ws = nullptr;

@@ -381,6 +381,20 @@ DEVFN bool f32_finite(float x) { return (__builtin_bit_cast(unsigned, x) & 0x7f8
 DEVFN void raise_nonfinite(int* nanflag, int step_no) { if (*nanflag == 0) *nanflag = step_no; }   // (every writer of a launch stores the same value)
 
 
+// ---- integer lane moves (edit_distance.h), in the three forms of the float ones above -------------------------------------------
+// wave_shr1_i: lane l >= 1 receives lane l - 1's value, lane 0 keeps its own (DPP wave_shr:1, as wave_shr1)
+// wave_readlane_i: every lane receives lane k's value; k is wave-uniform (v_readlane_b32: a scalar read, no LDS crossbar)
+#if defined(CLSTM_HIP_EMU)
+DEVFN int wave_shr1_i(int x) { const int l = emu_lane(); return wave_shfl_i(x, l == 0 ? 0 : l - 1); }
+DEVFN int wave_readlane_i(int x, int k) { return wave_shfl_i(x, k); }
+#elif defined(CLSTM_USE_SHFL)
+DEVFN int wave_shr1_i(int x) { return __shfl_up(x, 1, 64); }
+DEVFN int wave_readlane_i(int x, int k) { return __shfl(x, k, 64); }
+#else
+DEVFN int wave_shr1_i(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xF, 0xF, false); }
+DEVFN int wave_readlane_i(int x, int k) { return __builtin_amdgcn_readlane(x, k); }
+#endif
+
 // progress words (lstm_seq.h -> gemm_dw.h) sit one per 128-byte line: a workgroup rewrites its word every step
 constexpr int PROG_STRIDE = 32;
 

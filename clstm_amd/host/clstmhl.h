@@ -450,6 +450,89 @@ struct CLSTMOCR {
     predict_frames(lines, texts);
     score_current(batch_T, transcripts, nullptr, &spans);
   }
+  // ---- errors of the CURRENT minibatch against ground truths, counted on the device (clstm_net_errors: Levenshtein distance of every
+  // line's trivial_decode, the canonical script's substitutions / insertions / deletions, the confusion table; include/clstm_abi.h).
+  // One transcript per line of Ts, as score_current without `lines`.  A character the codec does not hold becomes label nclasses, which
+  // matches no output: the distance is levenshtein(predicted text, ground truth)'s.  Any result may be null.  counts: 3 per line;
+  // confusion: (nclasses + 1)^2, [reference label][output label], row / column 0 = insertions / deletions.
+  Classes encode_lenient(const ustring& s) const {
+    Classes cs;
+    for (char32_t ch : s) {
+      auto it = codec.encoder.find((int)ch);
+      cs.push_back(it == codec.encoder.end() || it->second == 0 ? nclasses : it->second);
+    }
+    return cs;
+  }
+  void errors_current(const vector<int>& Ts, const vector<ustring>& transcripts, vector<int>* dist, vector<int>* counts, vector<int>* confusion) {
+    const int n = (int)transcripts.size();
+    if (n != (int)Ts.size()) fail("errors: one transcript per line expected");
+    if (dist) dist->assign(n, 0);
+    if (counts) counts->assign((size_t)3 * n, 0);
+    if (confusion) confusion->assign((size_t)(nclasses + 1) * (nclasses + 1), 0);
+    if (n == 0 || (!dist && !counts && !confusion)) return;
+    Classes labels;
+    vector<int> L;
+    for (const ustring& t : transcripts) {
+      const Classes one = encode_lenient(t);
+      L.push_back((int)one.size());
+      labels.insert(labels.end(), one.begin(), one.end());
+    }
+    Classes dummy(1, 1);
+    chk(clstm_net_errors(net, labels.empty() ? dummy.data() : labels.data(), L.data(), dist ? dist->data() : nullptr,
+                         counts ? counts->data() : nullptr, confusion ? confusion->data() : nullptr), "clstm_net_errors");
+  }
+  // the same figures for texts the host already holds (clstm_edit_distance_batch): text k against transcript k
+  void errors_texts(const vector<ustring>& texts, const vector<ustring>& transcripts, vector<int>* dist, vector<int>* counts, vector<int>* confusion) {
+    const int n = (int)transcripts.size();
+    if (n != (int)texts.size()) fail("errors: one transcript per text expected");
+    if (dist) dist->assign(n, 0);
+    if (counts) counts->assign((size_t)3 * n, 0);
+    if (confusion) confusion->assign((size_t)(nclasses + 1) * (nclasses + 1), 0);
+    if (n == 0 || (!dist && !counts && !confusion)) return;
+    Classes hyp(1, 1), ref(1, 1);   // (never empty arrays)
+    vector<int> hoff(1, 0), roff(1, 0);
+    for (int k = 0; k < n; k++) {
+      const Classes h = encode_lenient(texts[k]), r = encode_lenient(transcripts[k]);
+      hyp.insert(hyp.end(), h.begin(), h.end());
+      ref.insert(ref.end(), r.begin(), r.end());
+      hoff.push_back((int)hyp.size() - 1);
+      roff.push_back((int)ref.size() - 1);
+    }
+    chk(clstm_edit_distance_batch(hyp.data() + 1, hoff.data(), n, ref.data() + 1, roff.data(), n, nullptr, nclasses + 1, dist ? dist->data() : nullptr,
+                                  counts ? counts->data() : nullptr, nullptr, nullptr, confusion ? confusion->data() : nullptr),
+        "clstm_edit_distance_batch");
+  }
+  // best-of-n ("oracle") distance: per line with a ground truth (gt_line[k] names the line of gts[k]) the smallest distance among the
+  // line's hypotheses and which one has it (-1: the line has none) -- one clstm_edit_distance_batch call in its ref_of form
+  void oracle_distance(const vector<vector<Hypothesis>>& hyps, const vector<ustring>& gts, const vector<int>& gt_line, vector<int>& best,
+                       vector<int>& best_k) {
+    best.assign(gts.size(), 0);
+    best_k.assign(gts.size(), -1);
+    Classes hyp, ref;
+    vector<int> hoff(1, 0), roff(1, 0), ref_of, first;
+    for (size_t k = 0; k < gts.size(); k++) {
+      const Classes r = encode_lenient(gts[k]);
+      ref.insert(ref.end(), r.begin(), r.end());
+      roff.push_back((int)ref.size());
+      first.push_back((int)ref_of.size());
+      for (const Hypothesis& h : hyps[gt_line[k]]) {
+        const Classes c = encode_lenient(h.text);
+        hyp.insert(hyp.end(), c.begin(), c.end());
+        hoff.push_back((int)hyp.size());
+        ref_of.push_back((int)k);
+      }
+    }
+    first.push_back((int)ref_of.size());
+    if (ref_of.empty()) return;
+    vector<int> dist(ref_of.size());
+    Classes dummy(1, 1);
+    chk(clstm_edit_distance_batch(hyp.empty() ? dummy.data() : hyp.data(), hoff.data(), (int)ref_of.size(), ref.empty() ? dummy.data() : ref.data(),
+                                  roff.data(), (int)gts.size(), ref_of.data(), nclasses + 1, dist.data(), nullptr, nullptr, nullptr, nullptr),
+        "clstm_edit_distance_batch");
+    for (size_t k = 0; k < gts.size(); k++)
+      for (int i = first[k]; i < first[k + 1]; i++)
+        if (best_k[k] < 0 || dist[i] < best[k]) { best[k] = dist[i]; best_k[k] = i - first[k]; }
+  }
   // ---- n-best transcripts (clstm_net_beam: CTC prefix beam search on the device, include/clstm_abi.h).  nbest_current works on the
   // net's CURRENT minibatch as score_current does; per line up to nbest hypotheses, best first.  A score is the log-probability the
   // beam gathered for the text -- not on the scale of score().

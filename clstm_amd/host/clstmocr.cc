@@ -1,5 +1,6 @@
 // clstmocr -- the reference's recognition driver (clstmocr.cc:40-117) on the MI355X path.
 #include "clstmhl.h"
+#include <sstream>
 using namespace clstmhost;
 
 static float scaled_log(float x) {  // clstmocr.cc:33-40 (float arithmetic, clamped to [0, 1])
@@ -17,6 +18,7 @@ static int main1(int argc, char** argv) {
               << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)\n"
               << "             beam nbest (beam=W: the nbest <= W best transcripts of every line follow its output; default off)   (not in the reference)\n"
               << "             lm lm_weight lm_bonus (with beam=W: a character n-gram model file inside the search; hypotheses gain an am_score column)   (not in the reference)\n"
+              << "             errs (1: ERRS / CER / CONF lines for the lines that have a .gt.txt beside them, counted on the device; default 0)   (not in the reference)\n"
               << "             gpu_prep (1: lines are normalised on the device, helper threads only read PNGs; default 0)   (not in the reference)\n";
     return EXIT_FAILURE;
   }
@@ -90,6 +92,64 @@ static int main1(int argc, char** argv) {
     }
     return true;
   };
+  // errs=1 (default 0: nothing changes): every input line with a ground truth beside it (<name up to its first '.'>.gt.txt) is followed by
+  // "ERRS <file> <dist> <sub> <ins> <del> <reflen>" -- the Levenshtein distance of its output against the ground truth and the
+  // substitutions, insertions (output only) and deletions (ground truth only) of the canonical edit script, counted on the device
+  // (CLSTMOCR::errors_current) -- and, with beam=W, by "ORACLE <file> <dist> <k>": the smallest distance among its n best and the first
+  // hypothesis that has it.  After the last line: "CER <total dist> <total reflen> <rate>", then the 20 largest off-diagonal entries of the
+  // confusion table as "CONF <count> <ref char or _> <out char or _>" (_: nothing -- an insertion or a deletion; ?: a character outside the
+  // codec), largest first, equal counts by the reference character's code, then the output character's, _ first.
+  const bool do_errs = getienv("errs", 0) != 0;
+  const int nsym = clstm.nclasses + 1;
+  vector<long long> confusion((size_t)nsym * nsym, 0);
+  long long total_dist = 0, total_ref = 0;
+  // the lines of the current minibatch (Ts) named `names`: ERRS and ORACLE lines by line index, the totals
+  auto count_errors = [&](const vector<string>& names, const vector<int>& Ts, const vector<ustring>& outs, const vector<vector<Hypothesis>>* hyps,
+                          vector<string>& lines_out) {
+    lines_out.assign(names.size(), "");
+    vector<ustring> with_gt;
+    vector<int> gt_line;
+    for (size_t k = 0; k < names.size(); k++) {
+      const string gtname = basename_noext(names[k]) + ".gt.txt";
+      if (!std::ifstream(gtname)) continue;
+      gt_line.push_back((int)k);
+      with_gt.push_back(utf8_to_utf32(read_text(gtname)));
+    }
+    if (gt_line.empty()) return;
+    // every line has one: the decoded classes are compared where they lie on the device; else the texts of the lines that have one
+    vector<int> dist, counts, conf;
+    if (gt_line.size() == names.size()) clstm.errors_current(Ts, with_gt, &dist, &counts, &conf);
+    else {
+      vector<ustring> texts;
+      for (int k : gt_line) texts.push_back(outs[k]);
+      clstm.errors_texts(texts, with_gt, &dist, &counts, &conf);
+    }
+    for (size_t i = 0; i < conf.size(); i++) confusion[i] += conf[i];
+    vector<int> best, best_k;
+    if (hyps) clstm.oracle_distance(*hyps, with_gt, gt_line, best, best_k);
+    for (size_t g = 0; g < gt_line.size(); g++) {
+      const int k = gt_line[g];
+      std::ostringstream o;
+      o << "ERRS " << names[k] << " " << dist[g] << " " << counts[3 * g] << " " << counts[3 * g + 1] << " " << counts[3 * g + 2] << " "
+        << with_gt[g].size() << "\n";
+      if (hyps) o << "ORACLE " << names[k] << " " << best[g] << " " << best_k[g] << "\n";
+      lines_out[k] = o.str();
+      total_dist += dist[g];
+      total_ref += (long long)with_gt[g].size();
+    }
+  };
+  auto print_error_totals = [&]() {
+    std::cout << "CER " << total_dist << " " << total_ref << " " << (total_ref ? (double)total_dist / (double)total_ref : 0.0) << std::endl;
+    struct Entry { long long n; int r, h; };
+    vector<Entry> top;
+    for (int r = 0; r < nsym; r++)
+      for (int h = 0; h < nsym; h++)
+        if (r != h && confusion[(size_t)r * nsym + h] > 0) top.push_back(Entry{confusion[(size_t)r * nsym + h], r, h});
+    std::stable_sort(top.begin(), top.end(), [](const Entry& x, const Entry& y) { return x.n > y.n; });   // (built in label = code order)
+    auto name_of = [&](int c) { return c == 0 ? string("_") : c == clstm.nclasses ? string("?") : utf32_to_utf8(ustring(1, (char32_t)clstm.codec.codec[c])); };
+    for (size_t i = 0; i < top.size() && i < 20; i++)
+      std::cout << "CONF " << top[i].n << " " << name_of(top[i].r) << " " << name_of(top[i].h) << std::endl;
+  };
   if (batch > 1 || gpu_prep) {
     if (output != "text" && output != "logs" && output != "posteriors") fail("unknown output format");
     vector<string> names;
@@ -145,6 +205,8 @@ static int main1(int argc, char** argv) {
         }
         clstm.score_current(clstm.batch_T, gts, &gt_score, &spans, &gt_line);
       }
+      vector<string> errs_lines;
+      if (do_errs) count_errors(cur.names, clstm.batch_T, outs, beam > 0 ? &hyps : nullptr, errs_lines);
       size_t next_gt = 0;
       for (size_t k = 0; k < cur.names.size(); k++) {
         const string& name = cur.names[k];
@@ -168,9 +230,11 @@ static int main1(int argc, char** argv) {
         if (beam > 0) print_nbest(name, hyps[k]);
         if (next_gt < gt_line.size() && gt_line[next_gt] == (int)k) { print_alignment(name, spans[next_gt], gt_score[next_gt]); next_gt++; }
         else if (do_align && !noalign[k].empty()) std::cout << noalign[k] << std::endl;
+        if (do_errs) std::cout << errs_lines[k] << std::flush;
       }
       if (helper.valid()) helper.get();
     }
+    if (do_errs) print_error_totals();
     return 0;
   }
   std::ifstream stream(argv[1]);
@@ -180,14 +244,17 @@ static int main1(int argc, char** argv) {
     string basename = line.substr(0, line.find_last_of("."));
     read_png(raw, line);
     for (float& v : raw.d) v = -v + 1.0f;
+    ustring out32;   // (errs=1: the line's output as text)
     if (!conf) {
       string out = clstm.predict_utf8(raw);
+      out32 = utf8_to_utf32(out);
       std::cout << line << "\t" << out << std::endl;
       if (save_text) write_text(basename + ".txt", out);
     } else {
       std::cout << "file " << line << std::endl;
       vector<CharPrediction> preds;
       clstm.predict(preds, raw);
+      for (auto& p : preds) out32.push_back(p.c);
       for (auto& p : preds) {
         ustring c(1, p.c);
         std::cout << p.i << "\t" << p.x << "\t" << utf32_to_utf8(c) << "\t" << p.p << std::endl;
@@ -218,7 +285,13 @@ static int main1(int argc, char** argv) {
       clstm.score_current(vector<int>(1, clstm.T), vector<ustring>(1, gt), &sc, &spans);
       print_alignment(line, spans[0], sc[0]);
     }
+    if (do_errs) {
+      vector<string> errs_lines;
+      count_errors(vector<string>(1, line), vector<int>(1, clstm.T), vector<ustring>(1, out32), beam > 0 ? &hyps : nullptr, errs_lines);
+      std::cout << errs_lines[0] << std::flush;
+    }
   }
+  if (do_errs) print_error_totals();
   return 0;
 }
 

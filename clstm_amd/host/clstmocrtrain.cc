@@ -149,7 +149,7 @@ static int print_usage(char** argv) {
             << "  Variables: load save_name nhidden lrate momentum target_height ntrain start charsep\n"
             << "             report_time test_every report_every save_every params   (clstmocrtrain.cc:99-115)\n"
             << "             gpu_prep (1: lines are normalised on the device, helper threads only decode PNGs; default 0)\n"
-            << "             batch (lines per update, default 1)  test_batch (lines per recognition call of the test-set pass, default batch)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
+            << "             batch (lines per update, default 1)  test_batch (lines per recognition call of the test-set pass, default batch)  gpu_errors (1: that pass counts its errors on the device, default 0)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
   return EXIT_FAILURE;
 }
 
@@ -241,6 +241,10 @@ static int main1(int argc, char** argv) {
   const bool use_cache = getienv("cache", 1) != 0;
   const int test_batch = std::max(1, getienv("test_batch", batch));
   const bool test_loss = getienv("test_loss", 0) != 0;   // (not in the reference) TESTLOSS line after every ERROR line
+  // gpu_errors=1 (not in the reference; default 0: nothing changes): the batched test pass (test_batch > 1) counts its errors on the
+  // device -- CLSTMOCR::errors_current on the minibatch the recognition call left -- instead of levenshtein() pair by pair on the host.
+  // The counts are integers: the ERROR line is the same bytes.
+  const bool gpu_errors = getienv("gpu_errors", 0) != 0;
   const int prep_threads = std::max(1, std::min(getienv("prep_threads", 16), (int)std::thread::hardware_concurrency()));
   vector<std::shared_ptr<CLSTMOCR::Line>> cache(use_cache ? trainingset.size() : 0);
   auto draw = [&](CLSTMOCR::Prepared& p) {
@@ -418,7 +422,12 @@ static int main1(int argc, char** argv) {
         if (gpu_prep) clstm.predict_batch_gpu(ptrs, tpreds);
         else clstm.predict_frames(ptrs, tpreds);
         if (test_loss) add_loss(clstm.batch_T, tgts);
-        for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += levenshtein(tpreds[k], tgts[k]); }
+        if (gpu_errors) {
+          vector<int> dist;
+          clstm.errors_current(clstm.batch_T, tgts, &dist, nullptr, nullptr);
+          for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += dist[k]; }
+        } else
+          for (int k = 0; k < n; k++) { count += tgts[k].size(); errors += levenshtein(tpreds[k], tgts[k]); }
       }
       test_error = errors / count;
       std::cout << "ERROR " << trial << " " << test_error << "     " << errors << " " << count << std::endl;

@@ -229,6 +229,24 @@ class Network:
                       ptr(nhyp), ptr(ln), ptr(sc), ptr(am), ptr(lab))
         return unpack_beam(self.T, nbest, nhyp, ln, sc, lab, am)
 
+    def errors(self, transcripts, counts=False, confusion=False):
+        """Edit distance of every line's trivial_decode against its transcript, computed where the decoded classes lie on the
+        device (clstm_net_errors).  transcripts: one label sequence per line; label `nclasses` stands for a character outside the
+        codec and matches nothing.  -> dist [bs]; with counts / confusion: (dist[, counts [bs, 3] = substitutions, insertions,
+        deletions][, confusion [nclasses + 1, nclasses + 1], rows = reference label, columns = output label, row / column 0 =
+        insertions / deletions])."""
+        assert len(transcripts) == len(self.T)
+        bs, nsym = len(self.T), self.nclasses + 1
+        L = i32([len(t) for t in transcripts])
+        flat = [int(c) for t in transcripts for c in t]
+        labels = i32(flat if flat else [0])
+        dist = np.zeros(bs, np.int32)
+        cnt = np.zeros((bs, 3), np.int32) if counts else None
+        conf = np.zeros((nsym, nsym), np.int32) if confusion else None
+        self.lib.call("clstm_net_errors", self.h, ptr(labels), ptr(L), ptr(dist), ptr(cnt), ptr(conf))
+        out = (dist,) + ((cnt,) if counts else ()) + ((conf,) if confusion else ())
+        return out if len(out) > 1 else dist
+
     def backward(self):
         self.lib.call("clstm_net_backward", self.h)
 
@@ -535,6 +553,51 @@ def unpack_beam(T, nbest, nhyp, ln, sc, lab, am=None):
         out.append(hyps)
         off += t
     return out
+
+
+def _pack(seqs):
+    off = i32(np.concatenate([[0], np.cumsum([len(x) for x in seqs])]))
+    flat = [int(c) for x in seqs for c in x]
+    return i32(flat if flat else [0]), off
+
+
+def edit_distance(hyps, refs, ref_of=None, nsym=None, script=False, confusion=False, lib=None):
+    """Levenshtein distance of hypothesis k against reference ref_of[k] (None: one reference per hypothesis) on the device
+    (clstm_edit_distance_batch; the algorithm and the canonical script rule in clstm_amd/csrc/edit_distance.h).  Sequences of
+    labels in [1, nsym); nsym defaults to the largest label + 1.  -> dist [n]; with script: (dist, counts [n, 3] =
+    substitutions, insertions, deletions, scripts = per pair an array of codes 0 match, 1 substitution, 2 insertion, 3 deletion);
+    with confusion a [nsym, nsym] table (rows = reference label, columns = hypothesis label, row / column 0 = insertions /
+    deletions) is appended."""
+    lib = lib or abi.load()
+    hyps, refs = [list(x) for x in hyps], [list(x) for x in refs]
+    n = len(hyps)
+    hyp, hoff = _pack(hyps)
+    ref, roff = _pack(refs)
+    ro = None if ref_of is None else i32(ref_of)
+    assert ro is None or len(ro) == n
+    if nsym is None:
+        nsym = max(2, 1 + max([int(c) for x in hyps + refs for c in x], default=1))
+    lb = [len(refs[q]) if 0 <= q < len(refs) else 0 for q in (range(n) if ro is None else ro.tolist())]   # (the library refuses a bad index)
+    dist = np.zeros(n, np.int32)
+    cnt = np.zeros((n, 3), np.int32) if script else None
+    nops = np.zeros(n, np.int32) if script else None
+    ops = np.zeros(max(1, int(hoff[-1]) + int(sum(lb))), np.int32) if script else None
+    conf = np.zeros((nsym, nsym), np.int32) if confusion else None
+    lib.call("clstm_edit_distance_batch", ptr(hyp), ptr(hoff), n, ptr(ref), ptr(roff), len(refs), ptr(ro), int(nsym),
+             ptr(dist), ptr(cnt), ptr(nops), ptr(ops), ptr(conf))
+    out = (dist,)
+    if script:
+        starts = np.asarray(hoff[:-1], np.int64) + np.concatenate([[0], np.cumsum(lb)[:-1]]).astype(np.int64) if n else []
+        out += (cnt, [ops[int(s):int(s) + int(k)].copy() for s, k in zip(starts, nops)])
+    if confusion:
+        out += (conf,)
+    return out if len(out) > 1 else dist
+
+
+def cer(dist, transcripts):
+    """character error rate: summed distances over summed transcript lengths (0 for no reference character at all)"""
+    n = sum(len(t) for t in transcripts)
+    return float(np.sum(dist)) / n if n else 0.0
 
 
 def spans(path, L):

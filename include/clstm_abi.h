@@ -150,6 +150,27 @@ int clstm_charlm_destroy(clstm_charlm* lm);
 int clstm_ctc_beam_lm_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
                             const clstm_charlm* lm, float weight, float bonus,
                             int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
+/* Unit-cost Levenshtein distance, the canonical edit script and the confusions of npairs (hypothesis, reference) pairs in one launch
+ * (clstm_amd/csrc/edit_distance.h states the algorithm).  Hypotheses: packed ints, pair p owns [hyp_off_h[p], hyp_off_h[p+1]).  References:
+ * nref of them, packed, reference q owns [ref_off_h[q], ref_off_h[q+1]).  Pair p is compared with reference ref_of_h[p] (NULL: nref ==
+ * npairs, pair p <-> reference p).  Labels lie in [1, nsym); 0 means "nothing" and is refused.  Any lengths, 0 included.  All inputs HOST
+ * (copied).  The distance is the reference's levenshtein (clstm.h:329-351).  The script is the canonical one: with D the usual table, from
+ * (la, lb), at (i, j): diagonal if i, j > 0 and D[i-1][j-1] + (h[i-1] != r[j-1]) == D[i][j]; else up (i - 1) if i > 0 and D[i-1][j] + 1 ==
+ * D[i][j]; else left (j - 1); reported in forward order as codes 0 match, 1 substitution, 2 insertion (a hypothesis symbol with nothing
+ * in the reference), 3 deletion (a reference symbol that was not output).  Outputs HOST, each may be NULL, at least one not:
+ *   dist_h      [npairs]      the distance
+ *   counts_h    [npairs*3]    substitutions, insertions, deletions of the script: their sum is the distance
+ *   nops_h      [npairs]      codes in the script (max(la, lb) <= nops <= la + lb)
+ *   ops_h                     pair p owns la + lb slots from (hyp_off_h[p] - hyp_off_h[0]) + (sum of lb over the pairs before p); its
+ *                             first nops_h[p] slots receive the codes, the others are left as they were
+ *   confusion_h [nsym*nsym]   summed over all pairs: [r*nsym + h] per match / substitution, [r*nsym + 0] per deletion, [0*nsym + h] per
+ *                             insertion; [0] stays 0
+ * dist_h alone keeps no directions.  A pair's results depend on nothing but the pair.  Refused, each by a message that names this entry
+ * and the offending index, before anything is enqueued or written: a negative or decreasing offset, a label <= 0 or >= nsym, a ref_of_h
+ * entry outside [0, nref), ref_of_h NULL with nref != npairs, nsym < 2, a confusion table above 2^26 ints, every output NULL.  npairs = 0
+ * launches nothing (confusion_h is zeroed).  Blocking. */
+int clstm_edit_distance_batch(const int* hyp_h, const int* hyp_off_h, int npairs, const int* ref_h, const int* ref_off_h, int nref,
+                              const int* ref_of_h, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h, int* confusion_h);
 /* mktargets  ctc.cc:148-157: 2L+1 state classes, blank (0) on even positions.  HOST arrays. */
 int clstm_mktargets(int* states_h, const int* transcript_h, int L);
 /* trivial_decode  ctc.cc:159-190 (+ argmax tensor.h:357-366), batched.  probs DEVICE [N][nc];
@@ -220,7 +241,7 @@ int clstm_net_set_gradient_clip(clstm_net* net, float clip);
  *   backward ran              else "input deltas not enabled / no backward yet" (clstm_net_enable_input_deltas, then a backward pass of THIS minibatch)
  *
  *   entry                                              | batch declared | current (no declared next) | saved (not predict's) | backward ran
- *   get_outputs_h, decode, score, beam, beam_lm        | yes            | yes                        |                       |
+ *   get_outputs_h, decode, score, beam, beam_lm, errors| yes            | yes                        |                       |
  *   get_state_h which = 5                              | yes            | yes                        |                       |
  *   get_state_h other, ctc, backward                   | yes            | yes                        | yes                   |
  *   set_output_deltas_h                                | yes            | yes                        | yes                   |
@@ -270,6 +291,14 @@ int clstm_net_beam(clstm_net* net, int beam, int nbest, int* nhyp_h, int* len_h,
  * time under "ctc_beam_lm". */
 int clstm_net_beam_lm(clstm_net* net, int beam, int nbest, const clstm_charlm* lm, float weight, float bonus,
                       int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
+/* clstm_edit_distance_batch for the net's current minibatch: the hypotheses are trivial_decode of every line, compared where
+ * decode_kernel leaves them on the device (nothing comes to the host but the results); the references are labels_h / L_h[bs], one packed
+ * transcript per line, with nsym = nclasses + 1 -- label nclasses, allowed in references only, stands for a character outside the codec and
+ * matches nothing.  dist_h [bs], counts_h [bs*3], confusion_h [(nclasses+1)^2] as there; each may be NULL, at least one not.  Exactly
+ * the preconditions and guarantees of clstm_net_score: needs a current minibatch; works after clstm_net_forward, after a training step
+ * and after clstm_net_predict; rank-local; parameters, derivs, grads, deltas, the step count, the device error words and a declared next
+ * minibatch are untouched.  Refusals as clstm_edit_distance_batch's, by this entry's name.  Kernel time under "edit_distance". */
+int clstm_net_errors(clstm_net* net, const int* labels_h, const int* L_h, int* dist_h, int* counts_h, int* confusion_h);
 /* net->backward(): accumulates this minibatch's gradient sum into grads (zeroed first). */
 int clstm_net_backward(clstm_net* net);
 /* input deltas of the first layer are only computed if enabled (nothing on the OCR path reads
@@ -506,6 +535,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *     max-plus form for vscore_h / path_h;
  *  29  beam-search launches (clstm_ctc_beam_batch / clstm_net_beam): one per call that had a line with frames;
  *  30  the same with a language model (clstm_ctc_beam_lm_batch / clstm_net_beam_lm); 29 does not move for them;
+ *  31  edit-distance launches (clstm_edit_distance_batch / clstm_net_errors): one per call that had a pair;
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
@@ -594,6 +624,13 @@ int clstm_debug_product_plan(const int* shape, int* plan);
  * Tests use it to make sure the path they mean to cover is the one that runs (tests/test_ctc_path_sweep.py). */
 int clstm_debug_ctc_plan(int nc, const int* line_off_h, const int* states_h, const int* state_off_h, int bs, int* batch_plan_h,
                          int* line_plan_h);
+/* Which form a pair of the edit-distance kernel takes (csrc/edit_distance.h: edit_plan -- the function the host sizes the launch with and
+ * the pair's wave addresses with): host arithmetic, no net, no device.  la, lb: hypothesis and reference length (for clstm_net_errors la is
+ * the line's frames); want_script: anything beyond dist_h is asked for.
+ * plan (5 ints, HOST out): 0 strips of 64 reference columns (0: an empty reference); 1 directions: 0 none (distances only, or an empty
+ *   side), 1 in the wave's LDS carve, 2 in the workspace; 2 the edge column between strips: 0 none (one strip), 1 LDS (la < 1024), 2
+ *   workspace; 3 direction words per column (ceil(la / 16) made odd); 4 words of the wave's LDS carve (at most 4096). */
+int clstm_debug_edit_plan(int la, int lb, int want_script, int* plan);
 /* How many workgroups the alignment launch gives every line that splits (csrc/ctc.h: ctc_nsplit): host arithmetic, no net, no device when
  * ncu > 0.  bs: lines of the minibatch; ncu: CUs (0: the current device's; the emulator's stand-in).  *nsplit_h (HOST out): 4, 2 or 1 --
  * the largest with bs * n <= ncu, or what the experiment option ctc_split (1, 2, 4) forces.  A line splits where clstm_debug_ctc_plan
