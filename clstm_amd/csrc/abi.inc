@@ -17,6 +17,15 @@ struct clstm_net {
 #define EW(kernel, len, ...) \
   CLSTM_LAUNCH(kernel, dim3(nblocks(len)), dim3(256), 0, g_stream, __VA_ARGS__); check_launch();
 
+// a net-level query entry's roctx range with its timing bracket on g_stream, both ended on every exit path
+struct QueryScope {
+  RoctxRange range;
+  Timing& timing;
+  bool timed = false;
+  QueryScope(Net& n, const char* range_name, const char* bracket = nullptr) : range(range_name), timing(n.timing) { if (bracket) time(bracket); }
+  void time(const char* bracket) { timing.begin(bracket, g_stream); timed = true; }   // (the launches from here on)
+  ~QueryScope() { if (timed) timing.end(g_stream); }
+};
 // What a per-minibatch entry point needs of the net is ONE line at its top: Net::require(needs, name) (net.inc; the table: include/clstm_abi.h).
 struct clstm_charlm { CharLm lm; };
 struct clstm_normalizer {
@@ -139,22 +148,19 @@ int clstm_mktargets(int* states_h, const int* transcript_h, int L) {
 int clstm_ctc_align_batch(const float* probs, float* deltas, float* aligned, int nc, const int* line_off_h,
                           const int* states_h, const int* state_off_h, int bs) {
   ABI_BEGIN
-  if (!g_ctc_ws) g_ctc_ws = new CtcWorkspace();
-  run_ctc(*g_ctc_ws, probs, deltas, aligned, nc, line_off_h, states_h, state_off_h, bs, g_stream);
+  run_ctc(thread_workspace<CtcWorkspace>(), probs, deltas, aligned, nc, line_off_h, states_h, state_off_h, bs, g_stream);
   ABI_END
 }
 int clstm_ctc_score_batch(const float* probs, int nc, const int* line_off_h, int bs, const int* states_h, const int* state_off_h,
                           const int* cand_line_h, int ncand, float* score_h, float* vscore_h, int* path_h) {
   ABI_BEGIN
-  if (!g_score_ws) g_score_ws = new ScoreWorkspace();
-  run_ctc_score(*g_score_ws, probs, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, score_h, vscore_h, path_h, g_stream);
+  run_ctc_score(thread_workspace<ScoreWorkspace>(), probs, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, score_h, vscore_h, path_h, g_stream);
   ABI_END
 }
 int clstm_ctc_beam_batch(const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest, int* nhyp_h, int* len_h,
                          float* score_h, int* labels_h) {
   ABI_BEGIN
-  if (!g_beam_ws) g_beam_ws = new BeamWorkspace();
-  run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
+  run_ctc_beam(thread_workspace<BeamWorkspace>(), probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
   ABI_END
 }
 int clstm_charlm_create(clstm_charlm** out, int order, int nc, const float* table_h, const float* end_h) {
@@ -183,16 +189,14 @@ int clstm_ctc_beam_lm_batch(const float* probs, int nc, const int* line_off_h, i
                             float weight, float bonus, int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h) {
   ABI_BEGIN
   REQUIRE(lm, "clstm_ctc_beam_lm: the language model is required");
-  if (!g_beam_ws) g_beam_ws = new BeamWorkspace();
   const BeamLm with{&lm->lm, weight, bonus, am_score_h};
-  run_ctc_beam(*g_beam_ws, probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
+  run_ctc_beam(thread_workspace<BeamWorkspace>(), probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
 }
 int clstm_edit_distance_batch(const int* hyp_h, const int* hyp_off_h, int npairs, const int* ref_h, const int* ref_off_h, int nref,
                               const int* ref_of_h, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h, int* confusion_h) {
   ABI_BEGIN
-  if (!g_edit_ws) g_edit_ws = new EditWorkspace();
-  edit_distance_batch(*g_edit_ws, hyp_h, hyp_off_h, npairs, ref_h, ref_off_h, nref, ref_of_h, nsym, dist_h, counts_h, nops_h, ops_h, confusion_h,
+  edit_distance_batch(thread_workspace<EditWorkspace>(), hyp_h, hyp_off_h, npairs, ref_h, ref_off_h, nref, ref_of_h, nsym, dist_h, counts_h, nops_h, ops_h, confusion_h,
                       g_stream);
   ABI_END
 }
@@ -200,8 +204,7 @@ int clstm_debug_edit_plan(int la, int lb, int want_script, int* plan) { ABI_BEGI
 int clstm_trivial_decode_batch(const float* probs, int nc, const int* line_off_h, int bs, int* classes_h,
                                int* locs_h, int* counts_h) {
   ABI_BEGIN
-  if (!g_dec_ws) g_dec_ws = new DecodeWorkspace();
-  run_decode(*g_dec_ws, probs, nc, line_off_h, bs, classes_h, locs_h, counts_h, g_stream);
+  run_decode(thread_workspace<DecodeWorkspace>(), probs, nc, line_off_h, bs, classes_h, locs_h, counts_h, g_stream);
   ABI_END
 }
 
@@ -293,9 +296,7 @@ int clstm_net_score(clstm_net* h, const int* labels_h, const int* L_h, const int
   REQUIRE(labels_h && L_h && ncand > 0, "null argument / no candidates");
   std::vector<int> soff, states;
   expand_transcripts(labels_h, L_h, ncand, states, soff);
-  RoctxRange range_("clstm:score");
-  n.timing.begin("ctc_score", g_stream);
-  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  QueryScope scope_(n, "clstm:score", "ctc_score");
   run_ctc_score(h->score, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, states.data(), soff.data(), cand_line_h, ncand,
                 score_h, vscore_h, path_h, g_stream);
   ABI_END
@@ -308,9 +309,7 @@ int clstm_net_beam(clstm_net* h, int beam, int nbest, int* nhyp_h, int* len_h, f
   n.require(Net::NEED_OUTPUTS, "clstm_net_beam");
   REQUIRE(nhyp_h && score_h, "clstm_net_beam: nhyp_h and score_h are required");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam: 1 <= nbest <= beam <= 32");
-  RoctxRange range_("clstm:beam");
-  n.timing.begin("ctc_beam", g_stream);
-  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  QueryScope scope_(n, "clstm:beam", "ctc_beam");
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream);
   ABI_END
 }
@@ -323,9 +322,7 @@ int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm,
   REQUIRE(lm, "clstm_net_beam_lm: the language model is required");
   REQUIRE(nhyp_h && score_h, "clstm_net_beam_lm: nhyp_h and score_h are required");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam_lm: 1 <= nbest <= beam <= 32");
-  RoctxRange range_("clstm:beam_lm");
-  n.timing.begin("ctc_beam_lm", g_stream);
-  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
+  QueryScope scope_(n, "clstm:beam_lm", "ctc_beam_lm");
   const BeamLm with{&lm->lm, weight, bonus, am_score_h};
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
@@ -353,13 +350,11 @@ int clstm_net_errors(clstm_net* h, const int* labels_h, const int* L_h, int* dis
   job.script = counts_h || confusion_h;
   const int* lo = n.line_off_h.data();
   for (int b = 0; b < n.bs; b++) edit_add_pair(job, E, b, lo[b], lo[b + 1] - lo[b], roff[b], L_h[b]);
-  RoctxRange range_("clstm:errors");
-  launch_decode(h->dec, n.Z.p, nc, lo, n.bs, g_stream, false);
-  n.timing.begin("edit_distance", g_stream);
-  struct End { Net& n; ~End() { n.timing.end(g_stream); } } end_{n};
-  static const int none = 0;
-  run_edit_distance(h->edit, job, roff[n.bs] ? labels_h : &none, roff[n.bs], nullptr, 0, h->dec.out.p + n.bs, h->dec.out.p, nsym, dist_h,
-                    counts_h, nullptr, nullptr, confusion_h, g_stream);
+  QueryScope scope_(n, "clstm:errors");
+  launch_decode(h->dec, n.Z.p, nc, lo, n.bs, g_stream, false);   // (outside the bracket)
+  scope_.time("edit_distance");
+  run_edit_distance(h->edit, job, roff[n.bs] ? labels_h : &EDIT_NO_LABELS, roff[n.bs], nullptr, 0, h->dec.cls.dev(), h->dec.cnt.dev(), nsym,
+                    dist_h, counts_h, nullptr, nullptr, confusion_h, g_stream);
   ABI_END
 }
 int clstm_net_backward(clstm_net* h) { ABI_BEGIN h->net.require(Net::NEED_PASS, "clstm_net_backward"); h->net.backward(); ABI_END }

@@ -6,10 +6,9 @@ struct CtcWorkspace {
   CtcArgs pending{};            // kernel arguments of a prepared-but-not-launched alignment (train step)
   size_t pending_smem = 0;
   int pending_bs = 0;
-  PinnedRing ring;
+  StagedBlock meta;             // [line records (32 bytes each, in workgroup order) | states]
   DevBuf<long long> prof;
   DevBuf<double> tables;
-  DevBuf<char> meta;
   DevBuf<float> lat;
   std::vector<int> nu, seen;    // host scratch of ctc_distinct_classes, kept across calls
 };
@@ -27,8 +26,13 @@ static void upload_ctc_tables(DevBuf<double>& tables) {
 // the alignment run_ctc prepared (w.pending): at once, or -- in a training step -- behind the forward pass (step.inc)
 static void launch_ctc_align(const CtcWorkspace& w, hipStream_t s) {
   const dim3 grid((unsigned)w.pending_bs * (unsigned)w.pending.nsplit);   // part-major: workgroup i is part i / bs of line record i % bs
-  if (!w.pending.float_logadd) CLSTM_LAUNCH(ctc_align_kernel<false>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
-  else CLSTM_LAUNCH(ctc_align_kernel<true>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  if (!w.pending.float_logadd) {
+    allow_dynamic_lds((const void*)ctc_align_kernel<false>, w.pending_smem);
+    CLSTM_LAUNCH(ctc_align_kernel<false>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  } else {
+    allow_dynamic_lds((const void*)ctc_align_kernel<true>, w.pending_smem);
+    CLSTM_LAUNCH(ctc_align_kernel<true>, grid, dim3(CTC_THREADS), w.pending_smem, s, w.pending);
+  }
   check_launch();
 }
 // n transcripts (packed labels, lengths) as blank-interleaved target states (clstm_mktargets) with their offsets: what the alignment
@@ -94,13 +98,11 @@ static void describe_ctc_plan(int nc, const int* line_off_h, const int* states_h
     memcpy(line_plan_h + (size_t)b * CTC_PLAN_INTS, rec, sizeof(rec));
   }
 }
-// The per-minibatch metadata block [line records | states] is staged in a pinned slot;
-// `defer` (non-null): do not enqueue its copy -- the caller folds it into a kernel it launches anyway before the CTC
-// kernel (the input-ingest launch of a training step) and receives source, destination and size here.
-struct CtcMetaCopy { const int* src = nullptr; int* dst = nullptr; int nwords = 0; };
+// `defer` (non-null): the copy of the metadata block is not enqueued -- the caller folds it into a kernel it launches anyway before
+// the CTC kernel (the input-ingest launch of a training step), receives source, destination and size here and commits the slot.
 static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* aligned, int nc,
                     const int* line_off_h, const int* states_h, const int* state_off_h, int bs,
-                    hipStream_t s, CtcMetaCopy* defer = nullptr, bool launch = true) {
+                    hipStream_t s, StagedCopy* defer = nullptr, bool launch = true) {
   REQUIRE(bs > 0, "empty batch");
   std::vector<long long> lo(bs + 1, 0);
   for (int b = 0; b < bs; b++) {
@@ -115,32 +117,25 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
   w.lat.reserve((size_t)(lo[bs] > 0 ? lo[bs] : 1));
   ctc_distinct_classes(nc, states_h, state_off_h, bs, w.nu, w.seen);
   const std::vector<int>& nus = w.nu;
-  // one pinned slot, one device block, one copy: [line records (bs x 32 bytes, in workgroup order) | states]
-  const size_t nln = (size_t)bs * sizeof(CtcLine), nst = (size_t)(ns > 0 ? ns : 1) * sizeof(int);
-  w.meta.reserve(nln + nst);
+  const size_t nst = (size_t)(ns > 0 ? ns : 1);   // (never an empty section)
+  CtcArgs a{};
+  w.meta.begin((size_t)bs * sizeof(CtcLine) + nst * sizeof(int));
   {
-    char* stage = (char*)w.ring.acquire(nln + nst);
     // workgroups take the lines largest lattice first (nsplit workgroups per line, part-major; more workgroups than CUs run in rounds)
     std::vector<int> order(bs);
     for (int b = 0; b < bs; b++) order[b] = b;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return lo[x + 1] - lo[x] > lo[y + 1] - lo[y]; });
-    CtcLine* ln = (CtcLine*)stage;
+    const auto ln = w.meta.add<CtcLine>(bs);
     for (int i = 0; i < bs; i++) {
       const int b = order[i];
-      ln[i] = CtcLine{lo[b], b, line_off_h[b], line_off_h[b + 1] - line_off_h[b], state_off_h[b], state_off_h[b + 1] - state_off_h[b], nus[b]};
+      ln.host[i] = CtcLine{lo[b], b, line_off_h[b], line_off_h[b + 1] - line_off_h[b], state_off_h[b], state_off_h[b + 1] - state_off_h[b], nus[b]};
     }
-    if (ns > 0) memcpy(stage + nln, states_h, (size_t)ns * sizeof(int));
-    if (defer) {
-      defer->src = (const int*)stage; defer->dst = (int*)w.meta.p; defer->nwords = (int)((nln + nst) / sizeof(int));
-    } else {
-      HIPCHECK(hipMemcpyAsync(w.meta.p, stage, nln + nst, hipMemcpyHostToDevice, s));
-      w.ring.commit(s);
-    }
+    const auto st = w.meta.add<int>(nst);
+    if (ns > 0) memcpy(st.host, states_h, (size_t)ns * sizeof(int));
+    a.lines = ln.dev; a.states = st.dev;
+    if (defer) *defer = w.meta.deferred(); else w.meta.send(s);
   }
-  CtcArgs a{};
-  a.lines = (const CtcLine*)w.meta.p;
   a.P = probs; a.Dz = deltas; a.aligned = aligned;
-  a.states = (const int*)(w.meta.p + nln);
   a.lat = w.lat.p; a.nc = nc;
   w.prof.reserve(16 * 4); a.prof = w.prof.p; g_last_ctc_prof = w.prof.p;   // (16 stamps per part of line 0)
   a.float_logadd = dbg_opt("ctc_float") != 0;   // experiment option (ctc.h: ctc_softplus_float); read per alignment
@@ -164,67 +159,58 @@ static void run_ctc(CtcWorkspace& w, const float* probs, float* deltas, float* a
     auto overlaps = [&](const float* o) { return o && (uintptr_t)o < p1 && (uintptr_t)o + (p1 - p0) > p0; };
     if (!any || overlaps(deltas) || overlaps(aligned)) a.nsplit = 1;
   }
-  const size_t smem = (size_t)bp.smem;
-#ifndef CLSTM_HIP_EMU
-  static size_t smem_set = 0;
-  if (smem > smem_set) {
-    HIPCHECK(hipFuncSetAttribute((const void*)ctc_align_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    HIPCHECK(hipFuncSetAttribute((const void*)ctc_align_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    smem_set = smem;
-  }
-#endif
-  w.pending = a; w.pending_smem = smem; w.pending_bs = bs;
+  w.pending = a; w.pending_smem = (size_t)bp.smem; w.pending_bs = bs;
   if (launch) launch_ctc_align(w, s);
 }
 struct DecodeWorkspace {
   DevBuf<int> line_off, idx;
   DevBuf<float> val;
-  DevBuf<int> out;            // [counts bs | classes N | locs N | peak values N (float bits)]: ONE copy brings the results back
-  PinnedBuf<int> host;       // pinned landing buffer of that copy
+  ResultBlock res;
+  ResultBlock::Sec<int> cnt, cls, loc;   // the sections of the last launch_decode, in the block's order: counts bs, classes N, locations N,
+  ResultBlock::Sec<float> conf;          // peak values N
 };
-// the two launches of a decode; the results stay in w.out on the device (run_decode brings them back, clstm_net_errors compares them
+// the two launches of a decode; the results stay in w.res on the device (run_decode brings them back, clstm_net_errors compares them
 // where they lie)
 static void launch_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, hipStream_t s, bool want_conf) {
   const int N = line_off_h[bs];
   REQUIRE(bs > 0 && N > 0, "empty batch");
-  const size_t nout = (size_t)bs + 3 * (size_t)N;
-  w.line_off.reserve(bs + 1); w.idx.reserve(N); w.val.reserve(N); w.out.reserve(nout);
-  int* cnt_d = w.out.p; int* cls_d = cnt_d + bs; int* loc_d = cls_d + N; float* conf_d = reinterpret_cast<float*>(loc_d + N);
+  w.line_off.reserve(bs + 1); w.idx.reserve(N); w.val.reserve(N);
+  w.res.begin();
+  w.cnt = w.res.add<int>(bs); w.cls = w.res.add<int>(N); w.loc = w.res.add<int>(N); w.conf = w.res.add<float>(N);
+  w.res.reserve();
   HIPCHECK(hipMemcpyAsync(w.line_off.p, line_off_h, (bs + 1) * sizeof(int), hipMemcpyHostToDevice, s));
   CLSTM_LAUNCH(argmax_kernel, dim3((N + 255) / 256), dim3(256), 0, s, probs, w.idx.p, w.val.p, N, nc);
   CLSTM_LAUNCH(decode_kernel, dim3(bs), dim3(64), 0, s, (const int*)w.idx.p, (const float*)w.val.p,
-               (const int*)w.line_off.p, cls_d, loc_d, cnt_d, want_conf ? conf_d : (float*)nullptr);
+               (const int*)w.line_off.p, w.cls.dev(), w.loc.dev(), w.cnt.dev(), want_conf ? w.conf.dev() : (float*)nullptr);
   check_launch();
 }
 // conf_h (may be null): the peak value of every emitted class (decode_kernel: out_val)
 static void run_decode(DecodeWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs,
                        int* classes_h, int* locs_h, int* counts_h, hipStream_t s, float* conf_h = nullptr) {
   launch_decode(w, probs, nc, line_off_h, bs, s, conf_h != nullptr);
-  const int N = line_off_h[bs];
-  const size_t nout = (size_t)bs + 3 * (size_t)N;
-  w.host.reserve(nout);
+  const size_t N = (size_t)line_off_h[bs];
   // (one transfer instead of one per array.  Measured on whole recognition calls of one line of 200 frames, before -> after this and
   //  predict's one-launch ingest: set_batch + set_inputs_d + forward + decode 199 -> 172 us per call, clstm_net_predict with conf 210 ->
   //  172 us; EXPERIMENTS 13.4)
-  const size_t ncopy = (size_t)bs + (conf_h ? 3 : locs_h ? 2 : classes_h ? 1 : 0) * (size_t)N;
-  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  memcpy(counts_h, w.host.p, (size_t)bs * sizeof(int));
-  if (classes_h) memcpy(classes_h, w.host.p + bs, (size_t)N * sizeof(int));
-  if (locs_h) memcpy(locs_h, w.host.p + bs + N, (size_t)N * sizeof(int));
-  if (conf_h) memcpy(conf_h, w.host.p + bs + 2 * (size_t)N, (size_t)N * sizeof(float));
+  ResultBlock::Span last = w.cnt;   // the block up to the last array asked for
+  if (classes_h) last = w.cls;
+  if (locs_h) last = w.loc;
+  if (conf_h) last = w.conf;
+  w.res.fetch(s, last);
+  memcpy(counts_h, w.cnt.host(), (size_t)bs * sizeof(int));
+  if (classes_h) memcpy(classes_h, w.cls.host(), N * sizeof(int));
+  if (locs_h) memcpy(locs_h, w.loc.host(), N * sizeof(int));
+  if (conf_h) memcpy(conf_h, w.conf.host(), N * sizeof(float));
 }
 
 // ---- scores and forced alignments (ctc_score.h) ------------------------------------------------------------------------
-// A workspace of its own: meta block, pinned ring slot, rolling rows / back-pointer words, result block.  Nothing here touches a
+// A workspace of its own: metadata block, rolling rows / back-pointer words, result block.  Nothing here touches a
 // CtcWorkspace: an alignment that clstm_net_train_step_next prepared and has not launched survives a score call.
 struct ScoreWorkspace {
-  PinnedRing ring;
+  StagedBlock meta;
   DevBuf<double> tables;
-  DevBuf<char> meta;
   DevBuf<unsigned long long> ws;
-  DevBuf<int> out;            // [score ncand | vscore ncand (float bits) | paths]: ONE copy brings the results back
-  PinnedBuf<int> host;       // pinned landing buffer of that copy
+  ResultBlock res;
 };
 // what the launch will be, decided on the host from the arguments alone (nothing is enqueued while this can still refuse)
 struct ScorePlan {
@@ -297,19 +283,6 @@ static void plan_ctc_score(ScorePlan& pl, int nc, const int* line_off_h, int bs,
     pl.items.insert(pl.items.end(), g.it.begin(), g.it.end());
   }
 }
-#ifndef CLSTM_HIP_EMU
-// the dynamic-LDS ceiling of a kernel is a property of the function ON A DEVICE: remembered per device, per calling thread
-static void score_allow_smem(const void* kernel, int which, size_t smem) {
-  static thread_local std::map<int, size_t> allowed[6];   // score sum, score max-plus, beam (all in LDS), beam, the two with a language model
-  int dev = 0;
-  HIPCHECK(hipGetDevice(&dev));
-  size_t& have = allowed[which][dev];
-  if (smem > have) {
-    HIPCHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    have = smem;
-  }
-}
-#endif
 static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, const int* states_h,
                           const int* state_off_h, const int* cand_line_h, int ncand, float* score_h, float* vscore_h,
                           int* path_h, hipStream_t s) {
@@ -317,53 +290,43 @@ static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const i
   ScorePlan pl;
   plan_ctc_score(pl, nc, line_off_h, bs, states_h, state_off_h, cand_line_h, ncand, sum || maxplus, maxplus);
   REQUIRE(probs, "null argument");
-  const size_t nout = 2 * (size_t)ncand + (path_h ? (size_t)pl.npath : 0);
   if (!pl.groups.empty()) {
-    const int ns = state_off_h[ncand];
-    const size_t ngr = pl.groups.size() * sizeof(ScoreGroup), nit = pl.items.size() * sizeof(ScoreItem), nst = (size_t)ns * sizeof(int);
-    w.meta.reserve(ngr + nit + nst);
-    w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
-    w.out.reserve(nout);
-    w.host.reserve(nout);
-    upload_ctc_tables(w.tables);
-    char* stage = (char*)w.ring.acquire(ngr + nit + nst);   // one pinned slot, one copy: [groups | items | states]
-    memcpy(stage, pl.groups.data(), ngr);
-    memcpy(stage + ngr, pl.items.data(), nit);
-    memcpy(stage + ngr + nit, states_h, nst);
-    HIPCHECK(hipMemcpyAsync(w.meta.p, stage, ngr + nit + nst, hipMemcpyHostToDevice, s));
-    w.ring.commit(s);
+    const size_t ns = (size_t)state_off_h[ncand];
     ScoreArgs a{};
-    a.groups = (const ScoreGroup*)w.meta.p;
-    a.items = (const ScoreItem*)(w.meta.p + ngr);
-    a.states = (const int*)(w.meta.p + ngr + nit);
+    w.meta.begin(pl.groups.size() * sizeof(ScoreGroup) + pl.items.size() * sizeof(ScoreItem) + ns * sizeof(int));
+    a.groups = w.meta.put(pl.groups);
+    a.items = w.meta.put(pl.items);
+    a.states = w.meta.put(states_h, ns);
+    w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
+    w.res.begin();
+    const auto score = w.res.add<float>(ncand), vscore = w.res.add<float>(ncand);
+    const auto path = w.res.add<int>(path_h ? (size_t)pl.npath : 0);
+    w.res.reserve();
+    upload_ctc_tables(w.tables);
+    w.meta.send(s);
     a.P = probs; a.tables = w.tables.p; a.ws = w.ws.p;
     a.nc = nc; a.ncp = nc | 1; a.tile = pl.tile; a.tmax = pl.tmax; a.ncand = ncand; a.npath = (int)pl.npath;
     const int ng = (int)pl.groups.size();
     if (sum) {
       const size_t smem = (size_t)score_lds_layout(a.tmax, a.tile, a.ncp, false).words * sizeof(float);
-#ifndef CLSTM_HIP_EMU
-      score_allow_smem((const void*)ctc_score_kernel<false>, 0, smem);
-#endif
-      a.score = reinterpret_cast<float*>(w.out.p); a.path = nullptr;
+      allow_dynamic_lds((const void*)ctc_score_kernel<false>, smem);
+      a.score = score.dev(); a.path = nullptr;
       CLSTM_LAUNCH(ctc_score_kernel<false>, dim3(ng), dim3(SCORE_THREADS), smem, s, a);
       check_launch();
       g_path_count[PC_SCORE]++;
     }
     if (maxplus) {
       const size_t smem = (size_t)score_lds_layout(a.tmax, a.tile, a.ncp, true).words * sizeof(float);
-#ifndef CLSTM_HIP_EMU
-      score_allow_smem((const void*)ctc_score_kernel<true>, 1, smem);
-#endif
-      a.score = reinterpret_cast<float*>(w.out.p) + ncand; a.path = path_h ? w.out.p + 2 * (size_t)ncand : nullptr;
+      allow_dynamic_lds((const void*)ctc_score_kernel<true>, smem);
+      a.score = vscore.dev(); a.path = path_h ? path.dev() : nullptr;
       CLSTM_LAUNCH(ctc_score_kernel<true>, dim3(ng), dim3(SCORE_THREADS), smem, s, a);
       check_launch();
       g_path_count[PC_SCORE]++;
     }
-    HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    if (score_h) memcpy(score_h, w.host.p, (size_t)ncand * sizeof(float));
-    if (vscore_h) memcpy(vscore_h, w.host.p + ncand, (size_t)ncand * sizeof(float));
-    if (path_h) memcpy(path_h, w.host.p + 2 * (size_t)ncand, (size_t)pl.npath * sizeof(int));
+    w.res.fetch(s, path);
+    if (score_h) memcpy(score_h, score.host(), (size_t)ncand * sizeof(float));
+    if (vscore_h) memcpy(vscore_h, vscore.host(), (size_t)ncand * sizeof(float));
+    if (path_h) memcpy(path_h, path.host(), (size_t)pl.npath * sizeof(int));
   }
   for (int c = 0; c < ncand; c++) {   // a line without frames has no lattice
     if (pl.path_off[c + 1] != pl.path_off[c]) continue;
@@ -375,12 +338,9 @@ static void run_ctc_score(ScoreWorkspace& w, const float* probs, int nc, const i
 // ---- n-best transcripts by prefix beam search (ctc_beam.h) -------------------------------------------------------------
 // A workspace of its own, as the score's: a beam call touches neither a prepared alignment nor a score in flight.
 struct BeamWorkspace {
-  PinnedRing ring;
-  DevBuf<char> meta;
+  StagedBlock meta;
   DevBuf<int> ws;
-  DevBuf<int> out;            // [nhyp bs | len bs nbest | score bs nbest (float bits) | labels nbest N]: ONE copy brings the results back
-                              // (with a language model: [nhyp | len | score | am_score bs nbest | labels])
-  PinnedBuf<int> host;
+  ResultBlock res;
 };
 // what the launch will be, from the arguments alone; every section of a line goes to LDS while the line's sections still fit
 struct BeamPlan {
@@ -443,8 +403,7 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
   BeamPlan pl;
   plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest, lm != nullptr);
   REQUIRE(probs && nhyp_h && score_h, "clstm_ctc_beam: probs, nhyp_h and score_h are required");
-  const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest, nsc = lm ? 2 : 1;
-  const size_t nout = (size_t)bs + (1 + nsc) * nslot + (labels_h ? (size_t)nbest * N : 0);
+  const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest;
   for (int b = 0; b < bs; b++) nhyp_h[b] = 0;
   for (size_t i = 0; i < nslot; i++) {
     score_h[i] = -INFINITY;
@@ -452,75 +411,56 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
     if (lm && lm->am_score_h) lm->am_score_h[i] = -INFINITY;
   }
   if (pl.lines.empty()) return;
-  const size_t nln = pl.lines.size() * sizeof(BeamLine);
-  w.meta.reserve(nln);
-  w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
-  w.out.reserve(nout);
-  w.host.reserve(nout);
-  char* stage = (char*)w.ring.acquire(nln);
-  memcpy(stage, pl.lines.data(), nln);
-  HIPCHECK(hipMemcpyAsync(w.meta.p, stage, nln, hipMemcpyHostToDevice, s));
-  w.ring.commit(s);
-  HIPCHECK(hipMemsetAsync(w.out.p, 0, nout * sizeof(int), s));   // lines without frames, label slots beyond a hypothesis
   BeamArgs a{};
-  a.lines = (const BeamLine*)w.meta.p;
+  w.meta.begin(pl.lines.size() * sizeof(BeamLine));
+  a.lines = w.meta.put(pl.lines);
+  w.ws.reserve((size_t)(pl.ws_words > 0 ? pl.ws_words : 1));
+  w.res.begin();   // (am_score: only with a language model; labels: only where asked for)
+  const auto nhyp = w.res.add<int>(bs), len = w.res.add<int>(nslot);
+  const auto score = w.res.add<float>(nslot), am_score = w.res.add<float>(lm ? nslot : 0);
+  const auto labels = w.res.add<int>(labels_h ? (size_t)nbest * N : 0);
+  w.res.reserve();
+  w.meta.send(s);
+  w.res.zero(s, nhyp, labels);   // the whole block: lines without frames, label slots beyond a hypothesis
   a.P = probs; a.ws = w.ws.p;
-  a.nhyp = w.out.p; a.len = w.out.p + bs; a.score = reinterpret_cast<float*>(w.out.p + bs + nslot);
-  a.labels = labels_h ? w.out.p + bs + (1 + nsc) * nslot : nullptr;
+  a.nhyp = nhyp.dev(); a.len = len.dev(); a.score = score.dev();
+  a.labels = labels_h ? labels.dev() : nullptr;
   a.nc = nc; a.beam = beam; a.nbest = nbest; a.K = pl.K; a.bs = bs; a.N = (int)N;
-  const size_t smem = (size_t)pl.lds_words * sizeof(float);
-  const dim3 grid((unsigned)pl.lines.size());
   if (lm) {
     a.table = lm->lm->table.p; a.end = lm->lm->has_end ? lm->lm->end.p : nullptr;
-    a.am_score = reinterpret_cast<float*>(w.out.p + bs + 2 * nslot);
+    a.am_score = am_score.dev();
     a.weight = lm->weight; a.bonus = lm->bonus; a.order = lm->lm->order;
-    if (pl.all_lds) {
-#ifndef CLSTM_HIP_EMU
-      score_allow_smem((const void*)ctc_beam_kernel<true, true>, 4, smem);
-#endif
-      CLSTM_LAUNCH((ctc_beam_kernel<true, true>), grid, dim3(BEAM_THREADS), smem, s, a);
-    } else {
-#ifndef CLSTM_HIP_EMU
-      score_allow_smem((const void*)ctc_beam_kernel<false, true>, 5, smem);
-#endif
-      CLSTM_LAUNCH((ctc_beam_kernel<false, true>), grid, dim3(BEAM_THREADS), smem, s, a);
-    }
-  } else if (pl.all_lds) {
-#ifndef CLSTM_HIP_EMU
-    score_allow_smem((const void*)ctc_beam_kernel<true>, 2, smem);
-#endif
-    CLSTM_LAUNCH(ctc_beam_kernel<true>, grid, dim3(BEAM_THREADS), smem, s, a);
-  } else {
-#ifndef CLSTM_HIP_EMU
-    score_allow_smem((const void*)ctc_beam_kernel<false>, 3, smem);
-#endif
-    CLSTM_LAUNCH(ctc_beam_kernel<false>, grid, dim3(BEAM_THREADS), smem, s, a);
   }
+  const size_t smem = (size_t)pl.lds_words * sizeof(float);
+  auto launch = [&](auto kernel) {
+    allow_dynamic_lds((const void*)kernel, smem);
+    CLSTM_LAUNCH(kernel, dim3((unsigned)pl.lines.size()), dim3(BEAM_THREADS), smem, s, a);
+  };
+  if (lm) { if (pl.all_lds) launch(ctc_beam_kernel<true, true>); else launch(ctc_beam_kernel<false, true>); }
+  else if (pl.all_lds) launch(ctc_beam_kernel<true, false>);
+  else launch(ctc_beam_kernel<false, false>);
   check_launch();
   g_path_count[lm ? PC_BEAM_LM : PC_BEAM]++;
-  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, nout * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
+  w.res.fetch(s, labels);
   for (const BeamLine& ln : pl.lines) {   // (lines without frames keep nhyp = 0, len = 0, score = -inf)
     const int b = ln.line;
-    nhyp_h[b] = w.host.p[b];
+    nhyp_h[b] = nhyp.host()[b];
     for (int k = 0; k < nbest; k++) {
       const size_t i = (size_t)b * nbest + k;
-      if (len_h) len_h[i] = w.host.p[bs + i];
-      memcpy(&score_h[i], &w.host.p[bs + nslot + i], sizeof(float));
-      if (lm && lm->am_score_h) memcpy(&lm->am_score_h[i], &w.host.p[bs + 2 * nslot + i], sizeof(float));
+      if (len_h) len_h[i] = len.host()[i];
+      memcpy(&score_h[i], score.host() + i, sizeof(float));
+      if (lm && lm->am_score_h) memcpy(&lm->am_score_h[i], am_score.host() + i, sizeof(float));
     }
   }
-  if (labels_h) memcpy(labels_h, w.host.p + bs + (1 + nsc) * nslot, (size_t)nbest * N * sizeof(int));
+  if (labels_h) memcpy(labels_h, labels.host(), (size_t)nbest * N * sizeof(int));
 }
 
 // ---- edit distance, edit script, confusions (edit_distance.h) ----------------------------------------------------------------
 // A workspace of its own, as the score's and the beam's: an error count touches neither a prepared alignment nor anything of the net's.
 struct EditWorkspace {
-  PinnedRing ring;
-  DevBuf<char> meta;          // [pair records | references | hypotheses (where they come from the host)]
+  StagedBlock meta;
   DevBuf<int> ws;             // direction words and edge columns beyond a wave's LDS carve
-  DevBuf<int> out;            // [dist np | counts 3 np | nops np | confusion nsym^2 | scripts]: ONE copy brings back what was asked for
-  PinnedBuf<int> host;
+  ResultBlock res;
 };
 // what the launch will be, from the arguments alone (nothing is enqueued while this can still refuse)
 struct EditJob {
@@ -566,6 +506,7 @@ static void edit_add_pair(EditJob& job, const char* entry, int idx, int hyp_off,
   REQUIRE(job.ws_words < (1ll << 33), std::string(entry) + ": workspace too large");
   job.pairs.push_back(pr);
 }
+static const int EDIT_NO_LABELS = 0;   // stands for an empty label array (no hypothesis symbol at all is still the host form: hyps_h set)
 // refs_h: nref_words packed reference labels; hyps_h (or NULL): nhyp_words packed hypothesis labels, copied behind them -- else the
 // hypotheses are hyp_d / hyp_len_d on the device (clstm_net_errors).  Everything has been validated.
 static void run_edit_distance(EditWorkspace& w, EditJob& job, const int* refs_h, long long nref_words, const int* hyps_h, long long nhyp_words,
@@ -580,28 +521,24 @@ static void run_edit_distance(EditWorkspace& w, EditJob& job, const int* refs_h,
   std::stable_sort(job.pairs.begin(), job.pairs.end(), [](const EditPair& x, const EditPair& y) {
     return (long long)x.la_cap * x.lb > (long long)y.la_cap * y.lb;
   });
-  const size_t npr = np * sizeof(EditPair), nrf = (size_t)nref_words * sizeof(int), nhy = (size_t)(hyps_h ? nhyp_words : 0) * sizeof(int);
-  const size_t nout = 5 * np + nconf + (size_t)job.ops_words;
-  w.meta.reserve(npr + nrf + nhy);
-  w.ws.reserve((size_t)(job.ws_words > 0 ? job.ws_words : 1));
-  w.out.reserve(nout);
-  w.host.reserve(nout);
-  char* stage = (char*)w.ring.acquire(npr + nrf + nhy);   // one pinned slot, one copy
-  memcpy(stage, job.pairs.data(), npr);
-  if (nrf) memcpy(stage + npr, refs_h, nrf);
-  if (nhy) memcpy(stage + npr + nrf, hyps_h, nhy);
-  HIPCHECK(hipMemcpyAsync(w.meta.p, stage, npr + nrf + nhy, hipMemcpyHostToDevice, s));
-  w.ring.commit(s);
-  if (nconf) HIPCHECK(hipMemsetAsync(w.out.p + 5 * np, 0, nconf * sizeof(int), s));
+  const size_t nrf = (size_t)nref_words, nhy = (size_t)(hyps_h ? nhyp_words : 0);
   EditArgs a{};
-  a.pairs = (const EditPair*)w.meta.p;
-  a.ref = (const int*)(w.meta.p + npr);
-  a.hyp = hyps_h ? (const int*)(w.meta.p + npr + nrf) : hyp_d;
+  w.meta.begin(np * sizeof(EditPair) + (nrf + nhy) * sizeof(int));   // [pair records | references | hypotheses, where they come from the host]
+  a.pairs = w.meta.put(job.pairs);
+  a.ref = w.meta.put(refs_h, nrf);
+  a.hyp = hyps_h ? w.meta.put(hyps_h, nhy) : hyp_d;
   a.hyp_len = hyps_h ? nullptr : hyp_len_d;
+  w.ws.reserve((size_t)(job.ws_words > 0 ? job.ws_words : 1));
+  w.res.begin();
+  const auto dist = w.res.add<int>(np), counts = w.res.add<int>(3 * np), nops = w.res.add<int>(np);
+  const auto conf = w.res.add<int>(nconf), ops = w.res.add<int>((size_t)job.ops_words);
+  w.res.reserve();
+  w.meta.send(s);
+  if (nconf) w.res.zero(s, conf, conf);
   a.ws = w.ws.p;
-  a.dist = w.out.p; a.counts = w.out.p + np; a.nops = w.out.p + 4 * np;
-  a.conf = nconf ? w.out.p + 5 * np : nullptr;
-  a.ops = w.out.p + 5 * np + nconf;
+  a.dist = dist.dev(); a.counts = counts.dev(); a.nops = nops.dev();
+  a.conf = nconf ? conf.dev() : nullptr;
+  a.ops = ops.dev();
   a.npairs = (int)np; a.nsym = nsym; a.lds_wave_words = job.lds_wave_words;
   const size_t smem = (size_t)EDIT_WAVES * job.lds_wave_words * sizeof(int);   // (<= 64 KiB: EDIT_WAVE_WORDS)
   const dim3 grid((unsigned)((np + EDIT_WAVES - 1) / EDIT_WAVES));
@@ -609,17 +546,15 @@ static void run_edit_distance(EditWorkspace& w, EditJob& job, const int* refs_h,
   else CLSTM_LAUNCH(edit_distance_kernel<false>, grid, dim3(EDIT_THREADS), smem, s, a);
   check_launch();
   g_path_count[PC_EDIT]++;
-  const size_t ncopy = !job.script ? np : 5 * np + nconf + (ops_h ? (size_t)job.ops_words : 0);
-  HIPCHECK(hipMemcpyAsync(w.host.p, w.out.p, ncopy * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  if (dist_h) memcpy(dist_h, w.host.p, np * sizeof(int));
-  if (counts_h) memcpy(counts_h, w.host.p + np, 3 * np * sizeof(int));
-  if (nops_h) memcpy(nops_h, w.host.p + 4 * np, np * sizeof(int));
-  if (conf_h) memcpy(conf_h, w.host.p + 5 * np, nconf * sizeof(int));
+  w.res.fetch(s, !job.script ? dist : ops_h ? ops : conf);   // (the distances alone; everything; everything but the scripts)
+  if (dist_h) memcpy(dist_h, dist.host(), np * sizeof(int));
+  if (counts_h) memcpy(counts_h, counts.host(), 3 * np * sizeof(int));
+  if (nops_h) memcpy(nops_h, nops.host(), np * sizeof(int));
+  if (conf_h) memcpy(conf_h, conf.host(), nconf * sizeof(int));
   if (ops_h)   // (only the codes of each script: the rest of a pair's slots stays the caller's)
     for (const EditPair& pr : job.pairs) {
-      const int n = w.host.p[4 * np + pr.idx];
-      memcpy(ops_h + pr.ops_off, w.host.p + 5 * np + nconf + pr.ops_off, (size_t)n * sizeof(int));
+      const int n = nops.host()[pr.idx];
+      memcpy(ops_h + pr.ops_off, ops.host() + pr.ops_off, (size_t)n * sizeof(int));
     }
 }
 // clstm_edit_distance_batch: validation, the job, the call
@@ -645,13 +580,14 @@ static void edit_distance_batch(EditWorkspace& w, const int* hyp_h, const int* h
     const int q = ref_of_h ? ref_of_h[p] : p;
     edit_add_pair(job, E, p, hyp_off_h[p] - h0, hyp_off_h[p + 1] - hyp_off_h[p], ref_off_h[q] - r0, ref_off_h[q + 1] - ref_off_h[q]);
   }
-  static const int none = 0;   // (no hypothesis symbol at all: still the host form)
-  run_edit_distance(w, job, nr ? ref_h + r0 : &none, nr, nh ? hyp_h + h0 : &none, nh, nullptr, nullptr, nsym, dist_h, counts_h, nops_h, ops_h, conf_h, s);
+  run_edit_distance(w, job, nr ? ref_h + r0 : &EDIT_NO_LABELS, nr, nh ? hyp_h + h0 : &EDIT_NO_LABELS, nh, nullptr, nullptr, nsym, dist_h, counts_h,
+                    nops_h, ops_h, conf_h, s);
 }
 
-static thread_local EditWorkspace* g_edit_ws = nullptr;
-static thread_local CtcWorkspace* g_ctc_ws = nullptr;
-static thread_local DecodeWorkspace* g_dec_ws = nullptr;
-static thread_local ScoreWorkspace* g_score_ws = nullptr;
-static thread_local BeamWorkspace* g_beam_ws = nullptr;
-
+// the calling thread's own workspace of a kind, made at its first use and kept (the stand-alone batch entries; a net brings its own)
+template <class W>
+static W& thread_workspace() {
+  static thread_local W* w = nullptr;
+  if (!w) w = new W();
+  return *w;
+}

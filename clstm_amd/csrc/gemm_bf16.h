@@ -1427,6 +1427,7 @@ inline void gemm_x3_pair(hipStream_t stream, GemmProblem p1, FE1 fe1, GemmProble
     CLSTM_LAUNCH((gemm_x3_pair_kernel<A1, B1, FE1, A2, B2, FE2, 2>), dim3(nb1 + nb2), dim3(256), 0, stream, p1, fe1, p2, fe2, nb1);
 }
 
+static void allow_dynamic_lds(const void* kernel, size_t bytes);   // (runtime.inc: the one rule of the dynamic-LDS ceiling)
 // f32-grade product on 128 x 128 tiles (gemm_x3_128_kernel); same signature as gemm_f32 / gemm_bf16
 template <int AMODE, int BMODE, class FE>
 inline void gemm_x3_big(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe, int R, int Cn, int K, int nsplit = 1, int nbatch = 1) {
@@ -1436,13 +1437,7 @@ inline void gemm_x3_big(hipStream_t stream, GemmOperand A, GemmOperand B, FE fe,
   const int kq = nsplit > 1 ? GB2_PF * GB_BK : GB_BK;   // whole ring rounds per slab
   ksplit = ((ksplit + kq - 1) / kq) * kq;
   const size_t smem = (size_t)8 * GB2_TILE * sizeof(unsigned short);   // 64 KB
-#ifndef CLSTM_HIP_EMU
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_x3_128_kernel<AMODE, BMODE, FE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-#endif
+  allow_dynamic_lds((const void*)gemm_x3_128_kernel<AMODE, BMODE, FE>, smem);
   dim3 grid((Cn + GB2_BT - 1) / GB2_BT, (R + GB2_BT - 1) / GB2_BT, nsplit * nbatch);
   CLSTM_LAUNCH((gemm_x3_128_kernel<AMODE, BMODE, FE>), grid, dim3(256), smem, stream, A, B, fe, R, Cn, K, ksplit, nsplit);
 }

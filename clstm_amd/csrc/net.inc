@@ -728,8 +728,7 @@ struct Net {
 #ifdef CLSTM_LSTM_PROF
     lstm_prof.reserve(128); a.prof = lstm_prof.p;
 #endif
-    static const bool smem_set = (coop_set_smem(lstm_fwd_mfma_kernel<NO, NI, SAVE>, (size_t)Gm::SMEM), true);
-    (void)smem_set;
+    allow_dynamic_lds((const void*)lstm_fwd_mfma_kernel<NO, NI, SAVE>, (size_t)Gm::SMEM);
     CLSTM_LAUNCH((lstm_fwd_mfma_kernel<NO, NI, SAVE>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gm::SMEM, s, a);
     if (l == 0) launch_routed_per_line(y, s, SAVE);
   }
@@ -786,8 +785,7 @@ struct Net {
     constexpr int NT = 2;
     using Gr = MfmaBwdRowsGeom<NO, NT>;
     const LstmMfmaBwdArgs a = mfma_bwd_args<NO, NT>(y, sa, s);
-    static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM), true);
-    (void)smem_set;
+    allow_dynamic_lds((const void*)lstm_bwd_mfma_rows_kernel<NO, NT>, (size_t)Gr::SMEM);
     CLSTM_LAUNCH((lstm_bwd_mfma_rows_kernel<NO, NT>), dim3((unsigned)((bs + 15) / 16), (unsigned)ndir), dim3(512), (size_t)Gr::SMEM, s, a);
   }
   // ... and as ONE launch with the weight-gradient items (lstm_mfma_bwd_dw.h), whose items are instantiated for three split terms
@@ -797,8 +795,7 @@ struct Net {
     using Gr = MfmaBwdRowsGeom<NO, NT>;
     const LstmMfmaBwdArgs a = mfma_bwd_args<NO, NT>(y, sa, s);
     const int ngroups = (bs + 15) / 16, nrec = ngroups * ndir;
-    static const bool smem_set = (coop_set_smem(lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM), true);
-    (void)smem_set;
+    allow_dynamic_lds((const void*)lstm_bwd_mfma_dw_kernel<NO, NT, 3>, (size_t)Gr::SMEM);
     CLSTM_LAUNCH((lstm_bwd_mfma_dw_kernel<NO, NT, 3>), dim3((unsigned)nrec + ngemm), dim3(512), (size_t)Gr::SMEM, s, a, g, nrec, ngroups);
   }
 #endif

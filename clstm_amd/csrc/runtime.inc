@@ -40,6 +40,24 @@ static inline int nblocks(size_t n, int bs = 256) {
   return (int)b;
 }
 static void check_launch() { HIPCHECK(hipGetLastError()); }
+// The dynamic-LDS ceiling of a kernel (hipFuncAttributeMaxDynamicSharedMemorySize), the one rule: raised when a launch asks for more
+// than the kernel has been given so far, never lowered -- a ceiling above a launch's own size is harmless, the launch states its size.
+// The ceiling belongs to the function, not to a thread, so the record is process-wide behind a lock (streams and workspaces are
+// thread_local; a per-thread record would let a second thread's smaller first request lower what the first thread relies on).
+// Not keyed by device: one process drives one GPU (DESIGN.md 4.2, 6), as g_dev_err and device_cu_count() assume.
+static void allow_dynamic_lds(const void* kernel, size_t bytes) {   // (declared in gemm_bf16.h, whose gemm_x3_big comes before this file)
+#ifndef CLSTM_HIP_EMU
+  static std::mutex lock;
+  static std::map<const void*, size_t> given;
+  const std::lock_guard<std::mutex> hold(lock);
+  size_t& have = given[kernel];
+  if (bytes <= have) return;
+  HIPCHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  have = bytes;
+#else
+  (void)kernel; (void)bytes;
+#endif
+}
 
 // zero-fill ordered before everything that follows on ANY stream (see DevBuf::reserve)
 static void zero_fill(void* p, size_t bytes) {
@@ -138,6 +156,67 @@ struct PinnedBuf {
   PinnedBuf() = default;
   PinnedBuf(const PinnedBuf&) = delete;
   ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+};
+// The metadata block of a batched call (ctc_run.inc): its small host arrays, written section by section into one pinned ring slot
+// and brought to the device by ONE copy.  add() / put() answer where a section WILL lie on the device and the kernel's arguments are
+// filled from that, so the order of the calls is the one statement of a layout.  Sections lie back to back: a block whose records
+// hold 8-byte members puts them first.
+struct StagedCopy { const int* src = nullptr; int* dst = nullptr; int nwords = 0; };   // a copy its caller folds into a launch (step.inc)
+struct StagedBlock {
+  template <class T> struct Sec { T* host; const T* dev; };
+  PinnedRing ring;
+  DevBuf<char> dev;
+  char* slot = nullptr;
+  size_t cap = 0, used = 0;
+  void begin(size_t bytes) { dev.reserve(bytes); slot = (char*)ring.acquire(bytes); cap = bytes; used = 0; }
+  template <class T> Sec<T> add(size_t n) {   // n elements the caller writes itself
+    REQUIRE(used % alignof(T) == 0 && used + n * sizeof(T) <= cap, "internal: a staged section is misaligned or exceeds its block");
+    const size_t at = used;
+    used += n * sizeof(T);
+    return Sec<T>{reinterpret_cast<T*>(slot + at), reinterpret_cast<const T*>(dev.p + at)};
+  }
+  template <class T> const T* put(const T* src, size_t n) {
+    const Sec<T> sec = add<T>(n);
+    if (n) memcpy(sec.host, src, n * sizeof(T));
+    return sec.dev;
+  }
+  template <class T> const T* put(const std::vector<T>& v) { return put(v.data(), v.size()); }
+  void send(hipStream_t s) {
+    HIPCHECK(hipMemcpyAsync(dev.p, slot, used, hipMemcpyHostToDevice, s));
+    ring.commit(s);
+  }
+  // ... or the caller folds the copy into a kernel it launches anyway, and commits the slot behind that launch
+  StagedCopy deferred() const { return StagedCopy{reinterpret_cast<const int*>(slot), reinterpret_cast<int*>(dev.p), (int)(used / sizeof(int))}; }
+  void commit(hipStream_t s) { ring.commit(s); }
+};
+// The result block of a batched call: 4-byte sections (floats travel as their bits) declared in order, in ONE device buffer with a
+// pinned landing buffer.  A section's handle gives its device address for the kernel's arguments and, after fetch(), its host copy.
+struct ResultBlock {
+  struct Span { size_t at = 0, n = 0; };   // words [at, at + n) of the block
+  template <class T> struct Sec : Span {
+    const ResultBlock* blk = nullptr;
+    T* dev() const { return reinterpret_cast<T*>(blk->buf.p + at); }
+    const T* host() const { return reinterpret_cast<const T*>(blk->land.p + at); }
+  };
+  DevBuf<int> buf;
+  PinnedBuf<int> land;
+  size_t words = 0;
+  void begin() { words = 0; }
+  template <class T> Sec<T> add(size_t n) {
+    static_assert(sizeof(T) == sizeof(int), "result sections are 4-byte words");
+    Sec<T> sec;
+    sec.at = words; sec.n = n; sec.blk = this;
+    words += n;
+    return sec;
+  }
+  void reserve() { buf.reserve(words); }   // every section declared: dev() holds from here on
+  void zero(hipStream_t s, Span from, Span to) { HIPCHECK(hipMemsetAsync(buf.p + from.at, 0, (to.at + to.n - from.at) * sizeof(int), s)); }
+  // ONE copy brings back the block up to the end of `last` -- the last section the caller asked for -- and the stream is drained
+  void fetch(hipStream_t s, Span last) {
+    land.reserve(words);
+    HIPCHECK(hipMemcpyAsync(land.p, buf.p, (last.at + last.n) * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
 };
 
 // ---- GEMM operand functors ---------------------------------------------------------------------
@@ -323,12 +402,6 @@ static int device_cu_count() {
 #else
   static const int n = getenv("CLSTM_EMU_CUS") ? atoi(getenv("CLSTM_EMU_CUS")) : 16;   // emulator: keeps cooperative test grids small
   return n;
-#endif
-}
-template <class K>
-static void coop_set_smem(K kernel, size_t smem) {
-#ifndef CLSTM_HIP_EMU
-  HIPCHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 #endif
 }
 // The per-step launches of one sequence pass are a launch-bound inner loop of up to a few hundred
@@ -938,7 +1011,7 @@ static bool launch_wide_persistent(const WidePlan& p, LstmWideArgs& a, XcdSync& 
     a.stamp_base = sync.take_stamps(a.tmax, s);
     a.out_sticky = dev_err_words();
     a.out_host = g_xcd_outcome.prepare();
-    coop_set_smem(kernel, (size_t)p.lds_bytes);
+    allow_dynamic_lds((const void*)kernel, (size_t)p.lds_bytes);
     // An ORDINARY launch: one workgroup per CU (LDS), at most as many workgroups as CUs, the stream's previous kernel complete --
     // they are all resident, and if they ever were not, the placement check of xcd_claim times out with error 1 before anything
     // has been written.  The first four launches of a process are checked synchronously and the per-step path redoes such a pass;

@@ -21,7 +21,7 @@ static Targets check_minibatch(int nclasses, const Minibatch& m) {
 
 // the frames at x (device) into the net's input block and layer 0's source rows; aux: the CTC metadata copy of a training step rides
 // the launch
-static void net_ingest(Net& n, CtcWorkspace& ctc, const float* x, const CtcMetaCopy* aux = nullptr) {
+static void net_ingest(Net& n, CtcWorkspace& ctc, const float* x, const StagedCopy* aux = nullptr) {
   n.ensure_training_buffers();   // (the ingest writes layer 0's source rows)
   RoctxRange range_("clstm:ingest");
   Layer& y = n.L[0];
@@ -42,7 +42,7 @@ static void net_ingest(Net& n, CtcWorkspace& ctc, const float* x, const CtcMetaC
                  lo, n.line_off.p, 2 * n.bs + 1, ax ? aux->src : nullptr, ax ? aux->dst : nullptr, ax ? aux->nwords : 0,
                  with_pack ? (const int*)n.pack_table(y) : (const int*)nullptr);
     if (lo) n.offsets_sent(g_stream);
-    if (ax) { ctc.ring.commit(g_stream); aux_done = true; }
+    if (ax) { ctc.meta.commit(g_stream); aux_done = true; }
     if (with_pack) n.packed_dirty = false;
   } else {
     CLSTM_LAUNCH(k_ingest, dim3(nblocks((size_t)n.N * (1 + y.ni))), dim3(256), 0, g_stream, x, n.X.p, y.S.p, (size_t)n.N, y.ni,
@@ -51,13 +51,13 @@ static void net_ingest(Net& n, CtcWorkspace& ctc, const float* x, const CtcMetaC
   check_launch();
   if (aux && aux->nwords > 0 && !aux_done) {   // not the fused launch: a plain asynchronous copy
     HIPCHECK(hipMemcpyAsync(aux->dst, aux->src, (size_t)aux->nwords * sizeof(int), hipMemcpyHostToDevice, g_stream));
-    ctc.ring.commit(g_stream);
+    ctc.meta.commit(g_stream);
   }
   n.frames_ingested(true);
 }
 // the same ingest as trailing workgroups of a step's last reduction (ops.h: IngestTail; Net::launch_deferred_reduce): the declared
 // geometry is the NEXT minibatch's
-static IngestTail ingest_tail(const Net& n, const float* x, const CtcMetaCopy& meta) {
+static IngestTail ingest_tail(const Net& n, const float* x, const StagedCopy& meta) {
   const Layer& y = n.L[0];
   IngestTail t{};
   t.x = x; t.X = n.X.p; t.S = y.S.p; t.N = (unsigned long long)n.N; t.ni = y.ni; t.lds = y.lds; t.ndir = n.ndir; t.sdir = (long long)n.N * y.lds;
@@ -69,7 +69,7 @@ static IngestTail ingest_tail(const Net& n, const float* x, const CtcMetaCopy& m
 // CTC alignment of the current minibatch against m's transcripts (m.labels, m.L; one per declared line): the host half, and --
 // launch -- the alignment itself.  launch = false (training steps): prepared here, launched behind the forward pass by net_ctc_launch.
 // made: the transcripts as check_minibatch has expanded them already.
-static void net_ctc(Net& n, CtcWorkspace& ctc, const Minibatch& m, float* aligned_h, CtcMetaCopy* defer = nullptr, bool launch = true,
+static void net_ctc(Net& n, CtcWorkspace& ctc, const Minibatch& m, float* aligned_h, StagedCopy* defer = nullptr, bool launch = true,
                     const Targets* made = nullptr) {
   Targets own;
   if (!made) expand_transcripts(m.labels, m.L, n.bs, own.states, own.soff);
@@ -107,7 +107,7 @@ static void train_step(Net& n, CtcWorkspace& ctc, const Minibatch& cur, const Mi
     g_path_count[PC_INGEST_TAIL_USED]++;
   } else {
     n.set_batch(cur.T, cur.bs);
-    CtcMetaCopy meta;
+    StagedCopy meta;
     net_ctc(n, ctc, cur, nullptr, &meta, false);
     net_ingest(n, ctc, cur.x, &meta);
   }
@@ -125,12 +125,12 @@ static void train_step(Net& n, CtcWorkspace& ctc, const Minibatch& cur, const Mi
     }
     if (tail) {
       n.set_batch(next.T, next.bs);
-      CtcMetaCopy meta;
+      StagedCopy meta;
       net_ctc(n, ctc, next, nullptr, &meta, false, &made);
       const IngestTail t = ingest_tail(n, next.x, meta);
       n.launch_deferred_reduce(left.deferred, &t);
       if (t.lo_src) n.offsets_sent(g_stream);
-      if (t.aux_src) ctc.ring.commit(g_stream);
+      if (t.aux_src) ctc.meta.commit(g_stream);
       n.frames_ingested(true);
       n.next_declared(next);
     } else n.launch_deferred_reduce(left.deferred, nullptr);
