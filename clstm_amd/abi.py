@@ -66,6 +66,11 @@ _SIGS = {
     "clstm_charlm_create": [_P, _I, _I, _P, _P],
     "clstm_charlm_destroy": [_P],
     "clstm_ctc_beam_lm_batch": [_P, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
+    "clstm_lexicon_create": [_P, _I, _P, _P, _P, _I],
+    "clstm_lexicon_destroy": [_P],
+    "clstm_lexicon_info": [_P, _P],
+    "clstm_lexicon_admits": [_P, _P, _I, _P],
+    "clstm_ctc_beam_lex_batch": [_P, _I, _P, _I, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P],
     "clstm_edit_distance_batch": [_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     "clstm_mktargets": [_P, _P, _I],
     "clstm_trivial_decode_batch": [_P, _I, _P, _I, _P, _P, _P],
@@ -94,6 +99,7 @@ _SIGS = {
     "clstm_net_score": [_P, _P, _P, _P, _I, _P, _P, _P],
     "clstm_net_beam": [_P, _I, _I, _P, _P, _P, _P],
     "clstm_net_beam_lm": [_P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
+    "clstm_net_beam_lex": [_P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P],
     "clstm_net_errors": [_P, _P, _P, _P, _P, _P],
     "clstm_net_backward": [_P],
     "clstm_net_enable_input_deltas": [_P, _I],

@@ -28,6 +28,7 @@ struct QueryScope {
 };
 // What a per-minibatch entry point needs of the net is ONE line at its top: Net::require(needs, name) (net.inc; the table: include/clstm_abi.h).
 struct clstm_charlm { CharLm lm; };
+struct clstm_lexicon { Lexicon lex; };
 struct clstm_normalizer {
   std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
   Normalizer nz;
@@ -193,6 +194,42 @@ int clstm_ctc_beam_lm_batch(const float* probs, int nc, const int* line_off_h, i
   run_ctc_beam(thread_workspace<BeamWorkspace>(), probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
   ABI_END
 }
+int clstm_lexicon_create(clstm_lexicon** out, int nc, const unsigned char* word_class_h, const int* words_h, const int* word_off_h, int nwords) {
+  ABI_BEGIN
+  REQUIRE(out, "clstm_lexicon_create: null argument");
+  std::unique_ptr<clstm_lexicon> h(new clstm_lexicon());
+  build_lexicon(h->lex, nc, word_class_h, words_h, word_off_h, nwords);   // (every refusal is here, before the upload)
+  REQUIRE(h->lex.W == beam_lex_words(nc), "internal: the trie's row width is not the kernel's");
+  h->lex.dev.reserve(h->lex.words.size());
+  HIPCHECK(hipMemcpyAsync(h->lex.dev.p, h->lex.words.data(), h->lex.words.size() * sizeof(int), hipMemcpyHostToDevice, g_stream));
+  HIPCHECK(hipStreamSynchronize(g_stream));
+  *out = h.release();
+  ABI_END
+}
+int clstm_lexicon_destroy(clstm_lexicon* lex) { ABI_BEGIN delete lex; ABI_END }
+int clstm_lexicon_info(const clstm_lexicon* lex, long long info[4]) {
+  ABI_BEGIN
+  REQUIRE(lex && info, "clstm_lexicon_info: null argument");
+  info[0] = lex->lex.nwords; info[1] = lex->lex.nnodes; info[2] = lex->lex.nedges;
+  info[3] = (long long)(lex->lex.words.size() * sizeof(int));
+  ABI_END
+}
+int clstm_lexicon_admits(const clstm_lexicon* lex, const int* labels_h, int L, int* out) {
+  ABI_BEGIN
+  REQUIRE(lex && out && L >= 0 && (labels_h || L == 0), "clstm_lexicon_admits: null argument or negative length");
+  *out = lexicon_admits(lex->lex, labels_h, L);
+  ABI_END
+}
+int clstm_ctc_beam_lex_batch(const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest, const clstm_lexicon* lex,
+                             const clstm_charlm* lm, float weight, float bonus, int* nhyp_h, int* len_h, float* score_h,
+                             float* am_score_h, int* labels_h) {
+  ABI_BEGIN
+  REQUIRE(lex, "clstm_ctc_beam_lex: the lexicon is required");
+  const BeamLm with{lm ? &lm->lm : nullptr, weight, bonus, am_score_h};
+  run_ctc_beam(thread_workspace<BeamWorkspace>(), probs, nc, line_off_h, bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with,
+               &lex->lex);
+  ABI_END
+}
 int clstm_edit_distance_batch(const int* hyp_h, const int* hyp_off_h, int npairs, const int* ref_h, const int* ref_off_h, int nref,
                               const int* ref_of_h, int nsym, int* dist_h, int* counts_h, int* nops_h, int* ops_h, int* confusion_h) {
   ABI_BEGIN
@@ -325,6 +362,21 @@ int clstm_net_beam_lm(clstm_net* h, int beam, int nbest, const clstm_charlm* lm,
   QueryScope scope_(n, "clstm:beam_lm", "ctc_beam_lm");
   const BeamLm with{&lm->lm, weight, bonus, am_score_h};
   run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with);
+  ABI_END
+}
+int clstm_net_beam_lex(clstm_net* h, int beam, int nbest, const clstm_lexicon* lex, const clstm_charlm* lm, float weight, float bonus,
+                       int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h) {
+  ABI_BEGIN
+  REQUIRE(h, "clstm_net_beam_lex: null net");
+  Net& n = h->net;
+  n.require(Net::NEED_OUTPUTS, "clstm_net_beam_lex");
+  REQUIRE(lex, "clstm_net_beam_lex: the lexicon is required");
+  REQUIRE(nhyp_h && score_h, "clstm_net_beam_lex: nhyp_h and score_h are required");
+  REQUIRE(beam >= 1 && beam <= BEAM_MAX && nbest >= 1 && nbest <= beam, "clstm_net_beam_lex: 1 <= nbest <= beam <= 32");
+  QueryScope scope_(n, "clstm:beam_lex", "ctc_beam_lex");
+  const BeamLm with{lm ? &lm->lm : nullptr, weight, bonus, am_score_h};
+  run_ctc_beam(h->beam, n.Z.p, n.desc.nclasses, n.line_off_h.data(), n.bs, beam, nbest, nhyp_h, len_h, score_h, labels_h, g_stream, &with,
+               &lex->lex);
   ABI_END
 }
 // edit distance of every line's trivial_decode against its transcript: the guards and guarantees of clstm_net_score (reads Z only; the

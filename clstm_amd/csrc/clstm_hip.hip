@@ -19,6 +19,7 @@
 #include "ctc_score.h"
 #include "ctc_beam.h"
 #include "edit_distance.h"
+#include "lexicon_trie.h"
 #include "devintrin.h"
 #include "gemm_mfma.h"
 #include "gemm_bf16.h"

@@ -55,6 +55,28 @@
 // read one frame ahead into the small LDS tile --, so ALL_LDS here means the other three sections.  Each entry gets ctx and lm from
 // its node when phase C names the node, so phase A reads them from LDS; the table itself lies in global memory (one read per
 // candidate, rows of one context contiguous).
+//
+// ---- constrained to a lexicon (ctc_beam_kernel<.., true, true>: clstm_ctc_beam_lex_batch / clstm_net_beam_lex) ----
+// A lexicon over nc classes has a flag per class, word_class[c]; class 0 (blank) is never a word class, the classes 1 .. nc-1 without
+// the flag are separators (space, punctuation, digits: whatever the caller leaves out), and a set of words: non-empty label sequences
+// over word classes.  The words form a trie with root 0; a node is terminal when a word ends there.  Every prefix l has a lexicon
+// state: x(()) = root; x(l + c) = root when c is a separator, allowed only if x(l) is the root or terminal; x(l + c) = child(x(l), c)
+// when c is a word class, allowed only if that child exists.  The second a of "a a" (through a blank) is an extension and moves the
+// state; a stay moves nothing.
+//   The search is the language model form above, expression for expression: (lb, lnb), stay, merge, extend, tot, the key
+// (logadd(lb', lnb') + lm(prefix), ~index), the same index and total order.  One difference: an extension (i, c) that is not allowed
+// is no candidate (key 0).  The character model is optional: without one (table == null) the table term is that of an all-zero table,
+// lm(l + c) = lm(l) + (weight 0 + bonus), and there is no end table.  After the last frame only the live entries whose state is the
+// root or terminal are ranked, by the LM form's final ranking; nhyp = min(nbest, their number), which can be 0: then len = 0, both
+// scores -inf and the label slots zero, exactly what a line without frames reports.
+//   Device form (BeamArgs::lex, one buffer of 32-bit words): [nodes, edges, W = ceil(nc / 32), 0], then per node W words of allowed
+// next classes -- bit c of a row: (i, c) is allowed, separators set on the root and on terminal nodes, and bit 0 (blank is no class)
+// says "root or terminal" --, then a CSR of children: nodes + 1 offsets, the labels sorted within a node, the targets.  "Is (i, c)
+// allowed" is one bit test, the same for both kinds of class.  The state depends on the prefix alone, so it is the sixth array of the
+// trie (nlex, beside nlm / nctx), written once by the lane that makes the node: a binary search over the parent state's children,
+// bounded by the child count; a class that was allowed and is no child is a separator (-> root).  A prefix that leaves the beam and
+// is extended again finds its node and with it the same state.  Phase C copies the new entries' rows to LDS (n W words, at most
+// 32 x 129), so phase A makes no extra global read per candidate, and the final ranking reads bit 0 there.
 #pragma once
 #include "devintrin.h"
 #include <math.h>
@@ -84,12 +106,16 @@ struct BeamArgs {
   float* am_score;     // [bs nbest], or null
   float weight, bonus;
   int order;
+  // lexicon form only (the header's third part); then table may be null
+  const int* lex;
 };
 // fixed LDS words in front of the sections
-struct BeamLds { int ent, stay, misc, ft, keys, surv, lm, sections; };
+struct BeamLds { int ent, stay, misc, ft, keys, surv, lm, lex, sections; };
 constexpr int BEAM_ENT_FIELDS = 7;   // node, last, lb, lnb, tot, ppos, pnode / written flag
 constexpr int BEAM_LM_WORDS = 5 * BEAM_MAX;   // language model form: ctx and lm of the entries, double-buffered, and the stays' tot
-inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K, bool lm = false) {
+inline __host__ __device__ int beam_lex_words(int nc) { return (nc + 31) >> 5; }   // lexicon form: words of a node's row of allowed classes
+// lex_rows: the entries' rows of allowed classes, beam * beam_lex_words(nc) (lexicon form), else 0
+inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K, bool lm = false, int lex_rows = 0) {
   BeamLds l;
   int o = 0;
   l.keys = o; o += 2 * (beam + beam * K);       // 64-bit keys first: 8-byte aligned
@@ -99,6 +125,7 @@ inline __host__ __device__ BeamLds beam_lds_layout(int beam, int K, bool lm = fa
   l.ft = o;   o += 2 * (2 * K + 2);             // the next frame's class list, their lp and lp[0], double-buffered
   l.misc = o; o += 4;
   l.lm = o;   o += lm ? BEAM_LM_WORDS : 0;
+  l.lex = o;  o += lex_rows;
   o += o & 1;
   l.sections = o;
   return l;
@@ -148,13 +175,16 @@ DEVFN BeamEnt beam_ent(float* base, int side) {
 // ALL_LDS: every section of every line of the launch lies in LDS (the OCR shapes): the section pointers are LDS addresses the
 // compiler can see, not a choice between two address spaces that only flat instructions can follow.  The arithmetic is the same.
 // LM: the language model form (the header's second part); without it the kernel is the plain search, instruction for instruction.
-template <bool ALL_LDS, bool LM = false>
+// LEX: the lexicon form (the third part), on top of LM only: <.., true, true>.
+template <bool ALL_LDS, bool LM = false, bool LEX = false>
 __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   float* lds = dyn_smem<float>();
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const BeamLine ln = a.lines[blockIdx.x];
   const int T = ln.T, nc = a.nc, beam = a.beam, K = a.K;
-  const BeamLds L = beam_lds_layout(beam, K, LM);
+  static_assert(LM || !LEX, "the lexicon rides the complete-class-list form");
+  const int W = LEX ? beam_lex_words(nc) : 0;
+  const BeamLds L = beam_lds_layout(beam, K, LM, beam * W);
   auto section = [&](int s) -> int* {
     if (LM && s == BS_CLS) return a.ws + ln.off[s];   // (the complete class list: always in the workspace)
     if constexpr (ALL_LDS) return reinterpret_cast<int*>(lds + L.sections) + (int)ln.off[s];
@@ -166,6 +196,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
   int* const ndep = nlab + ln.nnmax;
   int* const nlm = ndep + ln.nnmax;                          // (LM: the prefix's LM value as float bits, then its context)
   int* const nctx = nlm + ln.nnmax;
+  int* const nlex = nctx + ln.nnmax;                         // (LEX: the prefix's lexicon state)
+  unsigned* const ent_allow = reinterpret_cast<unsigned*>(lds + L.lex);   // (LEX) [beam][W] the current entries' allowed classes
+  const int lex_nodes = LEX ? a.lex[0] : 0, lex_edges = LEX ? a.lex[1] : 0;
+  const unsigned* const lex_allow = reinterpret_cast<const unsigned*>(a.lex + 4);   // (LEX) [nodes][W]
+  const int* const lex_off = a.lex + 4 + (size_t)lex_nodes * W;                   // (LEX) [nodes + 1]
+  const int* const lex_lab = lex_off + lex_nodes + 1;                             // (LEX) [edges] sorted within a node
+  const int* const lex_tgt = lex_lab + lex_edges;                                 // (LEX) [edges]
   int* const ent_ctx = reinterpret_cast<int*>(lds + L.lm);   // (LM) [side][BEAM_MAX]
   float* const ent_lm = lds + L.lm + 2 * BEAM_MAX;           // (LM) [side][BEAM_MAX]
   float* const stay_tot = lds + L.lm + 4 * BEAM_MAX;         // (LM)
@@ -191,7 +228,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
     const BeamEnt e = beam_ent(lds + L.ent, 0);
     e.node[0] = 0; e.last[0] = 0; e.lb[0] = 0.0f; e.lnb[0] = beam_neg_inf(); e.tot[0] = 0.0f; e.ppos[0] = -1;
     if constexpr (LM) { nlm[0] = 0; nctx[0] = 0; ent_ctx[0] = 0; ent_lm[0] = 0.0f; }
+    if constexpr (LEX) nlex[0] = 0;
   }
+  if constexpr (LEX) { if (tid < W) ent_allow[tid] = lex_allow[tid]; }   // the empty prefix: the root's row (W <= 129)
   drain_vmem();   // (sections in the workspace: written here, read by other waves -- the trie with system-scope loads)
   __syncthreads();
   const int ncl = nc - 1;   // classes 1 .. nc-1
@@ -261,7 +300,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
 #pragma unroll 8
       for (int k = 0; k < n; k++) skip |= (cur.ppos[k] == i) & (cur.last[k] == c);   // (no short circuit: independent reads)
       float s = v;
-      if constexpr (LM) s = v + (clm[i] + beam_lm_term(a.weight, a.table[(size_t)cctx[i] * nc + c], a.bonus));
+      if constexpr (LEX) {
+        skip |= !(ent_allow[i * W + (c >> 5)] >> (c & 31) & 1u);   // not allowed: no candidate
+        s = v + (clm[i] + beam_lm_term(a.weight, a.table ? a.table[(size_t)cctx[i] * nc + c] : 0.0f, a.bonus));
+      } else if constexpr (LM) s = v + (clm[i] + beam_lm_term(a.weight, a.table[(size_t)cctx[i] * nc + c], a.bonus));
       keys[beam + m] = skip ? 0ull : beam_key(s, (unsigned)(beam + i * nc + c));
     }
     __syncthreads();
@@ -345,9 +387,22 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
           if constexpr (LM) {   // the prefix's LM value and context, once
             const int pctx = load_i32_wt(nctx + pn);
             const float plm = __builtin_bit_cast(float, load_i32_wt(nlm + pn));
-            const float lmv = plm + beam_lm_term(a.weight, a.table[(size_t)pctx * nc + c], a.bonus);
+            float x = 0.0f;
+            if constexpr (LEX) { if (a.table) x = a.table[(size_t)pctx * nc + c]; }
+            else x = a.table[(size_t)pctx * nc + c];
+            const float lmv = plm + beam_lm_term(a.weight, x, a.bonus);
             store_i32_wt(nlm + nd, __builtin_bit_cast(int, lmv));
             store_i32_wt(nctx + nd, a.order == 3 ? nc * load_i32_wt(nlab + pn) + c : c);
+          }
+          if constexpr (LEX) {   // the prefix's lexicon state, once: the child of the parent's state by c; no such child: a separator
+            const int px = load_i32_wt(nlex + pn);
+            int lo = lex_off[px], hi = lex_off[px + 1], x = 0;
+            for (int it = 0; it < 32 && lo < hi; it++) {   // (binary search: at most log2 of the child count rounds)
+              const int mid = lo + ((hi - lo) >> 1), lc = lex_lab[mid];
+              if (lc == c) { x = lex_tgt[mid]; break; }
+              if (lc < c) lo = mid + 1; else hi = mid;
+            }
+            store_i32_wt(nlex + nd, x);
           }
           store_i32_wt(tab + slot, nd);
         }
@@ -362,6 +417,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
         }
       }
       wave_lds_fence();
+      if constexpr (LEX) {   // the new entries' rows of allowed classes, all lanes: word j of entry i
+        for (int q = lane; q < nn * W; q += 64) {
+          const int i = q / W, j = q - i * W;
+          ent_allow[q] = lex_allow[(size_t)load_i32_wt(nlex + nxt.node[i]) * W + j];
+        }
+      }
       if (lane < nn) {
         const int par = nd == 0 ? -1 : load_i32_wt(npar + nd);
         int pp = -1;
@@ -376,8 +437,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
 
   // ---- results: the first nbest entries, labels by the walk to the root ----
   const BeamEnt fin = beam_ent(lds + L.ent, T & 1);
-  const int nh = n < a.nbest ? n : a.nbest;
-  if (tid == 0) a.nhyp[ln.line] = nh;
+  int nh = n < a.nbest ? n : a.nbest;
+  if constexpr (!LEX) { if (tid == 0) a.nhyp[ln.line] = nh; }
   if constexpr (LM) {   // the live entries ranked by their total; entry ent_ctx[r] of the beam leaves as hypothesis r
     const float* const flm = ent_lm + (T & 1) * BEAM_MAX;
     int* const fctx = ent_ctx + (T & 1) * BEAM_MAX;
@@ -392,11 +453,18 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(BeamArgs a) {
         total = total + e;
       }
       stay_tot[tid] = total;
-      key = ((unsigned long long)beam_ord(total) << 32) | (unsigned)~(unsigned)tid;
+      key = ((unsigned long long)beam_ord(total) << 32) | (unsigned)~(unsigned)tid;   // (never 0: beam_ord(-inf) is not)
+      if constexpr (LEX) { if (!(ent_allow[tid * W] & 1u)) key = 0ull; }   // a word left unfinished: not ranked
       keys[tid] = key;
     }
     __syncthreads();
-    if (tid < n) {
+    if constexpr (LEX) {
+      int adm = 0;
+      for (int q = 0; q < n; q++) adm += keys[q] != 0ull ? 1 : 0;
+      nh = adm < a.nbest ? adm : a.nbest;
+      if (tid == 0) a.nhyp[ln.line] = nh;
+    }
+    if (tid < n && (!LEX || key != 0ull)) {
       int rank = 0;
       for (int q = 0; q < n; q++) rank += keys[q] > key ? 1 : 0;
       fctx[rank] = tid;

@@ -358,15 +358,18 @@ struct CharLm {
 };
 // what a language model call brings beside the plain search's arguments
 struct BeamLm { const CharLm* lm; float weight, bonus; float* am_score_h; };
-static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, int beam, int nbest, bool lm = false) {
+// a lexicon on the device (ctc_beam.h, third part): the trie is built and checked on the host (lexicon_trie.h), uploaded once, at creation
+struct Lexicon : LexiconTrie { DevBuf<int> dev; };
+static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, int beam, int nbest, bool lm = false, bool lex = false) {
   REQUIRE(bs > 0 && line_off_h, "empty batch / null argument");
   REQUIRE(nc >= 2 && nc < (1 << 26), "clstm_ctc_beam: the class count must lie in [2, 2^26)");
   REQUIRE(beam >= 1 && beam <= BEAM_MAX, "clstm_ctc_beam: beam must lie in [1, 32]");
   REQUIRE(nbest >= 1 && nbest <= beam, "clstm_ctc_beam: nbest must lie in [1, beam]");
   REQUIRE(line_off_h[0] >= 0, "bad offsets");
-  if (lm) REQUIRE((long long)beam * (nc - 1) <= BEAM_LM_CANDS, "clstm_ctc_beam_lm: beam * (nc - 1) exceeds 4096 (every class is a candidate of every entry)");
+  if (lex) REQUIRE((long long)beam * (nc - 1) <= BEAM_LM_CANDS, "clstm_ctc_beam_lex: beam * (nc - 1) exceeds 4096 (every class is a candidate of every entry)");
+  else if (lm) REQUIRE((long long)beam * (nc - 1) <= BEAM_LM_CANDS, "clstm_ctc_beam_lm: beam * (nc - 1) exceeds 4096 (every class is a candidate of every entry)");
   pl.K = lm ? nc - 1 : beam_classes(nc, beam);
-  const BeamLds L = beam_lds_layout(beam, pl.K, lm);
+  const BeamLds L = beam_lds_layout(beam, pl.K, lm, lex ? beam * beam_lex_words(nc) : 0);
   const long long room = BEAM_LDS_WORDS - L.sections;
   for (int b = 0; b < bs; b++) {
     const long long T = (long long)line_off_h[b + 1] - line_off_h[b];
@@ -376,7 +379,7 @@ static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, i
     const long long nn = 1 + T * beam;
     long long H = 64;
     while (H < 2 * nn) H *= 2;
-    const long long need[BS_COUNT] = {H, (lm ? 5 : 3) * nn, 2 * T * pl.K, T * nc};
+    const long long need[BS_COUNT] = {H, (lex ? 6 : lm ? 5 : 3) * nn, 2 * T * pl.K, T * nc};   // (nodes: + nlm, nctx; + nlex)
     BeamLine ln{};
     ln.row = line_off_h[b]; ln.T = (int)T; ln.line = b; ln.hmask = (int)(H - 1); ln.nnmax = (int)nn;
     long long used = 0;
@@ -393,15 +396,22 @@ static void plan_ctc_beam(BeamPlan& pl, int nc, const int* line_off_h, int bs, i
   pl.lds_words += L.sections;
 }
 static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int* line_off_h, int bs, int beam, int nbest,
-                         int* nhyp_h, int* len_h, float* score_h, int* labels_h, hipStream_t s, const BeamLm* lm = nullptr) {
-  if (lm) {   // (everything is refused before anything is enqueued or written)
+                         int* nhyp_h, int* len_h, float* score_h, int* labels_h, hipStream_t s, const BeamLm* lm = nullptr,
+                         const Lexicon* lex = nullptr) {
+  if (lex) {   // (the lexicon form: lm is given, its model may be null; everything is refused before anything is enqueued or written)
+    REQUIRE(lm, "internal: the lexicon form takes weight and bonus from a BeamLm");
+    REQUIRE(lex->nc == nc, "clstm_ctc_beam_lex: the lexicon was made for another class count");
+    REQUIRE(!lm->lm || lm->lm->nc == nc, "clstm_ctc_beam_lex: the language model was made for another class count");
+    REQUIRE(std::isfinite(lm->weight) && lm->weight >= 0.0f, "clstm_ctc_beam_lex: weight must be finite and not negative");
+    REQUIRE(std::isfinite(lm->bonus), "clstm_ctc_beam_lex: bonus must be finite");
+  } else if (lm) {   // (everything is refused before anything is enqueued or written)
     REQUIRE(lm->lm, "clstm_ctc_beam_lm: the language model is required");
     REQUIRE(lm->lm->nc == nc, "clstm_ctc_beam_lm: the language model was made for another class count");
     REQUIRE(std::isfinite(lm->weight) && lm->weight >= 0.0f, "clstm_ctc_beam_lm: weight must be finite and not negative");
     REQUIRE(std::isfinite(lm->bonus), "clstm_ctc_beam_lm: bonus must be finite");
   }
   BeamPlan pl;
-  plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest, lm != nullptr);
+  plan_ctc_beam(pl, nc, line_off_h, bs, beam, nbest, lm != nullptr, lex != nullptr);
   REQUIRE(probs && nhyp_h && score_h, "clstm_ctc_beam: probs, nhyp_h and score_h are required");
   const size_t N = (size_t)line_off_h[bs], nslot = (size_t)bs * nbest;
   for (int b = 0; b < bs; b++) nhyp_h[b] = 0;
@@ -427,20 +437,22 @@ static void run_ctc_beam(BeamWorkspace& w, const float* probs, int nc, const int
   a.labels = labels_h ? labels.dev() : nullptr;
   a.nc = nc; a.beam = beam; a.nbest = nbest; a.K = pl.K; a.bs = bs; a.N = (int)N;
   if (lm) {
-    a.table = lm->lm->table.p; a.end = lm->lm->has_end ? lm->lm->end.p : nullptr;
+    if (lm->lm) { a.table = lm->lm->table.p; a.end = lm->lm->has_end ? lm->lm->end.p : nullptr; }
     a.am_score = am_score.dev();
-    a.weight = lm->weight; a.bonus = lm->bonus; a.order = lm->lm->order;
+    a.weight = lm->weight; a.bonus = lm->bonus; a.order = lm->lm ? lm->lm->order : 2;
   }
+  if (lex) a.lex = lex->dev.p;
   const size_t smem = (size_t)pl.lds_words * sizeof(float);
   auto launch = [&](auto kernel) {
     allow_dynamic_lds((const void*)kernel, smem);
     CLSTM_LAUNCH(kernel, dim3((unsigned)pl.lines.size()), dim3(BEAM_THREADS), smem, s, a);
   };
-  if (lm) { if (pl.all_lds) launch(ctc_beam_kernel<true, true>); else launch(ctc_beam_kernel<false, true>); }
+  if (lex) { if (pl.all_lds) launch(ctc_beam_kernel<true, true, true>); else launch(ctc_beam_kernel<false, true, true>); }
+  else if (lm) { if (pl.all_lds) launch(ctc_beam_kernel<true, true>); else launch(ctc_beam_kernel<false, true>); }
   else if (pl.all_lds) launch(ctc_beam_kernel<true, false>);
   else launch(ctc_beam_kernel<false, false>);
   check_launch();
-  g_path_count[lm ? PC_BEAM_LM : PC_BEAM]++;
+  g_path_count[lex ? PC_BEAM_LEX : lm ? PC_BEAM_LM : PC_BEAM]++;
   w.res.fetch(s, labels);
   for (const BeamLine& ln : pl.lines) {   // (lines without frames keep nhyp = 0, len = 0, score = -inf)
     const int b = ln.line;

@@ -1,5 +1,6 @@
 // clstm_hosttool -- test helper exposing the GPU-free host pieces (PNG, normaliser, model files) to
 // the Python test-suite.  Raw float dumps are little-endian float32 preceded by two int32 (w, h).
+#include "lexicon.h"
 #include "model.h"
 #include "normalizer.h"
 #include "png_io.h"
@@ -107,8 +108,19 @@ int main(int argc, char** argv) {
       Model m;
       m.load(argv[2]);
       for (int c : m.codec) std::cout << c << std::endl;
+    } else if (cmd == "lexicon" && (argc == 4 || argc == 5)) {  // MODEL WORDLIST [WORD_CHARS]: what lexicon.h makes of a word list
+      Model m;                                                    // under the model's codec: counts, word classes, the words
+      m.load(argv[2]);
+      std::map<int, int> enc;
+      for (int i = 0; i < (int)m.codec.size(); i++) enc.insert(std::make_pair(m.codec[i], i));
+      const string wc = argc == 5 ? argv[4] : "";
+      const WordList wl = WordList::load(argv[3], enc, (int)m.codec.size(), argc == 5 ? &wc : nullptr);
+      std::cout << "lines " << wl.lines << " kept " << wl.words.size() << " dropped " << wl.dropped() << std::endl << "classes";
+      for (int c = 0; c < (int)wl.word_class.size(); c++) if (wl.word_class[c]) std::cout << " " << c;
+      std::cout << std::endl;
+      for (const auto& w : wl.words) { std::cout << "word"; for (int c : w) std::cout << " " << c; std::cout << std::endl; }
     } else {
-      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params|codec ...\n";
+      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params|codec|lexicon ...\n";
       return 2;
     }
     return 0;

@@ -8,6 +8,7 @@
 #include <future>
 #include <thread>
 #include "charlm.h"
+#include "lexicon.h"
 #include "normalizer.h"
 #include "png_io.h"
 
@@ -111,9 +112,12 @@ struct CLSTMOCR {
 
   clstm_charlm* lm = nullptr;                   // set_lm: the n-best calls search with it (clstm_net_beam_lm)
   float lm_weight = 0.0f, lm_bonus = 0.0f;
+  clstm_lexicon* lexicon = nullptr;             // set_lexicon: the n-best calls are constrained to it (clstm_net_beam_lex)
+  long long lexicon_words = 0, lexicon_dropped = 0;   // distinct words in the trie; lines of the word list that were dropped
   clstm_normalizer* gpu_normalizer = nullptr;   // the device twin of `normalizer` (created at first use: predict_batch_gpu, normalize_batch_gpu)
   ~CLSTMOCR() {
     if (lm) clstm_charlm_destroy(lm);
+    if (lexicon) clstm_lexicon_destroy(lexicon);
     if (gpu_normalizer) clstm_normalizer_destroy(gpu_normalizer);
     if (net) clstm_net_destroy(net);
   }
@@ -548,7 +552,26 @@ struct CLSTMOCR {
     chk(clstm_charlm_create(&lm, m.order, m.nc, m.table.data(), m.has_end ? m.end.data() : nullptr), "clstm_charlm_create");
     lm_weight = weight; lm_bonus = bonus;
   }
-  void nbest_current(const vector<int>& Ts, int beam, int nbest, vector<vector<Hypothesis>>& out) {
+  // set_lexicon: a UTF-8 word list, one word per line (lexicon.h), encoded through the model's codec; from then on predict_nbest /
+  // nbest_current report only transcripts whose every run of word characters is a word of the list (a line on which no such
+  // transcript survived has no hypotheses).  word_chars (UTF-8, or null: a class is a word character iff it occurs in a kept word)
+  // names the word characters; every other class is a separator.  Works with and without set_lm; without a model the score is the
+  // acoustic one plus lm_bonus per character.  An empty path takes the lexicon away again.
+  void set_lexicon(const string& path, const string* word_chars = nullptr) {
+    if (lexicon) chk(clstm_lexicon_destroy(lexicon), "clstm_lexicon_destroy");
+    lexicon = nullptr;
+    lexicon_words = lexicon_dropped = 0;
+    if (path.empty()) return;
+    const WordList wl = WordList::load(path, codec.encoder, nclasses, word_chars);
+    vector<int> flat, off;
+    wl.pack(flat, off);
+    chk(clstm_lexicon_create(&lexicon, nclasses, wl.word_class.data(), flat.data(), off.data(), (int)wl.words.size()), "clstm_lexicon_create");
+    long long info[4];
+    chk(clstm_lexicon_info(lexicon, info), "clstm_lexicon_info");
+    lexicon_words = info[0]; lexicon_dropped = wl.dropped();
+  }
+  // use_lexicon = false: the search without the lexicon although one is set (what a caller shows for a line the lexicon left empty)
+  void nbest_current(const vector<int>& Ts, int beam, int nbest, vector<vector<Hypothesis>>& out, bool use_lexicon = true) {
     const int bs = (int)Ts.size();
     out.assign(bs, vector<Hypothesis>());
     if (bs == 0) return;
@@ -556,7 +579,10 @@ struct CLSTMOCR {
     for (int t : Ts) N += t;
     vector<int> nhyp(bs), len((size_t)bs * nbest), labels(std::max<size_t>(N * nbest, 1));
     vector<float> sc((size_t)bs * nbest), am((size_t)bs * nbest);
-    if (lm) chk(clstm_net_beam_lm(net, beam, nbest, lm, lm_weight, lm_bonus, nhyp.data(), len.data(), sc.data(), am.data(), labels.data()), "clstm_net_beam_lm");
+    if (lexicon && use_lexicon)
+      chk(clstm_net_beam_lex(net, beam, nbest, lexicon, lm, lm ? lm_weight : 0.0f, lm_bonus, nhyp.data(), len.data(), sc.data(), am.data(), labels.data()),
+          "clstm_net_beam_lex");
+    else if (lm) chk(clstm_net_beam_lm(net, beam, nbest, lm, lm_weight, lm_bonus, nhyp.data(), len.data(), sc.data(), am.data(), labels.data()), "clstm_net_beam_lm");
     else {
       chk(clstm_net_beam(net, beam, nbest, nhyp.data(), len.data(), sc.data(), labels.data()), "clstm_net_beam");
       am = sc;

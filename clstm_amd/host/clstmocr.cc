@@ -18,6 +18,7 @@ static int main1(int argc, char** argv) {
               << "             batch (lines per recognition call, default 1)  prep_threads (<= 16)\n"
               << "             beam nbest (beam=W: the nbest <= W best transcripts of every line follow its output; default off)   (not in the reference)\n"
               << "             lm lm_weight lm_bonus (with beam=W: a character n-gram model file inside the search; hypotheses gain an am_score column)   (not in the reference)\n"
+              << "             lexicon word_chars (with beam=W: a UTF-8 word list, one word per line; every run of word characters of a hypothesis is a word of it)   (not in the reference)\n"
               << "             errs (1: ERRS / CER / CONF lines for the lines that have a .gt.txt beside them, counted on the device; default 0)   (not in the reference)\n"
               << "             gpu_prep (1: lines are normalised on the device, helper threads only read PNGs; default 0)   (not in the reference)\n";
     return EXIT_FAILURE;
@@ -57,12 +58,40 @@ static int main1(int argc, char** argv) {
   const bool with_lm = !lm_name.empty();
   if (with_lm && beam == 0) fail("lm= needs beam=W: the language model works inside the beam search");
   if (with_lm) clstm.set_lm(lm_name, (float)getdenv("lm_weight", 1.0), (float)getdenv("lm_bonus", 0.0));
-  auto print_nbest = [&](const string& name, const vector<Hypothesis>& hyps) {
+  // lexicon=FILE [word_chars=STRING] (with beam=W only; default none: nothing changes): the search is constrained to the word list of
+  // FILE (UTF-8, one word per line; CLSTMOCR::set_lexicon, clstm_net_beam_lex): every run of word characters of a hypothesis is a word
+  // of the list.  A class is a word character iff it occurs in a word of the list, or, with word_chars=, iff it occurs in that string;
+  // every other class separates words.  Works with and without lm=; lm_bonus= applies either way.  A line on which no admissible
+  // transcript survived gets the hypotheses of the search WITHOUT the lexicon, each prefixed "LEXMISS\t"; the number of such lines is
+  // reported on stderr at the end.
+  const string lex_name = getsenv("lexicon", "");
+  const bool with_lex = !lex_name.empty();
+  if (with_lex && beam == 0) fail("lexicon= needs beam=W: the lexicon works inside the beam search");
+  if (with_lex) {
+    const string word_chars = getsenv("word_chars", "");
+    clstm.set_lexicon(lex_name, word_chars.empty() ? nullptr : &word_chars);
+    if (!with_lm) clstm.lm_bonus = (float)getdenv("lm_bonus", 0.0);
+    std::cerr << "lexicon: " << clstm.lexicon_words << " words, " << clstm.lexicon_dropped << " lines of " << lex_name << " dropped" << std::endl;
+  }
+  long long lexmiss = 0;
+  // the lines of the current minibatch the lexicon left without a hypothesis: theirs are those of the search without it
+  auto fill_misses = [&](const vector<int>& Ts, vector<vector<Hypothesis>>& hyps, vector<char>& miss) {
+    miss.assign(hyps.size(), 0);
+    if (!with_lex) return;
+    bool any = false;
+    for (size_t k = 0; k < hyps.size(); k++) if (hyps[k].empty() && Ts[k] > 0) { miss[k] = 1; any = true; lexmiss++; }
+    if (!any) return;
+    vector<vector<Hypothesis>> plain;
+    clstm.nbest_current(Ts, beam, nbest, plain, false);
+    for (size_t k = 0; k < hyps.size(); k++) if (miss[k]) hyps[k] = plain[k];
+  };
+  auto print_nbest = [&](const string& name, const vector<Hypothesis>& hyps, bool miss = false) {
     std::cout << "nbest " << name << std::endl;
     for (size_t k = 0; k < hyps.size(); k++) {
       char buf[64], am[64];
       snprintf(buf, sizeof buf, "%.9g", (double)hyps[k].score);
       snprintf(am, sizeof am, "%.9g", (double)hyps[k].am_score);
+      if (miss) std::cout << "LEXMISS\t";
       std::cout << k << "\t" << buf << "\t";
       if (with_lm) std::cout << am << "\t";
       std::cout << utf32_to_utf8(hyps[k].text) << std::endl;
@@ -183,7 +212,8 @@ static int main1(int argc, char** argv) {
       vector<ustring> outs;
       vector<vector<CharPrediction>> preds;
       vector<vector<Hypothesis>> hyps;
-      if (beam > 0) clstm.predict_nbest(ptrs, beam, nbest, outs, hyps, conf ? &preds : nullptr, gpu_prep);
+      vector<char> miss;
+      if (beam > 0) { clstm.predict_nbest(ptrs, beam, nbest, outs, hyps, conf ? &preds : nullptr, gpu_prep); fill_misses(clstm.batch_T, hyps, miss); }
       else if (gpu_prep) clstm.predict_batch_gpu(ptrs, outs, conf ? &preds : nullptr);
       else clstm.predict_frames(ptrs, outs, conf ? &preds : nullptr);
       vector<Image> posteriors;
@@ -227,7 +257,7 @@ static int main1(int argc, char** argv) {
             for (float& v : posteriors[k].d) v = scaled_log(v);
           write_png(basename + (output == "logs" ? ".lp.png" : ".p.png"), posteriors[k]);
         }
-        if (beam > 0) print_nbest(name, hyps[k]);
+        if (beam > 0) print_nbest(name, hyps[k], miss[k] != 0);
         if (next_gt < gt_line.size() && gt_line[next_gt] == (int)k) { print_alignment(name, spans[next_gt], gt_score[next_gt]); next_gt++; }
         else if (do_align && !noalign[k].empty()) std::cout << noalign[k] << std::endl;
         if (do_errs) std::cout << errs_lines[k] << std::flush;
@@ -235,6 +265,7 @@ static int main1(int argc, char** argv) {
       if (helper.valid()) helper.get();
     }
     if (do_errs) print_error_totals();
+    if (with_lex) std::cerr << "lexicon: " << lexmiss << " lines without an admissible transcript (LEXMISS)" << std::endl;
     return 0;
   }
   std::ifstream stream(argv[1]);
@@ -270,8 +301,10 @@ static int main1(int argc, char** argv) {
     } else fail("unknown output format");
     vector<vector<Hypothesis>> hyps;
     if (beam > 0) {
+      vector<char> miss;
       clstm.nbest_current(vector<int>(1, clstm.T), beam, nbest, hyps);
-      print_nbest(line, hyps[0]);
+      fill_misses(vector<int>(1, clstm.T), hyps, miss);
+      print_nbest(line, hyps[0], miss[0] != 0);
     }
     ustring gt;
     string note;
@@ -292,6 +325,7 @@ static int main1(int argc, char** argv) {
     }
   }
   if (do_errs) print_error_totals();
+  if (with_lex) std::cerr << "lexicon: " << lexmiss << " lines without an admissible transcript (LEXMISS)" << std::endl;
   return 0;
 }
 

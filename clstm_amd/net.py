@@ -229,6 +229,23 @@ class Network:
                       ptr(nhyp), ptr(ln), ptr(sc), ptr(am), ptr(lab))
         return unpack_beam(self.T, nbest, nhyp, ln, sc, lab, am)
 
+    def beam_lex(self, lexicon, beam=8, nbest=None, lm=None, weight=0.0, bonus=0.0):
+        """beam_lm() constrained to a lexicon (clstm_amd.lexicon.Lexicon; clstm_net_beam_lex; the algorithm in
+        clstm_amd/csrc/ctc_beam.h, third part): every run of word classes of a transcript is a word of the lexicon.  lm (a CharLM)
+        is optional; without one score = am_score + bonus * length.  Returns what beam_lm() returns; a line on which no admissible
+        labelling survived has an empty list."""
+        nbest = beam if nbest is None else nbest
+        bs = len(self.T)
+        nhyp = np.zeros(bs, np.int32)
+        ln = np.zeros(max(1, bs * nbest), np.int32)
+        sc = np.zeros(max(1, bs * nbest), np.float32)
+        am = np.zeros(max(1, bs * nbest), np.float32)
+        lab = np.zeros(max(1, nbest * self.N), np.int32)
+        self.lib.call("clstm_net_beam_lex", self.h, int(beam), int(nbest), lexicon.handle(self.lib),
+                      None if lm is None else lm.handle(self.lib), float(weight), float(bonus),
+                      ptr(nhyp), ptr(ln), ptr(sc), ptr(am), ptr(lab))
+        return unpack_beam(self.T, nbest, nhyp, ln, sc, lab, am)
+
     def errors(self, transcripts, counts=False, confusion=False):
         """Edit distance of every line's trivial_decode against its transcript, computed where the decoded classes lie on the
         device (clstm_net_errors).  transcripts: one label sequence per line; label `nclasses` stands for a character outside the

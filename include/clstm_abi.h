@@ -150,6 +150,34 @@ int clstm_charlm_destroy(clstm_charlm* lm);
 int clstm_ctc_beam_lm_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
                             const clstm_charlm* lm, float weight, float bonus,
                             int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
+/* A lexicon for the beam search (clstm_amd/csrc/ctc_beam.h, third part).  word_class_h[nc] (HOST) flags the classes words are made of;
+ * class 0 (blank) is never one, the classes 1 .. nc-1 without the flag are separators.  The nwords words are packed label sequences,
+ * word w owns words_h[word_off_h[w] .. word_off_h[w+1]).  A labelling is admissible when every maximal run of word classes in it is a
+ * word.  The host builds a trie -- duplicates merged, the children of a node sorted by label, node numbers in the order of the sorted
+ * words -- and uploads it once.  Refused, each by name, before anything is uploaded: word_class_h[0] != 0, a label of a word outside
+ * 1 .. nc-1 or not a word class, an empty word, decreasing offsets, more than 2^24 labels in all words (a bound on the trie nodes), a
+ * device form above 2^28 bytes (4 + nodes * ceil(nc / 32) + nodes + 1 + 2 * edges words).  nwords == 0 is legal: only separators
+ * can be written.  The handle belongs to the creating thread's device.
+ *   clstm_lexicon_info    info[0..3] = distinct words, trie nodes (the root included), edges, device bytes
+ *   clstm_lexicon_admits  HOST only, walks the arrays that were uploaded: *out = 0 labels_h[0..L) is no admissible prefix (or holds a
+ *                         label outside 1 .. nc-1), 1 an admissible prefix whose last run is unfinished, 2 an admissible labelling */
+typedef struct clstm_lexicon clstm_lexicon;
+int clstm_lexicon_create(clstm_lexicon** out, int nc, const unsigned char* word_class_h, const int* words_h, const int* word_off_h,
+                         int nwords);
+int clstm_lexicon_destroy(clstm_lexicon* lex);
+int clstm_lexicon_info(const clstm_lexicon* lex, long long info[4]);
+int clstm_lexicon_admits(const clstm_lexicon* lex, const int* labels_h, int L, int* out);
+/* clstm_ctc_beam_lm_batch constrained to a lexicon: the same search, expression for expression, except that an extension the lexicon
+ * does not allow in the prefix's state is no candidate, and that after the last frame only the entries whose last run is finished are
+ * ranked.  lm may be NULL: then the table term is that of an all-zero table (lm(l + c) = lm(l) + bonus) and there is no end table.
+ * nhyp_h[b] = min(nbest, admissible live entries) can be 0 for a line WITH frames: then its slots read as a line without frames
+ * (len 0, both scores -INFINITY, labels 0).  A lexicon without word classes admits everything: clstm_ctc_beam_lm_batch's bytes (with
+ * lm == NULL and bonus == 0, clstm_ctc_beam_batch's).  Refused before anything is enqueued or written: lexicon or model made for
+ * another nc, beam * (nc - 1) > 4096, weight negative or non-finite, bonus non-finite, and clstm_ctc_beam_batch's offset / beam /
+ * nbest checks. */
+int clstm_ctc_beam_lex_batch(const float* probs /*DEVICE [N][nc]*/, int nc, const int* line_off_h, int bs, int beam, int nbest,
+                             const clstm_lexicon* lex, const clstm_charlm* lm /*NULL ok*/, float weight, float bonus,
+                             int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
 /* Unit-cost Levenshtein distance, the canonical edit script and the confusions of npairs (hypothesis, reference) pairs in one launch
  * (clstm_amd/csrc/edit_distance.h states the algorithm).  Hypotheses: packed ints, pair p owns [hyp_off_h[p], hyp_off_h[p+1]).  References:
  * nref of them, packed, reference q owns [ref_off_h[q], ref_off_h[q+1]).  Pair p is compared with reference ref_of_h[p] (NULL: nref ==
@@ -241,7 +269,8 @@ int clstm_net_set_gradient_clip(clstm_net* net, float clip);
  *   backward ran              else "input deltas not enabled / no backward yet" (clstm_net_enable_input_deltas, then a backward pass of THIS minibatch)
  *
  *   entry                                              | batch declared | current (no declared next) | saved (not predict's) | backward ran
- *   get_outputs_h, decode, score, beam, beam_lm, errors| yes            | yes                        |                       |
+ *   get_outputs_h, decode, score, beam, beam_lm,       |                |                            |                       |
+ *   beam_lex, errors                                   | yes           | yes                        |                       |
  *   get_state_h which = 5                              | yes            | yes                        |                       |
  *   get_state_h other, ctc, backward                   | yes            | yes                        | yes                   |
  *   set_output_deltas_h                                | yes            | yes                        | yes                   |
@@ -291,6 +320,10 @@ int clstm_net_beam(clstm_net* net, int beam, int nbest, int* nhyp_h, int* len_h,
  * time under "ctc_beam_lm". */
 int clstm_net_beam_lm(clstm_net* net, int beam, int nbest, const clstm_charlm* lm, float weight, float bonus,
                       int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
+/* clstm_ctc_beam_lex_batch on the outputs of the net's current minibatch (lm may be NULL): the preconditions and guarantees of
+ * clstm_net_beam.  Kernel time under "ctc_beam_lex". */
+int clstm_net_beam_lex(clstm_net* net, int beam, int nbest, const clstm_lexicon* lex, const clstm_charlm* lm, float weight, float bonus,
+                       int* nhyp_h, int* len_h, float* score_h, float* am_score_h, int* labels_h);
 /* clstm_edit_distance_batch for the net's current minibatch: the hypotheses are trivial_decode of every line, compared where
  * decode_kernel leaves them on the device (nothing comes to the host but the results); the references are labels_h / L_h[bs], one packed
  * transcript per line, with nsym = nclasses + 1 -- label nclasses, allowed in references only, stands for a character outside the codec and
@@ -536,6 +569,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *  29  beam-search launches (clstm_ctc_beam_batch / clstm_net_beam): one per call that had a line with frames;
  *  30  the same with a language model (clstm_ctc_beam_lm_batch / clstm_net_beam_lm); 29 does not move for them;
  *  31  edit-distance launches (clstm_edit_distance_batch / clstm_net_errors): one per call that had a pair;
+ *  32  beam-search launches constrained to a lexicon (clstm_ctc_beam_lex_batch / clstm_net_beam_lex); 29 and 30 do not move for them;
  *  21  minibatches whose forward pass the batched kernel handed to the per-line kernels on the device (inputs outside [-255, 255];
  *     counted on the device: blocking).
  * Tests use it to make sure the path they mean to cover is the one that ran. */
