@@ -8,4 +8,4 @@ search) and lexicon.py (word lists that constrain it).  See DESIGN.md and INTEGR
 from .abi import ClstmError, load  # noqa: F401
 from .lexicon import Lexicon  # noqa: F401
 from .lm import CharLM  # noqa: F401
-from .net import Network, Normalizer, make_net, sgd_update, mktargets, edit_distance, cer  # noqa: F401
+from .net import Degrader, Network, Normalizer, make_net, sgd_update, mktargets, edit_distance, cer  # noqa: F401

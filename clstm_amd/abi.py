@@ -19,6 +19,16 @@ class NetDesc(C.Structure):
                 ("nhidden", C.c_int * MAX_LAYERS), ("nclasses", C.c_int)]
 
 
+class DegradeLine(C.Structure):     # clstm_degrade_line
+    _fields_ = [("m", C.c_float * 4), ("tx", C.c_float), ("ty", C.c_float), ("sigma", C.c_float), ("maxdelta", C.c_float),
+                ("blur", C.c_float), ("seed", C.c_uint)]
+
+
+class DegradeRanges(C.Structure):   # clstm_degrade_ranges
+    _fields_ = [("angle", C.c_float), ("scale", C.c_float), ("aniso", C.c_float), ("translate", C.c_float),
+                ("sigma", C.c_float * 2), ("maxdelta", C.c_float * 2), ("blur", C.c_float * 2)]
+
+
 class ClstmError(RuntimeError):
     pass
 
@@ -116,6 +126,14 @@ _SIGS = {
     "clstm_normalizer_run_d": [_P, _P, _P, _P, _I, _P, _P, _P],
     "clstm_normalizer_get_frames_h": [_P, _P],
     "clstm_normalizer_device_bytes": [_P, _P],
+    "clstm_degrader_create": [_P],
+    "clstm_degrader_destroy": [_P],
+    "clstm_degrader_run_h": [_P, _P, _P, _P, _I, _P, _P],
+    "clstm_degrader_run_d": [_P, _P, _P, _P, _I, _P, _P],
+    "clstm_degrader_get_pixels_h": [_P, _P],
+    "clstm_degrader_device_bytes": [_P, _P],
+    "clstm_degrade_default_ranges": [_P],
+    "clstm_degrade_draw": [C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, _P, _I, _I, _P],
     "clstm_net_enable_timing": [_P, _I],
     "clstm_net_kernel_time_ms": [_P, C.c_char_p, _P, _P],
     "clstm_net_reset_timing": [_P],

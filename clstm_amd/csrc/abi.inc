@@ -33,6 +33,10 @@ struct clstm_normalizer {
   std::unique_ptr<size_t> dev_bytes;   // (declared first = destroyed last, as in clstm_net)
   Normalizer nz;
 };
+struct clstm_degrader {
+  std::unique_ptr<size_t> dev_bytes;
+  Degrader dg;
+};
 extern "C" {
 
 const char* clstm_last_error(void) { return g_err.c_str(); }
@@ -487,6 +491,56 @@ int clstm_normalizer_device_bytes(clstm_normalizer* h, long long* bytes) {
   ABI_BEGIN
   REQUIRE(h && bytes, "null argument");
   *bytes = (long long)*h->dev_bytes;
+  ABI_END
+}
+int clstm_degrader_create(clstm_degrader** out) {
+  ABI_BEGIN
+  REQUIRE(out, "null argument");
+  size_t* bytes = new size_t(0);
+  AcctScope acct_(bytes);
+  clstm_degrader* h = nullptr;
+  try { h = new clstm_degrader(); } catch (...) { delete bytes; throw; }
+  h->dev_bytes.reset(bytes);
+  *out = h;
+  ABI_END
+}
+int clstm_degrader_destroy(clstm_degrader* h) { ABI_BEGIN delete h; ABI_END }
+int clstm_degrader_run_h(clstm_degrader* h, const float* pix_h, const int* w_h, const int* h_h, int bs, const clstm_degrade_line* lines_h, float** out_pix_d) {
+  ABI_BEGIN REQUIRE(h, "null argument"); h->dg.run(pix_h, true, w_h, h_h, bs, lines_h, out_pix_d); ABI_END
+}
+int clstm_degrader_run_d(clstm_degrader* h, const float* pix_d, const int* w_h, const int* h_h, int bs, const clstm_degrade_line* lines_h, float** out_pix_d) {
+  ABI_BEGIN REQUIRE(h, "null argument"); h->dg.run(pix_d, false, w_h, h_h, bs, lines_h, out_pix_d); ABI_END
+}
+int clstm_degrader_get_pixels_h(clstm_degrader* h, float* out_h) {
+  ABI_BEGIN
+  REQUIRE(h && out_h, "null argument");
+  REQUIRE(h->dg.last_pixels > 0, "clstm_degrader_get_pixels_h: the last clstm_degrader_run_* call on this degrader produced nothing");
+  copy_d2h(out_h, h->dg.out.p, h->dg.last_pixels);
+  ABI_END
+}
+int clstm_degrader_device_bytes(clstm_degrader* h, long long* bytes) {
+  ABI_BEGIN
+  REQUIRE(h && bytes, "null argument");
+  *bytes = (long long)*h->dev_bytes;
+  ABI_END
+}
+int clstm_degrade_default_ranges(clstm_degrade_ranges* out) {
+  ABI_BEGIN
+  REQUIRE(out, "null argument");
+  *out = degrade_default_ranges();
+  ABI_END
+}
+int clstm_degrade_draw(unsigned long long seed, unsigned long long key, unsigned long long visit, const clstm_degrade_ranges* rg, int w, int h,
+                       clstm_degrade_line* out) {
+  ABI_BEGIN
+  REQUIRE(rg && out, "null argument");
+  REQUIRE(w >= 1 && h >= 1, "clstm_degrade_draw: w and h must be at least 1");
+  for (float a : {rg->angle, rg->scale, rg->aniso, rg->translate})
+    REQUIRE(std::isfinite(a) && a >= 0.0f, "clstm_degrade_draw: angle, scale, aniso and translate must be finite and not negative");
+  for (const float* iv : {rg->sigma, rg->maxdelta, rg->blur})
+    REQUIRE(std::isfinite(iv[0]) && std::isfinite(iv[1]) && iv[0] >= 0.0f && iv[0] <= iv[1],
+            "clstm_degrade_draw: the sigma, maxdelta and blur intervals must be finite, not negative, and ordered LO <= HI");
+  degrade_draw(seed, key, visit, *rg, w, h, out);
   ABI_END
 }
 int clstm_net_device_bytes(clstm_net* h, long long* bytes) {

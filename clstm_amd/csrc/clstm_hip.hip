@@ -34,6 +34,7 @@
 #include "lstm_mfma_bwd_dw.h"
 #include "ops.h"
 #include "normalize.h"
+#include "degrade.h"
 
 #include <algorithm>
 #include <chrono>
@@ -54,6 +55,7 @@ namespace clstm {
 #include "ctc_run.inc"   // CTC / score / decode launches, host side
 #include "step.inc"      // one training step: the sequence, its ingest and alignment launches
 #include "normalize_run.inc"   // the line normaliser (normalize.h), host side
+#include "degrade_run.inc"     // the line degrader (degrade.h), host side
 }  // namespace clstm
 
 #include "abi.inc"       // extern "C": include/clstm_abi.h

@@ -1,28 +1,11 @@
 // normalize_run.inc -- part of clstm_hip.hip (namespace clstm): host side of the device line normaliser (normalize.h): the Gaussian
 // masks, the item lists, the launches of one clstm_normalizer_run_* call.  Everything goes to the library's one stream (g_stream).
 
-struct Normalizer {
-  int target_height = 48;
-  float smooth2d = 1.0f, smooth1d = 0.3f, range = 4.0f;
-  // grow-only device buffers, constructed inside an AcctScope (clstm_normalizer_create): clstm_normalizer_device_bytes sums them
-  DevBuf<float> pix, tmp, smooth, amax, center, sums, masks, frames;
-  DevBuf<NzLine> lines;
-  DevBuf<NzItem> items;
-  DevBuf<NzWarp> warps;
-  ~Normalizer() {
-    for (DevBuf<float>* b : {&pix, &tmp, &smooth, &amax, &center, &sums, &masks, &frames}) b->release();
-    lines.release(); items.release(); warps.release();
-  }
-  // the mask pool: gauss1d's mask of every sigma seen so far (host copy; the device copy is refreshed when the pool has grown)
+// The mask pool of a normaliser or of one degrader call (degrade_run.inc): gauss1d's mask of every sigma seen so far, computed on the
+// host -- the device never evaluates exp -- and cached by the bits of sigma
+struct NzMasks {
   std::vector<float> mask_pool;
   std::map<unsigned, std::pair<int, int>> mask_of;   // bits of sigma -> (offset, reach)
-  size_t masks_uploaded = 0;
-  std::vector<NzLine> lines_h;
-  std::vector<NzItem> items_h;
-  std::vector<NzWarp> warps_h;
-  std::vector<float> sums_h;
-  size_t last_frames = 0;   // floats of the last successful call's frames (0: none)
-
   static int reach(float sigma) { return 1 + int(3.0 * sigma); }   // gauss1d :29
   std::pair<int, int> mask(float sigma) {
     unsigned key;
@@ -45,6 +28,27 @@ struct Normalizer {
     mask_of[key] = e;
     return e;
   }
+};
+
+struct Normalizer : NzMasks {
+  int target_height = 48;
+  float smooth2d = 1.0f, smooth1d = 0.3f, range = 4.0f;
+  // grow-only device buffers, constructed inside an AcctScope (clstm_normalizer_create): clstm_normalizer_device_bytes sums them
+  DevBuf<float> pix, tmp, smooth, amax, center, sums, masks, frames;
+  DevBuf<NzLine> lines;
+  DevBuf<NzItem> items;
+  DevBuf<NzWarp> warps;
+  ~Normalizer() {
+    for (DevBuf<float>* b : {&pix, &tmp, &smooth, &amax, &center, &sums, &masks, &frames}) b->release();
+    lines.release(); items.release(); warps.release();
+  }
+  size_t masks_uploaded = 0;   // floats of mask_pool the device copy holds (refreshed when the pool has grown)
+  std::vector<NzLine> lines_h;
+  std::vector<NzItem> items_h;
+  std::vector<NzWarp> warps_h;
+  std::vector<float> sums_h;
+  size_t last_frames = 0;   // floats of the last successful call's frames (0: none)
+
   template <class T>
   static void upload(DevBuf<T>& d, const std::vector<T>& h) {
     d.reserve(h.size());

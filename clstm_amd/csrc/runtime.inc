@@ -239,7 +239,7 @@ enum PathCounter {
   PC_FWD_FUSED_WX = 6, PC_PEER_EXCHANGE = 7, PC_DW_X_EXTERNAL = 8, PC_BWD_C32 = 9, PC_PACKS_FOLLOW_UPDATE = 10, PC_BWD_X3 = 11,
   PC_REPLICA_CHECK = 12, PC_DW_BIAS_OUT = 13, PC_DW_DX_ONE_LAUNCH = 14, PC_MFMA_NOSAVE = 15, PC_MFMA_FWD = 16, PC_MFMA_BWD = 17,
   PC_MFMA_BWD_DW = 18, PC_INGEST_TAIL = 19, PC_INGEST_TAIL_USED = 20, PC_MFMA_ROUTED = 21 /* counted on the device */,
-  PC_LINE_NOSAVE = 22, PC_FUSED_NOSAVE = 23, PC_PEER_TWO_PHASE = 24, PC_NORMALIZED = 25, PC_XD_PROLOGUE = 26, PC_XD_PRODUCERS = 27, PC_SCORE = 28, PC_BEAM = 29, PC_BEAM_LM = 30, PC_EDIT = 31, PC_BEAM_LEX = 32, PC_COUNT
+  PC_LINE_NOSAVE = 22, PC_FUSED_NOSAVE = 23, PC_PEER_TWO_PHASE = 24, PC_NORMALIZED = 25, PC_XD_PROLOGUE = 26, PC_XD_PRODUCERS = 27, PC_SCORE = 28, PC_BEAM = 29, PC_BEAM_LM = 30, PC_EDIT = 31, PC_BEAM_LEX = 32, PC_DEGRADED = 33, PC_COUNT
 };
 static long long g_path_count[PC_COUNT];
 struct StorePlain {

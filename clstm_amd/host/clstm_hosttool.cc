@@ -1,11 +1,22 @@
 // clstm_hosttool -- test helper exposing the GPU-free host pieces (PNG, normaliser, model files) to
 // the Python test-suite.  Raw float dumps are little-endian float32 preceded by two int32 (w, h).
+#include "degrade.h"
 #include "lexicon.h"
 #include "model.h"
 #include "normalizer.h"
 #include "png_io.h"
 #include <thread>
 using namespace clstmhost;
+
+static void read_raw(const string& fname, Image& im) {
+  std::ifstream f(fname, std::ios::binary);
+  int hdr[2] = {0, 0};
+  f.read((char*)hdr, 8);
+  if (!f || hdr[0] < 1 || hdr[1] < 1) fail("bad raw image: " + fname);
+  im.resize(hdr[0], hdr[1]);
+  f.read((char*)im.d.data(), im.d.size() * 4);
+  if ((size_t)f.gcount() != im.d.size() * 4) fail("short raw image: " + fname);
+}
 
 static void dump(const string& fname, const Image& im) {
   std::ofstream f(fname, std::ios::binary);
@@ -77,6 +88,56 @@ int main(int argc, char** argv) {
       long long frames = 0;
       for (int w : widths) frames += w;
       std::cout << ims.size() << " lines " << frames << " frames in " << dt << " s = " << ims.size() / dt << " lines/s" << std::endl;
+    } else if (cmd == "degrade-raw" && (argc == 14 || argc == 15)) {  // IN.raw OUT.raw m0 m1 m2 m3 tx ty sigma maxdelta blur seed [noise0|noise1]
+      // degrade_line (degrade.h) on a raw dump with ink = 1: the bit-level referee of the device degrader.  With noise0 / noise1
+      // OUT.raw is the UNSMOOTHED field 0 / 1 of step 1 instead (the statistics of the hash are tested on it)
+      Image im, out;
+      read_raw(argv[2], im);
+      DegradeLine p{};
+      for (int k = 0; k < 4; k++) p.m[k] = (float)atof(argv[4 + k]);
+      p.tx = (float)atof(argv[8]); p.ty = (float)atof(argv[9]);
+      p.sigma = (float)atof(argv[10]); p.maxdelta = (float)atof(argv[11]); p.blur = (float)atof(argv[12]);
+      p.seed = (unsigned)strtoul(argv[13], nullptr, 10);
+      if (argc == 15) {
+        const string which = argv[14];
+        if (which != "noise0" && which != "noise1") fail("degrade-raw: the optional last argument is noise0 or noise1");
+        degrade_noise(out, im.w, im.h, p.seed, which == "noise1");
+      } else degrade_line(im, p, out);
+      dump(argv[3], out);
+    } else if (cmd == "degrade-bench" && argc == 4) {  // IN.raws THREADS: the host degrader's rate on a file of raw dumps, parameters
+      std::ifstream f(argv[2], std::ios::binary);      // drawn at the default ranges (clstm_degrade_draw, seed 0, key = position, visit 0)
+      vector<Image> ims;
+      int hdr[2];
+      while (f.read((char*)hdr, 8)) {
+        ims.emplace_back();
+        ims.back().resize(hdr[0], hdr[1]);
+        f.read((char*)ims.back().d.data(), ims.back().d.size() * 4);
+      }
+      const int nthreads = std::max(1, atoi(argv[3]));
+      clstm_degrade_ranges rg;
+      if (clstm_degrade_default_ranges(&rg)) fail(clstm_last_error());
+      vector<DegradeLine> ps(ims.size());
+      static_assert(sizeof(DegradeLine) == sizeof(clstm_degrade_line), "DegradeLine is clstm_degrade_line");
+      for (size_t k = 0; k < ims.size(); k++)
+        if (clstm_degrade_draw(0, k, 0, &rg, ims[k].w, ims[k].h, (clstm_degrade_line*)&ps[k])) fail(clstm_last_error());
+      vector<double> ink(ims.size());
+      const double t0 = now();
+      vector<std::thread> pool;
+      for (int t = 0; t < nthreads; t++)
+        pool.emplace_back([&, t] {
+          for (size_t k = t; k < ims.size(); k += nthreads) {
+            Image out;
+            degrade_line(ims[k], ps[k], out);
+            double s = 0.0;
+            for (float v : out.d) s += v;
+            ink[k] = s;
+          }
+        });
+      for (auto& th : pool) th.join();
+      const double dt = now() - t0;
+      double total = 0.0;
+      for (double s : ink) total += s;
+      std::cout << ims.size() << " lines (ink " << total << ") in " << dt << " s = " << ims.size() / dt << " lines/s" << std::endl;
     } else if (cmd == "writepng" && argc == 4) {  // raw -> png (write_png)
       std::ifstream f(argv[2], std::ios::binary);
       int hdr[2];
@@ -120,7 +181,7 @@ int main(int argc, char** argv) {
       std::cout << std::endl;
       for (const auto& w : wl.words) { std::cout << "word"; for (int c : w) std::cout << " " << c; std::cout << std::endl; }
     } else {
-      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|writepng|init-model|roundtrip|params|codec|lexicon ...\n";
+      std::cerr << "usage: clstm_hosttool png2raw|normalize|normalize-raw|normalize-bench|degrade-raw|degrade-bench|writepng|init-model|roundtrip|params|codec|lexicon ...\n";
       return 2;
     }
     return 0;

@@ -115,10 +115,20 @@ struct CLSTMOCR {
   clstm_lexicon* lexicon = nullptr;             // set_lexicon: the n-best calls are constrained to it (clstm_net_beam_lex)
   long long lexicon_words = 0, lexicon_dropped = 0;   // distinct words in the trie; lines of the word list that were dropped
   clstm_normalizer* gpu_normalizer = nullptr;   // the device twin of `normalizer` (created at first use: predict_batch_gpu, normalize_batch_gpu)
+  // set_degrade: normalize_batch_gpu degrades its lines on the device first (clstm_degrader_*; training only, never recognition)
+  clstm_degrader* gpu_degrader = nullptr;
+  unsigned long long degrade_seed = 0;
+  clstm_degrade_ranges degrade_ranges{};
+  void set_degrade(unsigned long long seed, const clstm_degrade_ranges& ranges) {
+    if (!gpu_degrader) chk(clstm_degrader_create(&gpu_degrader), "clstm_degrader_create");
+    degrade_seed = seed;
+    degrade_ranges = ranges;
+  }
   ~CLSTMOCR() {
     if (lm) clstm_charlm_destroy(lm);
     if (lexicon) clstm_lexicon_destroy(lexicon);
     if (gpu_normalizer) clstm_normalizer_destroy(gpu_normalizer);
+    if (gpu_degrader) clstm_degrader_destroy(gpu_degrader);
     if (net) clstm_net_destroy(net);
   }
   void attach() {  // device network from the host model
@@ -355,21 +365,37 @@ struct CLSTMOCR {
   // ---- raw line images normalised ON THE DEVICE (clstm_normalizer_*: the frames are the host normaliser's, bit for bit).  Main
   // thread only: the call goes to the library's stream, which is per thread.
   // measure + normalize of `raws` in one call; T: frames per line, *frames_d: DEVICE [sum T][target_height], valid until the next call
-  void normalize_device(const vector<const Image*>& raws, vector<int>& T_out, float** frames_d) {
+  // keys / visits (with set_degrade; one of each per line): the lines are degraded first, in the same call sequence -- line b with the
+  // parameters clstm_degrade_draw gives (degrade_seed, keys[b], visits[b]) -- and the normaliser reads the degraded pixels where the
+  // degrader left them, on the device
+  void normalize_device(const vector<const Image*>& raws, vector<int>& T_out, float** frames_d, const vector<unsigned long long>* keys = nullptr,
+                        const vector<unsigned long long>* visits = nullptr) {
     if (!gpu_normalizer)
       chk(clstm_normalizer_create(&gpu_normalizer, target_height, normalizer.smooth2d, normalizer.smooth1d, normalizer.range), "clstm_normalizer_create");
     vector<int> w, h;
     vector<float> pix;
     for (const Image* r : raws) { w.push_back(r->w); h.push_back(r->h); pix.insert(pix.end(), r->d.begin(), r->d.end()); }
     T_out.assign(raws.size(), 0);
+    if (keys) {
+      if (!gpu_degrader) fail("normalize_device: keys without set_degrade");
+      if (!visits || keys->size() != raws.size() || visits->size() != raws.size()) fail("normalize_device: one key and one visit per line");
+      vector<clstm_degrade_line> lines(raws.size());
+      for (size_t b = 0; b < raws.size(); b++)
+        chk(clstm_degrade_draw(degrade_seed, (*keys)[b], (*visits)[b], &degrade_ranges, w[b], h[b], &lines[b]), "clstm_degrade_draw");
+      float* pix_d = nullptr;
+      chk(clstm_degrader_run_h(gpu_degrader, pix.data(), w.data(), h.data(), (int)raws.size(), lines.data(), &pix_d), "clstm_degrader_run_h");
+      chk(clstm_normalizer_run_d(gpu_normalizer, pix_d, w.data(), h.data(), (int)raws.size(), T_out.data(), nullptr, frames_d), "clstm_normalizer_run_d");
+      return;
+    }
     chk(clstm_normalizer_run_h(gpu_normalizer, pix.data(), w.data(), h.data(), (int)raws.size(), T_out.data(), nullptr, frames_d), "clstm_normalizer_run_h");
   }
   // the same with the frames read back once into one Image per line (what a dataset cache keeps)
-  void normalize_batch_gpu(const vector<const Image*>& raws, vector<Image*>& frames) {
+  void normalize_batch_gpu(const vector<const Image*>& raws, vector<Image*>& frames, const vector<unsigned long long>* keys = nullptr,
+                           const vector<unsigned long long>* visits = nullptr) {
     if (raws.empty()) return;
     vector<int> Ts;
     float* frames_d = nullptr;
-    normalize_device(raws, Ts, &frames_d);
+    normalize_device(raws, Ts, &frames_d, keys, visits);
     size_t N = 0;
     for (int t : Ts) N += t;
     vector<float> all(N * target_height);

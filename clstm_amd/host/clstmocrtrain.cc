@@ -149,6 +149,10 @@ static int print_usage(char** argv) {
             << "  Variables: load save_name nhidden lrate momentum target_height ntrain start charsep\n"
             << "             report_time test_every report_every save_every params   (clstmocrtrain.cc:99-115)\n"
             << "             gpu_prep (1: lines are normalised on the device, helper threads only decode PNGs; default 0)\n"
+            << "             degrade (1: every visit of a line is degraded afresh on the device -- elastic distortion, affine jitter, blur -- before it is\n"
+            << "                      normalised; needs batch > 1 or ngpu > 1, implies gpu_prep=1; default 0)  degrade_seed (default 0)\n"
+            << "                      degrade_angle degrade_scale degrade_aniso degrade_translate degrade_sigma=LO,HI degrade_maxdelta=LO,HI degrade_blur=LO,HI\n"
+            << "                      (over the defaults of clstm_degrade_default_ranges)\n"
             << "             batch (lines per update, default 1)  test_batch (lines per recognition call of the test-set pass, default batch)  gpu_errors (1: that pass counts its errors on the device, default 0)  nhidden2 (> 0: bidi2)  ngpu (processes, one GPU each; needs batch % ngpu == 0)   (not in the reference)\n";
   return EXIT_FAILURE;
 }
@@ -288,11 +292,45 @@ static int main1(int argc, char** argv) {
   // into the same Line cache entries and packs the minibatch.  That call is ordered on the library's stream behind the steps already
   // queued -- accepted: it happens only for files seen for the first time; from the second visit of a file on the loop is the
   // gpu_prep=0 loop.  The test-set pass goes through CLSTMOCR::predict_batch_gpu.
-  const bool gpu_prep = getienv("gpu_prep", 0) != 0;
+  // degrade=1 (default 0: nothing below changes): every visit of a line is a new image -- CLSTMOCR::set_degrade puts the device degrader in
+  // front of the device normaliser -- so the per-file cache holds the RAW image and the encoded labels, not frames, and every line of every
+  // minibatch goes through draw_device: degrade, normalise, read back, pack (the read-back path of normalize_batch_gpu; the frames do
+  // not stay on the device into the training step).  A line's parameters are clstm_degrade_draw's for (degrade_seed, key = sample index,
+  // visit = how often that sample has been drawn so far, counted over the whole minibatch on every rank from the lrand48 sequence the
+  // ranks share): what a line becomes depends neither on its place in the minibatch nor on the rank that trains on it.  The test-set pass is
+  // never degraded.
+  const bool degrade = getienv("degrade", 0) != 0;
+  if (degrade && !(batch > 1 || ngpu > 1)) fail("degrade=1 needs batch > 1 or ngpu > 1 (the batch=1 loop is the reference's, sample for sample)");
+  if (degrade && getenv("gpu_prep") && getienv("gpu_prep", 0) == 0)
+    fail("degrade=1 gpu_prep=0: the lines are degraded on the device, in front of the device normaliser; degrade=1 implies gpu_prep=1");
+  const bool gpu_prep = degrade || getienv("gpu_prep", 0) != 0;
+  if (degrade) {
+    clstm_degrade_ranges rg;
+    chk(clstm_degrade_default_ranges(&rg), "clstm_degrade_default_ranges");
+    rg.angle = (float)getdenv("degrade_angle", rg.angle); rg.scale = (float)getdenv("degrade_scale", rg.scale);
+    rg.aniso = (float)getdenv("degrade_aniso", rg.aniso); rg.translate = (float)getdenv("degrade_translate", rg.translate);
+    auto interval = [&](const char* name, float* iv) {
+      const string s = getsenv(name, "");
+      if (s == "") return;
+      double lo = 0.0, hi = 0.0;
+      char tail = 0;
+      if (sscanf(s.c_str(), "%lf,%lf%c", &lo, &hi, &tail) != 2) fail(string(name) + "=LO,HI expected, got " + s);
+      iv[0] = (float)lo; iv[1] = (float)hi;
+    };
+    interval("degrade_sigma", rg.sigma); interval("degrade_maxdelta", rg.maxdelta); interval("degrade_blur", rg.blur);
+    clstm.set_degrade(strtoull(getsenv("degrade_seed", "0").c_str(), nullptr, 10), rg);
+    clstm_degrade_line probe;   // (the ranges are checked here, by name, not at the first minibatch)
+    chk(clstm_degrade_draw(0, 0, 0, &rg, 1, 1, &probe), "clstm_degrade_draw");
+  }
+  struct RawLine { Image raw; Classes labels; ustring target; };   // what the cache keeps per file with degrade=1
+  vector<std::shared_ptr<RawLine>> raw_cache(degrade && use_cache ? trainingset.size() : 0);
+  vector<unsigned long long> drawn(degrade ? trainingset.size() : 0, 0);   // how often every sample has been drawn so far
   struct Pending {
     vector<int> samples, mine, todo;
     vector<std::shared_ptr<CLSTMOCR::Line>> lines;
     vector<Image> raws;   // raws[k]: the raw line of todo[k]
+    vector<unsigned long long> visits;              // degrade=1: visits[i]: the visit number of position i of the minibatch
+    vector<std::shared_ptr<RawLine>> rawlines;      // degrade=1: rawlines[k]: the raw line of todo[k] (todo = mine: every line has device work)
   };
   auto draw_host = [&](Pending& d) {
     d.samples.assign(batch, 0);
@@ -300,6 +338,35 @@ static int main1(int argc, char** argv) {
     d.lines.assign(batch, nullptr);
     d.mine = deal(d.samples);
     d.todo.clear();
+    if (degrade) {
+      d.visits.assign(batch, 0);
+      for (int i = 0; i < batch; i++) d.visits[i] = drawn[d.samples[i]]++;
+      d.todo = d.mine;
+      d.rawlines.assign(d.todo.size(), nullptr);
+      auto work = [&](int k0) {   // (the workers only read the cache; lines read from their files enter it below, on this thread)
+        for (size_t k = k0; k < d.todo.size(); k += prep_threads) {
+          const int s = d.samples[d.todo[k]];
+          if (use_cache && raw_cache[s]) { d.rawlines[k] = raw_cache[s]; continue; }
+          auto r = std::make_shared<RawLine>();
+          trainingset.readSample(r->raw, r->target, s);
+          clstm.codec.encode(r->labels, r->target);
+          d.rawlines[k] = r;
+        }
+      };
+      vector<std::future<void>> pool;
+      for (int t = 1; t < prep_threads && t < (int)d.todo.size(); t++) pool.push_back(std::async(std::launch::async, work, t));
+      work(0);
+      for (auto& f : pool) f.get();
+      for (size_t k = 0; k < d.todo.size(); k++) {
+        std::shared_ptr<RawLine>& slot = d.rawlines[k];
+        if (use_cache) { if (raw_cache[d.samples[d.todo[k]]]) slot = raw_cache[d.samples[d.todo[k]]]; else raw_cache[d.samples[d.todo[k]]] = slot; }
+        auto l = std::make_shared<CLSTMOCR::Line>();
+        l->labels = slot->labels;
+        l->target = slot->target;
+        d.lines[d.todo[k]] = l;
+      }
+      return;
+    }
     for (int i : d.mine) {
       if (use_cache && cache[d.samples[i]]) { d.lines[i] = cache[d.samples[i]]; continue; }
       bool first = true;
@@ -326,6 +393,18 @@ static int main1(int argc, char** argv) {
   auto draw_device = [&](Pending& d, CLSTMOCR::Prepared& p) {
     vector<const Image*> raws;
     vector<Image*> frames;
+    if (degrade) {
+      vector<unsigned long long> keys, visits;
+      for (size_t k = 0; k < d.todo.size(); k++) {
+        raws.push_back(&d.rawlines[k]->raw); frames.push_back(&d.lines[d.todo[k]]->frames);
+        keys.push_back((unsigned long long)d.samples[d.todo[k]]); visits.push_back(d.visits[d.todo[k]]);
+      }
+      clstm.normalize_batch_gpu(raws, frames, &keys, &visits);
+      vector<const CLSTMOCR::Line*> ptrs;
+      for (int i : d.mine) ptrs.push_back(d.lines[i].get());
+      clstm.pack(p, ptrs);
+      return;
+    }
     for (size_t k = 0; k < d.todo.size(); k++) { raws.push_back(&d.raws[k]); frames.push_back(&d.lines[d.todo[k]]->frames); }
     clstm.normalize_batch_gpu(raws, frames);
     for (int i : d.todo) if (use_cache) cache[d.samples[i]] = d.lines[i];

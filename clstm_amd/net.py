@@ -509,6 +509,84 @@ class Normalizer:
         return n.value
 
 
+def degrade_line(m=(1.0, 0.0, 0.0, 1.0), tx=0.0, ty=0.0, sigma=0.0, maxdelta=0.0, blur=0.0, seed=0):
+    """one line's degradation parameters (clstm_degrade_line); the defaults are the identity"""
+    return abi.DegradeLine((C.c_float * 4)(*m), tx, ty, sigma, maxdelta, blur, seed)
+
+
+def default_ranges(lib=None):
+    rg = abi.DegradeRanges()
+    (lib or abi.load()).call("clstm_degrade_default_ranges", C.byref(rg))
+    return rg
+
+
+def draw(seed, key, visit, w, h, ranges=None, lib=None):
+    """clstm_degrade_draw: the parameters of line `key` (the caller's name for it, not its place in a minibatch) on its `visit`-th
+    visit, drawn within `ranges` (default: clstm_degrade_default_ranges)"""
+    lib = lib or abi.load()
+    out = abi.DegradeLine()
+    lib.call("clstm_degrade_draw", int(seed), int(key), int(visit), C.byref(ranges if ranges is not None else default_ranges(lib)),
+             int(w), int(h), C.byref(out))
+    return out
+
+
+class Degrader:
+    """Training-time degradation of raw line images on the device (clstm_degrader_*, csrc/degrade.h): a small elastic distortion, an
+    affine jitter, a little blur, bit for bit degrade_line of clstm_amd/host/degrade.h.  images: [w, h] float arrays with ink = 1, as
+    Normalizer takes them; lines: one abi.DegradeLine (degrade_line(...), draw(...)) per image.  The output is packed the way
+    Normalizer.run_device_pixels takes it."""
+
+    def __init__(self, lib=None):
+        self.lib = lib or abi.load()
+        h = C.c_void_p()
+        self.lib.call("clstm_degrader_create", C.byref(h))
+        self.h = h
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                self.lib.call("clstm_degrader_destroy", self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def _run(self, name, pix, w, h, lines):
+        w, h = i32(w), i32(h)
+        arr = (abi.DegradeLine * max(len(lines), 1))(*lines)
+        out_d = C.c_void_p()
+        self.lib.call(name, self.h, ptr(pix), ptr(w), ptr(h), len(w), C.cast(arr, C.c_void_p), C.byref(out_d))
+        self.shapes = list(zip(w.tolist(), h.tolist()))
+        return out_d.value
+
+    def run_device(self, images, lines):
+        """-> address of the DEVICE pixels, the degraded lines packed back to back, valid until the next call on this degrader"""
+        return self._run("clstm_degrader_run_h", *Normalizer.pack(images), lines)
+
+    def run_device_pixels(self, pix_d, w, h, lines):
+        """the same for pixels already on the device (packed back to back; a torch tensor or an address); no host synchronisation"""
+        return self._run("clstm_degrader_run_d", pix_d, w, h, lines)
+
+    def pixels(self):
+        """the last call's output as a list of host arrays [w, h] (blocking)"""
+        out = np.empty(sum(w * h for w, h in self.shapes), np.float32)
+        self.lib.call("clstm_degrader_get_pixels_h", self.h, ptr(out))
+        res, o = [], 0
+        for w, h in self.shapes:
+            res.append(out[o:o + w * h].reshape(w, h))
+            o += w * h
+        return res
+
+    def run(self, images, lines):
+        """-> the degraded images, a list of host arrays [w, h]"""
+        self.run_device(images, lines)
+        return self.pixels()
+
+    def device_bytes(self):
+        n = C.c_longlong()
+        self.lib.call("clstm_degrader_device_bytes", self.h, C.byref(n))
+        return n.value
+
+
 class Comm:
     """RCCL communicator of the data-parallel ranks (clstm_comm_*): one per process / GPU.
     `exchange(id_bytes_or_None) -> id_bytes` ships rank 0's 128-byte id to every rank."""

@@ -401,6 +401,53 @@ int clstm_normalizer_get_frames_h(clstm_normalizer* nz, float* frames_h);
  * uploaded pixels, two intermediate images, the per-column arrays, masks and item lists */
 int clstm_normalizer_device_bytes(clstm_normalizer* nz, long long* bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Line degradation on the device, for training: a minibatch of RAW line images in, the same number of images of the same sizes
+ * out -- a small elastic distortion, an affine jitter, a little blur -- bit for bit what degrade_line of clstm_amd/host/degrade.h
+ * (the specification: noise fields from an integer hash, gauss2d, min / max bounding, bilinear warp with background outside,
+ * gauss2d) gives.  The output has the packed layout clstm_normalizer_run_d takes (ink = 1, pixel (x = i, y = j) of a line at
+ * pix + i*h + j, lines back to back).  Everything is enqueued on the library's one stream.
+ *   Per line: m[4], tx, ty -- output pixel (i, j) is read at x = m0 (i - cx) + m1 (j - cy) + cx + tx + d0, y alike from m2, m3, ty,
+ * d1, about the centre cx = (w - 1)/2, cy = (h - 1)/2; sigma, maxdelta -- the displacement fields d0, d1 are noise smoothed with sigma
+ * and scaled into [-maxdelta, maxdelta] (maxdelta = 0: no distortion, sigma is not used); blur -- the sigma of the final Gaussian
+ * (0: none); seed -- of the line's noise.  m = {1, 0, 0, 1}, tx = ty = maxdelta = blur = 0 gives the input back byte for byte.
+ *   Limits, refused by name before anything is touched: bs > 0; every w, h >= 1, at most 2^23, w*h <= 2^30; m, tx, ty, sigma finite;
+ * maxdelta and blur finite and >= 0; sigma > 0 where maxdelta > 0; 1 + int(3 sigma) <= 800 (NZ_MAXRANGE) for sigma (where used)
+ * and blur.  A refused call produces nothing and leaves the degrader usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct clstm_degrader clstm_degrader;
+typedef struct { float m[4]; float tx, ty; float sigma, maxdelta; float blur; unsigned seed; } clstm_degrade_line;
+/* the ranges clstm_degrade_draw draws within: rotation in +-angle (radians), log of the scale in +-scale, log of the x/y anisotropy
+ * in +-aniso, shift in +-translate*h pixels along each axis; sigma, maxdelta (pixels), blur in [LO, HI] */
+typedef struct { float angle, scale, aniso, translate; float sigma[2], maxdelta[2], blur[2]; } clstm_degrade_ranges;
+int clstm_degrader_create(clstm_degrader** out);
+int clstm_degrader_destroy(clstm_degrader* dg);
+/* pix_h: HOST, packed as above; w_h / h_h[bs], lines_h[bs]: HOST.  *out_pix_d: library-owned DEVICE, the degraded lines packed like
+ * the input -- what clstm_normalizer_run_d takes -- valid until the next call on this degrader.  Asynchronous. */
+int clstm_degrader_run_h(clstm_degrader* dg, const float* pix_h, const int* w_h, const int* h_h, int bs, const clstm_degrade_line* lines_h,
+                         float** out_pix_d);
+/* the same with the pixels already on the device (pix_d DEVICE; not modified).  No host synchronisation: the per-call arrays go up
+ * in one copy from pinned memory, the minimum and maximum of the noise fields stay on the device.  (A buffer that has to grow
+ * drains the stream once; buffers never shrink.) */
+int clstm_degrader_run_d(clstm_degrader* dg, const float* pix_d, const int* w_h, const int* h_h, int bs, const clstm_degrade_line* lines_h,
+                         float** out_pix_d);
+/* blocking copy of the last call's output, HOST [sum w*h]; refused if that call produced nothing */
+int clstm_degrader_get_pixels_h(clstm_degrader* dg, float* out_h);
+/* bytes of the degrader's grow-only device buffers: the output, the two noise fields of every distorted line after each filter pass,
+ * the blur's intermediate image, the uploaded pixels of run_h, the min / max partials, the per-call block */
+int clstm_degrader_device_bytes(clstm_degrader* dg, long long* bytes);
+/* Host only.  The default ranges, mild enough that a line stays legible: angle 0.02 rad (1.1 degrees), scale 0.03, aniso 0.02,
+ * translate 0.03 (of the height), sigma [3, 8], maxdelta [0, 1.5] pixels, blur [0, 0.7]. */
+int clstm_degrade_default_ranges(clstm_degrade_ranges* out);
+/* Host only.  THE statement of how a line's parameters are drawn: a counter-based generator (splitmix64's finaliser chained over seed,
+ * key, visit; csrc/degrade_run.inc) draws, uniformly within rg, the angle, the log-scale ls, the anisotropy an, tx, ty, sigma, maxdelta,
+ * blur and the noise seed; m = {c sx, -s sy, s sx, c sy} with sx = exp(ls + an), sy = exp(ls - an), c, s = cos, sin of the angle, in
+ * double, rounded to float once -- the device never evaluates a transcendental.  key is the caller's name for the line (its index in
+ * the training set), NOT its position in the minibatch; visit counts how often it has been drawn: what a line becomes does not depend
+ * on which lines it is batched with.  Ranges of zero width give the identity parameters exactly. */
+int clstm_degrade_draw(unsigned long long seed, unsigned long long key, unsigned long long visit, const clstm_degrade_ranges* rg, int w, int h,
+                       clstm_degrade_line* out);
+
 /* sum of the net's device allocations in bytes (parameters, packed weights, every per-minibatch buffer, CTC / decode scratch) */
 int clstm_net_device_bytes(clstm_net* net, long long* bytes);
 /* internal NPLSTM state for parity tests: which = 0 gi,1 gf,2 go,3 ci,4 state,5 output h,
@@ -559,7 +606,7 @@ int clstm_debug_gemm(int mode, const float* A, const float* B, float* C, int R, 
  *     declared by such a step;
  *  7  training steps whose gradient exchange was the peer-read all-reduce fused with the update (either form);  24  those of them that
  *     took the two-phase form;  12  replica consistency checks enqueued;
- *  25  lines normalised on the device (clstm_normalizer_run_*);
+ *  25  lines normalised on the device (clstm_normalizer_run_*);  33  lines degraded on the device (clstm_degrader_run_*);
  *  26  backward passes whose top layer's recurrence workgroups computed the softmax layer's input deltas themselves, in front of
  *     their first step (lstm_xd_prologue.h), instead of a product launch of its own (experiment option xd_prologue=0);
  *  27  backward passes that took the producer form of the same instead (the default where narrow_plan admits it; xd_prologue=1: never): every recurrence workgroup
